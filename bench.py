@@ -21,7 +21,12 @@ generator fuxi-planner_amd/synth.py):
              GPU take the frames in turn): sustained frames/s and p50 / p99 submit-to-paths latency over the 600 frames
              SURVEY 8d prescribes (its default --steps)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the timed path handed its caller in its last step (rank 0's part at N > 1) as .npy files,
+float32 / float64, at most 64 MB in all: offsets.npy, cells.npy, cost.npy, status.npy and query_ids.npy (dump_outputs).
+The inputs are generated from the workload's fixed seeds: the same arguments give the same inputs, so two builds can be
+compared output for output.
 
 N > 1, two ways (contiguous query shards, one broadcast of the grid over xGMI, no other collective), neither of
 which imports torch:
@@ -54,8 +59,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
-DEFAULT_STEPS = {"c5pipe": (600, 16), "c2pipe": (24, 6)}  # workload -> (steps, warmup); everything else 5 / 2
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak
+DEFAULT_STEPS = {"c5pipe": (600, 16), "c2pipe": (24, 6), "c1": (20, 1)}  # workload -> (steps, warmup); everything else 5 / 2
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: the files together, headers included
+DUMP_SEED = 20240601       # --dump-outputs: the permutation a sample of the queries is drawn from
 
 
 def kernel_src_sha16():
@@ -264,6 +271,37 @@ def measure(cx, name, steps, warmup, frames_in_flight=0):
     return out
 
 
+def dump_outputs(d, res):
+    """--dump-outputs: the CSR result of the timed path's last step, (offsets int64[n+1], cells int32[m, 2], cost float64[n],
+    status int32[n]), into directory `d`.  Every query when the files fit in DUMP_CAP_BYTES; otherwise the longest prefix of
+    a fixed seeded permutation of the n queries that fits, in ascending order (two builds that agree sample the same
+    queries; two that do not still share the prefix).  query_ids.npy names the queries written, offsets.npy indexes their
+    cells in cells.npy.  Integers go out as float64, cells as float32 (exact: coordinates < 2^24).  -> the record."""
+    off, cells, cost, status = res
+    off = np.asarray(off, np.int64)
+    n = len(status)
+    lens = np.diff(off)
+    need = 32 + 8 * lens  # per query: status, cost, offset, id (float64) + its cells (two float32 each)
+    room = DUMP_CAP_BYTES - 8 - 5 * 128  # (the closing offset, five .npy headers)
+    if int(need.sum()) <= room:
+        ids = np.arange(n, dtype=np.int64)
+    else:
+        perm = np.random.default_rng(DUMP_SEED).permutation(n)
+        ids = np.sort(perm[:int(np.searchsorted(np.cumsum(need[perm]), room, side="right"))])
+    ln = lens[ids]
+    o = np.zeros(len(ids) + 1, dtype=np.int64)
+    o[1:] = np.cumsum(ln)
+    src = np.repeat(off[ids] - o[:-1], ln) + np.arange(o[-1], dtype=np.int64)  # (each sampled query's cells, in order)
+    out = {"offsets": o.astype(np.float64), "cells": np.asarray(cells, np.int32).reshape(-1, 2)[src].astype(np.float32),
+           "cost": np.asarray(cost, np.float64)[ids], "status": np.asarray(status)[ids].astype(np.float64),
+           "query_ids": ids.astype(np.float64)}
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return {"dir": d, "queries": int(n), "queries_written": int(len(ids)), "sampled": bool(len(ids) < n),
+            "bytes": int(sum(os.path.getsize(os.path.join(d, k + ".npy")) for k in out))}
+
+
 def _sample_ids(lo, hi, k):
     """k query positions of the shard [lo, hi), evenly spread, its first and last among them"""
     n = hi - lo
@@ -318,7 +356,7 @@ def verify_multi(cx, wl, occ0, grid_now, starts, goals, res, strong, nq, per_sha
             "queries_checked_per_shard": checked, "against": "oracle/jps_oracle.c on rank 0: lengths, float64 cost bytes, cells of the last step"}
 
 
-def measure_c1(cx, reps=20):
+def measure_c1(cx, reps=20, warm=1):
     """BASELINE config 1 and the node's real call: ONE query per call on the reference's own maps (tests/golden/maps_png.npz:
     the 35 maps/*.png as the loader of global_planner_st.py:176-182 reads them).  The 147 x 112 map pasted into a zero
     256 x 256 canvas with the three queries of SURVEY 8(c), and every map with its first-free -> last-free query.  Every
@@ -334,8 +372,9 @@ def measure_c1(cx, reps=20):
         recs = json.load(f)
     p = cx.planner
 
-    def timed(fn, n):
-        fn()
+    def timed(fn, n, w=warm):
+        for _ in range(w):
+            fn()
         t0 = time.perf_counter()
         for _ in range(n):
             r = fn()
@@ -346,12 +385,14 @@ def measure_c1(cx, reps=20):
     occ[:147, :112] = np.unpackbits(z[name])[:147 * 112].reshape(147, 112)
     m64 = occ.astype(np.float64)  # what the node passes (st:248)
     canvas = []
+    planned = []  # (path, float64 cost) of the last timed call of every query: --dump-outputs
     p.set_grid_occ(occ)
     for rec in [r for r in recs if r.get("canvas") and r["map"] == name][:3]:
         s, g = tuple(rec["start"]), tuple(rec["goal"])
         want = [tuple(rec["path"][i:i + 2]) for i in range(0, len(rec["path"]), 2)]
         us, path = timed(lambda: p.plan(s, g, 2), reps)
         assert path == want, "c1: the path differs from the one captured from jps1.py"
+        planned.append((path, p.last_cost))
         with contextlib.redirect_stdout(io.StringIO()):
             us_m, r = timed(lambda: fx.jps1.method(m64, s, g, 2), reps)  # the map of the last tick again: not uploaded
             assert r[0] == want
@@ -384,6 +425,7 @@ def measure_c1(cx, reps=20):
         s, g = tuple(int(v) for v in free[0]), tuple(int(v) for v in free[-1])
         p.set_grid_occ(grid)
         us, path = timed(lambda: p.plan(s, g, 2), 5)
+        planned.append((path, p.last_cost))
         us_c, rc = timed(lambda: oracle.plan(grid, s, g, 2, literal=False), 5)
         assert (path if path else 0) == rc[0], "c1: %s differs from the oracle" % nm
         maps.append((us, us_c, W * H))
@@ -397,7 +439,7 @@ def measure_c1(cx, reps=20):
             "maps35_us_per_call": {"mean": float(mu.mean()), "median": float(np.median(mu)), "max": float(mu.max()), "min": float(mu.min())},
             "maps35_c_port_us_one_core": {"mean": float(mc.mean()), "median": float(np.median(mc)), "max": float(mc.max())},
             "maps35_cells": {"min": int(min(m[2] for m in maps)), "max": int(max(m[2] for m in maps))},
-            "checked": "every path against jps1.py's (canvas) / the C oracle (maps)"}
+            "checked": "every path against jps1.py's (canvas) / the C oracle (maps)", "planned": planned}
 
 
 def main():
@@ -413,6 +455,8 @@ def main():
     ap.add_argument("--frames-in-flight", type=int, default=0, help="c5pipe / c2pipe: planner handles taking the frames / batches in turn (0: the workload's)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="queries timed on the host cores (0: the workload's default)")
     ap.add_argument("--py-sample", type=int, default=64, help="queries timed with the pure-Python restatement of the reference (0: none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in "
+                    "its last step to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample of larger outputs)")
     a = ap.parse_args()
     d_steps, d_warm = DEFAULT_STEPS.get(a.workload, (5, 2))
     a.steps = d_steps if a.steps is None else a.steps
@@ -480,15 +524,23 @@ def main():
     if a.workload == "c1":  # single calls: a latency, reported on its own line
         if cx.world > 1 or a.gpus > 1:
             raise SystemExit("c1 is a single-GPU, single-process workload (one query per call)")
-        r = measure_c1(cx)
+        r = measure_c1(cx, a.steps, a.warmup)
+        planned = r.pop("planned")
+        if a.dump_outputs:  # (the canvas queries, then the 35 maps: as one CSR batch)
+            lens = np.array([len(pth) for pth, _ in planned], dtype=np.int64)
+            off = np.zeros(len(planned) + 1, dtype=np.int64)
+            off[1:] = np.cumsum(lens)
+            cells = np.array([c for pth, _ in planned for c in pth], dtype=np.int32).reshape(-1, 2)
+            r["dumped"] = dump_outputs(a.dump_outputs, (off, cells, np.array([c for _, c in planned], np.float64), lens))
         print(json.dumps({"metric": "start->goal plans/sec, one query per call, 256x256 canvas of a reference map", "value": r["value"], "unit": "plans/s",
-                          "n_gpus": 1, "steps": 20, "warmup": 1, "ms_per_step": r["us_per_call"] / 1e3, "higher_is_better": True, "scaling": "weak",
+                          "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": r["us_per_call"] / 1e3, "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "f64", "data": "the reference's maps/*.png (tests/golden/maps_png.npz)",
                           "config": {"workload": "c1: " + r["describe"], "detail": r}}), flush=True)
         cx.planner.close()
         return
     rc_final = 0
     m = measure(cx, a.workload, a.steps, a.warmup, a.frames_in_flight)
+    dumped = dump_outputs(a.dump_outputs, m["last"]) if (a.dump_outputs and m is not None) else None
 
     # ---- the other BASELINE workloads, behind the headline's timed region (default invocation only)
     also = {}
@@ -510,6 +562,7 @@ def main():
                 if r:
                     also["c4"] = brief(r, ("kernel_ms_per_device",))
                 also["c1"] = measure_c1(cx)
+                also["c1"].pop("planned")
                 r = measure(cx, "c3", 1, 1)  # BASELINE config 3: one warm-up and one timed step (100 000 queries on 4096^2, ~ 10 s each)
                 if r:
                     also["c3"] = brief(r, ("retried",))
@@ -639,6 +692,8 @@ def main():
                 rc_final = 3
         if also:
             out["config"]["also"] = also
+        if dumped:
+            out["config"]["dumped_outputs"] = dumped
         if not a.no_cpu_baseline:  # (at N > 1 too: rank 0's shard, the same leg)
             from oracle import oracle  # checker used as the CPU baseline ("port"), never by the planner
             ns = min(a.cpu_sample or wl.get("cpu_sample", m["wl"]["nq"]), m["n_local"])

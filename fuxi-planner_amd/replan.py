@@ -18,7 +18,8 @@ from concurrent.futures import FIRST_COMPLETED, ThreadPoolExecutor, wait
 
 import numpy as np
 
-HW_QUEUES = 16  # hardware queues the pipelines below want the HIP runtime to hand out (its default is 4)
+HW_QUEUES = 2  # hardware queues the pipelines below ask the HIP runtime for when the environment names none: a card's queue
+# slots are shared by every process on it, and more queues than slots is a state a shared card may reset under
 
 
 def configure_hw_queues(n=HW_QUEUES):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# config 5 with frames in flight: bench.py --workload c5pipe over "<queues>:<K>" pairs (GPU box), e.g. tools/c5pipe_sweep.sh 16:8 16:12 24:12
+# config 5 with frames in flight: bench.py --workload c5pipe over "<queues>:<K>" pairs (GPU box), e.g. tools/c5pipe_sweep.sh 2:8 2:12 (at most 2 queues on a shared card)
 mkdir -p gpurun_out/c5pipe
 for qk in "$@"; do
   q=${qk%%:*}; k=${qk##*:}

@@ -34,7 +34,7 @@ except Exception as e:
 PY
   done;;
 queues)
-  for qk in ${FX_QK:-16:12 16:16}; do
+  for qk in ${FX_QK:-2:12 2:2}; do
     IFS=: read q k one <<< "$qk"
     P=$OUT/queues_${q}_${k}${one:+_one}; rm -rf $P
     GPU_MAX_HW_QUEUES=$q FXJPS_ONE_STREAM=${one:+1} timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $P -- python3 bench.py --workload c5pipe --steps ${FX_QSTEPS:-240} --warmup 24 --frames-in-flight $k --no-also --no-cpu-baseline > $P.json 2> $P.err
