@@ -152,10 +152,8 @@ struct DevCtx {
     int solo_timeouts = 0;              // waits for that counter that ran into their 5 ms bound, since the handle was created
     int solo_timeouts_run = 0;          // ... in a row (3: no more head launches on this device; a cold first launch of a
                                         // kernel -- its code object is loaded then -- is a lone timeout and means nothing)
-    int xcc_rr = -1;                    // 1: the blocks of a grid run on XCD b % 8 (probed once); 0: not so; -1: not probed yet
     size_t cells_bound = 0;             // bytes the batch in progress may still allocate for its packed paths
     bool lds_attr_done[8] = {};         // k_search instantiations whose dynamic-LDS limit has been raised on this device
-    bool lds_attr_coop[2] = {};         // ... and k_search_coop's
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_solo0 = nullptr, ev_solo1 = nullptr;
     hipEvent_t ev_hd0 = nullptr, ev_hd1 = nullptr, ev_bt0 = nullptr, ev_bt1 = nullptr;  // around the head launch / the batch's launch alone
     bool had_solo = false;              // the last regular-pool launch was two launches
@@ -755,46 +753,11 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
     if (nsolo != 0u) waves = std::min<uint32_t>(waves, (uint32_t)wpb_down(c.nwaves - nsolo));
 
     if (pool != 0 || nsolo != 0u || (uint64_t)nrun > (uint64_t)d.n_cu * live_main || d.share * h->mem_div > 1) live_main = 0u;
-    // One query per BLOCK (k_search_coop: a searching wavefront and a stager that keeps the LDS tier of its open list in
-    // shape, two SIMDs of a CU): for what a handful of long queries decide -- the head launch above, and batches small
-    // enough for every query to get a block at once (the frames of config 5, single calls).  Tables indexed by the cell
-    // only (grids of up to 2^20 slots), no read-set recording.  FXJPS_COOP=0 / FXJPS_COOP_MAX=n: measurement and test aids.
-    uint32_t coop_max = 1024u;
-    if (const char* e = getenv("FXJPS_COOP_MAX")) coop_max = (uint32_t)std::max(0, atoi(e));
-    // (measured in round 4 and left OFF: the stager answers within ~230 cycles of being asked and takes two refills in three
-    // off the searching wavefront -- but a refill turned out to cost that wavefront ~2 300 cycles, not the 6 000 the
-    // instrumented build had shown, and taking a block plus re-inserting the late list costs about as much: query 9206
-    // alone 69.0 -> 70.7 ms, config 2 130.7 k -> 123 k plans/s with the head launch on such blocks, a config-5 frame
-    // 64.5 -> 64.0 ms.  FXJPS_COOP=1 switches it on; tests/test_gpu_fullsize.py::test_cooperative_blocks keeps it exact.)
-    const bool coop_ok = pool == 0 && !track && c.direct_ly > 0 && getenv("FXJPS_COOP") && atoi(getenv("FXJPS_COOP")) != 0;
-    const bool coop_all = coop_ok && nsolo == 0u && live_main == 0u && nrun <= coop_max && nrun <= c.nwaves;
-    if (coop_all) waves = std::min<uint32_t>(c.nwaves, nrun);  // blocks, one scratch slot each
-    // A library built with -DFXJPS_XCC=1 and FXJPS_HEAD_XCC=1 in the environment (measurement: see DESIGN.md section 3.1c,
-    // `make libfxjps_xcc.so`): the head launch on XCD 0 alone -- an L2 of its own --
-    // and the batch's launch on the other seven.  Needs the round-robin rule "block b runs on XCD b % 8" (probed once).
-    bool xcc_split = FXJPS_XCC != 0 && nsolo != 0u && live_solo == 1u && !coop_ok && d.n_cu == 256 && getenv("FXJPS_HEAD_XCC") && atoi(getenv("FXJPS_HEAD_XCC")) != 0;
-    if (xcc_split && d.xcc_rr < 0) {
-        d.xcc_rr = 0;
-        uint32_t* dp = nullptr;
-        uint32_t hp[64];
-        if (hipMalloc((void**)&dp, sizeof(hp)) == hipSuccess) {
-            hipLaunchKernelGGL(fx::k_xcc_probe, dim3(64), dim3(64), 0, d.stream, dp);
-            if (hipMemcpyAsync(hp, dp, sizeof(hp), hipMemcpyDeviceToHost, d.stream) == hipSuccess && hipStreamSynchronize(d.stream) == hipSuccess) {
-                d.xcc_rr = 1;
-                for (int b = 0; b < 64; b++)
-                    if (hp[b] != (uint32_t)(b % 8)) d.xcc_rr = 0;
-            }
-            (void)hipFree(dp);
-        }
-        (void)hipGetLastError();
-    }
-    if (xcc_split && (d.xcc_rr != 1 || nsolo > 32u)) xcc_split = false;
-    if (xcc_split) waves = std::min<uint32_t>(waves, (uint32_t)(d.n_cu / 8 * 7) * 4u * (uint32_t)fx::OCC);  // what seven XCDs hold at once
     if (pool == 0) d.waves_used = waves;
     HIPCHK(h, hipMemsetAsync(d.d_next.p, 0, 4 * sizeof(unsigned int), d.stream));
     const dim3 block(fx::WAVE * fx::WPB);
-    DBG("launch k_search pool=%d waves=%u nrun=%u buckets=%u far_cap=%u solo=%u x %u spread=%u coop=%d", pool, waves, nrun, c.nbuckets, c.far_cap, nsolo,
-        live_solo, live_main, coop_all ? 2 : (coop_ok ? 1 : 0));
+    DBG("launch k_search pool=%d waves=%u nrun=%u buckets=%u far_cap=%u solo=%u x %u spread=%u", pool, waves, nrun, c.nbuckets, c.far_cap, nsolo,
+        live_solo, live_main);
     HIPCHK(h, hipEventRecord(d.ev0, d.stream));
     // instantiations: heuristic x read-set recording (fxjps_replan_frame) x table indexed by the cell
     {
@@ -817,17 +780,6 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
                 }
             }
         }
-        const KFn cfn = hchoice == 1 ? fx::k_search_coop<1> : fx::k_search_coop<2>;
-        static const size_t cpad = 100u << 10;  // the head launch's blocks: 21 KB of their own + this: no second block, and none of the batch's (66 KB), fits the CU
-        bool coop_head = coop_ok && nsolo != 0u && live_solo == 1u;
-        if (coop_head && !d.lds_attr_coop[hchoice == 1 ? 0 : 1]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cpad) == hipSuccess) {
-                d.lds_attr_coop[hchoice == 1 ? 0 : 1] = true;
-            } else {
-                (void)hipGetLastError();
-                coop_head = false;
-            }
-        }
         if (nsolo != 0u) {
             SearchArgs B = A;
             B.nrun = nsolo;
@@ -837,21 +789,10 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
             A.q0 = nsolo;
             A.nrun = nrun - nsolo;
             B.started = d.solo_started;
-            if (xcc_split) {  // eight times the blocks: every eighth one finds itself on XCD 0 and works
-                B.xcc_only = 1u;
-                B.slot_ctr = d.d_next.p + 3;
-                B.max_blocks = nsolo;
-                A.xcc_only = 0xFEu;
-                A.slot_ctr = d.d_next.p + 2;
-                A.max_blocks = waves / (uint32_t)fx::WPB;
-            }
             HIPCHK(h, hipEventRecord(d.ev_solo0, d.stream));
             HIPCHK(h, hipStreamWaitEvent(d.stream_solo, d.ev_solo0, 0));
             HIPCHK(h, hipEventRecord(d.ev_hd0, d.stream_solo));
-            if (coop_head)
-                hipLaunchKernelGGL(cfn, dim3(nsolo), dim3(fx::WAVE * 2), cpad, d.stream_solo, B);
-            else
-            hipLaunchKernelGGL(fn, dim3((nsolo / live_solo) * (xcc_split ? 8u : 1u)), block, pad, d.stream_solo, B);
+            hipLaunchKernelGGL(fn, dim3(nsolo / live_solo), block, pad, d.stream_solo, B);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipEventRecord(d.ev_hd1, d.stream_solo));
             HIPCHK(h, hipEventRecord(d.ev_solo1, d.stream_solo));
@@ -874,14 +815,11 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
             d.solo_timeouts_run = late ? d.solo_timeouts_run + 1 : 0;
         }
         if (nsolo != 0u) HIPCHK(h, hipEventRecord(d.ev_bt0, d.stream));
-        if (coop_all) {
-            hipLaunchKernelGGL(cfn, dim3(waves), dim3(fx::WAVE * 2), 0, d.stream, A);
-        } else if (live_main != 0u) {
+        if (live_main != 0u) {
             A.solo = live_main;
             hipLaunchKernelGGL(fn, dim3(waves / live_main), block, pad, d.stream, A);
         } else {
-            // (split over the XCDs: as many blocks as the whole chip holds, an eighth of them leave at once)
-            hipLaunchKernelGGL(fn, dim3(xcc_split ? (unsigned)(d.n_cu * 2) : waves / fx::WPB), block, 0, d.stream, A);
+            hipLaunchKernelGGL(fn, dim3(waves / fx::WPB), block, 0, d.stream, A);
         }
         HIPCHK(h, hipGetLastError());
         if (nsolo != 0u) {
@@ -959,28 +897,6 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
         d.nrun = head[KMAX + 2u];
         for (int64_t i = 0; i < nq; i++)
             if (in(i)) d.h_order[head[KMAX - key(i)]++] = (uint32_t)i;
-        // Measurement aid (round 6, DESIGN.md section 4: no gain, off): within classes of 128 key values the queries in Morton
-        // order of the middle of start and goal, so that wavefronts that start together read neighbouring lines of the maps.
-        // The order is not an output: results are the same bytes either way.
-        static const bool morton = getenv("FXJPS_ORDER_MORTON") && atoi(getenv("FXJPS_ORDER_MORTON")) != 0;
-        if (morton && d.nrun > 1) {
-            auto spread = [](uint32_t v) -> uint64_t {  // bits of v to the even positions
-                uint64_t x = v & 0xFFFFu;
-                x = (x | (x << 8)) & 0x00FF00FFull;
-                x = (x | (x << 4)) & 0x0F0F0F0Full;
-                x = (x | (x << 2)) & 0x33333333ull;
-                x = (x | (x << 1)) & 0x55555555ull;
-                return x;
-            };
-            std::vector<std::pair<uint64_t, uint32_t>> ks((size_t)d.nrun);
-            for (int64_t j = 0; j < d.nrun; j++) {
-                const int64_t i = d.h_order[(size_t)j];
-                const uint32_t mx = (uint32_t)((S[2 * i] + G[2 * i]) / 2), my = (uint32_t)((S[2 * i + 1] + G[2 * i + 1]) / 2);
-                ks[(size_t)j] = {((uint64_t)((KMAX - key(i)) >> 7) << 32) | (spread(mx >> 3) << 1) | spread(my >> 3), (uint32_t)i};
-            }
-            std::sort(ks.begin(), ks.end());
-            for (int64_t j = 0; j < d.nrun; j++) d.h_order[(size_t)j] = ks[(size_t)j].second;
-        }
         HIPCHK(h, d.d_order.ensure((size_t)nq));
         if (d.nrun > 0)
             HIPCHK(h, hipMemcpyAsync(d.d_order.p, d.h_order.data(), (size_t)d.nrun * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));

@@ -123,22 +123,7 @@ struct SearchArgs {
     uint32_t single = 0;          // one query, one wavefront, no work counter: (start, goal) = imm, results straight into the
     int32_t imm[4] = {0, 0, 0, 0};  // host's pinned buffers (the node's real call: jps1.method, one query per tick)
     unsigned long long* host_counters = nullptr;  // ... out_counters too: zeroed by the kernel, copied there when it is done (no memset, no copy back)
-    // (-DFXJPS_XCC=1, measurement build.)  A launch kept to some of the chip's XCDs (8 on MI355X, an L2 each).  The hardware deals the blocks of a grid out
-    // over the XCDs round-robin (block b runs on XCD b % 8: tools/cumask_probe.hip) and a queue's CU mask cannot take an
-    // XCD out (an empty per-XCD mask means "all of it"), so the kernel decides: a block that finds itself on an XCD
-    // outside xcc_only leaves at once, and the blocks that stay take their scratch slot from a counter instead of
-    // blockIdx.  The head launch (section 3.1c) runs on XCD 0 alone, the batch's launch beside it on the other seven.
-    uint32_t xcc_only = 0;              // bit per XCD whose blocks work (0: all of them, slots by blockIdx)
-    unsigned int* slot_ctr = nullptr;   // ... the counter the working blocks take their slot from
-    uint32_t max_blocks = 0;            // ... and how many slots there are
 };
-#ifndef FXJPS_XCC
-#define FXJPS_XCC 0  // 1: k_search can be kept to some XCDs (FXJPS_HEAD_XCC; DESIGN.md section 3.1c: measured, no gain, costs registers)
-#endif
-__device__ __forceinline__ uint32_t xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 15u; }  // HW_REG_XCC_ID[3:0]
-__global__ void k_xcc_probe(uint32_t* out) {  // which XCD does block b run on (fxjps_create checks the round-robin rule once)
-    if (threadIdx.x == 0) out[blockIdx.x] = xcc_id();
-}
 
 // nodeNeighbours (jps1.py:49-93) as a table: entry [pd*256 + nbm] holds, for each of a node's 8 rays,
 // the direction code (dx+1)*4+(dy+1) it follows or DIR_NONE.  Filled by the host at fxjps_create
@@ -565,39 +550,8 @@ struct WaveLds {  // LDS of one wavefront.  One base pointer: every array below 
     uint32_t hz[HZ_SIZE];        // HZ_SIZE cells (all ones at rest): slot-collision detector of the vectorised commit
     uint32_t bcnt[NBANDS];       // entries in each region of the far band's ring (k_search<2, ..>)
 };
-// ---- a block that works on ONE query (k_search_coop, round 4): wavefront 0 searches, wavefront 1 -- the stager -- keeps the
-// LDS tier of the open list in shape for it.  An R refill (read M, find the threshold that gives R its share, gather, sort
-// the 96-bit keys, close the gaps in M: ~6 000 cycles, once per ~7 iterations) is 14 % of a lone query's time and needs
-// nothing but M: the searching wavefront asks for it ahead of time (the request names the entries of M and the room R
-// will have), goes on with its iteration, and at the top of the next one finds the next block of R sorted in LDS.  While
-// the stager owns M the searching wavefront's pushes that belong to M wait in a list of their own (`late`) and go
-// through the ordinary insertion once the block is in R.  The mailbox: plain LDS words, written before a release store
-// of the sequence number that announces them, read behind an acquire load of it.
-struct CoopLds {
-    unsigned long long bf[WAVE];  // the staged block: the next entries of R, sorted
-    uint32_t bx[WAVE], bs[WAVE];
-    uint16_t bc[WAVE];
-    unsigned long long lf[WAVE];  // pushes of the iteration during which the stager owned M
-    uint32_t lx[WAVE], ls[WAVE];
-    uint16_t lc[WAVE];
-    // request (searching wavefront -> stager)
-    uint32_t req_seq;             // bumped last
-    uint32_t req_m_n, req_room, req_Tx, req_Rx;
-    unsigned long long req_Tbits, req_Rbits;
-    uint32_t quit;                // the block is out of queries
-    // reply (stager -> searching wavefront)
-    uint32_t rdy_seq;             // == req_seq once everything else is written
-    uint32_t rep_take, rep_m_n, rep_Rx;
-    unsigned long long rep_Rbits;
-};
-struct Coop {          // the searching wavefront's side of it, wave-uniform
-    uint32_t pending;  // a request is out: M belongs to the stager, M pushes go to the late list
-    uint32_t seq;      // sequence number of the last request
-    uint32_t late_n;   // entries in the late list
-};
 struct Mid {
     LDS_PTR(WaveLds) w;
-    LDS_PTR(CoopLds) co;             // k_search_coop only
     LDS_PTR(const uint32_t) dirlut;  // block-wide LDS copy of c_dirlut
     LDS_PTR(unsigned long long) bx;  // read set (k_search<HC, true> only), see ReadSet: [64] rows = y tiles, bits = x tiles;
                                      // followed by by[64]: rows = x tiles, bits = y tiles
@@ -663,9 +617,6 @@ __device__ __forceinline__ uint64_t lane_get64(uint64_t v, int i) {
 }
 __device__ __forceinline__ uint32_t lane_pull(uint32_t v, uint32_t src_lane) {  // v of lane src_lane (per lane)
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v);
-}
-__device__ __forceinline__ uint32_t lane_push(uint32_t v, uint32_t dst_lane) {  // my v lands in lane dst_lane (0 where nothing lands)
-    return (uint32_t)__builtin_amdgcn_ds_permute((int)(dst_lane << 2), (int)v);
 }
 
 // The midpoint of a key range [(lo), (hi)] as a threshold that keeps the minimum and releases the maximum:
@@ -876,8 +827,9 @@ __device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, Far
     return true;
 }
 
-// ---- the register tier sorted by a bitonic network (round 6).  The rank sort below costs 63 three-dword comparisons per lane
-// -- 252 vector instructions, 298 with the tie handling and the moves, once per ~ 5 iterations: 9 % of the vector
+// ---- Sort the n entries in lanes 0 .. n-1 of R ascending by (f, x) (R is empty beyond them): a bitonic network (round 6).
+// The rank sort it replaced (every lane ranked its 96-bit key among the others, wave_rank96) cost 63 three-dword comparisons
+// per lane -- 252 vector instructions, 298 with the tie handling and the moves, once per ~ 5 iterations: 9 % of the vector
 // instructions of a full chip's iteration (profiles/r06_phase_insts.txt).  A bitonic network in its "mirror" form (every
 // block ascending: level k first pairs lane i with i ^ (2^k - 1), then i ^ 2^(j-1) for j = k-1 .. 1) needs 21
 // compare-exchange stages of 8 vector instructions: the 96-bit subtraction partner - mine through the borrow chain
@@ -889,9 +841,6 @@ __device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, Far
 // Partners beyond a DPP row operation's reach (i ^ 4, i ^ 16, i ^ 31, i ^ 63) come over the LDS crossbar (ds_swizzle /
 // ds_bpermute: no vector-ALU issue).  Empty lanes hold the all-ones key and sort to the end; with n <= 32 (16) entries the
 // last level (two levels) has nothing to do and is skipped.
-#ifndef FXJPS_SORT_BITONIC
-#define FXJPS_SORT_BITONIC 1
-#endif
 // (s_xnor writes scc: it is in the clobber list -- without it the compiler kept the outcome of `n > 16` there, across the
 // stages.)  (The masks are literals of the scalar instructions: as register operands the compiler hoists the six 64-bit constants out
 // of the search loop and keeps them -- 12 scalar registers the kernel does not have -- in spill slots)
@@ -945,7 +894,7 @@ __device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, Far
 #define FX_U3 "0xff00ff00", "0xff00ff00"
 #define FX_U4 "0xffff0000", "0xffff0000"
 #define FX_U5 "0", "-1"
-__device__ __forceinline__ void r_sort_bitonic(RTier& R, int lane, int n) {
+__device__ __forceinline__ void r_sort(RTier& R, int lane, int n) {
     uint32_t flo = (uint32_t)R.f, fhi = (uint32_t)(R.f >> 32), kx = R.x, ks = R.s, kc = R.c, scr;
     asm volatile("s_nop 1" : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(ks), "+v"(kc));  // (DPP reads want two wait states behind the VALU writes)
     // blocks of 2
@@ -991,49 +940,9 @@ __device__ __forceinline__ void r_sort_bitonic(RTier& R, int lane, int n) {
     R.c = kc;
 }
 
-// Sort the n entries in lanes 0 .. n-1 of R ascending by (f, x) (R is empty beyond them).  Every lane ranks its full
-// 96-bit key among the others (wave_rank96: 63 independent three-dword comparisons) and the entries move to the lane
-// of their rank.  (Until round 2 a 32-bit quantised f was ranked, with a serial exact sort whenever two quantised keys
-// tied: 30 % of the refills with hchoice 2, all of them with hchoice 1 -- 3 900 cycles per sort on average.)
-__device__ __forceinline__ bool r_sort(RTier& R, int lane, int n, bool try_fast, uint64_t fmin) {  // -> some keys tied
-    (void)try_fast;
-    (void)fmin;
-#if FXJPS_SORT_BITONIC
-    r_sort_bitonic(R, lane, n);
-    return false;
-#endif
-    const bool valid = lane < n;
-    // (empty lanes hold the all-ones key: they rank behind every entry)
-    uint32_t rk = wave_rank96((uint32_t)(R.f >> 32), (uint32_t)R.f, R.x, lane);
-    // Entries with the very same key (one cell pushed twice, the better g rounding to the same f) share a rank; any
-    // order among them is right.  Every entry sends its lane number to the lane of its rank and reads back who got
-    // through: the ones that did not are in a tie group, and each group spreads over the ranks it owns.
-    uint32_t recv = 0;
-    if (valid) recv = lane_push((uint32_t)lane, rk);
-    RECONV();
-    const uint32_t winner = lane_pull(recv, rk & 63u);
-    uint64_t lm = __ballot(valid && winner != (uint32_t)lane);
-    const bool tied = lm != 0ull;
-    while (lm != 0ull) {
-        const uint32_t r0 = lane_get(rk, (int)__builtin_ctzll(lm));
-        const uint64_t grp = __ballot(valid && rk == r0);
-        rk = (valid && rk == r0) ? r0 + rank_below(grp) : rk;
-        lm &= ~grp;
-    }
-    if (valid) {
-        const uint32_t flo = lane_push((uint32_t)R.f, rk), fhi = lane_push((uint32_t)(R.f >> 32), rk);
-        R.f = ((uint64_t)fhi << 32) | (uint64_t)flo;
-        R.x = lane_push(R.x, rk);
-        R.s = lane_push(R.s, rk);
-        R.c = lane_push(R.c, rk);
-    }
-    RECONV();
-    return tied;
-}
-
 // R runs low: hand it the smallest M entries, as many as it has room for, sorted behind the entries it still holds
 // (every M key is at or above the R / M threshold, every R key below it), and close the gaps in M.
-__device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, int lane, bool try_fast_sort, uint32_t room_limit = (uint32_t)WAVE) {
+__device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, int lane) {
     open_uniform(Q);
 #ifdef FXJPS_PROF
     unsigned long long rt_ = __builtin_readcyclecounter();
@@ -1052,7 +961,7 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
 #endif
     RT_MARK(39);
     const uint32_t n = Q.m_n;
-    const uint32_t room = min((uint32_t)(WAVE - Q.r_n), rfl(room_limit));  // (the stager is told how much room R will have)
+    const uint32_t room = min((uint32_t)(WAVE - Q.r_n), (uint32_t)WAVE);  // (r_n >= 0: the clamp is a no-op, kept for the instruction schedule it was measured with)
     uint64_t f[MSLOT];
     uint32_t x[MSLOT];
     uint64_t lo = ~0ull, hi = 0ull;
@@ -1081,13 +990,7 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
         bool done = false, xm = false;
         for (int attempt = 0; attempt < 12 && !done; attempt++) {
             DBG_COUNT(M, 21, 1);
-#if FXJPS_RFILL_F32
-            // (where the threshold aims is a guess, not a result: single precision -- one v_rcp_f32 instead of the ~ 40
-            // instructions of a double division on this wavefront's critical path)
-            const double frac = (double)((float)FXJPS_RFILL * (float)room * __builtin_amdgcn_rcpf((float)cand));
-#else
             const double frac = FXJPS_RFILL * (double)room / (double)cand;
-#endif
             if (!xm) {
                 const double dmn = __longlong_as_double((long long)fmn), dmx = __longlong_as_double((long long)fmx);
                 const double mid = dmn + (dmx - dmn) * frac;
@@ -1171,7 +1074,7 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
     DBG_COUNT(M, 20, 1);
     DBG_COUNT(M, 23, take_n);
     RT_MARK(41);  // select + gather
-    if (r_sort(R, lane, (int)(r0 + take_n), try_fast_sort, fmin_all)) DBG_COUNT(M, 22, 1);
+    r_sort(R, lane, (int)(r0 + take_n));
     RT_MARK(42);  // sort
     // ---- close the gaps (entries move down only, onto slots already read)
     uint32_t mw = 0;
@@ -1254,29 +1157,20 @@ __device__ __forceinline__ void r_merge(OpenList& Q, RTier& R, int lane, int dro
 // The open list after a batch: the first `drop` entries of R (the committed nodes) leave, and the entries held by the
 // lanes with `w` (key (kf, kx), payload ks, kc) go into R when below the R / M threshold, into M when below the
 // M / far threshold, else into the far tier.  jps1.py:227-228 for a whole batch.
-template <bool BANDED, bool COOP = false>
+template <bool BANDED>
 __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
                                             int lane, int lane_c, int drop, bool w, uint64_t kf, uint32_t kx, uint32_t ks,
-                                            uint32_t kc PF_PARAMS, Coop* C = nullptr) {  // lane_c: the lane number again, for the rarely taken paths
+                                            uint32_t kc PF_PARAMS) {  // lane_c: the lane number again, for the rarely taken paths
     PF(2);
     uint16_t* fci = far_ci(far, A.far_cap);
     bool toR;
     uint64_t rm;
-    // (a cooperative block whose stager owns M right now: nothing of M is touched -- no split of R into it, no split of M,
-    // no append.  What would go to M waits in the late list; if R itself has no room, so does what would go to R: the
-    // searching wavefront takes the staged block and re-inserts the late list before it pops again.)
-    const bool held = COOP && rfl(C->pending) != 0u;
     for (;;) {  // make room in R by splitting it
         open_uniform(Q);
         drop = rfli(drop);
         toR = w && key_lt(kf, kx, Q.Rbits, Q.Rx);
         rm = __ballot(toR);
         if (FX_USUAL(Q.r_n - drop + __popcll(rm) <= WAVE)) break;
-        if (held) {
-            toR = false;
-            rm = 0ull;
-            break;
-        }
         if (drop > 0) {  // (rare: take the committed nodes out first, then halve what is left)
             r_merge(Q, R, lane_c, drop, false, 0ull, 0ull, 0u, 0u, 0u);
             drop = 0;
@@ -1289,7 +1183,6 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
         open_uniform(Q);
         toM = w && !toR && key_lt(kf, kx, Q.Tbits, Q.Tx);
         mm = __ballot(toM);
-        if (held) break;
         if (FX_USUAL(Q.m_n + (uint32_t)__popcll(mm) <= (uint32_t)MCAP)) break;
         if (!m_split(Q, M, far, fci, lane_c, A.far_cap)) return false;
     }
@@ -1303,117 +1196,17 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
     if (rm != 0ull || drop > 0) r_merge(Q, R, lane, drop, toR, rm, kf, kx, ks, kc);
     PF(13);
     if (mm != 0ull) {
-        if (held) {
-            if (toM) {
-                const uint32_t j = C->late_n + rank_below(mm);
-                M.co->lf[j] = kf;
-                M.co->lx[j] = kx;
-                M.co->ls[j] = ks;
-                M.co->lc[j] = (uint16_t)kc;
-            }
-            RECONV();
-            C->late_n += (uint32_t)__popcll(mm);
-        } else {
-            if (toM) {
-                const uint32_t j = Q.m_n + rank_below(mm);
-                M.w->f[j] = kf;
-                M.w->x[j] = kx;
-                M.w->s[j] = ks;
-                M.w->c[j] = (uint16_t)kc;
-            }
-            RECONV();
-            Q.m_n += (uint32_t)__popcll(mm);
+        if (toM) {
+            const uint32_t j = Q.m_n + rank_below(mm);
+            M.w->f[j] = kf;
+            M.w->x[j] = kx;
+            M.w->s[j] = ks;
+            M.w->c[j] = (uint16_t)kc;
         }
+        RECONV();
+        Q.m_n += (uint32_t)__popcll(mm);
     }
     PF(14);
-    return true;
-}
-
-// ---- the searching wavefront's side of a cooperative block (see CoopLds)
-__device__ __forceinline__ void coop_wait(const Mid& M, const Coop& C) {  // until the stager has answered the request that is out
-    while (rfl(__hip_atomic_load(&M.co->rdy_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != C.seq) __builtin_amdgcn_s_sleep(1);
-}
-// Ask for the next block of R: the stager gets M as it is (m_n entries), the thresholds, and the room R has.
-__device__ __forceinline__ void coop_request(const OpenList& Q, const Mid& M, Coop& C, int lane) {
-    C.seq = rfl(C.seq + 1u);
-    if (lane == 0) {
-        M.co->req_m_n = Q.m_n;
-        M.co->req_room = (uint32_t)(WAVE - Q.r_n);
-        M.co->req_Tbits = Q.Tbits;
-        M.co->req_Tx = Q.Tx;
-        M.co->req_Rbits = Q.Rbits;
-        M.co->req_Rx = Q.Rx;
-        __hip_atomic_store(&M.co->req_seq, C.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    RECONV();
-    C.pending = 1u;
-    C.late_n = 0u;
-}
-// The staged block goes behind the entries R still holds (its keys are at or above the old R / M threshold, every R key
-// below it); what does not fit goes back to M, which is the searching wavefront's again; the late list goes through the
-// ordinary insertion.
-template <bool BANDED>
-__device__ __forceinline__ bool coop_take(const SearchArgs& A, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far, Coop& C,
-                                          int lane, int lane_c PF_PARAMS) {
-#ifdef FXJPS_HWID
-    const unsigned long long cw0_ = __builtin_readcyclecounter();
-#endif
-    coop_wait(M, C);
-#ifdef FXJPS_HWID
-    if (A.out_counters && lane == 0) {
-        atomicAdd(&A.out_counters[42], __builtin_readcyclecounter() - cw0_);
-        atomicAdd(&A.out_counters[43], 1ull);
-        atomicAdd(&A.out_counters[45], (unsigned long long)C.late_n);
-        atomicAdd(&A.out_counters[46], (unsigned long long)M.co->rep_take);
-    }
-    RECONV();
-#endif
-    open_uniform(Q);
-    const uint32_t take_n = rfl(M.co->rep_take);
-    Q.m_n = rfl(M.co->rep_m_n);
-    Q.Rbits = rfl64(M.co->rep_Rbits);
-    Q.Rx = rfl(M.co->rep_Rx);
-    const uint32_t r0 = (uint32_t)Q.r_n;
-    const uint32_t k = min(take_n, (uint32_t)WAVE - r0);
-    if ((uint32_t)lane >= r0 && (uint32_t)lane < r0 + k) {
-        const uint32_t j = (uint32_t)lane - r0;
-        R.f = M.co->bf[j];
-        R.x = M.co->bx[j];
-        R.s = M.co->bs[j];
-        R.c = M.co->bc[j];
-    }
-    RECONV();
-    Q.r_n = (int)(r0 + k);
-    if (FX_RARE(k < take_n)) {  // (R had less room than it said: the rest of the block is M's again, and the first key of it the threshold)
-        Q.Rbits = rfl64(M.co->bf[k]);
-        Q.Rx = rfl(M.co->bx[k]);
-        const uint32_t j = k + (uint32_t)lane;
-        if (j < take_n) {
-            const uint32_t d = Q.m_n + (uint32_t)lane;  // (M gave these entries: it has room for them)
-            M.w->f[d] = M.co->bf[j];
-            M.w->x[d] = M.co->bx[j];
-            M.w->s[d] = M.co->bs[j];
-            M.w->c[d] = M.co->bc[j];
-        }
-        RECONV();
-        Q.m_n += take_n - k;
-    }
-    C.pending = 0u;
-    const uint32_t ln = rfl(C.late_n);
-    C.late_n = 0u;
-    if (ln != 0u) {
-        const bool w = (uint32_t)lane < ln;
-        uint64_t kf = 0ull;
-        uint32_t kx = 0u, ks = 0u, kc = 0u;
-        if (w) {
-            kf = M.co->lf[lane];
-            kx = M.co->lx[lane];
-            ks = M.co->ls[lane];
-            kc = M.co->lc[lane];
-        }
-        RECONV();
-        return open_insert<BANDED, false>(A, Q, R, M, far, lane, lane_c, 0, w, kf, kx, ks, kc PF_ARGS);
-    }
     return true;
 }
 
@@ -1428,7 +1221,7 @@ __device__ __forceinline__ bool coop_take(const SearchArgs& A, OpenList& Q, RTie
 // the open list is empty.
 template <bool BANDED, bool NOCI = false>  // NOCI: nobody reads the entries' cell info (rays on the jump-distance records)
 __device__ __forceinline__ bool open_fill(const SearchArgs& A, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
-                                          int lane, bool try_fast_sort) {
+                                          int lane) {
     uint16_t* fci = far_ci(far, A.far_cap);
     bool topped = false;
     for (;;) {
@@ -1438,14 +1231,10 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, OpenList& Q, RTie
         if (FX_USUAL(Q.r_n >= RLOW || (Q.r_n > 0 && (Q.m_n == 0 || topped)))) return true;
         if (FX_USUAL(Q.m_n > 0)) {
             topped = true;
-#ifdef FXJPS_HWID
-            if (A.out_counters && lane == 0) atomicAdd(&A.out_counters[44], 1ull);
-            RECONV();
-#endif
 #ifdef FXJPS_PROF
             const unsigned long long t0_ = __builtin_readcyclecounter();
 #endif
-            r_refill(Q, R, M, lane, try_fast_sort);
+            r_refill(Q, R, M, lane);
 #ifdef FXJPS_PROF
             DBG_COUNT(M, 28, __builtin_readcyclecounter() - t0_);
             DBG_COUNT(M, 29, 1);
@@ -2039,27 +1828,6 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, OpenList& Q, RTie
 #ifndef FXJPS_KN
 #define FXJPS_KN 16
 #endif
-#ifndef FXJPS_PTR_SGPR
-#define FXJPS_PTR_SGPR 0  // 1: the map and table pointers stay scalar (measurement build for five wavefronts per SIMD)
-#endif
-#ifndef FXJPS_R2_REC
-#define FXJPS_R2_REC 1  // second round on cell-indexed tables: the whole jump-distance record of s, requested beside the direction lookup (round 6: query 9206 alone 59.4 -> 59.1 ms, c4shard + 1.5 %)
-#endif
-#ifndef FXJPS_RFILL_F32
-#define FXJPS_RFILL_F32 0  // R refill: the fraction its threshold aims at in single precision
-#endif
-#ifndef FXJPS_ONE_INSERT
-#define FXJPS_ONE_INSERT 1  // cell-indexed tables: one call site of open_insert instead of three inlined copies (round 6: c2 + 1.8 %; on
-                            // the hashed-table instantiation the same change costs config 3 1.6 - 2.4 %: not taken there)
-#endif
-#ifndef FXJPS_R2_HASH
-#define FXJPS_R2_HASH 1  // second round: a hash sieve in front of the loop over the cells s could have touched (round 6: query 9206 alone 61.9 -> 59.6 ms)
-#endif
-#ifndef FXJPS_COOP_REQ_LOW
-#define FXJPS_COOP_REQ_LOW 24
-#endif
-constexpr int COOP_REQ_LOW = FXJPS_COOP_REQ_LOW;  // cooperative block: the next block of R is asked for when R holds this many entries or fewer
-constexpr int COOP_REQ_MIN_M = 8;                 // ... and M at least this many
 constexpr int KN = FXJPS_KN;        // nodes per batch, at most: the lanes of the first one or two DPP rows of R
 static_assert(KN >= 1 && KN <= 32, "the lane allotment scans two 16-lane rows");
 constexpr int SL = 1;               // lanes per ray (round 1 spread a ray over up to four)
@@ -2274,15 +2042,14 @@ __device__ __forceinline__ void expand_batch(const GridDev& G, uint32_t r0, uint
 
 // The whole of jps1.method (jps1.py:183-230) for one query on one wavefront.
 // Returns the result code; *res_cost is gscore[goal].
-template <int HC, bool TRK, bool DIRECT, bool COOP = false>
+template <int HC, bool TRK, bool DIRECT>
 __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_t q, const int sx, const int sy, const int gx,
                               const int gy, const Mid& S, TEnt* __restrict__ tab, FarEnt* __restrict__ far,
-                              const uint32_t gen, double* res_cost, unsigned long long* cnt4, Coop* C = nullptr) {
+                              const uint32_t gen, double* res_cost, unsigned long long* cnt4) {
     // The map pointers, the table pointer and the scan-line stride are used in per-lane address arithmetic only, a
     // dozen times per iteration.  Held in SGPRs they were spilled (the kernel runs at the scalar-register limit) and
     // re-read with v_readlane before every use; kept in vector registers on purpose they are plain operands.
     GridDev G = A.G;
-#if !FXJPS_PTR_SGPR
     {
         uint64_t vbm = (uint64_t)G.bm, vci = (uint64_t)G.ci, vtab = (uint64_t)tab, vjd = (uint64_t)G.jd;
         int vwords = G.WORDS;
@@ -2295,7 +2062,6 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         G.WORDS = vwords;
         tab = (TEnt*)reinterpret_cast<__attribute__((address_space(1))) TEnt*>(vtab);
     }
-#endif
     const int lane0 = threadIdx.x & 63;
     // On hashed tables (grids of more than 2^20 cells: every read is an HBM request, and requests are what the chip runs out
     // of) the node's lane reads the whole jump-distance record at the lane deal -- the neighbour byte comes with it, no cell
@@ -2390,18 +2156,9 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         PF(9);
         // (the refill code gets the plain lane number: what it derives from it is loop-invariant and stays in VGPRs
         // instead of being recomputed at every loop head)
-        if (COOP && rfl(C->pending) != 0u) {  // the block asked for during the last iteration: into R, before anything is popped
-            if (!coop_take<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0>(A, Q, R, S, far, *C, lane0, lane0 PF_ARGS)) {
-                res_len = (uint32_t)QI_FAR_FULL;
-                break;
-            }
-            COLD_SYNC();
-        }
         // (the read-set instantiations on hashed tables have no registers to spare for those: there the values are
         // derived again where they are used -- held, two of them went to scratch)
-        if (!open_fill<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, JD2>(A, Q, R, S, far, (TRK && !DIRECT) ? lane : lane0, true)) break;  // (0, t): jps1.py:230
-        // R is running low and M has entries: the stager prepares the next block while this iteration runs
-        if (COOP && Q.r_n <= COOP_REQ_LOW && Q.m_n >= (uint32_t)COOP_REQ_MIN_M) coop_request(Q, S, *C, lane0);
+        if (!open_fill<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, JD2>(A, Q, R, S, far, (TRK && !DIRECT) ? lane : lane0)) break;  // (0, t): jps1.py:230
         if (FX_RARE(Q.fail != 0u)) {  // a region of the far band's ring is full: the large pool takes the query
             res_len = (uint32_t)QI_FAR_FULL;
             break;
@@ -2537,8 +2294,8 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         bool done_fast = false;
         // ONE call site of open_insert for the vectorised commit and the two exits of the general form that insert (its code
         // -- R and M splits inlined -- is 1 250 instructions; three copies of it were 15 KB of the kernel's 61).  On the
-        // cell-indexed tables only: the same on hashed tables costs config 3 1.6 - 2.4 % (A/B of round 6).
-        constexpr bool ONE_INS = FXJPS_ONE_INSERT != 0 && DIRECT;
+        // cell-indexed tables only (round 6: c2 + 1.8 %): the same on hashed tables costs config 3 1.6 - 2.4 %.
+        constexpr bool ONE_INS = DIRECT;
         bool xi_do = false, xi_w = false;
         int xi_drop = 0;
         uint64_t xi_f = 0ull;
@@ -2795,25 +2552,18 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
 #endif
                             // ---- expand s on the idle lanes nlanes .. nlanes + 7 (jps1.py:166-179)
                             on2 = lane >= nlanes && lane < nlanes + 8;
-                            uint32_t rs0 = 0u, rs1 = 0u, rs2 = 0u, rs3 = 0u;  // s's jump-distance record (every lane reads the same one)
-                            uint32_t s_nb = s_ci & 0xFFu;
-                            // (cell-indexed tables, FXJPS_R2_REC: s's whole record -- one address for all lanes -- is requested
-                            // here, beside the LDS lookup of its directions, instead of one u16 per lane behind it)
-                            constexpr bool S_REC = JD2 || FXJPS_R2_REC != 0;
-                            if (S_REC) {
-                                const uint4 t4 = *reinterpret_cast<const uint4*>(G.jd + (size_t)(__umul24((uint32_t)(sx2 + 1), (uint32_t)G.NS) + (uint32_t)(sy2 + 1)) * 8u);
-                                rs0 = t4.x;
-                                rs1 = t4.y;
-                                rs2 = t4.z;
-                                rs3 = t4.w;
-                                if (JD2) s_nb = jd_nb8(rs0, rs1);
-                            }
+                            // s's jump-distance record (every lane reads the same one): the whole of it -- one address for all
+                            // lanes -- is requested here, beside the LDS lookup of its directions, instead of one u16 per lane
+                            // behind it (round 6: query 9206 alone 59.4 -> 59.1 ms, c4shard + 1.5 %)
+                            const uint4 t4 = *reinterpret_cast<const uint4*>(G.jd + (size_t)(__umul24((uint32_t)(sx2 + 1), (uint32_t)G.NS) + (uint32_t)(sy2 + 1)) * 8u);
+                            const uint32_t rs0 = t4.x, rs1 = t4.y, rs2 = t4.z, rs3 = t4.w;
+                            const uint32_t s_nb = JD2 ? jd_nb8(rs0, rs1) : s_ci & 0xFFu;
                             const uint32_t codes2 = S.dirlut[s_code * 256u + s_nb];
                             code2 = on2 ? ((codes2 >> (4u * (uint32_t)(lane - nlanes))) & 0xFu) : DIR_NONE;
                             bool has2;
                             uint32_t jci2;
                             int kres2 = 0;
-                            expand_batch<S_REC>(G, rs0, rs1, rs2, rs3, sx2 + 1, sy2 + 1, code2, on2, gpx, gpy, &has2, &cellj2, &jci2, tab, 0u, nullptr, TRK ? &kres2 : nullptr PF_ARGS);
+                            expand_batch<true>(G, rs0, rs1, rs2, rs3, sx2 + 1, sy2 + 1, code2, on2, gpx, gpy, &has2, &cellj2, &jci2, tab, 0u, nullptr, TRK ? &kres2 : nullptr PF_ARGS);
                             has2 = has2 && on2;
                             const int jx2 = (int)(cellj2 >> 13), jy2 = (int)(cellj2 & 0x1FFFu);
                             const uint32_t b2 = probe_at(cellj2);
@@ -2834,7 +2584,6 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
                                 const bool oldray = node_on && has && mynode >= nvalid;       // the rays of the former
                                 const uint32_t rcell2 = R.x >> 4;
                                 uint64_t cm2 = __ballot(has2) | (1ull << 63);                 // s's successors, and (bit 63) s itself
-#if FXJPS_R2_HASH
                                 // Mostly none of these cells is a node or a successor of this batch, and the loop below -- a
                                 // trip of ~ 55 instructions per cell -- finds nothing.  So first a sieve through the (idle)
                                 // collision detector: s and its successors leave a mark at the hash of their cell, every lane
@@ -2859,7 +2608,6 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
                                     if (__ballot(hit_n || hit_r) == 0ull) cm2 = 0ull;
                                     DBG_COUNT(S, 57, cm2 != 0ull ? 1 : 0);
                                 }
-#endif
                                 DBG_COUNT(S, 48, __popcll(cm2));
                                 while (cm2 != 0ull) {
                                     const int src = (int)__builtin_ctzll(cm2);
@@ -3004,7 +2752,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
                         xi_x = ins_x;
                         xi_s = ins_s;
                         xi_c = ins_c;
-                    } else if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, COOP>(A, Q, R, S, far, lane, lane0, ndrop, w_ins, ins_f, ins_x, ins_s, ins_c PF_ARGS, C)) {
+                    } else if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0>(A, Q, R, S, far, lane, lane0, ndrop, w_ins, ins_f, ins_x, ins_s, ins_c PF_ARGS)) {
                         res_len = (uint32_t)QI_FAR_FULL;
                     }
                 }
@@ -3086,7 +2834,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
                     xi_drop = 1;
                     xi_w = false;
                 } else {
-                    (void)open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, COOP>(A, Q, R, S, far, lane, lane0, 1, false, 0ull, 0u, 0u, 0u PF_ARGS, C);
+                    (void)open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0>(A, Q, R, S, far, lane, lane0, 1, false, 0ull, 0u, 0u, 0u PF_ARGS);
                 }
                 GEN_NEXT;
             }
@@ -3215,7 +2963,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
                 xi_x = (ncellj << 4) | ncode;
                 xi_s = jslot;
                 xi_c = nneed_ci ? nlci : njci;
-            } else if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, COOP>(A, Q, R, S, far, lane, lane0, 1, pl, fb, (ncellj << 4) | ncode, jslot, nneed_ci ? nlci : njci PF_ARGS, C)) {
+            } else if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0>(A, Q, R, S, far, lane, lane0, 1, pl, fb, (ncellj << 4) | ncode, jslot, nneed_ci ? nlci : njci PF_ARGS)) {
                 res_len = (uint32_t)QI_FAR_FULL;
                 GEN_NEXT;
             }
@@ -3223,7 +2971,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         }
         } while (0);
         if (ONE_INS && xi_do) {
-            if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, COOP>(A, Q, R, S, far, lane, lane0, xi_drop, xi_w, xi_f, xi_x, xi_s, xi_c PF_ARGS, C)) {
+            if (!open_insert<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0>(A, Q, R, S, far, lane, lane0, xi_drop, xi_w, xi_f, xi_x, xi_s, xi_c PF_ARGS)) {
                 res_len = (uint32_t)QI_FAR_FULL;
             }
         }
@@ -3231,11 +2979,6 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         if (!FX_USUAL(done_fast)) COLD_SYNC();  // (see GEN_NEXT)
     }
     PF_FLUSH;
-    if (COOP && rfl(C->pending) != 0u) {  // the stager still works on M: the next query must not find it busy
-        coop_wait(S, *C);
-        C->pending = 0u;
-        C->late_n = 0u;
-    }
 
     if (A.qstat && lane0 == 0) A.qstat[4 * (size_t)q + 2] = (unsigned long long)pops;
     if (cnt4 && lane0 == 0) {
@@ -3250,9 +2993,9 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
     return (int32_t)rfl(res_len);
 }
 
-template <int HC, bool TRK, bool DIRECT, bool COOP = false>
+template <int HC, bool TRK, bool DIRECT>
 __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q, const Mid& S, TEnt* __restrict__ tab,
-                          FarEnt* __restrict__ far, uint32_t& gen, Coop* C = nullptr) {
+                          FarEnt* __restrict__ far, uint32_t& gen) {
     const GridDev& G = A.G;
     const int lane = threadIdx.x & 63;
     const bool imm = A.single != 0u;
@@ -3303,7 +3046,7 @@ __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q,
             A.qstat[4 * (size_t)q + 3] = (unsigned long long)(tab - A.tables) / ((size_t)BUCKET * A.nbuckets);
         }
         RECONV();
-        res_len = search_one<HC, TRK, DIRECT, COOP>(A, q, sx, sy, gx, gy, S, tab, far, gen, &res_cost, A.out_counters, C);
+        res_len = search_one<HC, TRK, DIRECT>(A, q, sx, sy, gx, gy, S, tab, far, gen, &res_cost, A.out_counters);
         if (TRK) {  // hand the read set over (one row of each bitmap per lane) and clear it for the next query
             unsigned long long* dst = A.qread + (size_t)q * 128;
             dst[lane] = S.bx[lane];
@@ -3342,19 +3085,6 @@ __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
     __shared__ WaveLds s_w[WPB];             // per wavefront: the M tier, transfer indices, collision detector
     __shared__ uint32_t s_dirlut[11 * 256];  // nodeNeighbours table: LDS latency instead of an L2 round trip per batch
     __shared__ unsigned long long s_rs[TRK ? WPB : 1][TRK ? 128 : 1];  // read-set bitmaps (tracking instantiation only)
-#if FXJPS_XCC
-    __shared__ uint32_t s_slot;
-#endif
-    uint32_t bslot = blockIdx.x;  // this block's scratch slot
-#if FXJPS_XCC  // (measurement build only: these few lines cost k_search<2, false, true> 12 VGPRs and put the hashed instantiations into scratch)
-    if (A.xcc_only != 0u) {       // (wave-uniform, and the same for every wavefront of the block)
-        if (((A.xcc_only >> xcc_id()) & 1u) == 0u) return;
-        if (threadIdx.x == 0) s_slot = atomicAdd(A.slot_ctr, 1u);
-        __syncthreads();
-        bslot = s_slot;
-        if (bslot >= A.max_blocks) return;
-    }
-#endif
     if (TRK)
         for (int i = threadIdx.x; i < WPB * 128; i += WAVE * WPB) (&s_rs[0][0])[i] = 0ull;
     for (int i = threadIdx.x; i < 11 * 256; i += WAVE * WPB) s_dirlut[i] = c_dirlut[i];
@@ -3366,12 +3096,11 @@ __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
         if ((uint32_t)wib >= A.solo) return;  // (behind the barrier)
         if (A.started != nullptr && wib == 0 && lane == 0) __hip_atomic_fetch_add(A.started, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    const size_t wave = A.solo != 0u ? (size_t)A.wave_base + (size_t)bslot * A.solo + wib : (size_t)bslot * WPB + wib;
+    const size_t wave = A.solo != 0u ? (size_t)A.wave_base + (size_t)blockIdx.x * A.solo + wib : (size_t)blockIdx.x * WPB + wib;
     TEnt* tab = A.tables + wave * ((size_t)BUCKET * A.nbuckets);
     FarEnt* far = A.far + wave * (size_t)(A.far_cap + A.far_cap / 8);  // entries + their u16 cell info
     Mid S;
     S.w = (LDS_PTR(WaveLds))&s_w[wib];
-    S.co = nullptr;
     S.dirlut = (LDS_PTR(const uint32_t))s_dirlut;
     S.bx = (LDS_PTR(unsigned long long))s_rs[TRK ? wib : 0];
 #ifdef FXJPS_PROF
@@ -3411,117 +3140,6 @@ __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
 #else
         A.host_counters[lane] = lane == 62 ? t_begin : lane == 63 ? wall_clock64() : lane == 60 ? c_begin : lane == 61 ? __builtin_readcyclecounter() : v;
 #endif
-    }
-}
-
-// One query per BLOCK (round 4; north_star: "one query per block ... block-local LDS-resident priority queue"): two
-// wavefronts on two SIMDs of a CU.  Wavefront 0 is the search of k_search<HC, false, true> (tables indexed by the cell, no
-// read sets); wavefront 1, the stager, serves its requests for the next sorted block of the register tier out of the LDS
-// tier (see CoopLds) until the block runs out of queries.  Used for what a handful of long queries decide: the head of a
-// batch's longest-first order, small batches (the frames of config 5), single calls.
-__device__ __forceinline__ void coop_stager(const Mid& S) {
-    const int lane = threadIdx.x & 63;
-    uint32_t seen = 0;
-    for (;;) {
-        uint32_t rs, quit;
-        for (;;) {
-            rs = rfl(__hip_atomic_load(&S.co->req_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-            quit = rfl(__hip_atomic_load(&S.co->quit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-            if (rs != seen || quit != 0u) break;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (rs == seen) break;  // (quit, and nothing left to answer)
-        seen = rs;
-        OpenList Q;
-        Q.r_n = 0;
-        Q.m_n = rfl(S.co->req_m_n);
-        Q.far_n = 0;
-        Q.farb_n = 0;
-        Q.T2hi = INF_HI;
-        Q.Rbits = rfl64(S.co->req_Rbits);
-        Q.Rx = rfl(S.co->req_Rx);
-        Q.Tbits = rfl64(S.co->req_Tbits);
-        Q.Tx = rfl(S.co->req_Tx);
-        Q.dxs = 0;
-        Q.delta = 1.0;
-        Q.hshift = 0;
-        Q.cur0 = 0;
-        Q.fail = 0;
-        Q.banded = 0;
-        const uint32_t room = rfl(S.co->req_room);
-        RTier R;
-        R.f = ~0ull;
-        R.x = ~0u;
-        R.s = 0u;
-        R.c = 0u;
-        r_refill(Q, R, S, lane, true, room);  // M's smallest entries, sorted, in lanes 0 .. r_n - 1; the gaps in M closed
-        if (lane < Q.r_n) {
-            S.co->bf[lane] = R.f;
-            S.co->bx[lane] = R.x;
-            S.co->bs[lane] = R.s;
-            S.co->bc[lane] = (uint16_t)R.c;
-        }
-        RECONV();
-        if (lane == 0) {
-            S.co->rep_take = (uint32_t)Q.r_n;
-            S.co->rep_m_n = Q.m_n;
-            S.co->rep_Rbits = Q.Rbits;
-            S.co->rep_Rx = Q.Rx;
-        }
-        RECONV();
-        // (every lane's LDS writes are in program order in front of this store: one wavefront, one LDS queue)
-        __hip_atomic_store(&S.co->rdy_seq, seen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-
-template <int HC>
-__global__ __launch_bounds__(WAVE * 2, OCC) void k_search_coop(SearchArgs A) {
-    __shared__ WaveLds s_w[1];
-    __shared__ CoopLds s_c;
-    __shared__ uint32_t s_dirlut[11 * 256];
-    for (int i = threadIdx.x; i < 11 * 256; i += WAVE * 2) s_dirlut[i] = c_dirlut[i];
-    for (int i = threadIdx.x; i < HZ_SIZE; i += WAVE * 2) s_w[0].hz[i] = ~0u;
-    if (threadIdx.x == 0) {
-        s_c.req_seq = 0u;
-        s_c.rdy_seq = 0u;
-        s_c.quit = 0u;
-    }
-    __syncthreads();  // the only block-wide barrier
-    const int lane = threadIdx.x & 63;
-    const int wib = rfli((int)(threadIdx.x >> 6));
-    Mid S;
-    S.w = (LDS_PTR(WaveLds))&s_w[0];
-    S.co = (LDS_PTR(CoopLds))&s_c;
-    S.dirlut = (LDS_PTR(const uint32_t))s_dirlut;
-    S.bx = nullptr;
-#ifdef FXJPS_PROF
-    S.dbg = A.out_counters;
-#endif
-#ifdef FXJPS_HWID  // diagnostics: which SIMD / CU the two wavefronts of the first block run on (HW_REG_HW_ID: simd 5:4, cu 11:8)
-    if (A.out_counters && blockIdx.x == 0 && lane == 0) A.out_counters[40 + wib] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-#endif
-    if (wib != 0) {
-        coop_stager(S);
-        return;
-    }
-    if (A.started != nullptr && lane == 0) __hip_atomic_fetch_add(A.started, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    const size_t wave = (size_t)A.wave_base + (size_t)blockIdx.x;  // one scratch slot per block
-    TEnt* tab = A.tables + wave * ((size_t)BUCKET * A.nbuckets);
-    FarEnt* far = A.far + wave * (size_t)(A.far_cap + A.far_cap / 8);
-    uint32_t gen = rfl(A.wave_gen[wave]);
-    Coop C;
-    C.pending = 0u;
-    C.seq = 0u;
-    C.late_n = 0u;
-    for (;;) {
-        const uint32_t qi = rfl(atomicAdd(A.next, lane == 0 ? 1u : 0u));
-        if (qi >= A.nrun) break;
-        const uint32_t q = A.order ? rfl(A.order[qi + A.q0]) : qi + A.q0;
-        run_query<HC, false, true, true>(A, q, S, tab, far, gen, &C);
-    }
-    if (lane == 0) {
-        A.wave_gen[wave] = gen;
-        __hip_atomic_store(&S.co->quit, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
 
@@ -3566,7 +3184,6 @@ __global__ __launch_bounds__(WAVE) void k_selftest_openlist(SearchArgs A, const 
     __syncthreads();
     Mid S;
     S.w = (LDS_PTR(WaveLds))&s_w[0];
-    S.co = nullptr;
     S.dirlut = nullptr;
     S.bx = nullptr;
 #ifdef FXJPS_PROF
@@ -3600,7 +3217,7 @@ __global__ __launch_bounds__(WAVE) void k_selftest_openlist(SearchArgs A, const 
     for (uint32_t st = 0; fail == 0u; st++) {
         open_uniform(Q);
         const bool scripted = st < nsteps;
-        const bool any = open_fill<BANDED>(A, Q, R, S, far, lane, true);
+        const bool any = open_fill<BANDED>(A, Q, R, S, far, lane);
         if (Q.fail != 0u) {
             fail = 2u;
             break;

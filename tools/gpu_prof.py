@@ -46,7 +46,7 @@ for nq in nqs:
     if c[4] and c[18]:
         print("   diagonal rounds %.2f / batch, rays in flight %.1f / round" % (c[18] / c[4], c[19] / c[18]), flush=True)
     if c[4] and c[20]:
-        print("   R refills: one per %.1f batches, %.1f entries each, %.2f aiming rounds each, exact sort in %.1f %%" % (c[4] / c[20], c[23] / c[20], c[21] / c[20], 100.0 * c[22] / c[20]), flush=True)
+        print("   R refills: one per %.1f batches, %.1f entries each, %.2f aiming rounds each" % (c[4] / c[20], c[23] / c[20], c[21] / c[20]), flush=True)
     if c[4]:
         if c[29]: print("   R refill: %.0f cycles each (%d of them): read M + threshold %.0f, select + gather %.0f, sort %.0f, compaction %.0f" % (
             c[28] / c[29], c[29], c[40] / c[29], c[41] / c[29], c[42] / c[29], (c[28] - c[40] - c[41] - c[42]) / c[29]), flush=True)

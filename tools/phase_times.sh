@@ -12,7 +12,7 @@ if [ "$MODE" = build ]; then
   done; wait; ls fuxi-planner_amd/libfxjps_ph_*.so
 else
   for iv in $IV; do s=${iv%%:*}; e=${iv#*:}
-    FXJPS_COOP=0 FXJPS_LIB=$PWD/fuxi-planner_amd/libfxjps_ph_${s}_${e}.so python3 - $s $e $Q <<'PY'
+    FXJPS_LIB=$PWD/fuxi-planner_amd/libfxjps_ph_${s}_${e}.so python3 - $s $e $Q <<'PY'
 import ctypes as C, os, sys
 sys.path.insert(0, os.getcwd())
 import fuxi_planner_amd as fx
