@@ -140,7 +140,26 @@ struct ScratchCfg {
     uint32_t far_cap = 0;
 };
 
-struct DevCtx {
+// A grid on one device and its derived maps: the handle's resident grid (DevCtx derives from it) or a grid slot.
+struct GridBufs {
+    int W = 0, H = 0, PW = 0, PH = 0, NS = 0, LINES = 0, WORDS = 0, tsh = 0;
+    DBuf<uint8_t> occ, nb8;
+    DBuf<fx::BmWord> bm;
+    DBuf<int> comp;
+    DBuf<uint16_t> ci;
+    DBuf<uint16_t> jd;  // jump distances [PW][NS][8] (k_derive_jd)
+    void release() {
+        occ.release();
+        comp.release();
+        nb8.release();
+        ci.release();
+        jd.release();
+        bm.release();
+        W = H = 0;
+    }
+};
+
+struct DevCtx : GridBufs {
     int dev = -1;
     int n_cu = 256;
     int share = 1;  // contexts of this handle on the same physical device (they split its memory and wavefront slots)
@@ -153,23 +172,30 @@ struct DevCtx {
     int solo_timeouts_run = 0;          // ... in a row (3: no more head launches on this device; a cold first launch of a
                                         // kernel -- its code object is loaded then -- is a lone timeout and means nothing)
     size_t cells_bound = 0;             // bytes the batch in progress may still allocate for its packed paths
-    bool lds_attr_done[8] = {};         // k_search instantiations whose dynamic-LDS limit has been raised on this device
+    bool lds_attr_done[12] = {};        // k_search instantiations whose dynamic-LDS limit has been raised on this device
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_solo0 = nullptr, ev_solo1 = nullptr;
     hipEvent_t ev_hd0 = nullptr, ev_hd1 = nullptr, ev_bt0 = nullptr, ev_bt1 = nullptr;  // around the head launch / the batch's launch alone
     bool had_solo = false;              // the last regular-pool launch was two launches
     double head_ms = 0, batch_ms = 0;   // ... and how long each of them ran
-    // grid
-    int W = 0, H = 0, PW = 0, PH = 0, NS = 0, LINES = 0, WORDS = 0, tsh = 0;
-    DBuf<uint8_t> occ, nb8;
-    DBuf<fx::BmWord> bm;
-    DBuf<int> comp;
-    DBuf<uint16_t> ci;
-    DBuf<uint16_t> jd;  // jump distances [PW][NS][8] (k_derive_jd)
+    // grid slots (fxjps_set_grid_slot): their maps, and their descriptors on the device (what k_search<.., .., .., true> reads)
+    std::vector<GridBufs> slots;  // [FXJPS_MAX_GRID_SLOTS] once the first slot is set; W == 0: empty
+    std::vector<GridDev> h_slot_desc;
+    DBuf<GridDev> d_slot_desc;
+    DBuf<int32_t> d_grid_ids;
+    // a slots batch in progress: its grid ids (the caller's array) and the largest extents of the slots it names, which
+    // size the scratch, the watchdog and the far band's form in place of the resident grid's
+    const int32_t* mg_ids = nullptr;
+    int mg_W = 0, mg_H = 0;
+    uint64_t mg_cells = 0;
+    int plan_W() const { return mg_ids ? mg_W : W; }
+    int plan_H() const { return mg_ids ? mg_H : H; }
+    uint64_t plan_cells() const { return mg_ids ? mg_cells : (uint64_t)W * H; }
     // search scratch (two pools: the regular one and the large retry one)
     DBuf<TEnt> tables[2];
     DBuf<FarEnt> far[2];
     DBuf<uint32_t> wave_gen[2];
     ScratchCfg cfg[2];
+    int cfg_W = 0, cfg_H = 0;  // the batch extents (plan_W / plan_H) pool 0 was last configured for
     bool pool_clean[2] = {false, false};
     // batch buffers
     DBuf<int32_t> d_starts, d_goals, d_len, d_cells;
@@ -244,6 +270,8 @@ struct fxjps {
     fxjps_timing_t timing{};
     int64_t last_nq = 0;
     bool last_on_host = false;  // the last batch was a single call: its CSR is in the pinned host buffers only
+    bool last_slots = false;    // the last batch ran on grid slots: its paths are not the resident grid's ...
+    int last_slots_W = 0, last_slots_H = 0;  // ... they lie within these extents (the largest of the slots it named)
     // persistent query set of the streaming-replan entry points (fxjps_set_queries / fxjps_replan_frame)
     std::vector<int32_t> q_starts, q_goals;
     int q_hchoice = 0, q_max_len = 0;
@@ -326,7 +354,7 @@ uint32_t dirlut_entry(uint32_t pd, uint32_t nbm) {
     return v;
 }
 
-GridDev grid_of(const DevCtx& d) {
+GridDev grid_of(const GridBufs& d) {
     GridDev G;
     G.bm = d.bm.p;
     G.ci = d.ci.p;
@@ -349,39 +377,44 @@ GridDev grid_of(const DevCtx& d) {
 // cell updates since the last rebuild can have changed (DevCtx::dirty and its box) -- the neighbour bytes and scan
 // words of the box, the cell infos of the rows and columns through it; the labels were kept up to date by
 // k_ccl_update unless a full relabelling is due.
-int derive_maps(fxjps* h, DevCtx& d, bool whole = true) {
+// slot != nullptr: the whole build of a grid slot's maps on d's streams (the same kernels; d's update state untouched).
+int derive_maps(fxjps* h, DevCtx& d, bool whole = true, GridBufs* slot = nullptr) {
     HIPCHK(h, hipSetDevice(d.dev));
+    GridBufs& g = slot ? *slot : d;
+    if (slot) whole = true;
     if (!whole && !d.dirty && !d.ccl_full) return FXJPS_OK;
-    const bool box = !whole && d.dirty && (d.bx1 - d.bx0 + 1) * 2 <= d.PW && (d.by1 - d.by0 + 1) * 2 <= d.PH;
-    const GridDev G = grid_of(d);
+    const bool box = !whole && d.dirty && (d.bx1 - d.bx0 + 1) * 2 <= g.PW && (d.by1 - d.by0 + 1) * 2 <= g.PH;
+    const GridDev G = grid_of(g);
     // A whole build (a new grid): the component labels need nothing but the occupancy bytes, the five map kernels nothing of
     // the labels -- the three label kernels run on the handle's second stream beside them and join in front of whatever is
     // queued next (round 6: 27 of the 76 us of a 256 x 256 build; 221 of 382 us at 1024 x 1024).
     // A small grid: four launches instead of eight (k_build_1 .. 3, then k_derive_jd): what a build of tiny kernels waits for
     // is the runtime launching them one by one.  FXJPS_FUSED_BUILD=0: the separate kernels (test / measurement aid).
     const char* fused_env = getenv("FXJPS_FUSED_BUILD");  // (read per build: the tests compare the two forms in one process)
-    if (whole && !(fused_env && atoi(fused_env) == 0) && (long long)d.W * d.H <= (1ll << 18)) {
-        const long long ncell = (long long)d.W * d.H, npad = (long long)d.PW * d.PH;
-        const unsigned nb_rows = (unsigned)(((long long)d.PW * d.WORDS + 3) / 4), nb_cols = (unsigned)(((long long)d.PH * d.WORDS + 3) / 4);
+    if (whole && !(fused_env && atoi(fused_env) == 0) && (long long)g.W * g.H <= (1ll << 18)) {
+        const long long ncell = (long long)g.W * g.H, npad = (long long)g.PW * g.PH;
+        const unsigned nb_rows = (unsigned)(((long long)g.PW * g.WORDS + 3) / 4), nb_cols = (unsigned)(((long long)g.PH * g.WORDS + 3) / 4);
         const unsigned nb_cell = (unsigned)((ncell + 255) / 256), nb_ci = (unsigned)((npad + 255) / 256);
-        const unsigned nb_diag = (unsigned)((4ll * G.DLINES * d.WORDS + 15) / 16), nb_flat = (unsigned)((ncell + 1023) / 1024);
-        hipLaunchKernelGGL(fx::k_build_1, dim3(nb_rows + nb_cols + nb_cell), dim3(256), 0, d.stream, d.occ.p, G, d.nb8.p, d.bm.p, d.comp.p, nb_rows, nb_cols);
-        hipLaunchKernelGGL(fx::k_build_2, dim3(nb_ci + nb_cell), dim3(256), 0, d.stream, d.occ.p, G, d.ci.p, d.comp.p, nb_ci);
-        hipLaunchKernelGGL(fx::k_build_3, dim3(nb_diag + nb_flat), dim3(1024), 0, d.stream, d.occ.p, G, d.bm.p + (size_t)4 * d.LINES * d.WORDS, d.comp.p, nb_diag);
-        hipLaunchKernelGGL(fx::k_derive_jd, dim3((unsigned)((npad * 8 + 255) / 256)), dim3(256), 0, d.stream, G, d.jd.p, fx::DiagRange{1, d.bx0, d.bx1, d.by0, d.by1});
+        const unsigned nb_diag = (unsigned)((4ll * G.DLINES * g.WORDS + 15) / 16), nb_flat = (unsigned)((ncell + 1023) / 1024);
+        hipLaunchKernelGGL(fx::k_build_1, dim3(nb_rows + nb_cols + nb_cell), dim3(256), 0, d.stream, g.occ.p, G, g.nb8.p, g.bm.p, g.comp.p, nb_rows, nb_cols);
+        hipLaunchKernelGGL(fx::k_build_2, dim3(nb_ci + nb_cell), dim3(256), 0, d.stream, g.occ.p, G, g.ci.p, g.comp.p, nb_ci);
+        hipLaunchKernelGGL(fx::k_build_3, dim3(nb_diag + nb_flat), dim3(1024), 0, d.stream, g.occ.p, G, g.bm.p + (size_t)4 * g.LINES * g.WORDS, g.comp.p, nb_diag);
+        hipLaunchKernelGGL(fx::k_derive_jd, dim3((unsigned)((npad * 8 + 255) / 256)), dim3(256), 0, d.stream, G, g.jd.p, fx::DiagRange{1, d.bx0, d.bx1, d.by0, d.by1});
         HIPCHK(h, hipGetLastError());
-        d.ccl_small = 0;
-        d.dirty = false;
-        d.ccl_full = false;
+        if (!slot) {
+            d.ccl_small = 0;
+            d.dirty = false;
+            d.ccl_full = false;
+        }
         return FXJPS_OK;
     }
     const bool ccl_beside = whole && d.stream_solo != nullptr && d.ev_ccl0 != nullptr;
     const auto launch_ccl = [&](hipStream_t st) {
-        const long long n = (long long)d.W * d.H;
+        const long long n = (long long)g.W * g.H;
         const unsigned nb = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(fx::k_ccl_init, dim3(nb), dim3(256), 0, st, d.occ.p, n, d.H, d.comp.p);
-        hipLaunchKernelGGL(fx::k_ccl_merge, dim3(nb), dim3(256), 0, st, d.occ.p, d.W, d.H, d.comp.p);
-        hipLaunchKernelGGL(fx::k_ccl_flatten, dim3(nb), dim3(256), 0, st, n, d.comp.p);
+        hipLaunchKernelGGL(fx::k_ccl_init, dim3(nb), dim3(256), 0, st, g.occ.p, n, g.H, g.comp.p);
+        hipLaunchKernelGGL(fx::k_ccl_merge, dim3(nb), dim3(256), 0, st, g.occ.p, g.W, g.H, g.comp.p);
+        hipLaunchKernelGGL(fx::k_ccl_flatten, dim3(nb), dim3(256), 0, st, n, g.comp.p);
     };
     if (ccl_beside) {
         HIPCHK(h, hipEventRecord(d.ev_ccl0, d.stream));  // (behind the copy / broadcast that brought the grid)
@@ -390,18 +423,18 @@ int derive_maps(fxjps* h, DevCtx& d, bool whole = true) {
         HIPCHK(h, hipEventRecord(d.ev_ccl1, d.stream_solo));
     }
     if (whole || d.dirty) {
-        fx::MapRange rr{0, d.PW - 1, 0, d.WORDS - 1}, rc{0, d.PH - 1, 0, d.WORDS - 1};
+        fx::MapRange rr{0, g.PW - 1, 0, g.WORDS - 1}, rc{0, g.PH - 1, 0, g.WORDS - 1};
         if (box) {
             rr = fx::MapRange{d.bx0, d.bx1, d.by0 >> 6, d.by1 >> 6};
             rc = fx::MapRange{d.by0, d.by1, d.bx0 >> 6, d.bx1 >> 6};
         }
         const long long nrw = (long long)(rr.l1 - rr.l0 + 1) * (rr.w1 - rr.w0 + 1), ncw = (long long)(rc.l1 - rc.l0 + 1) * (rc.w1 - rc.w0 + 1);
-        hipLaunchKernelGGL(fx::k_derive_rows, dim3((unsigned)((nrw + 3) / 4)), dim3(256), 0, d.stream, d.occ.p, G, d.nb8.p, d.bm.p, rr);
-        hipLaunchKernelGGL(fx::k_derive_cols, dim3((unsigned)((ncw + 3) / 4)), dim3(256), 0, d.stream, d.occ.p, G, d.bm.p, rc);
+        hipLaunchKernelGGL(fx::k_derive_rows, dim3((unsigned)((nrw + 3) / 4)), dim3(256), 0, d.stream, g.occ.p, G, g.nb8.p, g.bm.p, rr);
+        hipLaunchKernelGGL(fx::k_derive_cols, dim3((unsigned)((ncw + 3) / 4)), dim3(256), 0, d.stream, g.occ.p, G, g.bm.p, rc);
         fx::ChangeOut chg{nullptr, nullptr, nullptr, 0u, fx::MapRange{1, 0, 1, 0}};
         if (box) {  // the rows and the columns through the box (a straight jump ends where the line's next stop bit is)
-            const fx::MapRange sa{d.bx0, d.bx1, 0, d.PH - 1}, sb{0, d.PW - 1, d.by0, d.by1};
-            const long long na = (long long)(sa.l1 - sa.l0 + 1) * d.PH, nb = (long long)d.PW * (sb.w1 - sb.w0 + 1);
+            const fx::MapRange sa{d.bx0, d.bx1, 0, g.PH - 1}, sb{0, g.PW - 1, d.by0, d.by1};
+            const long long na = (long long)(sa.l1 - sa.l0 + 1) * g.PH, nb = (long long)g.PW * (sb.w1 - sb.w0 + 1);
             // ... and which of those cells changed: where the re-scan of the jump distances starts (k_jd_walk)
             const bool walk = !(getenv("FXJPS_JD_WALK") && atoi(getenv("FXJPS_JD_WALK")) == 0);  // (0: measurement / test aid -- every record is read)
             if (walk) {
@@ -411,9 +444,9 @@ int derive_maps(fxjps* h, DevCtx& d, bool whole = true) {
                 // rebuilt, every record read: chg.map stays nullptr).
                 bool room = true;
                 if (!d.chg_ready) {  // (streaming callers only: with the first partial rebuild on a grid)
-                    room = d.d_chgmap.ensure((size_t)d.PW * d.NS) == hipSuccess && d.d_chgcnt.ensure(4) == hipSuccess;
+                    room = d.d_chgmap.ensure((size_t)g.PW * g.NS) == hipSuccess && d.d_chgcnt.ensure(4) == hipSuccess;
                     if (room) {
-                        HIPCHK(h, hipMemsetAsync(d.d_chgmap.p, 0, (size_t)d.PW * d.NS, d.stream));
+                        HIPCHK(h, hipMemsetAsync(d.d_chgmap.p, 0, (size_t)g.PW * g.NS, d.stream));
                         HIPCHK(h, hipMemsetAsync(d.d_chgcnt.p, 0, 4 * sizeof(unsigned int), d.stream));
                         d.chg_ready = true;
                     }
@@ -427,41 +460,41 @@ int derive_maps(fxjps* h, DevCtx& d, bool whole = true) {
                 } else
                     (void)hipGetLastError();  // (the failed allocation's sticky error: not this update's business)
             }
-            hipLaunchKernelGGL(fx::k_derive_cellinfo, dim3((unsigned)((na + nb + 255) / 256)), dim3(256), 0, d.stream, G, d.ci.p, sa, sb, chg);
+            hipLaunchKernelGGL(fx::k_derive_cellinfo, dim3((unsigned)((na + nb + 255) / 256)), dim3(256), 0, d.stream, G, g.ci.p, sa, sb, chg);
         } else {
-            const long long ncell = (long long)d.PW * d.PH;
-            hipLaunchKernelGGL(fx::k_derive_cellinfo, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, d.stream, G, d.ci.p,
-                               fx::MapRange{0, d.PW - 1, 0, d.PH - 1}, fx::MapRange{1, 0, 1, 0}, chg);
+            const long long ncell = (long long)g.PW * g.PH;
+            hipLaunchKernelGGL(fx::k_derive_cellinfo, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, d.stream, G, g.ci.p,
+                               fx::MapRange{0, g.PW - 1, 0, g.PH - 1}, fx::MapRange{1, 0, 1, 0}, chg);
         }
         {  // the diagonal scan words: a function of the cell infos (and the occupancy) cell by cell -- of the cells above
             const fx::DiagRange dr{box ? 0 : 1, d.bx0, d.bx1, d.by0, d.by1};
-            const long long per = box ? (long long)((d.bx1 >> 6) - (d.bx0 >> 6) + 1) + (((d.by1 - d.by0 + 63) >> 6) + 1) : (long long)d.WORDS;
+            const long long per = box ? (long long)((d.bx1 >> 6) - (d.bx0 >> 6) + 1) + (((d.by1 - d.by0 + 63) >> 6) + 1) : (long long)g.WORDS;
             const long long nw = 4ll * G.DLINES * per;
             if (box && chg.map != nullptr)  // (the changed cells alone, bit by bit)
                 hipLaunchKernelGGL(fx::k_diag_update, dim3((unsigned)std::min<long long>(((long long)chg.cap * 4 + 255) / 256, 256)), dim3(256), 0, d.stream,
-                                   d.occ.p, G, d.bm.p + (size_t)4 * d.LINES * d.WORDS, chg);
+                                   g.occ.p, G, g.bm.p + (size_t)4 * g.LINES * g.WORDS, chg);
             else
-                hipLaunchKernelGGL(fx::k_derive_diag, dim3((unsigned)((nw + 15) / 16)), dim3(1024), 0, d.stream, d.occ.p, G,
-                                   d.bm.p + (size_t)4 * d.LINES * d.WORDS, dr);
+                hipLaunchKernelGGL(fx::k_derive_diag, dim3((unsigned)((nw + 15) / 16)), dim3(1024), 0, d.stream, g.occ.p, G,
+                                   g.bm.p + (size_t)4 * g.LINES * g.WORDS, dr);
             // ... and the jump distances: the goal-free jumps themselves, from every cell along every direction, read off
             // the scan words above (after an update: the entries whose old ray passes what the update can have changed)
             if (box && chg.map != nullptr) {
                 // what the update can have changed, found from the changed cells backwards (a walker per changed cell and
                 // direction) instead of by reading every record
                 const int walk_max = getenv("FXJPS_JD_WALK_MAX") ? std::max(1, atoi(getenv("FXJPS_JD_WALK_MAX"))) : FXJPS_JD_WALK_MAX;  // (test aid)
-                const long long nt = (long long)chg.cap * 8, nc = (long long)d.W * d.H;
+                const long long nt = (long long)chg.cap * 8, nc = (long long)g.W * g.H;
                 // (walks pay while the changed cells are few against the table: past W * H / 128 of them the records are streamed
                 // -- measured at 4096^2 over obstacle densities 0 ... 0.2, profiles/r06_map_build.txt)
                 const int div = getenv("FXJPS_JD_STREAM_DIV") ? std::max(1, atoi(getenv("FXJPS_JD_STREAM_DIV"))) : 128;  // (measurement / test aid)
                 const uint32_t stream_over = (uint32_t)std::max<long long>(nc / div, 1024);
-                hipLaunchKernelGGL(fx::k_jd_walk, dim3((unsigned)std::min<long long>((nt + 255) / 256, 2048)), dim3(256), 0, d.stream, G, d.jd.p, chg, dr, walk_max, stream_over);
-                hipLaunchKernelGGL(fx::k_jd_finish, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1024)), dim3(256), 0, d.stream, G, d.jd.p, chg, dr);
+                hipLaunchKernelGGL(fx::k_jd_walk, dim3((unsigned)std::min<long long>((nt + 255) / 256, 2048)), dim3(256), 0, d.stream, G, g.jd.p, chg, dr, walk_max, stream_over);
+                hipLaunchKernelGGL(fx::k_jd_finish, dim3((unsigned)std::min<long long>((nc + 255) / 256, 1024)), dim3(256), 0, d.stream, G, g.jd.p, chg, dr);
             } else if (box) {
-                const long long nc = (long long)d.W * d.H;
-                hipLaunchKernelGGL(fx::k_update_jd, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, d.stream, G, d.jd.p, dr);
+                const long long nc = (long long)g.W * g.H;
+                hipLaunchKernelGGL(fx::k_update_jd, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, d.stream, G, g.jd.p, dr);
             } else {
-                const long long nj = (long long)d.PW * d.PH * 8;
-                hipLaunchKernelGGL(fx::k_derive_jd, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, d.stream, G, d.jd.p, dr);
+                const long long nj = (long long)g.PW * g.PH * 8;
+                hipLaunchKernelGGL(fx::k_derive_jd, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, d.stream, G, g.jd.p, dr);
             }
         }
         HIPCHK(h, hipGetLastError());
@@ -469,15 +502,36 @@ int derive_maps(fxjps* h, DevCtx& d, bool whole = true) {
     if (ccl_beside) {
         HIPCHK(h, hipStreamWaitEvent(d.stream, d.ev_ccl1, 0));  // the join: whatever is queued on the main stream next sees the labels
         HIPCHK(h, hipGetLastError());
-        d.ccl_small = 0;
+        if (!slot) d.ccl_small = 0;
     } else if (whole || d.ccl_full) {
         // component labels for the unreachable-goal early-out
         launch_ccl(d.stream);
         HIPCHK(h, hipGetLastError());
-        d.ccl_small = 0;
+        if (!slot) d.ccl_small = 0;
     }
+    if (slot) return FXJPS_OK;  // (the resident grid's update state is not the slot's business)
     d.dirty = false;
     d.ccl_full = false;
+    return FXJPS_OK;
+}
+
+// the extents and the buffers of a W x H grid (the resident grid's or a slot's; the current device)
+int alloc_grid_bufs(fxjps* h, GridBufs& d, int W, int H) {
+    d.W = W;
+    d.H = H;
+    d.PW = W + 2;
+    d.PH = H + 2;
+    d.NS = (d.PH + 63) & ~63;
+    d.LINES = std::max(d.PW, d.PH);
+    d.WORDS = (std::max(d.PW, d.PH) + 63) / 64;
+    d.tsh = 0;  // read-set tiles (streaming replan): at most 64 x 64 of them cover the grid
+    while (((std::max(W, H) - 1) >> d.tsh) > 63) d.tsh++;
+    HIPCHK(h, d.occ.ensure((size_t)W * H));
+    HIPCHK(h, d.comp.ensure((size_t)W * H));
+    HIPCHK(h, d.nb8.ensure((size_t)d.PW * d.NS));
+    HIPCHK(h, d.ci.ensure((size_t)d.PW * d.NS));
+    HIPCHK(h, d.jd.ensure((size_t)d.PW * d.NS * 8));
+    HIPCHK(h, d.bm.ensure((size_t)4 * d.LINES * d.WORDS + (size_t)4 * (d.PW + d.PH - 1) * d.WORDS));  // straight + diagonal scan lines
     return FXJPS_OK;
 }
 
@@ -499,22 +553,7 @@ int alloc_grid(fxjps* h, DevCtx& d, int W, int H) {
         d.owner_ready = false;  // (the update lists' owner cells follow the grid's shape -- and are all -1 between two updates,
         d.chg_ready = false;    // as the marks of the changed cells are all zero: a grid of the same shape finds them in order)
     }
-    d.W = W;
-    d.H = H;
-    d.PW = W + 2;
-    d.PH = H + 2;
-    d.NS = (d.PH + 63) & ~63;
-    d.LINES = std::max(d.PW, d.PH);
-    d.WORDS = (std::max(d.PW, d.PH) + 63) / 64;
-    d.tsh = 0;  // read-set tiles (streaming replan): at most 64 x 64 of them cover the grid
-    while (((std::max(W, H) - 1) >> d.tsh) > 63) d.tsh++;
-    HIPCHK(h, d.occ.ensure((size_t)W * H));
-    HIPCHK(h, d.comp.ensure((size_t)W * H));
-    HIPCHK(h, d.nb8.ensure((size_t)d.PW * d.NS));
-    HIPCHK(h, d.ci.ensure((size_t)d.PW * d.NS));
-    HIPCHK(h, d.jd.ensure((size_t)d.PW * d.NS * 8));
-    HIPCHK(h, d.bm.ensure((size_t)4 * d.LINES * d.WORDS + (size_t)4 * (d.PW + d.PH - 1) * d.WORDS));  // straight + diagonal scan lines
-    return FXJPS_OK;
+    return alloc_grid_bufs(h, d, W, H);
 }
 
 // wavefront counts are whole blocks of fx::WPB wavefronts (any block size: a measurement build runs ten per block)
@@ -540,8 +579,9 @@ void release_pool0(DevCtx& d) {
 
 // Size the per-wavefront scratch.  pool 0: many wavefronts, tables sized for the
 // typical query; pool 1: few wavefronts, tables that cannot overflow.
+// (A slots batch sizes them from the largest extents among the slots it names: DevCtx::plan_W / plan_H / plan_cells.)
 int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
-    const uint64_t cells = (uint64_t)d.W * d.H;
+    const uint64_t cells = d.plan_cells();
     ScratchCfg c;
     // Memory budget.  A handle that has the device to itself gives pool 0 up to 80 % of it, less what the batch still
     // has to allocate behind the search (the packed paths: at most nq * max_len cells), the smallest retry pool and a
@@ -593,7 +633,7 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
         // slots: 1024^2, where it is exactly as large as the hashed table was); larger grids keep the hashed table.
         // FXJPS_DIRECT=0: measurement / test aid.
         {
-            const uint32_t lx = std::max(ceil_log2((uint64_t)d.W), 1u), ly = std::max(ceil_log2((uint64_t)d.H), 1u);
+            const uint32_t lx = std::max(ceil_log2((uint64_t)d.plan_W()), 1u), ly = std::max(ceil_log2((uint64_t)d.plan_H()), 1u);
             const uint32_t ld = std::max(lx + ly, 12u);
             const uint64_t full = (uint64_t)d.n_cu * 4u * (uint64_t)fx::OCC / (uint64_t)(d.share * h->mem_div);
             const uint64_t cap = (d.mem_total ? (uint64_t)(d.mem_total * 0.4) : ((uint64_t)32 << 30)) / (uint64_t)(d.share * h->mem_div);
@@ -617,7 +657,7 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
             const uint64_t want = std::max<uint64_t>(wpb_up(want_waves), (uint64_t)fx::WPB);
             const double per_entry = (double)sizeof(TEnt) + (1.0 + 1.0 / 8) * sizeof(FarEnt) / 8.0;
             const ScratchCfg& have = d.cfg[0];
-            if (have.nbuckets != 0u && have.direct_ly == 0u && have.nwaves >= want) {
+            if (have.nbuckets != 0u && have.direct_ly == 0u && have.nwaves >= want && d.cfg_W == d.plan_W() && d.cfg_H == d.plan_H()) {
                 // (the pool in place serves this batch: its size stays -- sizes that follow the free memory of the
                 // moment would have the pool allocated and wiped again and again)
                 entries = (uint64_t)have.nbuckets * (uint64_t)fx::BUCKET;
@@ -646,11 +686,15 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
     const size_t per_wave = ((size_t)fx::BUCKET * c.nbuckets) * sizeof(TEnt) + (size_t)(c.far_cap + c.far_cap / 8) * sizeof(FarEnt);
     uint32_t maxw = (uint32_t)std::min<size_t>(budget / per_wave, 1u << 20);
     maxw = (uint32_t)wpb_down(maxw);
-    if (maxw < (uint32_t)fx::WPB) return fail(h, FXJPS_E_NOMEM, "grid %dx%d needs %zu bytes of scratch per wavefront", d.W, d.H, per_wave);
+    if (maxw < (uint32_t)fx::WPB) return fail(h, FXJPS_E_NOMEM, "grid %dx%d needs %zu bytes of scratch per wavefront", d.plan_W(), d.plan_H(), per_wave);
     if ((uint32_t)wpb_up(c.nwaves) > maxw) d.waves_short = true;
     c.nwaves = std::max((uint32_t)fx::WPB, std::min((uint32_t)wpb_up(c.nwaves), maxw));
     ScratchCfg& cur = d.cfg[pool];
     const bool same = cur.nbuckets == c.nbuckets && cur.usable == c.usable && cur.direct_ly == c.direct_ly && cur.far_cap == c.far_cap && cur.nwaves >= c.nwaves;
+    if (pool == 0) {  // (the pool in place, or the one configured below, now serves these extents)
+        d.cfg_W = d.plan_W();
+        d.cfg_H = d.plan_H();
+    }
     if (same && d.pool_clean[pool]) return FXJPS_OK;
     if (!same) {
         // the old buffers die inside ensure(): forget the old configuration first, so that a failed allocation can
@@ -713,7 +757,7 @@ void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* 
     // The far band of the open list in f bands that a refill takes whole (no scan, no compaction): pays where open lists
     // hold thousands of entries (4096^2: + 10 %), costs where they hold hundreds (1024^2: - 10 %, an LDS atomic and a
     // scattered store per push instead of an append at a rank).  FXJPS_BANDED=0/1: measurement / test aid.
-    A.banded = (uint64_t)d.W * (uint64_t)d.H >= (1ull << 22) ? 1u : 0u;
+    A.banded = d.plan_cells() >= (1ull << 22) ? 1u : 0u;
     if (const char* e = getenv("FXJPS_BANDED")) A.banded = atoi(e) != 0 ? 1u : 0u;
     if (pool != 0) A.banded = 0u;  // the large pool is the last resort: its far tier has no regions that could fill up
     A.far_cap = c.far_cap;
@@ -722,7 +766,11 @@ void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* 
     if (const char* e = getenv("FXJPS_NEAR_MAX")) A.near_max = (uint32_t)std::max(1, atoi(e));
     A.next = d.d_next.p;
     A.wave_gen = d.wave_gen[pool].p;
-    A.max_pops = 64ull * (unsigned long long)d.W * d.H + 4096ull;
+    A.max_pops = 64ull * (unsigned long long)d.plan_cells() + 4096ull;
+    if (d.mg_ids) {  // a slots batch: every query reads the descriptor of its slot
+        A.grids = d.d_slot_desc.p;
+        A.grid_ids = d.d_grid_ids.p;
+    }
 }
 
 int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const ScratchCfg& c, const uint32_t* d_order, uint32_t nrun, int hchoice, bool track) {
@@ -762,14 +810,19 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
     // instantiations: heuristic x read-set recording (fxjps_replan_frame) x table indexed by the cell
     {
         using KFn = void (*)(SearchArgs);
-        static const KFn kfn[2][2][2] = {{{fx::k_search<1, false, false>, fx::k_search<1, false, true>},
-                                          {fx::k_search<1, true, false>, fx::k_search<1, true, true>}},
-                                         {{fx::k_search<2, false, false>, fx::k_search<2, false, true>},
-                                          {fx::k_search<2, true, false>, fx::k_search<2, true, true>}}};
-        const KFn fn = kfn[hchoice == 1 ? 0 : 1][track ? 1 : 0][c.direct_ly > 0 ? 1 : 0];
+        static const KFn kfn[2][2][2] = {{{fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>},
+                                          {fx::k_search<1, true, false, false>, fx::k_search<1, true, true, false>}},
+                                         {{fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>},
+                                          {fx::k_search<2, true, false, false>, fx::k_search<2, true, true, false>}}};
+        // ... and a grid per query (a slots batch: never with read-set recording)
+        static const KFn kfn_mg[2][2] = {{fx::k_search<1, false, false, true>, fx::k_search<1, false, true, true>},
+                                         {fx::k_search<2, false, false, true>, fx::k_search<2, false, true, true>}};
+        const bool mg = A.grids != nullptr;
+        if (mg && track) return fail(h, FXJPS_E_ARG, "read-set recording on grid slots");
+        const KFn fn = mg ? kfn_mg[hchoice == 1 ? 0 : 1][c.direct_ly > 0 ? 1 : 0] : kfn[hchoice == 1 ? 0 : 1][track ? 1 : 0][c.direct_ly > 0 ? 1 : 0];
         static const size_t pad = 36u << 10;  // 66 .. 74 KB of the block's own + this: no second block fits the CU's 160 KB
         if (nsolo != 0u || live_main != 0u) {
-            const int ki = (hchoice == 1 ? 0 : 4) + (track ? 2 : 0) + (c.direct_ly > 0 ? 1 : 0);
+            const int ki = mg ? 8 + (hchoice == 1 ? 0 : 2) + (c.direct_ly > 0 ? 1 : 0) : (hchoice == 1 ? 0 : 4) + (track ? 2 : 0) + (c.direct_ly > 0 ? 1 : 0);
             if (!d.lds_attr_done[ki]) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad) == hipSuccess) {
                     d.lds_attr_done[ki] = true;
@@ -866,6 +919,10 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
     HIPCHK(h, d.h_counters.ensure(64));
     HIPCHK(h, hipMemcpyAsync(d.d_starts.p, starts + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
     HIPCHK(h, hipMemcpyAsync(d.d_goals.p, goals + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    if (d.mg_ids) {
+        HIPCHK(h, d.d_grid_ids.ensure((size_t)nq));
+        HIPCHK(h, hipMemcpyAsync(d.d_grid_ids.p, d.mg_ids + d.q0, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    }
     HIPCHK(h, hipMemsetAsync(d.d_counters.p, 0, 64 * sizeof(unsigned long long), d.stream));
     if (getenv("FXJPS_QSTAT")) {  // diagnostics: per-query start / end time, pops, wavefront (tools/qstat.py)
         HIPCHK(h, d.d_qstat.ensure((size_t)nq * 4));
@@ -1053,8 +1110,8 @@ int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals
     A.host_counters = (unsigned long long*)dp_cnt;
     {
         using KFn = void (*)(SearchArgs);
-        static const KFn kfn[2][2] = {{fx::k_search<1, false, false>, fx::k_search<1, false, true>},
-                                      {fx::k_search<2, false, false>, fx::k_search<2, false, true>}};
+        static const KFn kfn[2][2] = {{fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>},
+                                      {fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>}};
         hipLaunchKernelGGL(kfn[hchoice == 1 ? 0 : 1][c.direct_ly > 0 ? 1 : 0], dim3(1), dim3(fx::WAVE * fx::WPB), 0, d.stream, A);
         HIPCHK(h, hipGetLastError());
     }
@@ -1081,9 +1138,11 @@ int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals
 int update_cells_async(fxjps* h, const int32_t* xy, const uint8_t* val, int64_t n, bool derive);  // (below, with the streaming entry points)
 void drain_all(fxjps* h);
 
-int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len, int mode = 0) {
+// grid_ids != nullptr: a slots batch (fxjps_plan_batch_slots_csr, which checked the ids and set every context's mg_* fields)
+int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len, int mode = 0,
+              const int32_t* grid_ids = nullptr) {
     if (!h) return FXJPS_E_ARG;
-    if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "fxjps_plan_batch before fxjps_set_grid");
+    if (!h->have_grid && !grid_ids) return fail(h, FXJPS_E_NOGRID, "fxjps_plan_batch before fxjps_set_grid");
     if (nq < 0 || (nq > 0 && (!starts || !goals))) return fail(h, FXJPS_E_ARG, "bad query arrays");
     if (hchoice != 1 && hchoice != 2)
         return fail(h, FXJPS_E_ARG, "hchoice must be 1 or 2 (the reference raises TypeError, jps1.py:188)");
@@ -1092,7 +1151,8 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
     // Until this batch is complete (emit_csr) no earlier batch is "the last batch": the resident-path forms of the
     // waypoint entry points refuse with FXJPS_E_ARG instead of reading lengths and offsets of different batches.
     h->last_nq = 0;
-    if (h->maps_stale) {  // deferred cell updates: the maps are rebuilt once, in front of the search
+    h->last_slots = grid_ids != nullptr;
+    if (h->maps_stale && !grid_ids) {  // deferred cell updates: the maps are rebuilt once, in front of the search
         int rc = update_cells_async(h, nullptr, nullptr, 0, true);
         if (rc) return rc;
     }
@@ -1107,7 +1167,7 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
     h->last_on_host = false;
     static const bool single_ok = !(getenv("FXJPS_SINGLE") && atoi(getenv("FXJPS_SINGLE")) == 0) && !getenv("FXJPS_QSTAT");  // (0: test / measurement aid)
     bool done = false;
-    if (nq == 1 && nd == 1 && mode == 0 && single_ok) {
+    if (nq == 1 && nd == 1 && mode == 0 && single_ok && !grid_ids) {  // (a lone query on a slot takes the batch path)
         rc = plan_single(h, h->devs[0], starts, goals, hchoice, max_len);
         if (rc == 1) {
             rc = FXJPS_OK;  // (rare: on to the batch path)
@@ -1602,6 +1662,9 @@ void fxjps_destroy(fxjps_t* h) {
         d.h_counters.release();
         d.h_upd_xy.release();
         d.h_path1.release();
+        for (auto& g : d.slots) g.release();
+        d.d_slot_desc.release();
+        d.d_grid_ids.release();
         if (d.ev_upd) (void)hipEventDestroy(d.ev_upd);
         if (d.ev_stage) (void)hipEventDestroy(d.ev_stage);
         d.h_occ_stage.release();
@@ -2145,6 +2208,127 @@ int fxjps_plan_batch_csr(fxjps_t* h, const int32_t* starts_xy, const int32_t* go
     return rc;
 }
 
+namespace {
+bool slot_in_use(fxjps_t* h, int32_t slot) {
+    const DevCtx& d0 = h->devs[0];
+    return slot >= 0 && slot < FXJPS_MAX_GRID_SLOTS && (size_t)slot < d0.slots.size() && d0.slots[(size_t)slot].W > 0;
+}
+}  // namespace
+
+int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W, int32_t H) {
+    if (!h) return FXJPS_E_ARG;
+    if (slot < 0 || slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "slot %d is not in 0 .. %d", (int)slot, FXJPS_MAX_GRID_SLOTS - 1);
+    if (occ && (W < 1 || H < 1 || W > 8190 || H > 8190)) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
+    if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid_slot")) return rr;
+    // Every context gets its own copy from the host (no collective), builds the maps on its own streams, and refreshes its
+    // table of slot descriptors.  The resident grid and its update state are not touched.
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int {
+        DevCtx& d = h->devs[r];
+        HIPCHK(h, hipSetDevice(d.dev));
+        if (d.slots.empty()) {
+            d.slots.resize(FXJPS_MAX_GRID_SLOTS);
+            d.h_slot_desc.assign(FXJPS_MAX_GRID_SLOTS, GridDev{});
+            HIPCHK(h, d.d_slot_desc.ensure(FXJPS_MAX_GRID_SLOTS));
+        }
+        GridBufs& g = d.slots[(size_t)slot];
+        HIPCHK(h, hipStreamSynchronize(d.stream));  // (whatever is queued may still read the slot's buffers)
+        if (!occ) {
+            g.release();
+            d.h_slot_desc[(size_t)slot] = GridDev{};
+        } else {
+            g.W = 0;  // (empty until its maps are built: a failure below leaves the slot released, not half-set)
+            d.h_slot_desc[(size_t)slot] = GridDev{};
+            int e = alloc_grid_bufs(h, g, W, H);
+            if (e) {
+                g.release();
+                return e;
+            }
+            HIPCHK(h, hipMemcpyAsync(g.occ.p, occ, (size_t)W * H, hipMemcpyHostToDevice, d.stream));
+            e = derive_maps(h, d, true, &g);
+            if (e) {
+                g.release();
+                return e;
+            }
+            d.h_slot_desc[(size_t)slot] = grid_of(g);
+        }
+        HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p + slot, &d.h_slot_desc[(size_t)slot], sizeof(GridDev), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+        return FXJPS_OK;
+    });
+    if (rc) {
+        drain_all(h);
+        for (auto& d : h->devs)  // (a slot that failed on one context is released on all of them)
+            if ((size_t)slot < d.slots.size()) {
+                if (hipSetDevice(d.dev) == hipSuccess) d.slots[(size_t)slot].release();
+                d.slots[(size_t)slot].W = 0;
+                d.h_slot_desc[(size_t)slot] = GridDev{};
+                if (hipSetDevice(d.dev) == hipSuccess)
+                    (void)hipMemcpy(d.d_slot_desc.p + slot, &d.h_slot_desc[(size_t)slot], sizeof(GridDev), hipMemcpyHostToDevice);
+            }
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+int fxjps_get_grid_slot(fxjps_t* h, int32_t slot, uint8_t* out, int32_t* out_W, int32_t* out_H) {
+    if (!h) return FXJPS_E_ARG;
+    if (!slot_in_use(h, slot)) return fail(h, FXJPS_E_ARG, "grid slot %d is empty or out of range", (int)slot);
+    DevCtx& d = h->devs[0];
+    const GridBufs& g = d.slots[(size_t)slot];
+    if (out_W) *out_W = g.W;
+    if (out_H) *out_H = g.H;
+    if (out) {
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, hipMemcpyAsync(out, g.occ.p, (size_t)g.W * g.H, hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+    }
+    return FXJPS_OK;
+}
+
+int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
+                               int32_t hchoice, int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy,
+                               int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
+    const double t0 = now_s();
+    if (!h) return FXJPS_E_ARG;
+    if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
+    if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
+    // every id checked before anything is queued; the batch is sized by the largest extents among the slots it names
+    int mw = 1, mh = 1;
+    uint64_t mc = 1;
+    {
+        std::vector<uint8_t> seen(FXJPS_MAX_GRID_SLOTS, 0);
+        for (int64_t q = 0; q < nq; q++) {
+            const int32_t id = grid_ids[q];
+            if (!slot_in_use(h, id))
+                return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)id,
+                            id < 0 || id >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
+            if (seen[(size_t)id]) continue;
+            seen[(size_t)id] = 1;
+            const GridBufs& g = h->devs[0].slots[(size_t)id];
+            mw = std::max(mw, g.W);
+            mh = std::max(mh, g.H);
+            mc = std::max(mc, (uint64_t)g.W * (uint64_t)g.H);
+        }
+    }
+    static const int32_t no_ids = 0;  // (an empty batch may pass no array: it is a slots batch all the same)
+    const int32_t* ids = grid_ids ? grid_ids : &no_ids;
+    for (auto& d : h->devs) {
+        d.mg_ids = ids;
+        d.mg_W = mw;
+        d.mg_H = mh;
+        d.mg_cells = mc;
+    }
+    int rc = plan_core(h, starts_xy, goals_xy, nq, hchoice, max_path_len, 0, ids);
+    for (auto& d : h->devs) d.mg_ids = nullptr;  // (the caller's array is only borrowed for the call)
+    if (rc) return rc;
+    h->last_slots_W = mw;
+    h->last_slots_H = mh;
+    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
+    h->timing.total_ms = (now_s() - t0) * 1e3;
+    if (out_seconds_total) *out_seconds_total = now_s() - t0;
+    return rc;
+}
+
 int fxjps_last_cells(fxjps_t* h, int32_t* out_cells_xy, int64_t cells_capacity) {
     if (!h || !out_cells_xy) return FXJPS_E_ARG;
     int64_t base = 0;
@@ -2266,6 +2450,8 @@ int fxjps_waypoint_ccst_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, co
     if (nq < 0 || !origin || (nq > 0 && (!pos || !goal || !out_wp))) return fail(h, FXJPS_E_ARG, "bad waypoint arguments");
     if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
     if (!cells_xy && nq != h->last_nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
+    if (!cells_xy && h->last_slots)  // (the line tests read the resident grid: those paths were planned on other grids)
+        return fail(h, FXJPS_E_ARG, "the last batch ran on grid slots: pass its paths explicitly");
     if (!cells_xy && h->last_on_host) {  // (a single call leaves its path in the pinned host buffers: handed over like a caller's CSR)
         static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
         offsets = reinterpret_cast<const int64_t*>(h->devs[0].h_offsets.p);
@@ -2370,9 +2556,9 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
                 cy0 = std::min<long long>(cy0, cells_xy[2 * i + 1]);
                 cy1 = std::max<long long>(cy1, cells_xy[2 * i + 1]);
             }
-        } else {  // (resident paths lie on the grid)
-            cx1 = h->devs[0].W - 1;
-            cy1 = h->devs[0].H - 1;
+        } else {  // (resident paths lie on the grid; a slots batch's within the largest slot it named)
+            cx1 = (h->last_slots ? h->last_slots_W : h->devs[0].W) - 1;
+            cy1 = (h->last_slots ? h->last_slots_H : h->devs[0].H) - 1;
         }
         long long am = 0, bm = 0;
         for (int64_t q = 0; q < nq; q++) {
@@ -2715,24 +2901,18 @@ int fxjps_selftest_openlist(fxjps_t* h, int32_t banded, int32_t far_cap, int32_t
     return FXJPS_OK;
 }
 
-int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes) {
-    if (!h) return FXJPS_E_ARG;
-    if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "no grid");
-    DevCtx& d = h->devs[0];
-    HIPCHK(h, hipSetDevice(d.dev));
-    if (h->maps_stale) {  // deferred cell updates: the maps follow the grid first
-        int rc = update_cells_async(h, nullptr, nullptr, 0, true);
-        if (rc) return rc;
-    }
+namespace {
+// which = 0 .. 5 of a grid's derived maps (fxjps_debug_read_maps, fxjps_debug_read_slot_maps)
+int read_maps(fxjps_t* h, DevCtx& d, const GridBufs& g, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes) {
     const void* src = nullptr;
     size_t bytes = 0;
     switch (which) {
-        case 0: src = d.bm.p; bytes = (size_t)4 * d.LINES * d.WORDS * sizeof(fx::BmWord); break;  // scan words [4][LINES][WORDS] x {stop, occ}
-        case 1: src = d.ci.p; bytes = (size_t)d.PW * d.NS * sizeof(uint16_t); break;               // cell infos [PW][NS] (columns >= PH unused)
-        case 2: src = d.comp.p; bytes = (size_t)d.W * d.H * sizeof(int); break;                    // component forest [W][H]
-        case 3: src = d.nb8.p; bytes = (size_t)d.PW * d.NS; break;                                 // neighbour bytes [PW][NS]
-        case 4: src = d.bm.p + (size_t)4 * d.LINES * d.WORDS; bytes = (size_t)4 * (d.PW + d.PH - 1) * d.WORDS * sizeof(fx::BmWord); break;  // diagonal scan words
-        case 5: src = d.jd.p; bytes = (size_t)d.PW * d.NS * 8 * sizeof(uint16_t); break;              // jump distances [PW][NS][8]
+        case 0: src = g.bm.p; bytes = (size_t)4 * g.LINES * g.WORDS * sizeof(fx::BmWord); break;  // scan words [4][LINES][WORDS] x {stop, occ}
+        case 1: src = g.ci.p; bytes = (size_t)g.PW * g.NS * sizeof(uint16_t); break;               // cell infos [PW][NS] (columns >= PH unused)
+        case 2: src = g.comp.p; bytes = (size_t)g.W * g.H * sizeof(int); break;                    // component forest [W][H]
+        case 3: src = g.nb8.p; bytes = (size_t)g.PW * g.NS; break;                                 // neighbour bytes [PW][NS]
+        case 4: src = g.bm.p + (size_t)4 * g.LINES * g.WORDS; bytes = (size_t)4 * (g.PW + g.PH - 1) * g.WORDS * sizeof(fx::BmWord); break;  // diagonal scan words
+        case 5: src = g.jd.p; bytes = (size_t)g.PW * g.NS * 8 * sizeof(uint16_t); break;              // jump distances [PW][NS][8]
         default: return fail(h, FXJPS_E_ARG, "which must be 0 .. 5");
     }
     if (out_bytes) *out_bytes = (int64_t)bytes;
@@ -2742,6 +2922,28 @@ int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity
     HIPCHK(h, hipStreamSynchronize(d.stream));
     return FXJPS_OK;
 }
+}  // namespace
+
+int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes) {
+    if (!h) return FXJPS_E_ARG;
+    if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "no grid");
+    DevCtx& d = h->devs[0];
+    HIPCHK(h, hipSetDevice(d.dev));
+    if (h->maps_stale) {  // deferred cell updates: the maps follow the grid first
+        int rc = update_cells_async(h, nullptr, nullptr, 0, true);
+        if (rc) return rc;
+    }
+    return read_maps(h, d, d, which, buf, capacity_bytes, out_bytes);
+}
+
+int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes) {
+    if (!h) return FXJPS_E_ARG;
+    if (!slot_in_use(h, slot)) return fail(h, FXJPS_E_ARG, "grid slot %d is empty or out of range", (int)slot);
+    DevCtx& d = h->devs[0];
+    HIPCHK(h, hipSetDevice(d.dev));
+    return read_maps(h, d, d.slots[(size_t)slot], which, buf, capacity_bytes, out_bytes);
+}
+
 
 int fxjps_debug_read_nbmask(fxjps_t* h, uint8_t* buf) {
     if (!h || !buf) return FXJPS_E_ARG;

@@ -6,8 +6,9 @@
 //   k_ccl_init / k_ccl_merge / k_ccl_flatten            4-connected components of the free cells (union-find forest)
 //   k_update_cells / k_ccl_update                       cell updates; small ones united into the forest
 //   k_prepare_grid / k_transpose_map                    the callers' grid preparation, wire / image adapters
-//   k_search<HC, TRK, DIRECT>                           one (start, goal) query per wavefront, whole A*+JPS on device
-//                                                       (heuristic; read-set recording; visited table indexed by the cell)
+//   k_search<HC, TRK, DIRECT, MG>                       one (start, goal) query per wavefront, whole A*+JPS on device
+//                                                       (heuristic; read-set recording; visited table indexed by the cell;
+//                                                       each query on the grid of its own slot)
 //   k_scan_len / k_gather_paths                         dense per-query path slots -> CSR
 //   k_waypoint_ccst                                     the ccst node's waypoint selection, one wavefront per path
 //   k_sqrt_selftest / k_selftest_wavemin / k_selftest_openlist   arithmetic and open-list proofs used by the tests
@@ -123,6 +124,9 @@ struct SearchArgs {
     uint32_t single = 0;          // one query, one wavefront, no work counter: (start, goal) = imm, results straight into the
     int32_t imm[4] = {0, 0, 0, 0};  // host's pinned buffers (the node's real call: jps1.method, one query per tick)
     unsigned long long* host_counters = nullptr;  // ... out_counters too: zeroed by the kernel, copied there when it is done (no memset, no copy back)
+    // k_search<.., .., .., true> (grid slots): query q runs on grids[grid_ids[q]] instead of G (the host checked every id)
+    const GridDev* grids = nullptr;     // [FXJPS_MAX_GRID_SLOTS] descriptors of the context's slots
+    const int32_t* grid_ids = nullptr;  // [nq]
 };
 
 // nodeNeighbours (jps1.py:49-93) as a table: entry [pd*256 + nbm] holds, for each of a node's 8 rays,
@@ -1220,7 +1224,7 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
 // Make sure the minimum of the open list is in R (the heappop of jps1.py:198 then reads lane 0).  Returns false when
 // the open list is empty.
 template <bool BANDED, bool NOCI = false>  // NOCI: nobody reads the entries' cell info (rays on the jump-distance records)
-__device__ __forceinline__ bool open_fill(const SearchArgs& A, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
+__device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
                                           int lane) {
     uint16_t* fci = far_ci(far, A.far_cap);
     bool topped = false;
@@ -1258,7 +1262,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, OpenList& Q, RTie
             const uint32_t rmask = (uint32_t)NBANDS - 1u;
             const auto cell_info = [&](uint32_t xyd) -> uint32_t {
                 if (NOCI) return 0u;
-                return A.G.ci[(size_t)((xyd >> 17) + 1u) * (size_t)A.G.NS + (size_t)(((xyd >> 4) & 0x1FFFu) + 1u)];
+                return G.ci[(size_t)((xyd >> 17) + 1u) * (size_t)G.NS + (size_t)(((xyd >> 4) & 0x1FFFu) + 1u)];
             };
             bool took = false;
             if (Q.far_n == 0) {  // (then the ring is not empty: the far tier is not)
@@ -2042,14 +2046,14 @@ __device__ __forceinline__ void expand_batch(const GridDev& G, uint32_t r0, uint
 
 // The whole of jps1.method (jps1.py:183-230) for one query on one wavefront.
 // Returns the result code; *res_cost is gscore[goal].
-template <int HC, bool TRK, bool DIRECT>
-__device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_t q, const int sx, const int sy, const int gx,
+template <int HC, bool TRK, bool DIRECT, bool MG>
+__device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev& Gq, const uint32_t q, const int sx, const int sy, const int gx,
                               const int gy, const Mid& S, TEnt* __restrict__ tab, FarEnt* __restrict__ far,
                               const uint32_t gen, double* res_cost, unsigned long long* cnt4) {
     // The map pointers, the table pointer and the scan-line stride are used in per-lane address arithmetic only, a
     // dozen times per iteration.  Held in SGPRs they were spilled (the kernel runs at the scalar-register limit) and
     // re-read with v_readlane before every use; kept in vector registers on purpose they are plain operands.
-    GridDev G = A.G;
+    GridDev G = Gq;  // (A.G, or the query's slot: k_search<.., .., .., true>)
     {
         uint64_t vbm = (uint64_t)G.bm, vci = (uint64_t)G.ci, vtab = (uint64_t)tab, vjd = (uint64_t)G.jd;
         int vwords = G.WORDS;
@@ -2158,7 +2162,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
         // instead of being recomputed at every loop head)
         // (the read-set instantiations on hashed tables have no registers to spare for those: there the values are
         // derived again where they are used -- held, two of them went to scratch)
-        if (!open_fill<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, JD2>(A, Q, R, S, far, (TRK && !DIRECT) ? lane : lane0)) break;  // (0, t): jps1.py:230
+        if (!open_fill<HC == 2 && !DIRECT && !TRK && FXJPS_BANDED != 0, JD2>(A, Gq, Q, R, S, far, (TRK && !DIRECT) ? lane : lane0)) break;  // (0, t): jps1.py:230
         if (FX_RARE(Q.fail != 0u)) {  // a region of the far band's ring is full: the large pool takes the query
             res_len = (uint32_t)QI_FAR_FULL;
             break;
@@ -2993,10 +2997,26 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const uint32_
     return (int32_t)rfl(res_len);
 }
 
-template <int HC, bool TRK, bool DIRECT>
+template <int HC, bool TRK, bool DIRECT, bool MG>
 __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q, const Mid& S, TEnt* __restrict__ tab,
                           FarEnt* __restrict__ far, uint32_t& gen) {
-    const GridDev& G = A.G;
+    // The grid: the handle's resident one, or (MG) the slot this query names -- its descriptor read once, with scalar loads
+    // (the id is wave-uniform; read through the constant address space, the descriptor's 80 bytes are scalar loads).
+    // Nothing else of the search depends on which grid a wavefront's previous queries ran on: every search writes its
+    // visited-table entries under a generation tag of its own and reads only entries with that tag (a cell-indexed slot
+    // x << direct_ly | y that another grid's search left behind carries an older tag and reads as empty), and the wipe at
+    // GEN_WRAP clears the whole per-wavefront table whatever its entries were.  direct_ly is sized by the host from the
+    // largest H of the slots in the batch, so every slot's cells fit the same table.
+    GridDev Gs;
+    if (MG) {
+        const int32_t gid = rfli(A.grid_ids[q]);
+        const auto* src = reinterpret_cast<__attribute__((address_space(4))) const uint32_t*>((uint64_t)(A.grids + gid));
+        uint32_t w[sizeof(GridDev) / 4];
+#pragma unroll
+        for (int i = 0; i < (int)(sizeof(GridDev) / 4); i++) w[i] = src[i];
+        __builtin_memcpy(&Gs, w, sizeof(GridDev));
+    }
+    const GridDev& G = MG ? Gs : A.G;
     const int lane = threadIdx.x & 63;
     const bool imm = A.single != 0u;
     const int sx = imm ? A.imm[0] : rfli(A.starts[2 * q]), sy = imm ? A.imm[1] : rfli(A.starts[2 * q + 1]);
@@ -3046,7 +3066,7 @@ __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q,
             A.qstat[4 * (size_t)q + 3] = (unsigned long long)(tab - A.tables) / ((size_t)BUCKET * A.nbuckets);
         }
         RECONV();
-        res_len = search_one<HC, TRK, DIRECT>(A, q, sx, sy, gx, gy, S, tab, far, gen, &res_cost, A.out_counters);
+        res_len = search_one<HC, TRK, DIRECT, MG>(A, G, q, sx, sy, gx, gy, S, tab, far, gen, &res_cost, A.out_counters);
         if (TRK) {  // hand the read set over (one row of each bitmap per lane) and clear it for the next query
             unsigned long long* dst = A.qread + (size_t)q * 128;
             dst[lane] = S.bx[lane];
@@ -3080,7 +3100,7 @@ __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q,
     RECONV();
 }
 
-template <int HC, bool TRK, bool DIRECT>
+template <int HC, bool TRK, bool DIRECT, bool MG>
 __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
     __shared__ WaveLds s_w[WPB];             // per wavefront: the M tier, transfer indices, collision detector
     __shared__ uint32_t s_dirlut[11 * 256];  // nodeNeighbours table: LDS latency instead of an L2 round trip per batch
@@ -3128,7 +3148,7 @@ __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
             if (qi >= A.nrun) break;
             q = A.order ? rfl(A.order[qi + A.q0]) : qi + A.q0;
         }
-        run_query<HC, TRK, DIRECT>(A, q, S, tab, far, gen);  // (ONE call site: the search is inlined here, once)
+        run_query<HC, TRK, DIRECT, MG>(A, q, S, tab, far, gen);  // (ONE call site: the search is inlined here, once)
         if (single) break;
     }
     if (lane == 0) A.wave_gen[wave] = gen;
@@ -3217,7 +3237,7 @@ __global__ __launch_bounds__(WAVE) void k_selftest_openlist(SearchArgs A, const 
     for (uint32_t st = 0; fail == 0u; st++) {
         open_uniform(Q);
         const bool scripted = st < nsteps;
-        const bool any = open_fill<BANDED>(A, Q, R, S, far, lane);
+        const bool any = open_fill<BANDED>(A, A.G, Q, R, S, far, lane);
         if (Q.fail != 0u) {
             fail = 2u;
             break;

@@ -287,6 +287,68 @@ class Planner(object):
         self.last_seconds = secs.value
         return offsets, cells, cost, status
 
+    # -- grid slots: several resident grids, one batch over all of them
+    def set_grid_slot(self, slot, matrix):
+        """Upload `matrix` (as set_grid takes it: matrix[x][y], obstacle iff == 1) into grid slot `slot`
+        (0 .. _lib.MAX_GRID_SLOTS - 1) and build its maps.  The resident grid is not touched."""
+        occ = as_occ(matrix)
+        if occ.ndim != 2:
+            raise ValueError("grid must be 2-D")
+        W, H = occ.shape
+        self._chk(self._L.fxjps_set_grid_slot(self._h, int(slot), _lib.ptr(occ, C.c_uint8), W, H))
+
+    def clear_grid_slot(self, slot):
+        """Release grid slot `slot` (its device memory goes back; a batch that names it is refused)."""
+        self._chk(self._L.fxjps_set_grid_slot(self._h, int(slot), None, 0, 0))
+
+    def get_grid_slot(self, slot):
+        """The uint8 [W][H] occupancy grid of slot `slot` (1 = obstacle)."""
+        W, H = C.c_int32(), C.c_int32()
+        self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), None, C.byref(W), C.byref(H)))
+        out = np.empty((W.value, H.value), dtype=np.uint8)
+        self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), _lib.ptr(out, C.c_uint8), None, None))
+        return out
+
+    def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
+        """plan_batch with a grid per query: query q runs on the grid of slot grid_ids[q].  -> (offsets, cells, cost,
+        status) as plan_batch.  max_path_len=None: the default slot of the largest grid named, grown when a path needs it."""
+        ids = np.ascontiguousarray(grid_ids, dtype=np.int32).reshape(-1)
+        starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 2)
+        goals = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
+        if len(starts) != len(goals) or len(ids) != len(starts):
+            raise ValueError("grid_ids, starts and goals lengths differ")
+        if hchoice not in (1, 2):
+            raise TypeError("unsupported operand type(s) for +: 'float' and 'NoneType' (hchoice must be 1 or 2)")
+        n = len(starts)
+        auto = max_path_len is None
+        if auto:  # (each referenced slot's own default and bound, the largest of them)
+            mpl, limit = 1, 1
+            for k in np.unique(ids):  # (an empty or unknown slot is the call's to refuse)
+                w, h = C.c_int32(), C.c_int32()
+                if 0 <= k < _lib.MAX_GRID_SLOTS and self._L.fxjps_get_grid_slot(self._h, int(k), None, C.byref(w), C.byref(h)) == 0:
+                    W, H = w.value, h.value
+                    mpl = max(mpl, int(min(W * H + 1, max(256, 4 * max(W, H)))))
+                    limit = max(limit, W * H + 1)
+        else:
+            mpl = int(max_path_len)
+        while True:
+            offsets = np.zeros(n + 1, dtype=np.int64)
+            status = np.zeros(n, dtype=np.int32)
+            cost = np.zeros(n, dtype=np.float64)
+            secs = C.c_double(0.0)
+            self._chk(self._L.fxjps_plan_batch_slots_csr(self._h, _lib.ptr(ids, C.c_int32), _lib.ptr(starts, C.c_int32),
+                                                         _lib.ptr(goals, C.c_int32), n, int(hchoice), mpl, _lib.ptr(offsets, C.c_int64),
+                                                         None, 0, _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double), C.byref(secs)))
+            cells = np.empty((int(offsets[n]), 2), dtype=np.int32)
+            if offsets[n] > 0:
+                self._chk(self._L.fxjps_last_cells(self._h, _lib.ptr(cells, C.c_int32), int(offsets[n])))
+            if auto and mpl < limit and (status == _lib.Q_PATH_TOO_LONG).any():
+                mpl = min(limit, mpl * 8)  # rare: a path with more jump points than the default slot
+                continue
+            break
+        self.last_seconds = secs.value
+        return offsets, cells, cost, status
+
     # -- streaming replan (persistent goals, one call per frame)
     def set_queries(self, starts, goals, hchoice=2, max_path_len=None):
         """Store the persistent (start, goal) set that replan_frame plans every frame."""
@@ -426,6 +488,16 @@ class Planner(object):
         "comp": int32[W, H] (union-find parent links), "nb8": uint8[W+2, H+2], "dbm": uint64[4, W+H+3, WORDS, 2] (the
         diagonal scan words), "jd": uint16[W+2, H+2, 8] (the jump distances)}."""
         W, H = self.shape
+        return self._read_maps(W, H, lambda which, buf, cap, nb: self._L.fxjps_debug_read_maps(self._h, which, buf, cap, nb))
+
+    def debug_slot_maps(self, slot):
+        """The derived device maps of grid slot `slot` (fxjps_debug_read_slot_maps), as debug_maps() returns them."""
+        W, H = C.c_int32(), C.c_int32()
+        self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), None, C.byref(W), C.byref(H)))
+        return self._read_maps(W.value, H.value,
+                               lambda which, buf, cap, nb: self._L.fxjps_debug_read_slot_maps(self._h, int(slot), which, buf, cap, nb))
+
+    def _read_maps(self, W, H, read):
         PW, PH = W + 2, H + 2
         NS = (PH + 63) & ~63
         LINES = max(PW, PH)
@@ -435,7 +507,7 @@ class Planner(object):
                                        (3, "nb8", np.uint8, (PW, NS)), (4, "dbm", np.uint64, (4, PW + PH - 1, WORDS, 2)), (5, "jd", np.uint16, (PW, NS, 8))):
             a = np.zeros(shape, dtype=dt)
             nb = C.c_int64(0)
-            self._chk(self._L.fxjps_debug_read_maps(self._h, which, a.ctypes.data_as(C.c_void_p), a.nbytes, C.byref(nb)))
+            self._chk(read(which, a.ctypes.data_as(C.c_void_p), a.nbytes, C.byref(nb)))
             assert nb.value == a.nbytes, (name, nb.value, a.nbytes)
             out[name] = a[:, :PH] if name in ("ci", "nb8", "jd") else a
         # (lines the kernels neither write nor read -- the +-x scans have a line per padded y, the +-y scans per padded

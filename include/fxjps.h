@@ -74,8 +74,10 @@ typedef struct fxjps fxjps_t;
  *   600  round 6: fxjps_get_grid_context (the resident grid of ONE context of a multi-device handle: what a host compares
  *        after the broadcast); the library exports nothing but the functions of this header (-fvisibility=hidden + an
  *        export map); the text of a failed fxjps_create* is kept per calling thread.
+ *   700  grid slots: fxjps_set_grid_slot, fxjps_get_grid_slot, fxjps_plan_batch_slots_csr (one batch, each query on the
+ *        grid of the slot it names), fxjps_debug_read_slot_maps.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 600
+#define FXJPS_VERSION 700
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -227,6 +229,26 @@ int fxjps_plan_batch_csr(fxjps_t* h, const int32_t* starts_xy, const int32_t* go
 /* Copy the jump points of the most recent batch (CSR order) into out_cells_xy. */
 int fxjps_last_cells(fxjps_t* h, int32_t* out_cells_xy, int64_t cells_capacity);
 
+/* ---- Grid slots: several resident grids per handle, one batch over all of them (e.g. one prepared map per vehicle). */
+#define FXJPS_MAX_GRID_SLOTS 256
+/* Upload an occupancy grid into slot `slot` (0 .. FXJPS_MAX_GRID_SLOTS-1), with the same conventions and limits as
+ * fxjps_set_grid (1..8190 a side), and build its derived maps.  occ == NULL releases the slot.  Slots and the
+ * resident grid are independent: neither call touches the other.  A handle with several contexts holds every slot on
+ * every context.  A rank handle (fxjps_create_rank, world > 1) refuses with FXJPS_E_ARG. */
+int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W, int32_t H);
+/* The occupancy bytes [W][H] of a slot (out == NULL: the extents only); FXJPS_E_ARG for an empty slot. */
+int fxjps_get_grid_slot(fxjps_t* h, int32_t slot, uint8_t* out, int32_t* out_W, int32_t* out_H);
+/* Like fxjps_plan_batch_csr, but query q is planned on the grid of slot grid_ids[q].  Bounds (BAD_START, a goal off
+ * the grid), the component early-out and max_path_len apply per query against THAT grid.  If any grid_id is out of
+ * range or names an empty slot, the call returns FXJPS_E_ARG, queues nothing, and fxjps_last_error names the first
+ * such query.  fxjps_last_cells, fxjps_last_timing* and fxjps_debug_counters describe it as they describe any batch; it
+ * drops the stored results of fxjps_set_queries / fxjps_replan_frame; fxjps_waypoint_ccst_batch without explicit paths
+ * refuses to run on its paths (they were not planned on the resident grid). */
+int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy,
+                               int64_t nq, int32_t hchoice, int32_t max_path_len, int64_t* out_offsets,
+                               int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len, double* out_cost,
+                               double* out_seconds_total);
+
 /* Measurement hooks (bench.py, tests). */
 typedef struct fxjps_timing {
     double search_kernel_ms; /* HIP-event time of the search kernel launches of the last batch */
@@ -312,6 +334,8 @@ int fxjps_debug_read_nbmask(fxjps_t* h, uint8_t* buf);
  * directions in the order (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1)).  out_bytes receives the size;
  * buf == NULL: the size only. */
 int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
+/* Like fxjps_debug_read_maps, for a slot (tests compare it byte for byte with a fresh fxjps_set_grid). */
+int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
 
 /* Measurement aids of tools/ (not used by the planner's Python host code).  fxjps_debug_counters: the 64 raw device
  * counters of the last batch on the first context ([0] pops, [1] pushes, [2] far refills, [3] slow pops, [7] table wipes;
@@ -346,7 +370,9 @@ int fxjps_waypoint_ccst(const int32_t* cells, int32_t n, const uint8_t* occ, int
 
 /* ---- The same for every path of a batch.  offsets / cells_xy: the paths as fxjps_plan_batch_csr returns them (nq + 1
  * offsets, (x, y) pairs); both NULL: the paths of the handle's most recent batch, which are still resident on the
- * device(s) -- nq must be that batch's.  A query without a path gets the goal as its waypoint (`wp = global_goal`,
+ * device(s) -- nq must be that batch's (after a grid-slots batch: fxjps_waypoint_st_batch takes its paths, which lie
+ * within the largest slot it named; fxjps_waypoint_ccst_batch refuses with FXJPS_E_ARG, its line tests read the
+ * resident grid).  A query without a path gets the goal as its waypoint (`wp = global_goal`,
  * scripts/global_planner_st.py:287-290, scripts/global_planner_ccst.py:481-485).  pos, goal, out_wp, out_goal are nq x 3
  * doubles, end_occu nq flags (NULL: all 0), reso and origin one value for the batch (one grid).
  *

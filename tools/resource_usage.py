@@ -9,13 +9,14 @@ for line in sys.stdin:
         cur = m.group(1)
         rows[cur] = {}
         continue
-    m = re.search(r'remark:\s+(.*?): (\S+) \[-Rpass', line)
+    # ("remark: file:line:col: Key: value" or "file:line:col: remark: Key: value", by hipcc's mode)
+    m = re.search(r':\s+([A-Za-z][^:]*?): (\S+) \[-Rpass', line)
     if m and cur:
         rows[cur][m.group(1).strip()] = m.group(2)
 keys = ('TotalSGPRs', 'VGPRs', 'AGPRs', 'SGPRs Spill', 'VGPRs Spill', 'ScratchSize [bytes/lane]', 'Occupancy [waves/SIMD]', 'LDS Size [bytes/block]')
 print("kernel," + ",".join(keys))
 for k, v in sorted(rows.items()):
     if 'k_search' in k:
-        m = re.search(r'k_searchILi(\d)ELb(\d)ELb(\d)E', k)
-        name = "k_search<%s,%s,%s>" % (m.group(1), "true" if m.group(2) == "1" else "false", "true" if m.group(3) == "1" else "false") if m else k
+        m = re.search(r'k_searchILi(\d)((?:ELb\d)+)E', k)
+        name = "k_search<%s,%s>" % (m.group(1), ",".join("true" if b == "1" else "false" for b in re.findall(r'ELb(\d)', m.group(2)))) if m else k
         print(name + "," + ",".join(v.get(a, "") for a in keys))
