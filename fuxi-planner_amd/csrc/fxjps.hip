@@ -1703,7 +1703,8 @@ int fxjps_set_grid(fxjps_t* h, const uint8_t* occ, int32_t W, int32_t H) {
     // the search of the same tick is queued right behind them, no host wait in between (round 6: 437 -> ~ 300 us for a tick
     // whose map changed; the caller's buffer is its own again when the call returns, as the ABI promises).  An error of the
     // build itself would surface at the next call that waits.  FXJPS_SETGRID_WAIT=1: wait as before (test / measurement aid).
-    static const bool always_wait = getenv("FXJPS_SETGRID_WAIT") && atoi(getenv("FXJPS_SETGRID_WAIT")) != 0;
+    const char* wait_env = getenv("FXJPS_SETGRID_WAIT");  // (read per call, as FXJPS_FUSED_BUILD: the tests take both paths in one process)
+    const bool always_wait = wait_env && atoi(wait_env) != 0;
     const size_t bytes = (size_t)W * H;
     if (h->devs.size() == 1 && bytes <= ((size_t)1 << 18) && !always_wait && d0.ev_stage != nullptr) {
         if (d0.stage_pending) HIPCHK(h, hipEventSynchronize(d0.ev_stage));  // (the previous grid has left the buffer)

@@ -326,13 +326,26 @@ int fxjps_debug_read_nbmask(fxjps_t* h, uint8_t* buf);
 
 /* The derived device maps as they are (tests compare them after cell updates -- which rebuild only what the changed
  * cells can reach -- with those of a fresh upload): which = 0 the scan words ([4][LINES][WORDS] pairs of u64 {stop, occ},
- * LINES = max(W, H) + 2, WORDS = ceil(LINES / 64)), 1 the cell infos (u16 [W + 2][NS], NS = H + 2 rounded up to 64; the
- * columns from H + 2 on are unused), 2 the component forest (int32 [W][H]: parent links, a root points at itself, -1
- * never free), 3 the neighbour bytes ([W + 2][NS]), 4 the diagonal scan words ([4][W + H + 3][WORDS] pairs of u64 {stop, occ}:
- * travel directions (+,+), (-,-), (+,-), (-,+), one line per diagonal, bit = padded x), 5 the jump distances (u16
- * [W + 2][NS][8]: per cell and direction, steps to the cell that ends the goal-free jump | "it is a jump point" << 15;
- * directions in the order (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1)).  out_bytes receives the size;
- * buf == NULL: the size only. */
+ * LINES = max(W, H) + 2, WORDS = ceil(LINES / 64); travel directions +x, -x (line = padded y, bit = padded x), +y, -y
+ * (line = padded x, bit = padded y); occ = the cell is occupied, the 1-cell border and every position past it counted
+ * occupied; stop = occ, or the cell has a forced neighbour for that travel direction), 1 the cell infos (u16 [W + 2][NS],
+ * NS = H + 2 rounded up to 64; the columns from H + 2 on are unused.  Bits 0-7 the neighbour byte; on free cells only,
+ * bits 8-11 "the goal-free straight jump from here along +x, -x, +y, -y finds a jump point", bits 12-13 / 14-15 the
+ * read-set tiles its +-x / +-y rays reach beyond the cell's own, at most 3: max(tile(end of the + ray) - tile(p),
+ * tile(p) - tile(end of the - ray), 0) with p the padded coordinate, tile(p) = min(max((p - 1) >> tsh, 0), 63), tsh the
+ * least shift with (max(W, H) - 1) >> tsh <= 63), 2 the component forest (int32 [W][H]: parent links, a root points at
+ * itself, -1 never free since the last full labelling), 3 the neighbour bytes ([W + 2][NS]: bit k = the k-th neighbour
+ * in the direction order below is occupied, the border and beyond counted occupied), 4 the diagonal scan words
+ * ([4][W + H + 3][WORDS] pairs of u64 {stop, occ}: travel directions (+,+), (-,-), (+,-), (-,+), line px - py + H + 1
+ * for (+,+) / (-,-) and px + py for the others, bit = padded x; occ = occupied or squeezed (jps1.py dblock), stop = free
+ * and (a forced neighbour, or the goal-free straight jump along either axis of the direction finds a jump point);
+ * positions off the diagonal occ = 1, stop = 0), 5 the jump distances (u16 [W + 2][NS][8]: per cell and direction, bits
+ * 0-12 the Chebyshev steps to the cell on which the goal-free jump returned -- its jump point, or the cell that ended it
+ * -- | "it is a jump point" << 15; bits 13-14 of the first four entries carry the cell's neighbour byte, two bits each:
+ * entry s holds bits 2s and 2s + 1; the border's records are 0; directions in the order (-1,-1), (-1,0), (-1,1), (0,-1),
+ * (0,1), (1,-1), (1,0), (1,1)).  Deferred cell updates (fxjps_update_cells_deferred) are rebuilt into the maps -- and a
+ * full relabelling they asked for is run -- before they are read.  out_bytes receives the size; buf == NULL: the size
+ * only. */
 int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
 /* Like fxjps_debug_read_maps, for a slot (tests compare it byte for byte with a fresh fxjps_set_grid). */
 int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);

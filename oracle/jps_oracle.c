@@ -35,6 +35,7 @@ typedef struct {
     int32_t W, H;
     int32_t gx, gy;
     int literal;
+    const uint8_t* memo; /* jump(): straight sub-jump results [W][H][8] (found), NULL: recurse */
     fxo_stats st;
     /* per-cell state */
     double* g;
@@ -148,72 +149,77 @@ static int dblock(ws_t* w, int32_t cX, int32_t cY, int32_t dX, int32_t dY) {
 
 static inline int32_t sgn(int32_t v) { return (v > 0) - (v < 0); }
 
-/* jps1.py:95-164.  Returns 1 and (*rx,*ry) for a jump point, 0 for None. */
+/* The test each loop of jump() makes first at the cell (oX, oY) it stands on: a forced neighbour for travel along
+ * (dX, dY) -- jps1.py:110-113 (diagonal), :134-137 (along x), :150-153 (along y). */
+static int forced(ws_t* w, int32_t oX, int32_t oY, int32_t dX, int32_t dY) {
+    if (dX != 0 && dY != 0)
+        return (!blocked(w, oX, oY, -dX, dY) && blocked(w, oX, oY, -dX, 0)) ||
+               (!blocked(w, oX, oY, dX, -dY) && blocked(w, oX, oY, 0, -dY));
+    if (dX != 0)
+        return (!blocked(w, oX, oY, dX, 1) && blocked(w, oX, oY, 0, 1)) ||
+               (!blocked(w, oX, oY, dX, -1) && blocked(w, oX, oY, 0, -1));
+    return (!blocked(w, oX, oY, 1, dY) && blocked(w, oX, oY, 1, 0)) ||
+           (!blocked(w, oX, oY, -1, dY) && blocked(w, oX, oY, -1, 0));
+}
+
+/* direction (dX, dY) -> its slot in a jump table: (-1,-1) 0, (-1,0) 1, (-1,1) 2, (0,-1) 3, (0,1) 4, (1,-1) 5, (1,0) 6,
+ * (1,1) 7 -- the order of the neighbour-mask bits and of the library's jump-distance records */
+static inline int dslot(int32_t dX, int32_t dY) {
+    const int k = (dX + 1) * 3 + (dY + 1);
+    return k > 4 ? k - 1 : k;
+}
+
+/* jps1.py:95-164.  Returns 1 and (*rx,*ry) for a jump point, 0 for None; on None (*rx,*ry) is the cell on which the
+ * loop returned (:99, :123, :126 or the straight loops' blocked test -- possibly off the grid).  w->memo (goal-free
+ * jump tables only, fxo_jump_table): the straight sub-jumps of the diagonal loop (:116-117) are looked up in the
+ * straight-direction entries already computed instead of recursing. */
 static int jump(ws_t* w, int32_t cX, int32_t cY, int32_t dX, int32_t dY, int32_t* rx, int32_t* ry) {
     w->st.jumps++;
     int32_t nX = cX + dX, nY = cY + dY;
+    *rx = nX;
+    *ry = nY;
     if (blocked(w, nX, nY, 0, 0)) return 0; /* :99 */
-    if (nX == w->gx && nY == w->gy) {       /* :102 */
-        *rx = nX;
-        *ry = nY;
-        return 1;
-    }
+    if (nX == w->gx && nY == w->gy) return 1; /* :102 */
     int32_t oX = nX, oY = nY;
     if (dX != 0 && dY != 0) { /* :108-130 */
         for (;;) {
-            if ((!blocked(w, oX, oY, -dX, dY) && blocked(w, oX, oY, -dX, 0)) ||
-                (!blocked(w, oX, oY, dX, -dY) && blocked(w, oX, oY, 0, -dY))) {
-                *rx = oX;
-                *ry = oY;
-                return 1;
-            }
+            *rx = oX;
+            *ry = oY;
+            if (forced(w, oX, oY, dX, dY)) return 1; /* :110-114 */
             int32_t tx, ty;
-            if (jump(w, oX, oY, dX, 0, &tx, &ty) || jump(w, oX, oY, 0, dY, &tx, &ty)) { /* :116-118 */
-                *rx = oX;
-                *ry = oY;
+            if (w->memo) { /* :116-118 from the table */
+                const uint8_t* f = w->memo + ((size_t)oX * (size_t)w->H + (size_t)oY) * 8;
+                if (f[dslot(dX, 0)] || f[dslot(0, dY)]) return 1;
+            } else if (jump(w, oX, oY, dX, 0, &tx, &ty) || jump(w, oX, oY, 0, dY, &tx, &ty)) { /* :116-118 */
                 return 1;
             }
             oX += dX;
             oY += dY;
-            if (blocked(w, oX, oY, 0, 0)) return 0;   /* :123 */
-            if (dblock(w, oX, oY, dX, dY)) return 0;  /* :126 */
-            if (oX == w->gx && oY == w->gy) {         /* :129 */
-                *rx = oX;
-                *ry = oY;
-                return 1;
-            }
+            *rx = oX;
+            *ry = oY;
+            if (blocked(w, oX, oY, 0, 0)) return 0;  /* :123 */
+            if (dblock(w, oX, oY, dX, dY)) return 0; /* :126 */
+            if (oX == w->gx && oY == w->gy) return 1; /* :129 */
         }
     } else if (dX != 0) { /* :132-146 */
         for (;;) {
-            if ((!blocked(w, oX, nY, dX, 1) && blocked(w, oX, nY, 0, 1)) ||
-                (!blocked(w, oX, nY, dX, -1) && blocked(w, oX, nY, 0, -1))) {
-                *rx = oX;
-                *ry = nY;
-                return 1;
-            }
+            *rx = oX;
+            *ry = nY;
+            if (forced(w, oX, nY, dX, 0)) return 1;
             oX += dX;
+            *rx = oX;
             if (blocked(w, oX, nY, 0, 0)) return 0;
-            if (oX == w->gx && nY == w->gy) {
-                *rx = oX;
-                *ry = nY;
-                return 1;
-            }
+            if (oX == w->gx && nY == w->gy) return 1;
         }
     } else { /* :148-162 */
         for (;;) {
-            if ((!blocked(w, nX, oY, 1, dY) && blocked(w, nX, oY, 1, 0)) ||
-                (!blocked(w, nX, oY, -1, dY) && blocked(w, nX, oY, -1, 0))) {
-                *rx = nX;
-                *ry = oY;
-                return 1;
-            }
+            *rx = nX;
+            *ry = oY;
+            if (forced(w, nX, oY, 0, dY)) return 1;
             oY += dY;
+            *ry = oY;
             if (blocked(w, nX, oY, 0, 0)) return 0;
-            if (nX == w->gx && oY == w->gy) {
-                *rx = nX;
-                *ry = oY;
-                return 1;
-            }
+            if (nX == w->gx && oY == w->gy) return 1;
         }
     }
 }
@@ -434,6 +440,114 @@ int fxo_plan_batch(const uint8_t* occ, int32_t W, int32_t H, const int32_t* star
     }
     if (nthreads > 1)
         for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+    return 0;
+}
+
+/* ---- derived maps, recomputed on the host (tests/test_derived_maps_*.py) ---- */
+typedef struct {
+    const uint8_t* occ;
+    int32_t W, H, x0, x1, s0, s1, literal;
+    const int* slots;
+    uint8_t* found;
+    uint16_t* k;
+    uint8_t* flags;
+} jt_job_t;
+
+static const int k_straight[4] = {1, 3, 4, 6}, k_diagonal[4] = {0, 2, 5, 7};
+
+/* squeezed (jps1.py:34-38) with the cells off the grid counted occupied, as the library's padded maps count them */
+static int dblock_padded(ws_t* w, int32_t x, int32_t y, int32_t dX, int32_t dY) {
+    const int inx = x - dX >= 0 && x - dX < w->W, iny = y - dY >= 0 && y - dY < w->H;
+    if (inx && iny) return dblock(w, x, y, dX, dY);
+    if (inx) return M1(w, x - dX, y);
+    if (iny) return M1(w, x, y - dY);
+    return 1;
+}
+
+static void* jt_worker(void* arg) {
+    jt_job_t* j = (jt_job_t*)arg;
+    ws_t w;
+    memset(&w, 0, sizeof(w));
+    w.occ = j->occ;
+    w.W = j->W;
+    w.H = j->H;
+    w.gx = -1000000; /* a goal off the grid: no cell ever matches it */
+    w.gy = -1000000;
+    if (!j->literal) w.memo = j->found;
+    for (int32_t x = j->x0; x < j->x1; x++)
+        for (int32_t y = 0; y < j->H; y++) {
+            const size_t c = ((size_t)x * (size_t)j->H + (size_t)y) * 8;
+            for (int t = j->s0; t < j->s1; t++) {
+                const int s = j->slots[t];
+                const int code = s + (s >= 4), dX = code / 3 - 1, dY = code % 3 - 1;
+                int32_t rx, ry;
+                const int f = jump(&w, x, y, dX, dY, &rx, &ry);
+                const int32_t ax = rx > x ? rx - x : x - rx, ay = ry > y ? ry - y : y - ry;
+                j->found[c + s] = (uint8_t)f;
+                j->k[c + s] = (uint16_t)(ax > ay ? ax : ay);
+                if (j->flags)
+                    j->flags[c + s] = (uint8_t)(forced(&w, x, y, dX, dY) | ((dX != 0 && dY != 0 && dblock_padded(&w, x, y, dX, dY)) << 1));
+            }
+        }
+    return NULL;
+}
+
+static void jt_run(jt_job_t* proto, int s0, int s1, int32_t nthreads) {
+    pthread_t th[16];
+    jt_job_t jobs[16];
+    for (int t = 0; t < nthreads; t++) {
+        jobs[t] = *proto;
+        jobs[t].x0 = (int32_t)((int64_t)proto->W * t / nthreads);
+        jobs[t].x1 = (int32_t)((int64_t)proto->W * (t + 1) / nthreads);
+        jobs[t].s0 = s0;
+        jobs[t].s1 = s1;
+        if (nthreads == 1)
+            jt_worker(&jobs[t]);
+        else
+            pthread_create(&th[t], NULL, jt_worker, &jobs[t]);
+    }
+    if (nthreads > 1)
+        for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+}
+
+int fxo_jump_table(const uint8_t* occ, int32_t W, int32_t H, int32_t literal, uint8_t* out_found, uint16_t* out_k,
+                   uint8_t* out_flags, int32_t nthreads) {
+    if (W < 1 || H < 1 || W > 65534 || H > 65534) return FXO_ERR_BAD_ARG;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if (nthreads > W) nthreads = W;
+    jt_job_t proto = {occ, W, H, 0, 0, 0, 0, literal, NULL, out_found, out_k, out_flags};
+    proto.slots = k_straight; /* the straight entries first: the memoised diagonal loop reads them */
+    jt_run(&proto, 0, 4, nthreads);
+    proto.slots = k_diagonal;
+    jt_run(&proto, 0, 4, nthreads);
+    return 0;
+}
+
+int fxo_components(const uint8_t* occ, int32_t W, int32_t H, int32_t* out_label) {
+    const size_t n = (size_t)W * (size_t)H;
+    int32_t* q = (int32_t*)malloc((n ? n : 1) * sizeof(int32_t));
+    if (!q) return FXO_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++) out_label[i] = -1;
+    for (size_t i = 0; i < n; i++) {
+        if (occ[i] || out_label[i] >= 0) continue;
+        size_t head = 0, tail = 0;
+        out_label[i] = (int32_t)i; /* BFS from the first cell of the component in index order */
+        q[tail++] = (int32_t)i;
+        while (head < tail) {
+            const int32_t c = q[head++], x = c / H, y = c % H;
+            const int32_t nbr[4][2] = {{x - 1, y}, {x + 1, y}, {x, y - 1}, {x, y + 1}};
+            for (int k = 0; k < 4; k++) {
+                const int32_t ax = nbr[k][0], ay = nbr[k][1];
+                if (ax < 0 || ay < 0 || ax >= W || ay >= H) continue;
+                const int32_t a = ax * H + ay;
+                if (occ[a] || out_label[a] >= 0) continue;
+                out_label[a] = (int32_t)i;
+                q[tail++] = a;
+            }
+        }
+    }
+    free(q);
     return 0;
 }
 

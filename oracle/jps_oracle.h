@@ -58,6 +58,24 @@ int fxo_plan_batch(const uint8_t* occ, int32_t W, int32_t H,
                    int32_t* out_cells_xy, int32_t* out_len, double* out_cost,
                    fxo_stats* stats, int32_t nthreads);
 
+/* Goal-free jump table (what the library's derived maps are checked against).  For every cell (x, y) of the grid and
+ * every direction slot s -- (-1,-1) 0, (-1,0) 1, (-1,1) 2, (0,-1) 3, (0,1) 4, (1,-1) 5, (1,0) 6, (1,1) 7 -- jump()
+ * with a goal off the grid:
+ *   out_found[(x*H + y)*8 + s]  1: it returned a jump point, 0: None;
+ *   out_k[...]                  Chebyshev distance from (x, y) to the cell on which it returned: the jump point, or
+ *                               the cell of jps1.py:99 / :123 / :126 / the straight loops' blocked test (maybe off the
+ *                               grid);
+ *   out_flags[...] (may be NULL) bit 0 the forced-neighbour test of jump()'s loop at (x, y) for that direction,
+ *                               bit 1 (diagonals) dblock at (x, y), jps1.py:34-38, cells off the grid counted occupied.
+ * literal == 0: the diagonal loop looks its straight sub-jumps (:116-117) up in the straight entries computed first;
+ * != 0: it recurses as jps1.py does (quadratic on open maps).  Sides up to 65534; at most 16 threads.  Returns 0. */
+int fxo_jump_table(const uint8_t* occ, int32_t W, int32_t H, int32_t literal, uint8_t* out_found, uint16_t* out_k,
+                   uint8_t* out_flags, int32_t nthreads);
+
+/* 4-connected components of the free cells: out_label[x*H + y] = the smallest index x*H + y of the cell's component,
+ * -1 for an occupied cell.  Returns 0. */
+int fxo_components(const uint8_t* occ, int32_t W, int32_t H, int32_t* out_label);
+
 /* Synthetic inputs: counter-based splitmix64. */
 uint64_t fxo_splitmix64(uint64_t x);
 void fxo_synth_grid(uint8_t* occ, int32_t W, int32_t H, uint64_t seed, double p);

@@ -51,6 +51,11 @@ def lib():
         L.fxo_plan_batch.argtypes = [p_u8, C.c_int32, C.c_int32, p_i32, p_i32, C.c_int64,
                                      C.c_int32, C.c_int32, C.c_int32, p_i32, p_i32, p_f64,
                                      C.c_void_p, C.c_int32]
+        L.fxo_jump_table.restype = C.c_int
+        L.fxo_jump_table.argtypes = [p_u8, C.c_int32, C.c_int32, C.c_int32, p_u8, C.POINTER(C.c_uint16), C.c_void_p,
+                                     C.c_int32]
+        L.fxo_components.restype = C.c_int
+        L.fxo_components.argtypes = [p_u8, C.c_int32, C.c_int32, p_i32]
         L.fxo_splitmix64.restype = C.c_uint64
         L.fxo_splitmix64.argtypes = [C.c_uint64]
         L.fxo_synth_grid.restype = None
@@ -109,6 +114,33 @@ def plan_batch(matrix, starts, goals, hchoice=2, literal=False, max_len=1024, nt
                          _ptr(cost, C.c_double),
                          stats.ctypes.data_as(C.c_void_p) if want_stats else None, int(nthreads))
     return cells, length, cost, stats
+
+
+def jump_table(occ, literal=False, nthreads=16, flags=False):
+    """The goal-free jump() of every cell and direction (fxo_jump_table): -> (found uint8[W, H, 8], k uint16[W, H, 8])
+    and, with flags=True, flags uint8[W, H, 8] (bit 0 forced neighbour, bit 1 dblock).  Directions in the slot order
+    (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1); k = Chebyshev distance to the cell the jump returned
+    on.  literal=True: the diagonal loop recurses into its straight sub-jumps as jps1.py does."""
+    occ = np.ascontiguousarray(occ, dtype=np.uint8)
+    W, H = occ.shape
+    found = np.zeros((W, H, 8), dtype=np.uint8)
+    k = np.zeros((W, H, 8), dtype=np.uint16)
+    fl = np.zeros((W, H, 8), dtype=np.uint8) if flags else None
+    rc = lib().fxo_jump_table(_ptr(occ, C.c_uint8), W, H, 1 if literal else 0, _ptr(found, C.c_uint8),
+                              _ptr(k, C.c_uint16), fl.ctypes.data_as(C.c_void_p) if flags else None, int(nthreads))
+    if rc != 0:
+        raise ValueError("oracle error %d" % rc)
+    return (found, k, fl) if flags else (found, k)
+
+
+def components(occ):
+    """4-connected components of the free cells (fxo_components): int32[W, H], the smallest flat index x*H + y of the
+    cell's component, -1 on occupied cells."""
+    occ = np.ascontiguousarray(occ, dtype=np.uint8)
+    W, H = occ.shape
+    lab = np.empty((W, H), dtype=np.int32)
+    lib().fxo_components(_ptr(occ, C.c_uint8), W, H, _ptr(lab, C.c_int32))
+    return lab
 
 
 def synth_grid(W, H, seed, p=0.20):
