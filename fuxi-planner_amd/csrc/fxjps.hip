@@ -2763,6 +2763,25 @@ int fxjps_debug_qstat(fxjps_t* h, unsigned long long* out, int64_t nq) {
     return FXJPS_OK;
 }
 
+// the read sets of the stored results (tests): what fxjps_replan_frame tests the next frame's updates against
+int fxjps_debug_read_sets(fxjps_t* h, uint64_t* out, int64_t nq, int32_t* out_tile_shift) {
+    if (!h || !out || !out_tile_shift) return FXJPS_E_ARG;
+    if (!h->q_results_valid) return fail(h, FXJPS_E_ARG, "no tracked results: the last call was not a tracked fxjps_replan_frame");
+    int64_t total = 0;
+    for (auto& d : h->devs) total += d.nq;
+    if (nq != total) return fail(h, FXJPS_E_ARG, "the stored results hold %lld queries, not %lld", (long long)total, (long long)nq);
+    for (auto& d : h->devs) {  // (shard order: the contexts' q0 ascend)
+        uint64_t* dst = out + (size_t)d.q0 * 128;
+        const size_t n = (size_t)d.nq * 128;
+        if (d.h_qread.size() >= n)
+            memcpy(dst, d.h_qread.data(), n * sizeof(uint64_t));
+        else  // (no tracked search ever ran on this context: every query it holds ended without one)
+            memset(dst, 0, n * sizeof(uint64_t));
+    }
+    *out_tile_shift = h->devs[0].tsh;
+    return FXJPS_OK;
+}
+
 int fxjps_selftest_wavemin(fxjps_t* h, int32_t rounds, uint64_t seed, int64_t* mismatches) {
     if (!h || !mismatches || rounds < 1 || rounds > (1 << 16)) return FXJPS_E_ARG;
     DevCtx& d = h->devs[0];

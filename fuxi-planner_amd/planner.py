@@ -516,6 +516,14 @@ class Planner(object):
         out["bm"][2:4, PW:] = 0
         return out
 
+    def debug_read_sets(self):
+        """The read sets of the stored results of replan_frame (fxjps_debug_read_sets): -> (uint64[nq, 128], tsh).  Tile
+        (tx, ty) of (1 << tsh)^2 cells is marked for query q iff bit tx of [q, ty] or bit ty of [q, 64 + tx] is set."""
+        out = np.zeros((self._nq, 128), dtype=np.uint64)
+        tsh = C.c_int32(-1)
+        self._chk(self._L.fxjps_debug_read_sets(self._h, _lib.ptr(out, C.c_uint64), self._nq, C.byref(tsh)))
+        return out, tsh.value
+
     def debug_nbmask(self):
         W, H = self.shape
         buf = np.empty((W + 2, H + 2), dtype=np.uint8)

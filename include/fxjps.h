@@ -76,8 +76,9 @@ typedef struct fxjps fxjps_t;
  *        export map); the text of a failed fxjps_create* is kept per calling thread.
  *   700  grid slots: fxjps_set_grid_slot, fxjps_get_grid_slot, fxjps_plan_batch_slots_csr (one batch, each query on the
  *        grid of the slot it names), fxjps_debug_read_slot_maps.
+ *   710  fxjps_debug_read_sets (the read sets behind fxjps_replan_frame's exact reuse, for tests).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 700
+#define FXJPS_VERSION 710
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -349,6 +350,15 @@ int fxjps_debug_read_nbmask(fxjps_t* h, uint8_t* buf);
 int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
 /* Like fxjps_debug_read_maps, for a slot (tests compare it byte for byte with a fresh fxjps_set_grid). */
 int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
+/* The read sets of the stored results of fxjps_replan_frame (tests check them against the cells the reference reads): the
+ * grid is covered by tiles of (1 << tsh) cells a side, tsh the least shift with (max(W, H) - 1) >> tsh <= 63; for query
+ * q (the order of fxjps_set_queries) out[q * 128 + ty] has bit tx set and / or out[q * 128 + 64 + tx] bit ty set for
+ * every tile (tx, ty) its last search marked.  The next frame returns q without a search iff q has a path and no update
+ * touches a marked tile, an update of cell (x, y) touching the tiles of [max(x-1, 0), min(x+1, W-1)] x [max(y-1, 0),
+ * min(y+1, H-1)].  A query that ended without a search (no path, start == goal) holds whatever its slot held before.
+ * nq must be the number of stored queries; *out_tile_shift receives tsh.  FXJPS_E_ARG unless the
+ * stored results are tracked (the last call was a fxjps_replan_frame that recorded read sets). */
+int fxjps_debug_read_sets(fxjps_t* h, uint64_t* out, int64_t nq, int32_t* out_tile_shift);
 
 /* Measurement aids of tools/ (not used by the planner's Python host code).  fxjps_debug_counters: the 64 raw device
  * counters of the last batch on the first context ([0] pops, [1] pushes, [2] far refills, [3] slow pops, [7] table wipes;

@@ -36,6 +36,7 @@ typedef struct {
     int32_t gx, gy;
     int literal;
     const uint8_t* memo; /* jump(): straight sub-jump results [W][H][8] (found), NULL: recurse */
+    uint8_t* rbits;      /* read set: bit x*H + y set by every read of cell (x, y) (fxo_read_sets), NULL: not recorded */
     fxo_stats st;
     /* per-cell state */
     double* g;
@@ -121,8 +122,10 @@ static hent hpop(ws_t* w) {
 
 /* matrix[x][y] == 1 with one counted element read */
 static inline int M1(ws_t* w, int32_t x, int32_t y) {
+    const size_t i = (size_t)x * (size_t)w->H + (size_t)y;
     w->st.cells++;
-    return w->occ[(size_t)x * (size_t)w->H + (size_t)y] != 0;
+    if (w->rbits) w->rbits[i >> 3] |= (uint8_t)(1u << (i & 7));
+    return w->occ[i] != 0;
 }
 
 /* jps1.py:14-31 */
@@ -437,6 +440,74 @@ int fxo_plan_batch(const uint8_t* occ, int32_t W, int32_t H, const int32_t* star
             worker(j);
         else
             pthread_create(&th[t], NULL, worker, j);
+    }
+    if (nthreads > 1)
+        for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+    return 0;
+}
+
+/* ---- read sets: the cells a literal search reads (tests/test_read_sets_*.py) ---- */
+typedef struct {
+    const uint8_t* occ;
+    int32_t W, H;
+    const int32_t *starts, *goals;
+    int64_t q0, q1;
+    int32_t hchoice;
+    size_t nbytes;
+    uint8_t* out_bits;
+    int32_t* out_len;
+} rs_job_t;
+
+static void* rs_worker(void* arg) {
+    rs_job_t* j = (rs_job_t*)arg;
+    const int64_t cells = (int64_t)j->W * j->H;
+    const int32_t max_len = cells + 1 < (1 << 16) ? (int32_t)cells + 1 : (1 << 16);
+    int32_t* xy = (int32_t*)malloc((size_t)max_len * 2 * sizeof(int32_t));
+    ws_t w;
+    if (!xy || ws_init(&w, j->occ, j->W, j->H) != 0) {
+        if (xy) ws_free(&w);
+        free(xy);
+        for (int64_t q = j->q0; q < j->q1; q++) j->out_len[q] = FXO_ERR_BAD_ARG;
+        return NULL;
+    }
+    w.literal = 1;
+    for (int64_t q = j->q0; q < j->q1; q++) {
+        double cost;
+        w.rbits = j->out_bits + (size_t)q * j->nbytes;
+        memset(w.rbits, 0, j->nbytes);
+        j->out_len[q] = plan_one(&w, j->starts[2 * q], j->starts[2 * q + 1], j->goals[2 * q], j->goals[2 * q + 1],
+                                 j->hchoice, xy, max_len, &cost);
+    }
+    ws_free(&w);
+    free(xy);
+    return NULL;
+}
+
+int fxo_read_sets(const uint8_t* occ, int32_t W, int32_t H, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
+                  int32_t hchoice, int32_t nthreads, uint8_t* out_bits, int32_t* out_len) {
+    if (W < 1 || H < 1 || nq < 0) return FXO_ERR_BAD_ARG;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if ((int64_t)nthreads > nq) nthreads = nq > 0 ? (int32_t)nq : 1;
+    pthread_t th[16];
+    rs_job_t jobs[16];
+    for (int t = 0; t < nthreads; t++) {
+        rs_job_t* j = &jobs[t];
+        j->occ = occ;
+        j->W = W;
+        j->H = H;
+        j->starts = starts_xy;
+        j->goals = goals_xy;
+        j->q0 = nq * t / nthreads;
+        j->q1 = nq * (t + 1) / nthreads;
+        j->hchoice = hchoice;
+        j->nbytes = ((size_t)W * (size_t)H + 7) / 8;
+        j->out_bits = out_bits;
+        j->out_len = out_len;
+        if (nthreads == 1)
+            rs_worker(j);
+        else
+            pthread_create(&th[t], NULL, rs_worker, j);
     }
     if (nthreads > 1)
         for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);

@@ -58,6 +58,15 @@ int fxo_plan_batch(const uint8_t* occ, int32_t W, int32_t H,
                    int32_t* out_cells_xy, int32_t* out_len, double* out_cost,
                    fxo_stats* stats, int32_t nthreads);
 
+/* Read sets: for each of nq queries, the cells whose occupancy a LITERAL search (jps1.method step for step) reads --
+ * every element read of blocked()/dblock(), jps1.py:14-38.  jps1.method is a deterministic function of the values it
+ * reads, so a grid that differs from occ only outside a query's read set gives that query the same answer.
+ * out_bits: [nq][ceil(W*H / 8)] bytes, bit i = x*H + y of the query's row at byte i >> 3, bit i & 7.  out_len: the
+ * status fxo_plan would return (>0 path length, 0 no path, <0 error; a path longer than 65536 jump points reads
+ * FXO_ERR_PATH_OVERFLOW, its read set is complete).  At most 16 threads.  Returns 0. */
+int fxo_read_sets(const uint8_t* occ, int32_t W, int32_t H, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
+                  int32_t hchoice, int32_t nthreads, uint8_t* out_bits, int32_t* out_len);
+
 /* Goal-free jump table (what the library's derived maps are checked against).  For every cell (x, y) of the grid and
  * every direction slot s -- (-1,-1) 0, (-1,0) 1, (-1,1) 2, (0,-1) 3, (0,1) 4, (1,-1) 5, (1,0) 6, (1,1) 7 -- jump()
  * with a goal off the grid:

@@ -51,6 +51,8 @@ def lib():
         L.fxo_plan_batch.argtypes = [p_u8, C.c_int32, C.c_int32, p_i32, p_i32, C.c_int64,
                                      C.c_int32, C.c_int32, C.c_int32, p_i32, p_i32, p_f64,
                                      C.c_void_p, C.c_int32]
+        L.fxo_read_sets.restype = C.c_int
+        L.fxo_read_sets.argtypes = [p_u8, C.c_int32, C.c_int32, p_i32, p_i32, C.c_int64, C.c_int32, C.c_int32, p_u8, p_i32]
         L.fxo_jump_table.restype = C.c_int
         L.fxo_jump_table.argtypes = [p_u8, C.c_int32, C.c_int32, C.c_int32, p_u8, C.POINTER(C.c_uint16), C.c_void_p,
                                      C.c_int32]
@@ -114,6 +116,28 @@ def plan_batch(matrix, starts, goals, hchoice=2, literal=False, max_len=1024, nt
                          _ptr(cost, C.c_double),
                          stats.ctypes.data_as(C.c_void_p) if want_stats else None, int(nthreads))
     return cells, length, cost, stats
+
+
+def read_sets(matrix, starts, goals, hchoice=2, nthreads=16):
+    """The cells a literal search of each query reads (fxo_read_sets): -> (bits uint8[nq, ceil(W*H / 8)], status
+    int32[nq]).  Row q is bit-packed little-endian over the flat index x*H + y; unpack_read_set turns it into a mask."""
+    occ = as_occ(matrix)
+    W, H = occ.shape
+    starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 2)
+    goals = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
+    nq = starts.shape[0]
+    bits = np.zeros((nq, (W * H + 7) // 8), dtype=np.uint8)
+    status = np.zeros(nq, dtype=np.int32)
+    rc = lib().fxo_read_sets(_ptr(occ, C.c_uint8), W, H, _ptr(starts, C.c_int32), _ptr(goals, C.c_int32), nq,
+                             int(hchoice), int(nthreads), _ptr(bits, C.c_uint8), _ptr(status, C.c_int32))
+    if rc != 0:
+        raise ValueError("oracle error %d" % rc)
+    return bits, status
+
+
+def unpack_read_set(row, W, H):
+    """One row of read_sets() -> bool[W, H]."""
+    return np.unpackbits(row, bitorder="little")[:W * H].reshape(W, H).astype(bool)
 
 
 def jump_table(occ, literal=False, nthreads=16, flags=False):
