@@ -21,7 +21,12 @@ generator fuxi-planner_amd/synth.py):
              GPU take the frames in turn): sustained frames/s and p50 / p99 submit-to-paths latency over the 600 frames
              SURVEY 8d prescribes (its default --steps)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+Without --full a run does what its headline figure needs and nothing else: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line.  --full adds everything that is measured or checked around the timed steps: the CPU
+baselines (which are also the cell-for-cell check of the last step against the C oracle), `config.also`, the oracle legs
+of c1 and the self-verification of an N > 1 line; --no-cpu-baseline and --no-also take single parts out of it again.
 
 --dump-outputs DIR writes what the timed path handed its caller in its last step (rank 0's part at N > 1) as .npy files,
 float32 / float64, at most 64 MB in all: offsets.npy, cells.npy, cost.npy, status.npy and query_ids.npy (dump_outputs).
@@ -36,15 +41,16 @@ which imports torch:
     id, the library broadcasts the grid (fxjps_create_rank / fxjps_set_grid_rank);
   * plain `python bench.py --gpus N` (no WORLD_SIZE): ONE process drives all N GPUs through the library's own
     multi-device handle -- fxjps_create(n_dev = N): ncclCommInitAll + one ncclBroadcast.
-An N > 1 line verifies itself outside the timed region (`config.verified`): the SHA-256 of the grid every device / rank
-holds equals rank 0's, a stratified sample of EVERY shard's results (>= 500 queries each) equals the C oracle's on rank 0 --
-lengths, float64 cost bytes, cells --, and the run FAILS (exit code 3) when the RCCL communicator does not span all N
-(unless FXJPS_BENCH_ONE_DEVICE marks the run as a one-device rehearsal).
+With --full an N > 1 line verifies itself outside the timed region (`config.verified`): the SHA-256 of the grid every
+device / rank holds equals rank 0's, and a stratified sample of EVERY shard's results (>= 500 queries each) equals the C
+oracle's on rank 0 -- lengths, float64 cost bytes, cells.  With or without it the run FAILS (exit code 3) when the RCCL
+communicator does not span all N (unless FXJPS_BENCH_ONE_DEVICE marks the run as a one-device rehearsal).
 
 Prints ONE JSON line on rank 0 (the driver contract) with `roofline` (HBM bound, algorithmic bytes / HIP-event kernel
-time), at N = 1 `cpu_baseline` (the C oracle on the host cores, bounded sample), and -- default workload only --
-`config.also`: the other BASELINE workloads measured right behind the timed region of the headline (c4shard, c1, c3,
-c5pipe and c2pipe at N = 1; the 1 M queries of c4 split N ways at N > 1), so that they are in the driver's record too.
+time of the timed steps) and, with --full, `cpu_baseline` (the C oracle on the host cores, bounded sample),
+`cpu_baseline_python` and -- default workload only -- `config.also`: the other BASELINE workloads measured right behind
+the timed region of the headline (c4shard, c4, c1, c3, c5pipe and c2pipe at N = 1; the 1 M queries of c4 split N ways at
+N > 1), so that they are in the driver's record too.
 """
 import argparse
 import hashlib
@@ -228,7 +234,7 @@ def measure(cx, name, steps, warmup, frames_in_flight=0):
         k_all = [c["kernel_ms"] for c in per_ctx]
     if (status < 0).any():
         raise SystemExit("bench: %d queries failed" % int((status < 0).sum()))
-    verified = verify_multi(cx, wl, occ, g_last if streaming else occ, starts, goals, last.get("res"), strong, nq) if (cx.world > 1 or cx.gpus > 1) and pipe is None else None
+    verified = verify_multi(cx, wl, occ, g_last if streaming else occ, starts, goals, last.get("res"), strong, nq) if cx.full and (cx.world > 1 or cx.gpus > 1) and pipe is None else None
     if cx.rank != 0:
         return None
 
@@ -360,13 +366,14 @@ def measure_c1(cx, reps=20, warm=1):
     """BASELINE config 1 and the node's real call: ONE query per call on the reference's own maps (tests/golden/maps_png.npz:
     the 35 maps/*.png as the loader of global_planner_st.py:176-182 reads them).  The 147 x 112 map pasted into a zero
     256 x 256 canvas with the three queries of SURVEY 8(c), and every map with its first-free -> last-free query.  Every
-    answer is checked (canvas: against the paths captured from the real jps1.py; maps: against the C oracle).  Microseconds
-    per call of Planner.plan on the resident grid and of the jps1.method drop-in (grid conversion + upload + map build +
-    search), beside the C port and the pure-Python restatement of the reference on one host core."""
+    canvas answer is checked against the paths captured from the real jps1.py.  Microseconds per call of Planner.plan on the
+    resident grid and of the jps1.method drop-in (grid conversion + upload + map build + search); with --full beside the C
+    port and the pure-Python restatement of the reference on one host core, and every map's answer against the C oracle."""
     import contextlib
     import io
     import fuxi_planner_amd as fx
-    from oracle import jps_python, oracle
+    if cx.full:
+        from oracle import jps_python, oracle
     z = np.load(os.path.join(ROOT, "tests", "golden", "maps_png.npz"))
     with open(os.path.join(ROOT, "tests", "golden", "maps_png.json")) as f:
         recs = json.load(f)
@@ -407,12 +414,14 @@ def measure_c1(cx, reps=20, warm=1):
                 return fx.jps1.method(m_alt[tick[0] & 1], s, g, 2)
             us_new, r = timed(new_map, reps)
         assert r[0] == want
-        us_c, rc = timed(lambda: oracle.plan(occ, s, g, 2, literal=False), reps)
-        assert rc[0] == want
-        t0 = time.perf_counter()
-        rp = jps_python.search(m64, s, g, 2)
-        ms_py = (time.perf_counter() - t0) * 1e3
-        assert rp[0] == want
+        us_c = ms_py = None
+        if cx.full:
+            us_c, rc = timed(lambda: oracle.plan(occ, s, g, 2, literal=False), reps)
+            assert rc[0] == want
+            t0 = time.perf_counter()
+            rp = jps_python.search(m64, s, g, 2)
+            ms_py = (time.perf_counter() - t0) * 1e3
+            assert rp[0] == want
         canvas.append({"start": list(s), "goal": list(g), "jump_points": len(want), "us_per_call_resident_grid": us,
                        "us_per_call_jps1_method": us_m, "us_per_call_jps1_method_new_map": us_new, "kernel_us": p.timing()["search_kernel_ms"] * 1e3,
                        "c_port_us_one_core": us_c, "python_restatement_ms_one_core": ms_py})
@@ -426,8 +435,10 @@ def measure_c1(cx, reps=20, warm=1):
         p.set_grid_occ(grid)
         us, path = timed(lambda: p.plan(s, g, 2), 5)
         planned.append((path, p.last_cost))
-        us_c, rc = timed(lambda: oracle.plan(grid, s, g, 2, literal=False), 5)
-        assert (path if path else 0) == rc[0], "c1: %s differs from the oracle" % nm
+        us_c = float("nan")
+        if cx.full:
+            us_c, rc = timed(lambda: oracle.plan(grid, s, g, 2, literal=False), 5)
+            assert (path if path else 0) == rc[0], "c1: %s differs from the oracle" % nm
         maps.append((us, us_c, W * H))
     mu = np.array([m[0] for m in maps])
     mc = np.array([m[1] for m in maps])
@@ -437,9 +448,9 @@ def measure_c1(cx, reps=20, warm=1):
                         "(mean of %d calls each); then the 35 reference maps, first-free -> last-free" % reps,
             "canvas_queries": canvas,
             "maps35_us_per_call": {"mean": float(mu.mean()), "median": float(np.median(mu)), "max": float(mu.max()), "min": float(mu.min())},
-            "maps35_c_port_us_one_core": {"mean": float(mc.mean()), "median": float(np.median(mc)), "max": float(mc.max())},
+            "maps35_c_port_us_one_core": {"mean": float(mc.mean()), "median": float(np.median(mc)), "max": float(mc.max())} if cx.full else None,
             "maps35_cells": {"min": int(min(m[2] for m in maps)), "max": int(max(m[2] for m in maps))},
-            "checked": "every path against jps1.py's (canvas) / the C oracle (maps)", "planned": planned}
+            "checked": "every path against jps1.py's (canvas)" + (" / the C oracle (maps)" if cx.full else ""), "planned": planned}
 
 
 def main():
@@ -450,14 +461,18 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c2h1", "c2pipe", "c3", "c4shard", "c4", "c5", "c5low", "c5local", "c5local4k", "c5pipe"])
     ap.add_argument("--inlib", action="store_true", help="one process, all GPUs through fxjps_create(n_dev = N) (the default when "
                     "bench.py is not started by torch.distributed.run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="default workload: skip the config.also measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="--full on the default workload without the config.also measurements")
     ap.add_argument("--frames-in-flight", type=int, default=0, help="c5pipe / c2pipe: planner handles taking the frames / batches in turn (0: the workload's)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="queries timed on the host cores (0: the workload's default)")
     ap.add_argument("--py-sample", type=int, default=64, help="queries timed with the pure-Python restatement of the reference (0: none)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in "
                     "its last step to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample of larger outputs)")
+    ap.add_argument("--full", action="store_true", help="also everything measured or checked around the timed steps: the CPU baselines, "
+                    "config.also, the oracle legs of c1, the self-verification at N > 1 (see --no-cpu-baseline, --no-also)")
     a = ap.parse_args()
+    want_also = a.full and not a.no_also and a.workload == "c2"
+    want_cpu = a.full and not a.no_cpu_baseline
     d_steps, d_warm = DEFAULT_STEPS.get(a.workload, (5, 2))
     a.steps = d_steps if a.steps is None else a.steps
     a.warmup = d_warm if a.warmup is None else a.warmup
@@ -472,6 +487,7 @@ def main():
     cx.world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cx.gpus = a.gpus
+    cx.full = a.full
     # Decided before anything touches a GPU: started by torch.distributed.run (WORLD_SIZE == N) -> one process per GPU;
     # otherwise ONE process drives all N GPUs through the library's multi-device handle (no torch is imported at all).
     cx.inlib = a.inlib or (cx.world == 1 and a.gpus > 1)
@@ -544,7 +560,7 @@ def main():
 
     # ---- the other BASELINE workloads, behind the headline's timed region (default invocation only)
     also = {}
-    if a.workload == "c2" and not a.no_also:
+    if want_also:
         def brief(r, extra=()):
             d = {"value": r["value"], "unit": "plans/s", "ms_per_step": r["ms_per_step"], "steps": r["steps"], "kernel_ms": r["kernel_ms"],
                  "frac": r["frac"], "achieved_GBps": r["achieved"], "queries_per_step": r["total_q"], "scaling": "strong" if r["strong"] else "weak"}
@@ -647,7 +663,7 @@ def main():
             out["roofline"].update({"achieved": None, "frac": None, "kernel_ms": None, "pipeline_GBps": m["pipeline_GBps"]})
             out["roofline"]["note"] = ("the launches of the batches in flight overlap: there is no kernel time and no roofline fraction of a "
                                        "kernel; pipeline_GBps = algorithmic bytes per batch / batch period; " + out["roofline"]["note"])
-        if a.workload == "c2" and not a.no_also and a.gpus == 1 and cx.world == 1:
+        if want_also and a.gpus == 1 and cx.world == 1:
             # config 5 with frames in flight, in a child process of its own (its handles want their own hardware
             # queues -- an environment variable the HIP runtime reads when it starts -- and their own memory)
             cx.planner.close()
@@ -694,7 +710,7 @@ def main():
             out["config"]["also"] = also
         if dumped:
             out["config"]["dumped_outputs"] = dumped
-        if not a.no_cpu_baseline:  # (at N > 1 too: rank 0's shard, the same leg)
+        if want_cpu:  # (at N > 1 too: rank 0's shard, the same leg)
             from oracle import oracle  # checker used as the CPU baseline ("port"), never by the planner
             ns = min(a.cpu_sample or wl.get("cpu_sample", m["wl"]["nq"]), m["n_local"])
             cores = min(os.cpu_count() or 1, 256)

@@ -645,7 +645,7 @@ else:
 
 @pytest.mark.parametrize("mode", ["c5pipe", "c2pipe"])
 def test_pipelines_the_way_bench_runs_them(mode, tmp_path, oracle):
-    """What the driver's default line runs as config.also.c5pipe / c2pipe, against the oracle, in a process of its own so
+    """What `bench.py --full` runs as config.also.c5pipe / c2pipe, against the oracle, in a process of its own so
     that GPU_MAX_HW_QUEUES is in place before the HIP runtime starts (fuxi_planner_amd.replan.configure_hw_queues):
     c5pipe -- BASELINE config 5 through the workload's own number of planner handles (12), four turns each, every path of
     every frame on that frame's grid; c2pipe -- TWO handles, three 10 000-query config-2 batches (memory share 2: no head

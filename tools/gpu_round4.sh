@@ -25,7 +25,7 @@ quick)
   timeout 1500 python -m pytest tests -m gpu -q -x --durations=8 -k "${FX_TESTS:-parity or map_updates}" > $OUT/pytest_quick.log 2>&1; rc=$?; echo "rc=$rc" >> $OUT/pytest_quick.log; tail -12 $OUT/pytest_quick.log
   chk $OUT/pytest_quick.log; if [ $rc -ne 0 ]; then exit 4; fi;;
 bench)
-  timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; cut -c1-4000 $OUT/bench_default.json
+  timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; cut -c1-4000 $OUT/bench_default.json
   chk $OUT/bench_default.err;;
 lines)
   for w in ${FX_WORKLOADS:-c2 c2h1 c4shard c5 c5local c3}; do
@@ -46,14 +46,14 @@ profiles)
       timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $P/pmc_$n -- python3 bench.py --workload $w --steps 1 --warmup 0 --no-cpu-baseline --no-also > $P/pmc_$n.log 2>&1
       chk $P/pmc_$n.log
     done
-    timeout 900 python bench.py --workload $w --steps 5 --warmup 2 --no-also > $P/bench.json 2> $P/bench.err
+    timeout 900 python bench.py --workload $w --steps 5 --warmup 2 --full --no-also > $P/bench.json 2> $P/bench.err
     chk $P/bench.err
     python3 tools/profile_summary.py $P $w > $P/summary.json 2> $P/summary.err; cut -c1-400 $P/summary.json
   done;;
 multi)
-  FXJPS_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/bench_inlib2.json 2> $OUT/bench_inlib2.err; echo "inlib x2 rc=$?"; cut -c1-1500 $OUT/bench_inlib2.json
+  FXJPS_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 2 --warmup 1 --full > $OUT/bench_inlib2.json 2> $OUT/bench_inlib2.err; echo "inlib x2 rc=$?"; cut -c1-1500 $OUT/bench_inlib2.json
   chk $OUT/bench_inlib2.err
-  FXJPS_BENCH_ONE_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/bench_torchrun2.json 2> $OUT/bench_torchrun2.err; echo "torchrun x2 (one device) rc=$?"; grep "^{" $OUT/bench_torchrun2.json | cut -c1-1500
+  FXJPS_BENCH_ONE_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --full > $OUT/bench_torchrun2.json 2> $OUT/bench_torchrun2.err; echo "torchrun x2 (one device) rc=$?"; grep "^{" $OUT/bench_torchrun2.json | cut -c1-1500
   chk $OUT/bench_torchrun2.err;;
 busy)
   for w in c2 c4shard; do

@@ -73,9 +73,9 @@ multi6)
   for wl in c2 c5; do
     extra=""; [ $wl = c5 ] && extra="--workload c5 --steps 3 --warmup 1"
     [ $wl = c2 ] && extra="--steps 2 --warmup 1"
-    FXJPS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python bench.py --gpus 2 $extra > $OUT/multi_inlib2_$wl.json 2> $OUT/multi_inlib2_$wl.err; echo "inlib x2 $wl rc=$?"
+    FXJPS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python bench.py --gpus 2 --full $extra > $OUT/multi_inlib2_$wl.json 2> $OUT/multi_inlib2_$wl.err; echo "inlib x2 $wl rc=$?"
     chk $OUT/multi_inlib2_$wl.err
-    FXJPS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 $extra > $OUT/multi_ranks2_$wl.json 2> $OUT/multi_ranks2_$wl.err; echo "ranks x2 $wl (one device) rc=$?"
+    FXJPS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full $extra > $OUT/multi_ranks2_$wl.json 2> $OUT/multi_ranks2_$wl.err; echo "ranks x2 $wl (one device) rc=$?"
     chk $OUT/multi_ranks2_$wl.err
     for f in $OUT/multi_inlib2_$wl.json $OUT/multi_ranks2_$wl.json; do
       python3 - $f <<'PY'
