@@ -182,6 +182,12 @@ struct DevCtx : GridBufs {
     std::vector<GridDev> h_slot_desc;
     DBuf<GridDev> d_slot_desc;
     DBuf<int32_t> d_grid_ids;
+    // fxjps_prepare_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw maps), pinned and
+    // on the device, and the per-job results of k_slots_goal
+    HBuf<uint8_t> h_slots_in;
+    DBuf<uint8_t> d_slots_in;
+    HBuf<int32_t> h_slots_res;
+    DBuf<int32_t> d_slots_res;
     // a slots batch in progress: its grid ids (the caller's array) and the largest extents of the slots it names, which
     // size the scratch, the watchdog and the far band's form in place of the resident grid's
     const int32_t* mg_ids = nullptr;
@@ -1665,6 +1671,10 @@ void fxjps_destroy(fxjps_t* h) {
         for (auto& g : d.slots) g.release();
         d.d_slot_desc.release();
         d.d_grid_ids.release();
+        d.h_slots_in.release();
+        d.d_slots_in.release();
+        d.h_slots_res.release();
+        d.d_slots_res.release();
         if (d.ev_upd) (void)hipEventDestroy(d.ev_upd);
         if (d.ev_stage) (void)hipEventDestroy(d.ev_stage);
         d.h_occ_stage.release();
@@ -2282,6 +2292,186 @@ int fxjps_get_grid_slot(fxjps_t* h, int32_t slot, uint8_t* out, int32_t* out_W, 
         HIPCHK(h, hipSetDevice(d.dev));
         HIPCHK(h, hipMemcpyAsync(out, g.occ.p, (size_t)g.W * g.H, hipMemcpyDeviceToHost, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));
+    }
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ many raw maps into grid slots, one call
+int fxjps_slot_job_size(void) { return (int)sizeof(fxjps_slot_job_t); }
+
+namespace {
+static_assert(fx::SLOT_JOBS_MAX == FXJPS_MAX_GRID_SLOTS, "the job table of fxjps_prepare_slots holds one job per slot");
+// What the host derives from a job before anything is queued (prepare_grid_impl's arithmetic, with its line citations).
+struct SlotPlan {
+    long long dx, dy, W1, H1, nsx, nsy, ngx, ngy;
+    size_t raw_off;  // of its raw map inside the staged input
+};
+// The staged input of a call: the job table, the context's 256 slot descriptors as they will be, then the raw maps.
+constexpr size_t SLOTS_IN_DESC = (sizeof(fx::SlotTable) + 15) & ~(size_t)15;
+constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS + 15) & ~(size_t)15;
+
+// One context's part of fxjps_prepare_slots: everything is queued on d.stream behind ONE copy in, and waited for ONCE,
+// whatever n is.  The results are left in d.h_slots_res.
+int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    if (d.slots.empty()) {
+        d.slots.resize(FXJPS_MAX_GRID_SLOTS);
+        d.h_slot_desc.assign(FXJPS_MAX_GRID_SLOTS, GridDev{});
+        HIPCHK(h, d.d_slot_desc.ensure(FXJPS_MAX_GRID_SLOTS));
+    }
+    // (no host wait in front: every call of the library that reads a slot has returned; a buffer that grows is freed by
+    // hipFree, which waits for the device itself)
+    HIPCHK(h, d.h_slots_in.ensure(in_bytes));
+    HIPCHK(h, d.d_slots_in.ensure(in_bytes));
+    HIPCHK(h, d.h_slots_res.ensure((size_t)n * fx::SLOT_RES));
+    HIPCHK(h, d.d_slots_res.ensure((size_t)n * fx::SLOT_RES));
+    fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
+    uint32_t at[fx::SL_LAUNCHES] = {};
+    bool any_large = false;
+    for (int j = 0; j < n; j++) {
+        const fxjps_slot_job_t& jb = jobs[j];
+        const SlotPlan& p = plan[(size_t)j];
+        GridBufs& g = d.slots[(size_t)jb.slot];
+        d.h_slot_desc[(size_t)jb.slot] = GridDev{};
+        int e = alloc_grid_bufs(h, g, (int)p.W1, (int)p.H1);  // (a slot that has room allocates nothing)
+        if (e) return e;
+        const GridDev G = grid_of(g);
+        d.h_slot_desc[(size_t)jb.slot] = G;
+        fx::SlotJobDev& J = T.job[j];
+        J.G = G;
+        J.occ = g.occ.p;
+        J.raw = d.d_slots_in.p + p.raw_off;
+        J.W0 = jb.W0;
+        J.H0 = jb.H0;
+        J.dx = (int32_t)p.dx;
+        J.dy = (int32_t)p.dy;
+        J.ifa = jb.ifa;
+        J.variant = jb.variant;
+        J.layout = jb.layout;
+        J.gx = (int32_t)p.ngx;
+        J.gy = (int32_t)p.ngy;
+        memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
+        // the blocks derive_maps would launch for this grid alone (the fused build: at most 2^18 cells)
+        const long long ncell = p.W1 * p.H1, npad = (long long)g.PW * g.PH;
+        const bool fused = ncell <= (1ll << 18);
+        any_large = any_large || !fused;
+        J.nb_rows = (uint32_t)(((long long)g.PW * g.WORDS + 3) / 4);
+        J.nb_cols = (uint32_t)(((long long)g.PH * g.WORDS + 3) / 4);
+        J.nb_ci = (uint32_t)((npad + 255) / 256);
+        J.nb_diag = (uint32_t)((4ll * G.DLINES * g.WORDS + 15) / 16);
+        const uint32_t nb_cell = (uint32_t)((ncell + 255) / 256), nb_flat = (uint32_t)((ncell + 1023) / 1024);
+        const uint32_t cnt[fx::SL_LAUNCHES] = {nb_cell, fused ? J.nb_rows + J.nb_cols + nb_cell : 0u, fused ? J.nb_ci + nb_cell : 0u,
+                                               fused ? J.nb_diag + nb_flat : 0u, fused ? (uint32_t)((npad * 8 + 255) / 256) : 0u};
+        for (int l = 0; l < fx::SL_LAUNCHES; l++) {
+            T.first[l][j] = at[l];
+            at[l] += cnt[l];
+        }
+    }
+    for (int l = 0; l < fx::SL_LAUNCHES; l++) T.first[l][n] = at[l];
+    memcpy(d.h_slots_in.p + SLOTS_IN_DESC, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS);
+    HIPCHK(h, hipMemcpyAsync(d.d_slots_in.p, d.h_slots_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+    const fx::SlotTable* dT = reinterpret_cast<const fx::SlotTable*>(d.d_slots_in.p);
+    hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
+    hipLaunchKernelGGL(fx::k_slots_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p);
+    if (at[fx::SL_BUILD_1] > 0) {
+        hipLaunchKernelGGL(fx::k_slots_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n);
+        hipLaunchKernelGGL(fx::k_slots_build_2, dim3(at[fx::SL_BUILD_2]), dim3(256), 0, d.stream, dT, n);
+        hipLaunchKernelGGL(fx::k_slots_build_3, dim3(at[fx::SL_BUILD_3]), dim3(1024), 0, d.stream, dT, n);
+        hipLaunchKernelGGL(fx::k_slots_derive_jd, dim3(at[fx::SL_JD]), dim3(256), 0, d.stream, dT, n);
+    }
+    HIPCHK(h, hipGetLastError());
+    if (any_large)  // (grids beyond the fused build: their maps one by one, as fxjps_set_grid_slot builds them)
+        for (int j = 0; j < n; j++)
+            if (plan[(size_t)j].W1 * plan[(size_t)j].H1 > (1ll << 18)) {
+                int e = derive_maps(h, d, true, &d.slots[(size_t)jobs[j].slot]);
+                if (e) return e;
+            }
+    HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p, d.h_slots_in.p + SLOTS_IN_DESC, sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d.d_slots_res.p, (size_t)n * fx::SLOT_RES * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    // a goal with no free cell in its row or column: that slot stays empty (its buffers keep their room)
+    for (int j = 0; j < n; j++)
+        if (d.h_slots_res.p[(size_t)j * fx::SLOT_RES + 3] != 0) {
+            const size_t s = (size_t)jobs[j].slot;
+            d.slots[s].W = d.slots[s].H = 0;
+            d.h_slot_desc[s] = GridDev{};
+            HIPCHK(h, hipMemcpy(d.d_slot_desc.p + s, &d.h_slot_desc[s], sizeof(GridDev), hipMemcpyHostToDevice));
+        }
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) {
+    if (!h) return FXJPS_E_ARG;
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
+    if (int rr = refuse_on_rank_handle(h, "fxjps_prepare_slots")) return rr;
+    // everything the host can judge, for every job, before anything is queued or any slot is touched
+    std::vector<SlotPlan> plan((size_t)n);
+    std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
+    size_t in_bytes = SLOTS_IN_RAWS;
+    for (int j = 0; j < n; j++) {
+        const fxjps_slot_job_t& jb = jobs[j];
+        if (jb.slot < 0 || jb.slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "job %d: slot %d is not in 0 .. %d", j, (int)jb.slot, FXJPS_MAX_GRID_SLOTS - 1);
+        if (named[(size_t)jb.slot] >= 0) return fail(h, FXJPS_E_ARG, "job %d: slot %d is already named by job %d", j, (int)jb.slot, named[(size_t)jb.slot]);
+        named[(size_t)jb.slot] = j;
+        if (!jb.raw) return fail(h, FXJPS_E_ARG, "job %d: NULL raw", j);
+        if (jb.W0 < 1 || jb.H0 < 1 || jb.ifa < 0 || jb.ifa > 64 || (jb.variant != 0 && jb.variant != 1) || (jb.layout != 0 && jb.layout != 1))
+            return fail(h, FXJPS_E_ARG, "job %d: bad arguments (W0 %d, H0 %d, ifa %d, variant %d, layout %d)", j, (int)jb.W0, (int)jb.H0, (int)jb.ifa,
+                        (int)jb.variant, (int)jb.layout);
+        const long long sx = jb.start_xy[0], sy = jb.start_xy[1], gx = jb.goal_xy[0], gy = jb.goal_xy[1], ifa = jb.ifa;
+        SlotPlan& p = plan[(size_t)j];
+        // global_planner_st.py:230-235 / global_planner_ccst.py:415-420
+        long long o2x = -2 * ifa, o2y = -2 * ifa;
+        if (gx < 0 || sx < 0) o2x += std::min(gx, sx);
+        if (gy < 0 || sy < 0) o2y += std::min(gy, sy);
+        p.dx = std::llabs(o2x);
+        p.dy = std::llabs(o2y);
+        // :246-247 / :431-432
+        p.W1 = std::max<long long>(std::max<long long>(jb.W0, gx), sx) + p.dx + 4 * ifa;
+        p.H1 = std::max<long long>(std::max<long long>(jb.H0, gy), sy) + p.dy + 4 * ifa;
+        if (p.W1 > 8190 || p.H1 > 8190) return fail(h, FXJPS_E_ARG, "job %d: prepared grid %lldx%lld exceeds 8190 cells a side", j, p.W1, p.H1);
+        // :266-267 (st: + map_d - 1) / :452-453 (ccst: + map_d)
+        const long long sh = jb.variant == 0 ? 1 : 0;
+        p.nsx = sx + p.dx - sh;
+        p.nsy = sy + p.dy - sh;
+        p.ngx = gx + p.dx - sh;
+        p.ngy = gy + p.dy - sh;
+        if (p.ngx < 0 || p.ngy < 0 || p.ngx >= p.W1 || p.ngy >= p.H1)
+            return fail(h, FXJPS_E_ARG, "job %d: goal (%lld, %lld) outside the prepared grid %lldx%lld", j, p.ngx, p.ngy, p.W1, p.H1);
+        p.raw_off = in_bytes;
+        in_bytes += ((size_t)jb.W0 * (size_t)jb.H0 + 15) & ~(size_t)15;
+    }
+    if (n == 0) return FXJPS_OK;
+    // every context prepares every job from the caller's raws (host copies, no collective, as fxjps_set_grid_slot)
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes); });
+    if (rc) {
+        drain_all(h);
+        for (auto& d : h->devs)  // (slots of a call that failed on one context are released on all of them)
+            for (int j = 0; j < n && !d.slots.empty(); j++) {
+                const size_t s = (size_t)jobs[j].slot;
+                if (hipSetDevice(d.dev) == hipSuccess) d.slots[s].release();
+                d.slots[s].W = 0;
+                d.h_slot_desc[s] = GridDev{};
+                if (hipSetDevice(d.dev) == hipSuccess) (void)hipMemcpy(d.d_slot_desc.p + s, &d.h_slot_desc[s], sizeof(GridDev), hipMemcpyHostToDevice);
+            }
+        (void)hipGetLastError();
+        return rc;
+    }
+    const int32_t* res = h->devs[0].h_slots_res.p;  // (every context computed the same)
+    for (int j = 0; j < n; j++) {
+        fxjps_slot_job_t& jb = jobs[j];
+        const SlotPlan& p = plan[(size_t)j];
+        jb.start_xy[0] = (int32_t)p.nsx;
+        jb.start_xy[1] = (int32_t)p.nsy;
+        jb.goal_xy[0] = res[(size_t)j * fx::SLOT_RES + 0];
+        jb.goal_xy[1] = res[(size_t)j * fx::SLOT_RES + 1];
+        jb.W = (int32_t)p.W1;
+        jb.H = (int32_t)p.H1;
+        jb.map_d[0] = (int32_t)p.dx;
+        jb.map_d[1] = (int32_t)p.dy;
+        jb.end_occu = res[(size_t)j * fx::SLOT_RES + 2];
+        jb.status = res[(size_t)j * fx::SLOT_RES + 3] != 0 ? FXJPS_E_ARG : FXJPS_OK;
     }
     return FXJPS_OK;
 }

@@ -682,6 +682,176 @@ __global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict_
     out[i] = v;
 }
 
+// ---- Many raw maps into grid slots in one call (fxjps_prepare_slots, DESIGN.md section 3.8): the preparation above, the
+// goal relocation and the four-launch build, each ONE launch over all jobs of the call.  A launch's blocks are the blocks
+// the single-grid kernel would run for job 0, then those for job 1, ...: SlotTable::first[launch][j] is the first block
+// of job j (first[launch][n] the grid size), and a block finds its job by a block-uniform binary search of that row (jobs
+// differ in size: a 2-D grid padded to the largest job would waste most of its blocks).  Everything per item is the
+// single-grid code: the *_item functions are called as they stand.
+constexpr int SLOT_JOBS_MAX = 256;  // FXJPS_MAX_GRID_SLOTS
+enum { SL_PREPARE = 0, SL_BUILD_1, SL_BUILD_2, SL_BUILD_3, SL_JD, SL_LAUNCHES };
+struct SlotJobDev {
+    GridDev G;           // the slot's extents and maps (what its descriptor in d_slot_desc will say)
+    uint8_t* occ;        // [W][H] the prepared grid
+    const uint8_t* raw;  // this job's raw map inside the staged input
+    int32_t W0, H0, dx, dy, ifa, variant, layout;
+    int32_t gx, gy;      // the shifted goal (inside the prepared grid: the host checked)
+    uint32_t nb_rows, nb_cols, nb_ci, nb_diag;  // k_build_1 .. 3: where the kinds of blocks change within the job's part
+};
+struct SlotTable {
+    uint32_t first[SL_LAUNCHES][SLOT_JOBS_MAX + 1];
+    SlotJobDev job[SLOT_JOBS_MAX];
+};
+// per job, k_slots_goal -> host: the (moved) goal, end_occu, status (0, or -1: row and column fully occupied)
+constexpr int SLOT_RES = 4;
+
+__device__ __forceinline__ int slot_job_of(const uint32_t* __restrict__ first, int n, unsigned b) {
+    int lo = 0, hi = n;  // first[lo] <= b < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// k_prepare_grid's gather, for every output cell of every job.
+__global__ __launch_bounds__(256) void k_prepare_slots(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const uint8_t* __restrict__ raw = J.raw;
+    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
+    if (i >= (long long)W1 * H1) return;
+    const int x = (int)(i / H1), y = (int)(i % H1);
+    const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
+    uint8_t v = 0;
+    for (int a = -ifa; a <= ifa; a += step)
+        for (int b = -ifa; b <= ifa; b += step) {
+            const int sx = x - dx - a, sy = y - dy - b;
+            if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
+                const bool o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * W0 + sx] > 0)
+                                          : (raw[(size_t)sx * H0 + sy] != 0);
+                if (o) v = 1;
+            }
+        }
+    J.occ[i] = v;
+}
+
+// The free cell of line[0], line[stride], .. (n cells) nearest to index c, the lower index of two equally near ones
+// (np.argmin over the ascending indices of np.where: global_planner_st.py:269-272), or -1.  One wavefront: lane l of
+// step k looks at distance 64 k + l on either side, a ballot finds the least distance with a free cell.
+__device__ __forceinline__ int slot_nearest_free(const uint8_t* __restrict__ line, long long stride, int n, int c, int lane) {
+    const int dmax = max(c, n - 1 - c);
+    for (int d0 = 0; d0 <= dmax; d0 += 64) {
+        const int d = d0 + lane, lo = c - d, hi = c + d;
+        const bool flo = lo >= 0 && line[(long long)lo * stride] == 0;
+        const bool fhi = hi < n && line[(long long)hi * stride] == 0;
+        const uint64_t blo = __ballot(flo), bhi = __ballot(fhi);
+        if (blo | bhi) {
+            const int t = __builtin_ctzll(blo | bhi);
+            return ((blo >> t) & 1ull) ? c - (d0 + t) : c + (d0 + t);
+        }
+    }
+    return -1;
+}
+// One wavefront per job: what prepare_grid_impl does on the host with blocking row / column copies -- the goal moved off
+// an obstacle (st:268-272 / ccst:454-458), end_occu (st:273 / ccst:461-464 with numpy's slice rules: a negative bound
+// counts from the end, everything is clipped to the array).
+__global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res) {
+    const int j = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const SlotJobDev& J = T->job[j];
+    const int W1 = J.G.W, H1 = J.G.H, ifa = J.ifa, variant = J.variant;
+    const uint8_t* __restrict__ occ = J.occ;
+    int gx = J.gx, gy = J.gy, end_occu = 0, status = 0;
+    if (occ[(size_t)gx * H1 + gy]) {
+        if (variant == 0) end_occu = 1;
+        int best = slot_nearest_free(occ + (size_t)gx * H1, 1, H1, gy, lane);
+        if (best >= 0) {
+            gy = best;
+        } else {
+            best = slot_nearest_free(occ + gy, H1, W1, gx, lane);
+            if (best >= 0) gx = best; else status = -1;  // FXJPS_E_ARG: the reference raises here
+        }
+    }
+    if (variant == 1 && ifa > 0 && status == 0) {
+        auto bound = [](int v, int n) { return v < 0 ? max(v + n, 0) : min(v, n); };
+        const int x0 = bound(gx - ifa, W1), x1 = bound(gx + ifa, W1), y0 = bound(gy - ifa, H1), y1 = bound(gy + ifa, H1);
+        bool any = false;
+        if (x1 > x0 && y1 > y0) {
+            const int ny = y1 - y0, nc = (x1 - x0) * ny;  // (at most 128 x 128)
+            for (int i = lane; i < nc; i += 64) any = any || occ[(size_t)(x0 + i / ny) * H1 + (y0 + i % ny)] != 0;
+        }
+        end_occu = __ballot(any) != 0ull ? 1 : 0;
+    }
+    if (lane == 0) {
+        res[j * SLOT_RES + 0] = gx;
+        res[j * SLOT_RES + 1] = gy;
+        res[j * SLOT_RES + 2] = end_occu;
+        res[j * SLOT_RES + 3] = status;
+    }
+}
+
+// k_build_1 .. 3 and k_derive_jd over all jobs whose grid takes the fused build (at most 2^18 cells; the others have no
+// blocks here and are built by derive_maps behind these launches).
+__global__ __launch_bounds__(256) void k_slots_build_1(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const GridDev G = J.G;
+    const uint8_t* __restrict__ occ = J.occ;
+    const unsigned nb_rows = J.nb_rows, nb_cols = J.nb_cols;
+    const int lane = (int)(threadIdx.x & 63);
+    const MapRange rr{0, G.PW - 1, 0, G.WORDS - 1}, rc{0, G.PH - 1, 0, G.WORDS - 1};
+    unsigned b = blockIdx.x - T->first[SL_BUILD_1][j];
+    if (b < nb_rows) {
+        derive_rows_item(occ, G, const_cast<uint8_t*>(G.nb8), const_cast<BmWord*>(G.bm), rr, (long long)b * 4 + (threadIdx.x >> 6), lane);
+        return;
+    }
+    b -= nb_rows;
+    if (b < nb_cols) {
+        derive_cols_item<true>(occ, G, const_cast<BmWord*>(G.bm), rc, (long long)b * 4 + (threadIdx.x >> 6), lane);
+        return;
+    }
+    b -= nb_cols;
+    ccl_init_item(occ, (long long)G.W * G.H, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_slots_build_2(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const GridDev G = J.G;
+    const uint8_t* __restrict__ occ = J.occ;
+    const unsigned nb_ci = J.nb_ci;
+    unsigned b = blockIdx.x - T->first[SL_BUILD_2][j];
+    if (b < nb_ci) {
+        const ChangeOut none{nullptr, nullptr, nullptr, 0u, MapRange{1, 0, 1, 0}};
+        derive_cellinfo_item(G, const_cast<uint16_t*>(G.ci), MapRange{0, G.PW - 1, 0, G.PH - 1}, MapRange{1, 0, 1, 0}, none, (long long)b * 256 + threadIdx.x,
+                             (int)(threadIdx.x & 63));
+        return;
+    }
+    b -= nb_ci;
+    ccl_merge_item(occ, G.W, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(1024) void k_slots_build_3(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const GridDev G = J.G;
+    const uint8_t* __restrict__ occ = J.occ;
+    const unsigned nb_diag = J.nb_diag;
+    unsigned b = blockIdx.x - T->first[SL_BUILD_3][j];
+    if (b < nb_diag) {
+        const DiagRange whole{1, 0, 0, 0, 0};
+        derive_diag_item(occ, G, const_cast<BmWord*>(G.bm) + (size_t)4 * G.LINES * G.WORDS, whole, (long long)b * 16 + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
+        return;
+    }
+    b -= nb_diag;
+    ccl_flatten_item((long long)G.W * G.H, const_cast<int*>(G.comp), (long long)b * 1024 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_slots_derive_jd(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_JD], n, blockIdx.x);
+    const GridDev G = T->job[j].G;
+    const DiagRange whole{1, 0, 0, 0, 0};
+    derive_jd_item(G, const_cast<uint16_t*>(G.jd), whole, (long long)(blockIdx.x - T->first[SL_JD][j]) * 256 + threadIdx.x);
+}
+
 // Wire / on-disk adapters (SURVEY.md 8f, N3): one tiled byte transpose with a value map.
 //   dst[(fb ? B-1-b : b)][(fa ? A-1-a : a)][0..ch) = map(src[a][b])      src [A][B], dst [B][A][ch]
 // TM_OCC_TO_MSG   grid -> nav_msgs/OccupancyGrid data[] (global_planner_st.py:103,115: 1 -> 100, data.T)

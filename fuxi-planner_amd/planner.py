@@ -309,6 +309,38 @@ class Planner(object):
         self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), _lib.ptr(out, C.c_uint8), None, None))
         return out
 
+    def prepare_slots(self, jobs):
+        """The fleet's map half of a tick in ONE call (fxjps_prepare_slots): every job's raw map is padded, dilated and
+        built into its grid slot as prepare_grid / prepare_occupancy_msg would prepare the resident grid.  A job is
+        (slot, raw, start, goal, ifa, variant) with raw[x][y] (> 0 = occupied), or (slot, (data, width, height), start,
+        goal, ifa, variant) for a nav_msgs/OccupancyGrid; variant "st" / "ccst".  -> per job (start', goal', map_d,
+        (W, H), end_occu, ok); ok False: the goal's row and column are fully occupied (the reference raises there) and
+        that slot is empty.  The resident grid is not touched."""
+        jobs = list(jobs)
+        arr = (_lib.SlotJob * max(len(jobs), 1))()
+        keep = []  # (the raws, alive until the call has returned)
+        for j, (slot, raw, start, goal, ifa, variant) in zip(arr, jobs):
+            if isinstance(raw, tuple):
+                data, width, height = raw
+                a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+                if a.size != width * height:
+                    raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+                j.layout, j.W0, j.H0 = 1, int(width), int(height)
+            else:
+                a = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
+                if a.ndim != 2:
+                    raise ValueError("grid must be 2-D")
+                j.layout, j.W0, j.H0 = 0, a.shape[0], a.shape[1]
+            keep.append(a)
+            j.raw = a.ctypes.data
+            j.slot, j.ifa = int(slot), int(ifa)
+            j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+            j.start_xy[0], j.start_xy[1] = int(start[0]), int(start[1])
+            j.goal_xy[0], j.goal_xy[1] = int(goal[0]), int(goal[1])
+        self._chk(self._L.fxjps_prepare_slots(self._h, arr, len(jobs)))
+        return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy[0], j.goal_xy[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
+                 j.status == 0) for j in arr[:len(jobs)]]
+
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
         """plan_batch with a grid per query: query q runs on the grid of slot grid_ids[q].  -> (offsets, cells, cost,
         status) as plan_batch.  max_path_len=None: the default slot of the largest grid named, grown when a path needs it."""

@@ -77,8 +77,10 @@ typedef struct fxjps fxjps_t;
  *   700  grid slots: fxjps_set_grid_slot, fxjps_get_grid_slot, fxjps_plan_batch_slots_csr (one batch, each query on the
  *        grid of the slot it names), fxjps_debug_read_slot_maps.
  *   710  fxjps_debug_read_sets (the read sets behind fxjps_replan_frame's exact reuse, for tests).
+ *   720  fxjps_prepare_slots (n vehicles' raw maps padded, dilated and built into n grid slots by one call whose launches
+ *        and host waits do not depend on n), fxjps_slot_job_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 710
+#define FXJPS_VERSION 720
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -249,6 +251,41 @@ int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_
                                int64_t nq, int32_t hchoice, int32_t max_path_len, int64_t* out_offsets,
                                int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len, double* out_cost,
                                double* out_seconds_total);
+
+/* ---- Many vehicles' RAW maps into grid slots in one call (the map half of a fleet tick; fxjps_plan_batch_slots_csr is
+ * the planning half).  Job by job the semantics are those of fxjps_prepare_grid (layout 0) / fxjps_prepare_occupancy_msg
+ * (layout 1) with "the resident grid" replaced by "slot `slot`": same padding, same two dilation variants, same index
+ * shift, same goal relocation (nearest free cell of the goal's row, the first of two equally near ones; else of its
+ * column), same end_occu.  The number of kernel launches, copies and host waits of a call does not depend on n: all raws
+ * travel in one staged copy, one launch each prepares, relocates the goals of and builds the maps (four launches) of all
+ * jobs, one copy brings the results back.  Jobs whose prepared grid has more than 2^18 cells are prepared with the others
+ * and their maps built one by one behind them: correct, not the fast path.
+ *   Whole-call errors (FXJPS_E_ARG, nothing queued, no slot changed, fxjps_last_error names the first offending job): n
+ * outside 0 .. FXJPS_MAX_GRID_SLOTS, a slot out of range or named twice, NULL raw, W0 / H0 < 1, ifa outside 0 .. 64,
+ * variant or layout not 0 / 1, a prepared grid of more than 8190 cells a side, a shifted goal outside the prepared grid.
+ *   Per-job outcome: a goal whose row and column are both fully occupied (the reference raises there) sets that job's
+ * status = FXJPS_E_ARG and leaves its slot EMPTY; the other jobs are not disturbed and the call returns FXJPS_OK.  Every
+ * other job has status = FXJPS_OK.
+ *   The resident grid, its update state and its stored replan results are not touched; slots not named keep their
+ * contents.  A handle with several contexts prepares every job on every context (host copies, no collective); a rank
+ * handle (fxjps_create_rank, world > 1) refuses with FXJPS_E_ARG.  Slots that already have room allocate nothing. */
+typedef struct fxjps_slot_job {
+    const void* raw;      /* in: layout 0 -- uint8 [W0][H0], non-zero = occupied; layout 1 -- the int8 data[] of a
+                             nav_msgs/OccupancyGrid, row-major [y][x], W0 = width, H0 = height */
+    int32_t slot;         /* in: 0 .. FXJPS_MAX_GRID_SLOTS - 1 */
+    int32_t layout;       /* in: 0 / 1, see raw */
+    int32_t W0, H0;       /* in */
+    int32_t ifa;          /* in: 0 .. 64 */
+    int32_t variant;      /* in: 0 st, 1 ccst */
+    int32_t start_xy[2];  /* in: cell indices relative to raw (may be negative); out: in the prepared grid */
+    int32_t goal_xy[2];   /* in / out likewise; out: moved off an obstacle */
+    int32_t W, H;         /* out: extents of the prepared grid */
+    int32_t map_d[2];     /* out: the low-side padding (dx, dy) */
+    int32_t end_occu;     /* out: the reference's flag, as fxjps_prepare_grid returns it */
+    int32_t status;       /* out: FXJPS_OK, or FXJPS_E_ARG (goal row and column fully occupied: the slot is empty) */
+} fxjps_slot_job_t;
+int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n);
+int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was built (cf. fxjps_timing_size) */
 
 /* Measurement hooks (bench.py, tests). */
 typedef struct fxjps_timing {
