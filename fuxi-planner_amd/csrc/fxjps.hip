@@ -223,6 +223,10 @@ struct DevCtx : GridBufs {
     DBuf<int32_t> d_wp_ms, d_wp_pdim, d_wp_dim;
     DBuf<double> d_wp_prev, d_wp_ang, d_atab;
     int atab_a = -1, atab_b = -1;  // d_atab holds atan2(a, b) for a in [0, atab_a], b in [-atab_b, atab_b]
+    // ... both rules over a slots batch (fxjps_waypoint_slots_batch): the call's staged input (fx::WpSlotQuery per query |
+    // the caller's offsets | cells) and output (fx::WpSlotResult per query | the kept cells), pinned and on the device
+    HBuf<uint8_t> h_wps_in, h_wps_out;
+    DBuf<uint8_t> d_wps_in, d_wps_out;
     DBuf<int32_t> d_upd_xy;
     DBuf<uint8_t> d_upd_chg;
     DBuf<int> d_owner;        // [W][H], -1 at rest: which entry of an update list decides a cell it names several times
@@ -278,6 +282,7 @@ struct fxjps {
     bool last_on_host = false;  // the last batch was a single call: its CSR is in the pinned host buffers only
     bool last_slots = false;    // the last batch ran on grid slots: its paths are not the resident grid's ...
     int last_slots_W = 0, last_slots_H = 0;  // ... they lie within these extents (the largest of the slots it named)
+    std::vector<int32_t> last_slot_ids;      // ... and these are the slots its queries named (fxjps_waypoint_slots_batch)
     // persistent query set of the streaming-replan entry points (fxjps_set_queries / fxjps_replan_frame)
     std::vector<int32_t> q_starts, q_goals;
     int q_hchoice = 0, q_max_len = 0;
@@ -1410,6 +1415,46 @@ int wp_gather_parts(fxjps* h, int64_t nq, const int64_t* offsets, const int32_t*
     return FXJPS_OK;
 }
 
+// The st rule's table of angles (fx::WpAtab): atan2(a, b) by the HOST's libm for a in [0, am], b in [-bm, bm], on every
+// device of `parts` -- grown to the largest range seen on each device, filled once per range by `nthreads` host threads.
+constexpr long long ATAB_MAX = 1ll << 27;  // entries (1 GiB): a map_start far off the grid takes the host form of the rule
+bool wp_atab_fits(long long am, long long bm) { return (am + 1) * (2 * bm + 1) <= ATAB_MAX && am < (1ll << 30) && bm < (1ll << 30); }
+int wp_ensure_atab(fxjps* h, std::vector<WpPart>& parts, long long am, long long bm, int nthreads) {
+    // the table: grown to the largest range seen on each device, filled by the host's libm
+    std::vector<double> tab;
+    int ta = -1, tb = -1;
+    for (auto& P : parts) {
+        DevCtx& d = *P.d;
+        if (d.atab_a >= (int)am && d.atab_b >= (int)bm) continue;
+        const int na = std::max<int>((int)am, d.atab_a), nb = std::max<int>((int)bm, d.atab_b);
+        if ((long long)(na + 1) * (2ll * nb + 1) > ATAB_MAX) {  // (the union of two ranges may not fit: start over with this one)
+            d.atab_a = d.atab_b = -1;
+        }
+        const int wa = d.atab_a < 0 ? (int)am : na, wb = d.atab_b < 0 ? (int)bm : nb;
+        if (ta != wa || tb != wb) {
+            ta = wa;
+            tb = wb;
+            const size_t row = (size_t)(2 * tb + 1);
+            tab.resize((size_t)(ta + 1) * row);
+            int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 64));
+            nt = (int)std::min<long long>(nt, std::max<long long>((long long)tab.size() >> 16, 1));
+            double* T = tab.data();
+            (void)run_side_by_side((size_t)nt, [&](size_t t) {
+                for (long long a = (long long)(ta + 1) * (long long)t / nt; a < (long long)(ta + 1) * (long long)(t + 1) / nt; a++)
+                    for (long long b = -tb; b <= tb; b++) T[(size_t)a * row + (size_t)(b + tb)] = std::atan2((double)a, (double)b);
+                return 0;
+            });
+        }
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, d.d_atab.ensure(tab.size()));
+        HIPCHK(h, hipMemcpyAsync(d.d_atab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));  // (`tab` is pageable and dies with this call)
+        d.atab_a = ta;
+        d.atab_b = tb;
+    }
+    return FXJPS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1672,6 +1717,10 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_slot_desc.release();
         d.d_grid_ids.release();
         d.h_slots_in.release();
+        d.h_wps_in.release();
+        d.h_wps_out.release();
+        d.d_wps_in.release();
+        d.d_wps_out.release();
         d.d_slots_in.release();
         d.h_slots_res.release();
         d.d_slots_res.release();
@@ -2514,6 +2563,7 @@ int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_
     if (rc) return rc;
     h->last_slots_W = mw;
     h->last_slots_H = mh;
+    h->last_slot_ids.assign(ids, ids + nq);
     rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
     h->timing.total_ms = (now_s() - t0) * 1e3;
     if (out_seconds_total) *out_seconds_total = now_s() - t0;
@@ -2757,45 +2807,14 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
             am = std::max(am, std::max(std::llabs(cx0 + 1 - mx), std::llabs(cx1 + 1 - mx)));
             bm = std::max(bm, std::max(std::llabs(cy0 + 1 - my), std::llabs(cy1 + 1 - my)));
         }
-        constexpr long long ATAB_MAX = 1ll << 27;  // entries (1 GiB): a map_start far off the grid takes the host form below
-        if ((am + 1) * (2 * bm + 1) <= ATAB_MAX && am < (1ll << 30) && bm < (1ll << 30)) {
+        if (wp_atab_fits(am, bm)) {  // (else: a map_start far off the grid takes the host form below)
             std::vector<WpPart> parts;
             std::vector<int64_t> kept_at;
             int64_t kept_base = 0;
             int rc = wp_gather_parts(h, nq, offsets, cells_xy, false, parts, kept_at, kept_base);
             if (rc) return rc;
-            // the table: grown to the largest range seen on each device, filled by the host's libm
-            std::vector<double> tab;
-            int ta = -1, tb = -1;
-            for (auto& P : parts) {
-                DevCtx& d = *P.d;
-                if (d.atab_a >= (int)am && d.atab_b >= (int)bm) continue;
-                const int na = std::max<int>((int)am, d.atab_a), nb = std::max<int>((int)bm, d.atab_b);
-                if ((long long)(na + 1) * (2ll * nb + 1) > ATAB_MAX) {  // (the union of two ranges may not fit: start over with this one)
-                    d.atab_a = d.atab_b = -1;
-                }
-                const int wa = d.atab_a < 0 ? (int)am : na, wb = d.atab_b < 0 ? (int)bm : nb;
-                if (ta != wa || tb != wb) {
-                    ta = wa;
-                    tb = wb;
-                    const size_t row = (size_t)(2 * tb + 1);
-                    tab.resize((size_t)(ta + 1) * row);
-                    int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 64));
-                    nt = (int)std::min<long long>(nt, std::max<long long>((long long)tab.size() >> 16, 1));
-                    double* T = tab.data();
-                    (void)run_side_by_side((size_t)nt, [&](size_t t) {
-                        for (long long a = (long long)(ta + 1) * (long long)t / nt; a < (long long)(ta + 1) * (long long)(t + 1) / nt; a++)
-                            for (long long b = -tb; b <= tb; b++) T[(size_t)a * row + (size_t)(b + tb)] = std::atan2((double)a, (double)b);
-                        return 0;
-                    });
-                }
-                HIPCHK(h, hipSetDevice(d.dev));
-                HIPCHK(h, d.d_atab.ensure(tab.size()));
-                HIPCHK(h, hipMemcpyAsync(d.d_atab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
-                HIPCHK(h, hipStreamSynchronize(d.stream));  // (`tab` is pageable and dies with this call)
-                d.atab_a = ta;
-                d.atab_b = tb;
-            }
+            rc = wp_ensure_atab(h, parts, am, bm, nthreads);
+            if (rc) return rc;
             rc = [&]() -> int {
                 for (auto& P : parts) {  // queue every device, then collect
                     DevCtx& d = *P.d;
@@ -2833,9 +2852,7 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
                     A.ang_wp_tre = ang_wp_tre;
                     A.prev_wp = prev_wp ? d.d_wp_prev.p : nullptr;
                     A.prev_dim = prev_wp ? d.d_wp_pdim.p : nullptr;
-                    A.atab = d.d_atab.p;
-                    A.amax = d.atab_a;
-                    A.bmax = d.atab_b;
+                    A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
                     A.out_wp = d.d_wp_out.p;
                     A.out_dim = d.d_wp_dim.p;
                     A.out_goal = d.d_wp_out.p + n * 3;
@@ -2900,6 +2917,240 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
     });
     for (int b : bad)
         if (b) return fail(h, FXJPS_E_ARG, "fxjps_waypoint_st failed on a path");
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ both waypoint rules over a grid-slots batch
+// Per context ONE copy in (the queries' records, and the caller's paths behind them), ONE launch, ONE copy back and one
+// wait, whatever nq is and however many slots the queries name.  The slot of a ccst query is resolved HERE, from the
+// context's own slot records (d.slots, the records every other slot call keeps): its record carries the occupancy pointer
+// and the extents, so there is no second table on the device that could fall behind fxjps_set_grid_slot /
+// fxjps_prepare_slots, and fx::GridDev stays as it is.
+int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                               const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
+                               const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
+                               const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
+                               int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads) {
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_waypoint_slots_batch")) return rr;
+    if (nq < 0 || (nq > 0 && (!rule || !reso || !origin || !pos || !goal || !out_wp))) return fail(h, FXJPS_E_ARG, "bad waypoint arguments");
+    if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
+    if ((prev_wp != nullptr) != (prev_dim != nullptr)) return fail(h, FXJPS_E_ARG, "prev_wp and prev_dim go together");
+    const bool resident = !cells_xy;
+    if (resident && !h->last_slots) return fail(h, FXJPS_E_ARG, "the last batch did not run on grid slots: pass the paths explicitly");
+    if (resident && (nq != h->last_nq || (int64_t)h->last_slot_ids.size() != nq))
+        return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
+    if (nq == 0) return FXJPS_OK;
+    // ---- everything the host can judge, for every query, before anything is queued
+    const int32_t* ids = grid_ids ? grid_ids : (resident ? h->last_slot_ids.data() : nullptr);
+    int64_t n_st = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        if (rule[q] != 0 && rule[q] != 1) return fail(h, FXJPS_E_ARG, "query %lld: rule %d is neither 0 (st) nor 1 (ccst)", (long long)q, (int)rule[q]);
+        if (rule[q] == 0) {
+            n_st++;
+            continue;
+        }
+        if (!ids) return fail(h, FXJPS_E_ARG, "query %lld: the ccst rule needs grid_ids with explicit paths", (long long)q);
+        if (!slot_in_use(h, ids[q]))
+            return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)ids[q],
+                        ids[q] < 0 || ids[q] >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
+    }
+    if (n_st > 0 && !map_start) return fail(h, FXJPS_E_ARG, "the st rule needs map_start");
+    if (!resident) {
+        if (offsets[0] != 0) return fail(h, FXJPS_E_ARG, "query 0: offsets[0] must be 0");
+        for (int64_t q = 0; q < nq; q++) {
+            if (offsets[q + 1] < offsets[q]) return fail(h, FXJPS_E_ARG, "query %lld: offsets must ascend", (long long)q);
+            if (rule[q] == 1)
+                for (int64_t i = 2 * offsets[q]; i < 2 * offsets[q + 1]; i++)
+                    if (cells_xy[i] < 0) return fail(h, FXJPS_E_ARG, "query %lld: negative cell", (long long)q);
+        }
+    }
+    // the paths: the caller's CSR (context 0 takes all of them, inside its staged input), or the last batch's, shard by shard
+    struct Part {
+        DevCtx* d;
+        int64_t q0, n, total, kept_at;
+        const long long* h_off;  // host copy of the part's offsets (local: h_off[0] == 0)
+    };
+    std::vector<Part> parts;
+    int64_t kept_base = 0;
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
+    if (!resident) {
+        parts.push_back(Part{&h->devs[0], 0, nq, offsets[nq], 0, reinterpret_cast<const long long*>(offsets)});
+        kept_base = offsets[nq];
+    } else {
+        for (auto& d : h->devs) {
+            if (d.nq == 0) continue;
+            parts.push_back(Part{&d, d.q0, d.nq, d.h_offsets.p[d.nq], kept_base, d.h_offsets.p});
+            kept_base += d.h_offsets.p[d.nq];
+        }
+    }
+    if (out_kept_cells && kept_capacity < kept_base)
+        return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)kept_base);
+    // path q on the host (the st rule's host form)
+    const auto path_of = [&](int64_t q, const int32_t** c) -> int64_t {
+        if (!resident) {
+            *c = cells_xy + 2 * offsets[q];
+            return offsets[q + 1] - offsets[q];
+        }
+        for (auto& P : parts)
+            if (q >= P.q0 && q < P.q0 + P.n) {
+                *c = P.d->h_cells.p + 2 * P.h_off[q - P.q0];
+                return P.h_off[q - P.q0 + 1] - P.h_off[q - P.q0];
+            }
+        *c = nullptr;
+        return 0;
+    };
+    // ---- the st rule's table of angles: the range of (cell + 1 - map_start) over the st queries of the call (resident paths
+    // lie within the largest slot their batch named)
+    bool st_on_host = n_st > 0 && getenv("FXJPS_WAYPOINT_ST_HOST") && atoi(getenv("FXJPS_WAYPOINT_ST_HOST")) != 0;
+    if (n_st > 0 && !st_on_host) {
+        long long am = 0, bm = 0;
+        for (int64_t q = 0; q < nq; q++) {
+            if (rule[q] != 0) continue;
+            const long long mx = map_start[2 * q], my = map_start[2 * q + 1];
+            if (resident) {
+                am = std::max(am, std::max(std::llabs(1 - mx), std::llabs((long long)h->last_slots_W - mx)));
+                bm = std::max(bm, std::max(std::llabs(1 - my), std::llabs((long long)h->last_slots_H - my)));
+            } else {
+                for (int64_t i = offsets[q]; i < offsets[q + 1]; i++) {
+                    am = std::max(am, std::llabs((long long)cells_xy[2 * i] + 1 - mx));
+                    bm = std::max(bm, std::llabs((long long)cells_xy[2 * i + 1] + 1 - my));
+                }
+            }
+        }
+        if (wp_atab_fits(am, bm)) {
+            std::vector<WpPart> tp;
+            for (auto& P : parts) tp.push_back(WpPart{P.d, P.q0, P.n, nullptr, nullptr, nullptr, 0});
+            int rc = wp_ensure_atab(h, tp, am, bm, nthreads);
+            if (rc) return rc;
+        } else {
+            st_on_host = true;
+        }
+    }
+    // ---- queue every context, then collect
+    static_assert(sizeof(fx::WpSlotQuery) % 8 == 0 && sizeof(fx::WpSlotResult) % 8 == 0, "the offsets and cells behind the records stay aligned");
+    int rc = [&]() -> int {
+        for (auto& P : parts) {
+            DevCtx& d = *P.d;
+            HIPCHK(h, hipSetDevice(d.dev));
+            const size_t n = (size_t)P.n, tot = (size_t)P.total;
+            const size_t in_off = n * sizeof(fx::WpSlotQuery), in_cells = in_off + (n + 1) * sizeof(long long);
+            const size_t in_bytes = resident ? in_off : in_cells + tot * 2 * sizeof(int32_t);
+            const size_t out_kept = n * sizeof(fx::WpSlotResult), out_bytes = out_kept + std::max<size_t>(tot, 1) * 2 * sizeof(int32_t);
+            HIPCHK(h, d.h_wps_in.ensure(in_bytes));
+            HIPCHK(h, d.d_wps_in.ensure(in_bytes));
+            HIPCHK(h, d.h_wps_out.ensure(out_bytes));
+            HIPCHK(h, d.d_wps_out.ensure(out_bytes));
+            fx::WpSlotQuery* Q = reinterpret_cast<fx::WpSlotQuery*>(d.h_wps_in.p);
+            for (size_t i = 0; i < n; i++) {
+                const int64_t q = P.q0 + (int64_t)i;
+                fx::WpSlotQuery& r = Q[i];
+                r = fx::WpSlotQuery{};
+                r.rule = rule[q];
+                if (r.rule == 1) {
+                    const GridBufs& g = d.slots[(size_t)ids[q]];
+                    r.occ = g.occ.p;
+                    r.W = g.W;
+                    r.H = g.H;
+                } else {
+                    r.msx = map_start[2 * q];
+                    r.msy = map_start[2 * q + 1];
+                    if (prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3)) {
+                        r.pdim = prev_dim[q];
+                        for (int k = 0; k < 3; k++) r.prev[k] = prev_wp[3 * q + k];
+                    }
+                    if (st_on_host) r.rule = 2;  // (not the kernel's: fxjps_waypoint_st below, on host threads)
+                }
+                r.reso = reso[q];
+                r.ox = origin[2 * q];
+                r.oy = origin[2 * q + 1];
+                r.eo = end_occu ? end_occu[q] : 0;
+                for (int k = 0; k < 3; k++) {
+                    r.pos[k] = pos[3 * q + k];
+                    r.goal[k] = goal[3 * q + k];
+                }
+            }
+            if (!resident) {
+                memcpy(d.h_wps_in.p + in_off, offsets, (n + 1) * sizeof(long long));
+                if (tot > 0) memcpy(d.h_wps_in.p + in_cells, cells_xy, tot * 2 * sizeof(int32_t));
+            }
+            HIPCHK(h, hipMemcpyAsync(d.d_wps_in.p, d.h_wps_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+            fx::WaypointSlotsArgs A;
+            A.in = reinterpret_cast<const fx::WpSlotQuery*>(d.d_wps_in.p);
+            A.out = reinterpret_cast<fx::WpSlotResult*>(d.d_wps_out.p);
+            A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
+            A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
+            A.len = resident ? d.d_len.p : nullptr;
+            A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
+            A.nq = (long long)P.n;
+            A.dis_wp_tre = dis_wp_tre;
+            A.ang_wp_tre = ang_wp_tre;
+            A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
+            hipLaunchKernelGGL(fx::k_waypoint_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(d.h_wps_out.p, d.d_wps_out.p, out_kept_cells ? out_kept + tot * 2 * sizeof(int32_t) : out_kept,
+                                     hipMemcpyDeviceToHost, d.stream));
+        }
+        return FXJPS_OK;
+    }();
+    if (rc) {
+        drain_all(h);
+        return rc;
+    }
+    // the st rule on host threads (a table of angles that would not fit, or FXJPS_WAYPOINT_ST_HOST=1), beside the device's work
+    int bad_q = -1;
+    if (st_on_host) {
+        int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 256));
+        nt = (int)std::min<int64_t>(nt, std::max<int64_t>(nq / 256, 1));
+        std::vector<int64_t> bad((size_t)nt, -1);
+        (void)run_side_by_side((size_t)nt, [&](size_t t) {
+            for (int64_t q = nq * (int64_t)t / nt; q < nq * (int64_t)(t + 1) / nt; q++) {
+                if (rule[q] != 0) continue;
+                const int32_t* c = nullptr;
+                const int64_t n = path_of(q, &c);
+                double gl[3], ang = 0.0;
+                int32_t dim = 3;
+                if (n <= 0) {  // no path: wp = global_goal    global_planner_st.py:287-290
+                    for (int k = 0; k < 3; k++) out_wp[3 * q + k] = gl[k] = goal[3 * q + k];
+                } else {
+                    const bool hp = prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3);
+                    if (fxjps_waypoint_st(c, (int32_t)std::min<int64_t>(n, 0x7FFFFFFF), map_start + 2 * q, reso[q], origin + 2 * q, pos + 3 * q,
+                                          goal + 3 * q, end_occu ? end_occu[q] : 0, dis_wp_tre, ang_wp_tre, hp ? prev_wp + 3 * q : nullptr,
+                                          hp ? prev_dim[q] : 0, out_wp + 3 * q, &dim, gl, &ang) != FXJPS_OK && bad[t] < 0)
+                        bad[t] = q;
+                }
+                if (out_dim) out_dim[q] = dim;
+                if (out_ang_wp) out_ang_wp[q] = ang;
+                if (out_n_kept) out_n_kept[q] = 0;
+                if (out_goal)
+                    for (int k = 0; k < 3; k++) out_goal[3 * q + k] = gl[k];
+            }
+            return 0;
+        });
+        for (int64_t b : bad)
+            if (b >= 0 && bad_q < 0) bad_q = (int)b;
+    }
+    for (auto& P : parts)
+        if (hipSetDevice(P.d->dev) != hipSuccess || hipStreamSynchronize(P.d->stream) != hipSuccess) rc = fail(h, FXJPS_E_HIP, "waypoint kernel failed");
+    if (rc) return rc;
+    if (bad_q >= 0) return fail(h, FXJPS_E_ARG, "query %d: fxjps_waypoint_st failed on its path", bad_q);
+    for (auto& P : parts) {
+        const fx::WpSlotResult* R = reinterpret_cast<const fx::WpSlotResult*>(P.d->h_wps_out.p);
+        const int32_t* kept = reinterpret_cast<const int32_t*>(P.d->h_wps_out.p + (size_t)P.n * sizeof(fx::WpSlotResult));
+        for (int64_t i = 0; i < P.n; i++) {
+            const int64_t q = P.q0 + i;
+            if (rule[q] == 0 && st_on_host) continue;
+            const fx::WpSlotResult& r = R[i];
+            for (int k = 0; k < 3; k++) out_wp[3 * q + k] = r.wp[k];
+            if (out_goal)
+                for (int k = 0; k < 3; k++) out_goal[3 * q + k] = r.goal[k];
+            if (out_dim) out_dim[q] = r.dim;
+            if (out_ang_wp) out_ang_wp[q] = r.ang;
+            if (out_n_kept) out_n_kept[q] = r.nkept;
+            if (out_kept_cells && rule[q] == 1 && r.nkept > 0)
+                memcpy(out_kept_cells + 2 * (P.kept_at + P.h_off[i]), kept + 2 * P.h_off[i], (size_t)r.nkept * 2 * sizeof(int32_t));
+        }
+    }
     return FXJPS_OK;
 }
 

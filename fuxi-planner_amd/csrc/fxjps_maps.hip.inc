@@ -946,6 +946,21 @@ __global__ void k_ccl_update(const uint8_t* __restrict__ occ, int W, int H, cons
 // map_line_col's first question -- is there any obstacle in the sub-map at all -- needs no scan of its own: the answer
 // only matters when a rasterised cell is occupied.  The next 64 points of the path sit in the lanes (one each), so that
 // stepping to the next point is a lane read, not a memory round trip.
+// What the rules below need to know about the grid and the frame of ONE query (wave-uniform): the two batch kernels fill
+// it from their arguments (one grid, one frame for the batch), k_waypoint_slots from its query's record.
+struct WpView {
+    const uint8_t* occ;  // ccst: the grid [W][H] the line tests read, obstacle iff == 1
+    int32_t W, H;
+    double reso, ox, oy;
+    int32_t msx, msy;    // st: map_start
+};
+// ... and what a rule returns (the same in every lane).
+struct WpSel {
+    double wx, wy, wz, ogx, ogy, ogz, ang;
+    int dim;  // st: valid components of the waypoint
+    int m;    // ccst: points that remain
+};
+
 struct WaypointArgs {
     const uint8_t* occ;      // resident grid [W][H], obstacle iff == 1
     int32_t W, H;
@@ -963,7 +978,7 @@ struct WaypointArgs {
     int32_t* kept;           // CSR with the offsets of the paths: the remaining cells of path q at offsets[q] .. + out_nkept[q]
 };
 
-__device__ __forceinline__ bool wp_line_is_free(const WaypointArgs& A, int ax, int ay, int bx, int by, int lane) {
+__device__ __forceinline__ bool wp_line_is_free(const WpView& V, int ax, int ay, int bx, int by, int lane) {
     const int x0 = min(ax, bx), x1 = max(ax, bx), y0 = min(ay, by), y1 = max(ay, by);
     // relative to p0 = (x0, y0); p1 is the end with the smaller x (ties keep a)        ccst:261-268
     double p1x = (double)(ax - x0), p1y = (double)(ay - y0), p2x = (double)(bx - x0), p2y = (double)(by - y0);
@@ -987,7 +1002,7 @@ __device__ __forceinline__ bool wp_line_is_free(const WaypointArgs& A, int ax, i
             // `lb in obstacles of the sub-map` (:279): the sub-map is mapu[x0:x1, y0:y1], clipped to the array
             if (cx >= 0 && cx < x1 - x0 && cy >= 0 && cy < y1 - y0) {
                 const int gx = x0 + cx, gy = y0 + cy;
-                if (gx < A.W && gy < A.H && A.occ[(size_t)gx * A.H + gy] == 1) hit = true;
+                if (gx < V.W && gy < V.H && V.occ[(size_t)gx * V.H + gy] == 1) hit = true;
             }
         }
         RECONV();
@@ -996,20 +1011,12 @@ __device__ __forceinline__ bool wp_line_is_free(const WaypointArgs& A, int ax, i
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
-    const int lane = threadIdx.x & 63;
-    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= A.nq) return;
-    const int n = rfli(A.len[q]);
-    const double px = A.pos[3 * q], py = A.pos[3 * q + 1], pz = A.pos[3 * q + 2];
-    const double gx = A.goal[3 * q], gy = A.goal[3 * q + 1], gz = A.goal[3 * q + 2];
-    const int eo = A.end_occu ? rfli(A.end_occu[q]) : 0;
+// The ccst rule for one path (n jump points at src, n <= 0: no path) by one wavefront; the remaining cells go to dst.
+__device__ __forceinline__ WpSel wp_rule_ccst(const WpView& V, const int2* __restrict__ src, int2* __restrict__ dst, int n, double px, double py,
+                                              double pz, double gx, double gy, double gz, int eo, int lane) {
     double wx = gx, wy = gy, wz = gz;  // no path: wp = global_goal   ccst:481-485
     int m = 0;
     if (n > 0) {
-        const long long off = A.offsets[q];
-        const int2* src = reinterpret_cast<const int2*>(A.cells) + off;
-        int2* dst = reinterpret_cast<int2*>(A.kept) + off;
         // ---- :507-513: drop the points (but the first) closer than 1.5 to the vehicle; path3 = (path + (1, 0)) * reso + origin, z = 0
         m = n;
         if (n > 2) {
@@ -1020,7 +1027,7 @@ __global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
                 bool keep = false;
                 if (i < n) {
                     c = src[i];
-                    const double dx = ((double)(c.x + 1) * A.reso + A.ox) - px, dy = ((double)c.y * A.reso + A.oy) - py, dz = 0.0 - pz;
+                    const double dx = ((double)(c.x + 1) * V.reso + V.ox) - px, dy = ((double)c.y * V.reso + V.oy) - py, dz = 0.0 - pz;
                     keep = i == 0 || !(sqrt(dx * dx + dy * dy + dz * dz) < 1.5);
                 }
                 RECONV();
@@ -1057,7 +1064,7 @@ __global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
             int2 a = point(0), b = point(1);
             for (int i = 2; i < m; i++) {
                 const int2 c = point(i);
-                if (!wp_line_is_free(A, a.x, a.y, c.x, c.y, lane)) {  // b stays: it becomes the end of the kept prefix
+                if (!wp_line_is_free(V, a.x, a.y, c.x, c.y, lane)) {  // b stays: it becomes the end of the kept prefix
                     if (lane == 0) dst[w] = b;  // (w <= i - 1: never a point this pass has not read yet -- they sit in the lanes)
                     RECONV();
                     k1 = w == 1 ? b : k1;
@@ -1077,8 +1084,8 @@ __global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
         // ---- :523-526
         if (m > 2) {
             const int2 c1 = k1, c2 = k2;
-            const double x1 = (double)(c1.x + 1) * A.reso + A.ox, y1 = (double)c1.y * A.reso + A.oy;
-            const double x2 = (double)(c2.x + 1) * A.reso + A.ox, y2 = (double)c2.y * A.reso + A.oy;
+            const double x1 = (double)(c1.x + 1) * V.reso + V.ox, y1 = (double)c1.y * V.reso + V.oy;
+            const double x2 = (double)(c2.x + 1) * V.reso + V.ox, y2 = (double)c2.y * V.reso + V.oy;
             wx = (x1 * 1.4 + x2 * 0.6) / 2;
             wy = (y1 * 1.4 + y2 * 0.6) / 2;
             wz = (0.0 * 1.4 + 0.0 * 0.6) / 2;
@@ -1090,14 +1097,29 @@ __global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
         wy = ogy = py;
         wz = ogz = pz;
     }
+    return WpSel{wx, wy, wz, ogx, ogy, ogz, 0.0, 3, m};
+}
+
+__global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= A.nq) return;
+    const int n = rfli(A.len[q]);
+    const double px = A.pos[3 * q], py = A.pos[3 * q + 1], pz = A.pos[3 * q + 2];
+    const double gx = A.goal[3 * q], gy = A.goal[3 * q + 1], gz = A.goal[3 * q + 2];
+    const int eo = A.end_occu ? rfli(A.end_occu[q]) : 0;
+    const long long off = n > 0 ? A.offsets[q] : 0;
+    const WpView V{A.occ, A.W, A.H, A.reso, A.ox, A.oy, 0, 0};
+    const WpSel S = wp_rule_ccst(V, reinterpret_cast<const int2*>(A.cells) + off, reinterpret_cast<int2*>(A.kept) + off, n, px, py, pz, gx, gy, gz,
+                                 eo, lane);
     if (lane == 0) {
-        A.out_wp[3 * q] = wx;
-        A.out_wp[3 * q + 1] = wy;
-        A.out_wp[3 * q + 2] = wz;
-        A.out_goal[3 * q] = ogx;
-        A.out_goal[3 * q + 1] = ogy;
-        A.out_goal[3 * q + 2] = ogz;
-        A.out_nkept[q] = m;
+        A.out_wp[3 * q] = S.wx;
+        A.out_wp[3 * q + 1] = S.wy;
+        A.out_wp[3 * q + 2] = S.wz;
+        A.out_goal[3 * q] = S.ogx;
+        A.out_goal[3 * q + 1] = S.ogy;
+        A.out_goal[3 * q + 2] = S.ogz;
+        A.out_nkept[q] = S.m;
     }
 }
 
@@ -1105,10 +1127,14 @@ __global__ __launch_bounds__(256) void k_waypoint_ccst(WaypointArgs A) {
 // global_planner_st.py:292-327 (fxjps_waypoint_st in fxjps_waypoints.cpp is the same rule for one path on the host), one
 // wavefront per path.  The rule's decisions, and the angle it returns, hang on math.atan2 -- the host's libm -- of INTEGER
 // pairs (cell - map_start): the device does not compute them, it looks them up in a table the host filled with its own
-// atan2 once per grid shape (WaypointStArgs::atab: a in [0, amax] x b in [-bmax, bmax], 8 bytes each: 17 MB for a
+// atan2 once per grid shape (WpAtab: a in [0, amax] x b in [-bmax, bmax], 8 bytes each: 17 MB for a
 // 1024 x 1024 grid), atan2(-a, b) = -atan2(a, b) being exact in libm (tests/test_host_cpu.py checks that it is).
 // The loop over the path -- "stop at the first point whose angle to the goal's bearing does not grow any more" -- is a
 // comparison of neighbouring lanes and one ballot per 64 points.
+struct WpAtab {
+    const double* atab;  // atan2((double)a, (double)b) by the host's libm, [amax + 1][2 bmax + 1]
+    int32_t amax, bmax;
+};
 struct WaypointStArgs {
     const int32_t* cells;     // CSR paths: (x, y) pairs
     const long long* offsets;
@@ -1122,40 +1148,35 @@ struct WaypointStArgs {
     double dis_wp_tre, ang_wp_tre;
     const double* prev_wp;    // [nq][3] or nullptr: the waypoint of the last tick (kept when the loop does not find one)
     const int32_t* prev_dim;  // [nq]: 2 / 3 components of it, anything else: none
-    const double* atab;       // atan2((double)a, (double)b) by the host's libm, [amax + 1][2 bmax + 1]
-    int32_t amax, bmax;
+    WpAtab T;
     double* out_wp;           // [nq][3]
     int32_t* out_dim;         // [nq]
     double* out_goal;         // [nq][3]
     double* out_ang;          // [nq]
 };
-__device__ __forceinline__ double wp_atan2(const WaypointStArgs& A, int a, int b) {
-    const int aa = min(abs(a), A.amax), bb = min(max(b, -A.bmax), A.bmax);  // (in range by construction: the host sized the table from the batch)
-    const double v = A.atab[(size_t)aa * (size_t)(2 * A.bmax + 1) + (size_t)(bb + A.bmax)];
+__device__ __forceinline__ double wp_atan2(const WpAtab& T, int a, int b) {
+    const int aa = min(abs(a), T.amax), bb = min(max(b, -T.bmax), T.bmax);  // (in range by construction: the host sized the table from the batch)
+    const double v = T.atab[(size_t)aa * (size_t)(2 * T.bmax + 1) + (size_t)(bb + T.bmax)];
     return a < 0 ? -v : v;
 }
-__global__ __launch_bounds__(256) void k_waypoint_st(WaypointStArgs A) {
-    const int lane = threadIdx.x & 63;
-    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= A.nq) return;
-    const int n = rfli(A.len[q]);
-    const double px = A.pos[3 * q], py = A.pos[3 * q + 1], pz = A.pos[3 * q + 2];
-    const double gx = A.goal[3 * q], gy = A.goal[3 * q + 1], gz = A.goal[3 * q + 2];
+// The st rule for one path (n jump points at c, n <= 0: no path) by one wavefront.  pd / prev: the components of the last
+// tick's waypoint (2 or 3; anything else: none) and where they are.
+__device__ __forceinline__ WpSel wp_rule_st(const WpView& V, const WpAtab& T, const int2* __restrict__ c, int n, double px, double py, double pz,
+                                            double gx, double gy, double gz, int eo, int pd, const double* __restrict__ prev, double dis_wp_tre,
+                                            double ang_wp_tre, int lane) {
     double wx = gx, wy = gy, wz = gz, ogx = gx, ogy = gy, ogz = gz, ang_wp = 0.0;
     int dim = 3;
     if (n > 0) {  // (no path: wp = global_goal, st:287-290)
-        const int2* c = reinterpret_cast<const int2*>(A.cells) + A.offsets[q];
-        const int msx = rfli(A.map_start[2 * q]), msy = rfli(A.map_start[2 * q + 1]);
+        const int msx = V.msx, msy = V.msy;
         dim = 0;  // None
-        const int pd = A.prev_wp ? rfli(A.prev_dim[q]) : 0;
         if (pd == 2 || pd == 3) {
             dim = pd;
-            wx = A.prev_wp[3 * q];
-            wy = A.prev_wp[3 * q + 1];
-            wz = pd == 3 ? A.prev_wp[3 * q + 2] : 0.0;
+            wx = prev[0];
+            wy = prev[1];
+            wz = pd == 3 ? prev[2] : 0.0;
         }
         const int2 ce = c[n - 1];
-        const double a_goal = wp_atan2(A, ce.x + 1 - msx, ce.y + 1 - msy);  // path2 = path + (1, 1), st:292
+        const double a_goal = wp_atan2(T, ce.x + 1 - msx, ce.y + 1 - msy);  // path2 = path + (1, 1), st:292
         double carry = 0.0;  // ang_wp as the loop enters the lanes' first point
         bool found = false;
         for (int k0 = 1; k0 < n && !found; k0 += WAVE) {  // :305-312
@@ -1163,20 +1184,20 @@ __global__ __launch_bounds__(256) void k_waypoint_st(WaypointStArgs A) {
             const bool on = k < n;
             const int2 p = c[on ? k : 0];
             const int dx = p.x + 1 - msx, dy = p.y + 1 - msy;
-            const double d = fabs(a_goal - wp_atan2(A, dx, dy));
-            double prev = __shfl_up(d, 1);
-            prev = lane == 0 ? carry : prev;
+            const double d = fabs(a_goal - wp_atan2(T, dx, dy));
+            double prv = __shfl_up(d, 1);
+            prv = lane == 0 ? carry : prv;
             const bool far2 = (long long)dx * dx + (long long)dy * dy > 4ll;  // np.linalg.norm(map_wp - map_start) > 2, of integers
-            const uint64_t hit = __ballot(on && d <= prev && far2);
+            const uint64_t hit = __ballot(on && d <= prv && far2);
             if (hit != 0ull) {
                 const int l = (int)__builtin_ctzll(hit);
                 const int kk = k0 + l;  // the first point that turns back: the waypoint is the one in front of it
                 const int2 w = c[kk - 1];
-                wx = (double)(w.x + 1) * A.reso + A.ox;
-                wy = (double)(w.y + 1) * A.reso + A.oy;
+                wx = (double)(w.x + 1) * V.reso + V.ox;
+                wy = (double)(w.y + 1) * V.reso + V.oy;
                 wz = 0.0;
                 dim = 2;
-                ang_wp = __longlong_as_double((long long)lane_get64((uint64_t)__double_as_longlong(prev), l));
+                ang_wp = __longlong_as_double((long long)lane_get64((uint64_t)__double_as_longlong(prv), l));
                 found = true;
             } else {
                 const int last = min(n - k0, WAVE) - 1;  // the chunk's last point
@@ -1192,27 +1213,110 @@ __global__ __launch_bounds__(256) void k_waypoint_st(WaypointStArgs A) {
         }
         const double ex = wx - px, ey = wy - py;
         const double uav2next_wp = sqrt(ex * ex + ey * ey);  // :315
-        const int eo = A.end_occu ? rfli(A.end_occu[q]) : 0;
         if (eo == 1) {  // :317-320
             wx = ogx = px;
             wy = ogy = py;
             wz = ogz = pz;
             dim = 3;
-        } else if (!(n > 2 && (uav2next_wp > A.dis_wp_tre || (ang_wp > A.ang_wp_tre && ang_wp < 3.14159265358979323846 * 0.5)))) {  // :321-322
+        } else if (!(n > 2 && (uav2next_wp > dis_wp_tre || (ang_wp > ang_wp_tre && ang_wp < 3.14159265358979323846 * 0.5)))) {  // :321-322
             wx = gx;
             wy = gy;
             wz = gz;
             dim = 3;
         }
     }
+    return WpSel{wx, wy, dim == 3 ? wz : 0.0, ogx, ogy, ogz, ang_wp, dim, 0};
+}
+__global__ __launch_bounds__(256) void k_waypoint_st(WaypointStArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= A.nq) return;
+    const int n = rfli(A.len[q]);
+    const double px = A.pos[3 * q], py = A.pos[3 * q + 1], pz = A.pos[3 * q + 2];
+    const double gx = A.goal[3 * q], gy = A.goal[3 * q + 1], gz = A.goal[3 * q + 2];
+    WpView V{nullptr, 0, 0, A.reso, A.ox, A.oy, 0, 0};
+    int pd = 0, eo = 0;
+    const int2* c = nullptr;
+    if (n > 0) {
+        c = reinterpret_cast<const int2*>(A.cells) + A.offsets[q];
+        V.msx = rfli(A.map_start[2 * q]);
+        V.msy = rfli(A.map_start[2 * q + 1]);
+        pd = A.prev_wp ? rfli(A.prev_dim[q]) : 0;
+        eo = A.end_occu ? rfli(A.end_occu[q]) : 0;
+    }
+    const WpSel S = wp_rule_st(V, A.T, c, n, px, py, pz, gx, gy, gz, eo, pd, A.prev_wp ? A.prev_wp + 3 * q : nullptr, A.dis_wp_tre, A.ang_wp_tre, lane);
     if (lane == 0) {
-        A.out_wp[3 * q] = wx;
-        A.out_wp[3 * q + 1] = wy;
-        A.out_wp[3 * q + 2] = dim == 3 ? wz : 0.0;
-        A.out_dim[q] = dim;
-        A.out_goal[3 * q] = ogx;
-        A.out_goal[3 * q + 1] = ogy;
-        A.out_goal[3 * q + 2] = ogz;
-        A.out_ang[q] = ang_wp;
+        A.out_wp[3 * q] = S.wx;
+        A.out_wp[3 * q + 1] = S.wy;
+        A.out_wp[3 * q + 2] = S.wz;
+        A.out_dim[q] = S.dim;
+        A.out_goal[3 * q] = S.ogx;
+        A.out_goal[3 * q + 1] = S.ogy;
+        A.out_goal[3 * q + 2] = S.ogz;
+        A.out_ang[q] = S.ang;
+    }
+}
+
+// ---------------------------------------------------------------- both rules over a grid-slots batch (DESIGN.md section 3.9)
+// fxjps_waypoint_slots_batch: every query brings its own rule, grid (the occupancy of the slot it names, resolved by the
+// host from its slot records when the call is staged), resolution, origin and map_start.  One launch, one wavefront per
+// path, which branches on its query's rule into the very functions the two kernels above call.  The record of a query is
+// wave-uniform: it is read through readfirstlane and stays in scalar registers.
+struct WpSlotQuery {
+    const uint8_t* occ;  // ccst: the slot's grid [W][H]; st: unused (nullptr)
+    int32_t W, H;
+    double reso, ox, oy;
+    int32_t msx, msy;
+    int32_t rule;        // 0 st, 1 ccst, anything else: not this kernel's (the st rule on host threads)
+    int32_t eo, pdim, pad_;
+    double pos[3], goal[3], prev[3];
+};
+struct WpSlotResult {
+    double wp[3], goal[3], ang;
+    int32_t dim, nkept;
+};
+struct WaypointSlotsArgs {
+    const WpSlotQuery* in;    // [nq]
+    WpSlotResult* out;        // [nq]
+    const int32_t* cells;     // CSR paths: (x, y) pairs
+    const long long* offsets;
+    const int32_t* len;       // > 0: jump points of the path, else no path; nullptr: offsets[q + 1] - offsets[q]
+    int32_t* kept;            // CSR with the offsets of the paths (ccst queries only)
+    long long nq;
+    double dis_wp_tre, ang_wp_tre;
+    WpAtab T;
+};
+__global__ __launch_bounds__(256) void k_waypoint_slots(WaypointSlotsArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= A.nq) return;
+    const WpSlotQuery& Q = A.in[q];
+    const int rule = rfli(Q.rule);
+    if (rule != 0 && rule != 1) return;
+    const long long off = (long long)rfl64((uint64_t)A.offsets[q]);
+    const int n = A.len ? rfli(A.len[q]) : rfli((int)min(A.offsets[q + 1] - off, 0x7FFFFFFFll));
+    const WpView V{reinterpret_cast<const uint8_t*>(rfl64((uint64_t)Q.occ)), rfli(Q.W), rfli(Q.H), rfld(Q.reso), rfld(Q.ox), rfld(Q.oy),
+                   rfli(Q.msx), rfli(Q.msy)};
+    const int eo = rfli(Q.eo);
+    const double px = rfld(Q.pos[0]), py = rfld(Q.pos[1]), pz = rfld(Q.pos[2]);
+    const double gx = rfld(Q.goal[0]), gy = rfld(Q.goal[1]), gz = rfld(Q.goal[2]);
+    const int2* c = reinterpret_cast<const int2*>(A.cells) + (n > 0 ? off : 0);
+    WpSel S;
+    if (rule == 1) {
+        S = wp_rule_ccst(V, c, reinterpret_cast<int2*>(A.kept) + (n > 0 ? off : 0), n, px, py, pz, gx, gy, gz, eo, lane);
+    } else {
+        S = wp_rule_st(V, A.T, c, n, px, py, pz, gx, gy, gz, eo, rfli(Q.pdim), Q.prev, A.dis_wp_tre, A.ang_wp_tre, lane);
+    }
+    if (lane == 0) {
+        WpSlotResult& R = A.out[q];
+        R.wp[0] = S.wx;
+        R.wp[1] = S.wy;
+        R.wp[2] = S.wz;
+        R.goal[0] = S.ogx;
+        R.goal[1] = S.ogy;
+        R.goal[2] = S.ogz;
+        R.ang = S.ang;
+        R.dim = S.dim;
+        R.nkept = S.m;
     }
 }

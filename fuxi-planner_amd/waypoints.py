@@ -150,3 +150,50 @@ def select_st_batch(planner, nq, map_start, map_reso, map_o, pos, global_goal, e
         None if pw is None else _lib.ptr(pw, C.c_double), None if pd is None else _lib.ptr(pd, C.c_int32),
         _lib.ptr(wp, C.c_double), _lib.ptr(dim, C.c_int32), _lib.ptr(gout, C.c_double), _lib.ptr(ang, C.c_double), int(nthreads)))
     return wp, dim, gout, ang
+
+
+def select_slots_batch(planner, rule, map_start, map_reso, map_o, pos, global_goal, end_occu=None, prev_wp=None, prev_dim=None,
+                       grid_ids=None, paths=None, return_kept=False, dis_wp_tre=2.0, ang_wp_tre=math.pi / 4, nthreads=0):
+    """Both rules over a grid-slots batch in one call (fxjps_waypoint_slots_batch): query q is selected by rule[q] (0 / "st":
+    global_planner_st.py:292-327; 1 / "ccst": global_planner_ccst.py:487-544 against the grid of slot grid_ids[q] as it is
+    now) with its own map_start[q], map_reso[q] and map_o[q].  paths=None: the paths of the planner's last plan_batch_slots,
+    resident on the device (len(rule) of them; grid_ids=None: the slots that batch named); else (offsets, cells), and
+    grid_ids is needed as soon as one query uses the ccst rule.  map_reso: a scalar or nq values; map_o: one pair or
+    nq x 2; map_start: one pair or nq x 2 (None when no query uses the st rule); pos / global_goal: one (x, y, z) or nq x 3.
+    -> (wp float64[nq, 3], dim int32[nq] (2 or 3 valid components; ccst: 3), global_goal float64[nq, 3], ang_wp float64[nq]
+    (ccst: 0.0), n_kept int32[nq] (st: 0)) [+ kept cells int32[total, 2], aligned with the offsets of the paths, when
+    return_kept]."""
+    r = np.ascontiguousarray([{"st": 0, "ccst": 1}[x] if isinstance(x, str) else int(x) for x in np.asarray(rule, dtype=object).ravel()],
+                             dtype=np.int32)  # (a number other than 0 / 1 goes through: the library refuses it and names the query)
+    nq, off, cells = _batch_paths(planner, paths, len(r))
+    if len(r) != nq:
+        raise ValueError("%d rules for %d paths" % (len(r), nq))
+    reso = np.ascontiguousarray(np.broadcast_to(np.asarray(map_reso, dtype=np.float64), (nq,)))
+    o = np.ascontiguousarray(np.broadcast_to(np.asarray(map_o, dtype=np.float64), (nq, 2)))
+    p, g = _batch_vec(pos, nq), _batch_vec(global_goal, nq)
+    ms = None if map_start is None else np.ascontiguousarray(np.broadcast_to(np.asarray(map_start, dtype=np.int32), (nq, 2)))
+    eo = None if end_occu is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_occu, dtype=np.int32), (nq,)))
+    ids = None if grid_ids is None else np.ascontiguousarray(np.broadcast_to(np.asarray(grid_ids, dtype=np.int32), (nq,)))
+    pw = pd = None
+    if prev_wp is not None:
+        pw = np.ascontiguousarray(np.asarray(prev_wp, dtype=np.float64).reshape(nq, 3))
+        pd = np.ascontiguousarray(np.asarray(prev_dim, dtype=np.int32).reshape(nq))
+    wp, gout, dim, ang, nk = np.zeros((nq, 3)), np.zeros((nq, 3)), np.zeros(nq, dtype=np.int32), np.zeros(nq), np.zeros(nq, dtype=np.int32)
+    kept = None
+    cap = 0
+    if return_kept:
+        if off is None:
+            raise ValueError("return_kept needs the paths (their offsets place the kept cells)")
+        cap = int(off[-1])
+        kept = np.zeros((max(cap, 1), 2), dtype=np.int32)
+
+    def opt(a, t):
+        return None if a is None else _lib.ptr(a, t)
+    planner._chk(planner._L.fxjps_waypoint_slots_batch(
+        planner._h, nq, opt(off, C.c_int64), opt(cells, C.c_int32), opt(ids, C.c_int32), _lib.ptr(r, C.c_int32), opt(ms, C.c_int32),
+        _lib.ptr(reso, C.c_double), _lib.ptr(o, C.c_double), _lib.ptr(p, C.c_double), _lib.ptr(g, C.c_double), opt(eo, C.c_int32),
+        float(dis_wp_tre), float(ang_wp_tre), opt(pw, C.c_double), opt(pd, C.c_int32), _lib.ptr(wp, C.c_double), _lib.ptr(dim, C.c_int32),
+        _lib.ptr(gout, C.c_double), _lib.ptr(ang, C.c_double), _lib.ptr(nk, C.c_int32), opt(kept, C.c_int32), cap, int(nthreads)))
+    if return_kept:
+        return wp, dim, gout, ang, nk, kept[:cap]
+    return wp, dim, gout, ang, nk

@@ -79,8 +79,10 @@ typedef struct fxjps fxjps_t;
  *   710  fxjps_debug_read_sets (the read sets behind fxjps_replan_frame's exact reuse, for tests).
  *   720  fxjps_prepare_slots (n vehicles' raw maps padded, dilated and built into n grid slots by one call whose launches
  *        and host waits do not depend on n), fxjps_slot_job_size.
+ *   730  fxjps_waypoint_slots_batch (both waypoint rules over a grid-slots batch in one call: a rule, a slot, a resolution
+ *        and an origin per query).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 720
+#define FXJPS_VERSION 730
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -432,7 +434,7 @@ int fxjps_waypoint_ccst(const int32_t* cells, int32_t n, const uint8_t* occ, int
  * offsets, (x, y) pairs); both NULL: the paths of the handle's most recent batch, which are still resident on the
  * device(s) -- nq must be that batch's (after a grid-slots batch: fxjps_waypoint_st_batch takes its paths, which lie
  * within the largest slot it named; fxjps_waypoint_ccst_batch refuses with FXJPS_E_ARG, its line tests read the
- * resident grid).  A query without a path gets the goal as its waypoint (`wp = global_goal`,
+ * resident grid: fxjps_waypoint_slots_batch below is the call for such a batch).  A query without a path gets the goal as its waypoint (`wp = global_goal`,
  * scripts/global_planner_st.py:287-290, scripts/global_planner_ccst.py:481-485).  pos, goal, out_wp, out_goal are nq x 3
  * doubles, end_occu nq flags (NULL: all 0), reso and origin one value for the batch (one grid).
  *
@@ -458,6 +460,42 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
                             const double* origin, const double* pos, const double* goal, const int32_t* end_occu, double dis_wp_tre,
                             double ang_wp_tre, const double* prev_wp, const int32_t* prev_dim, double* out_wp, int32_t* out_dim,
                             double* out_goal, double* out_ang_wp, int32_t nthreads);
+
+/* ---- Both rules over a grid-slots batch, one call (version 730): every query brings its own rule, slot, resolution and
+ * origin.  Per context of the handle the call costs one copy in, one kernel launch, one copy back and one wait, whatever
+ * nq is and however many slots are named.
+ *
+ * offsets / cells_xy: the paths as CSR, or both NULL: the paths of the handle's most recent batch, which must have been a
+ * fxjps_plan_batch_slots_csr batch of nq queries (else FXJPS_E_ARG).  Resident paths are processed shard by shard on the
+ * context that planned them, against that context's own copy of the slots; explicit paths go to context 0.
+ * grid_ids (nq): the slot of each query.  NULL with resident paths: the ids that batch was planned with.  Required with
+ * explicit paths if any query uses the ccst rule; ignored for st queries (the st rule reads no grid).
+ * rule (nq): 0 = the st rule (fxjps_waypoint_st), 1 = the ccst rule (fxjps_waypoint_ccst).
+ * Per query: reso (nq), origin (nq x 2), pos, goal (nq x 3), end_occu (nq, NULL: all 0); for the st rule map_start
+ * (nq x 2; may be NULL when no query uses that rule) and prev_wp (nq x 3) / prev_dim (nq), both NULL: no previous
+ * waypoints.  dis_wp_tre, ang_wp_tre once per call; nthreads as in fxjps_waypoint_st_batch.
+ * Outputs: out_wp (nq x 3), and optionally out_dim, out_goal (nq x 3), out_ang_wp, out_n_kept (nq each), out_kept_cells
+ * (kept_capacity pairs >= the number of cells of the paths): the remaining cells of ccst query q at the offset of path q.
+ * A ccst query reports dim 3 and ang_wp 0.0; an st query reports n_kept 0 and writes no kept cells.  A query without a path
+ * gets the goal as its waypoint under either rule.
+ *
+ * Query by query every output is bit-identical to fxjps_waypoint_st (st), or to fxjps_waypoint_ccst on the grid
+ * fxjps_get_grid_slot(grid_ids[q]) returns (ccst), for that path with that query's reso / origin.  The ccst rule reads the
+ * slot's occupancy AS IT IS WHEN THIS CALL RUNS, not as it was when the batch was planned.  The st rule's table of angles
+ * is the one of fxjps_waypoint_st_batch, sized from the st queries of the call (resident paths: from the largest slot the
+ * batch named); if it would not fit, or with FXJPS_WAYPOINT_ST_HOST=1, the st queries are walked on host threads while
+ * the ccst queries still run on the device.
+ *
+ * The whole call is refused with FXJPS_E_ARG, nothing queued, fxjps_last_error naming the first offending query: a ccst
+ * query whose slot is out of range or empty, a rule other than 0 / 1, offsets that do not ascend, a negative cell of a
+ * ccst query, nq not the last batch's, resident paths after a batch that was not a slots batch, a handle of
+ * fxjps_create_rank with world > 1.  The call changes neither the resident grid, nor any slot, nor the stored results of
+ * fxjps_replan_frame, nor the resident paths: a second call on the same batch returns the same bytes. */
+int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                               const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
+                               const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
+                               const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
+                               int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -10,7 +10,14 @@ variants alternate over the vehicles.  Both sides' slots are compared byte for b
 alternated in one process; a repetition is a window of as many ticks as make a side run >= 0.2 s; medians of --reps
 windows, per tick.  The bar: new / today <= 1/2 at n = 64 on `synth`.
 --trace-call N [--shape S]: ONE prepare_slots call of N jobs and nothing else (for rocprofv3 --kernel-trace --stats).
-Usage: python tools/fleet_tick_bench.py [--reps 5] [--ns 16 64 256]"""
+
+--stage waypoints: the waypoint third of the tick, one query per vehicle, the rules alternating
+over the vehicles as the variants do.  loop: what a node ran before fxjps_waypoint_slots_batch existed, per vehicle
+select_st, or get_grid_slot + select_ccst.  batch: ONE select_slots_batch on the resident paths.  Both sides' results are
+compared byte for byte before anything is timed; the first batch call (it fills the table of angles) is reported apart.
+For information the whole tick of three calls, and the same with the loop as its last third.  The bar: batch / loop <= 1/2
+at n = 64 on `synth`.  With --trace-call N: prepare, plan, one warm batch call, a pause of 50 ms, then ONE batch call.
+Usage: python tools/fleet_tick_bench.py [--stage maps|waypoints] [--reps 5] [--ns 16 64 256]"""
 import argparse
 import json
 import os
@@ -65,6 +72,84 @@ def slots_bytes(p, n, maps):
     return out
 
 
+def waypoint_inputs(jobs, outs):
+    """One query per vehicle: the keyword arguments of select_slots_batch on the paths of the tick's plan_batch_slots."""
+    import fuxi_planner_amd as fx
+    n = len(jobs)
+    rng = np.random.default_rng(n)
+    reso = np.array([(0.2, 0.5, 1.0)[v % 3] for v in range(n)])
+    rule = np.array([j[5] for j in jobs], np.int32)
+    s, g = np.array([o[0] for o in outs]), np.array([o[1] for o in outs])
+    origin = np.array([fx.Planner.shifted_origin(rng.uniform(-20, 20, 2), o[2], r) for o, r in zip(outs, reso)])
+    pos = np.c_[(s[:, 0] + 1) * reso + origin[:, 0] + rng.normal(0, 0.4, n), (s[:, 1] + 1 - rule) * reso + origin[:, 1] + rng.normal(0, 0.4, n),
+                np.zeros(n)]
+    goal = np.c_[(g[:, 0] + 1) * reso + origin[:, 0], (g[:, 1] + 1 - rule) * reso + origin[:, 1], np.full(n, 1.5)]
+    return dict(rule=rule, map_start=s, map_reso=reso, map_o=origin, pos=pos, global_goal=goal, end_occu=np.array([o[4] for o in outs], np.int32))
+
+
+def waypoints_loop(p, plan, a):
+    """The per-vehicle loop: -> (wp [n, 3], valid components, goal [n, 3])"""
+    from fuxi_planner_amd import waypoints
+    off, cells, cost, st = plan
+    n = len(st)
+    wp, dim, gout = np.zeros((n, 3)), np.full(n, 3, np.int32), np.array(a["global_goal"])
+    for v in range(n):
+        if st[v] <= 0:
+            wp[v] = a["global_goal"][v]
+            continue
+        path = cells[off[v]:off[v + 1]]
+        if a["rule"][v] == 0:
+            w, gout[v], _ = waypoints.select_st(path, a["map_start"][v], a["map_reso"][v], a["map_o"][v], a["pos"][v], a["global_goal"][v], a["end_occu"][v])
+        else:
+            w, _, gout[v] = waypoints.select_ccst(path, p.get_grid_slot(v), a["map_reso"][v], a["map_o"][v], a["pos"][v], a["global_goal"][v],
+                                                  a["end_occu"][v], return_goal=True)
+        wp[v, :len(w)] = w
+        dim[v] = len(w)
+    return wp, dim, gout
+
+
+def waypoint_stage(p, a):
+    from fuxi_planner_amd import waypoints
+    ms = lambda ts: round(float(np.median(ts)) * 1e3, 4)
+    spread = lambda ts: [round(min(ts) * 1e3, 4), round(max(ts) * 1e3, 4)]
+    out = {"tool": "fleet_tick_bench", "stage": "waypoints", "reps": a.reps, "window_s": WINDOW_S, "ifa": 1, "cases": []}
+    first_ms = None
+    for shape in a.shapes:
+        for n in a.ns:
+            jobs = fleet(shape, n)
+            outs = side_new(p, jobs)
+            assert all(o[5] for o in outs), (shape, n)
+            ids = np.arange(n, dtype=np.int32)
+            starts, goals = [o[0] for o in outs], [o[1] for o in outs]
+            plan = p.plan_batch_slots(ids, starts, goals, 2)
+            inp = waypoint_inputs(jobs, outs)
+            t0 = time.perf_counter()
+            got = waypoints.select_slots_batch(p, **inp)
+            first = (time.perf_counter() - t0) * 1e3
+            if first_ms is None:
+                first_ms = round(first, 4)  # (the process's first call: it fills the table of angles and loads the kernel)
+            want = waypoints_loop(p, plan, inp)
+            assert got[0].tobytes() == want[0].tobytes() and np.array_equal(got[1], want[1]) and got[2].tobytes() == want[2].tobytes(), (shape, n)
+            tick = lambda: (side_new(p, jobs), p.plan_batch_slots(ids, starts, goals, 2))
+            sides = {"batch": lambda: waypoints.select_slots_batch(p, **inp), "loop": lambda: waypoints_loop(p, plan, inp),
+                     "tick_batch": lambda: (tick(), waypoints.select_slots_batch(p, **inp)),
+                     "tick_loop": lambda: waypoints_loop(p, tick()[1], inp)}
+            t, per = windows(sides, a.reps)
+            case = {"shape": shape, "n": n, "planned": int((plan[3] > 0).sum()), "ccst": int((inp["rule"] == 1).sum()),
+                    "path_points_max": int(plan[3].max()), "intermediate_wp": int((got[0][:, :2] != inp["global_goal"][:, :2]).any(1).sum()),
+                    "calls_per_window": per, "batch_ms": ms(t["batch"]), "loop_ms": ms(t["loop"]),
+                    "ratio": round(float(np.median(t["batch"]) / np.median(t["loop"])), 4), "spread_batch_ms": spread(t["batch"]),
+                    "spread_loop_ms": spread(t["loop"]), "first_call_of_case_ms": round(first, 4), "tick_batch_ms": ms(t["tick_batch"]),
+                    "tick_loop_ms": ms(t["tick_loop"]), "spread_tick_batch_ms": spread(t["tick_batch"]), "spread_tick_loop_ms": spread(t["tick_loop"]),
+                    "batch_us_per_vehicle": round(float(np.median(t["batch"])) * 1e6 / n, 2),
+                    "loop_us_per_vehicle": round(float(np.median(t["loop"])) * 1e6 / n, 2)}
+            if shape == "synth" and n == 64:
+                case["bar_half_met"] = bool(np.median(t["batch"]) <= 0.5 * np.median(t["loop"]))
+            out["cases"].append(case)
+    out["first_call_ms"] = first_ms
+    print(json.dumps(out))
+
+
 def windows(sides, reps):
     """sides: {name: fn}.  -> {name: [seconds per call, one per window]}; the sides alternate window by window."""
     per = {}
@@ -90,10 +175,27 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=["synth", "png"])
     ap.add_argument("--trace-call", type=int, default=0)
     ap.add_argument("--shape", default="synth")
+    ap.add_argument("--stage", choices=["maps", "waypoints"], default="maps")
     a = ap.parse_args()
     import fuxi_planner_amd as fx
 
     p = fx.Planner([0])
+    if a.stage == "waypoints":
+        if a.trace_call:
+            from fuxi_planner_amd import waypoints
+            jobs = fleet(a.shape, a.trace_call)
+            outs = side_new(p, jobs)
+            plan = p.plan_batch_slots(np.arange(a.trace_call, dtype=np.int32), [o[0] for o in outs], [o[1] for o in outs], 2)
+            inp = waypoint_inputs(jobs, outs)
+            waypoints.select_slots_batch(p, **inp)
+            time.sleep(0.05)
+            got = waypoints.select_slots_batch(p, **inp)
+            print(json.dumps({"tool": "fleet_tick_bench", "stage": "waypoints", "trace_call": a.trace_call, "shape": a.shape,
+                              "planned": int((plan[3] > 0).sum()), "ccst_kept": int(got[4].sum())}))
+        else:
+            waypoint_stage(p, a)
+        p.close()
+        return
     if a.trace_call:
         outs = p.prepare_slots(fleet(a.shape, a.trace_call))
         print(json.dumps({"tool": "fleet_tick_bench", "trace_call": a.trace_call, "shape": a.shape, "ok": sum(o[5] for o in outs)}))
