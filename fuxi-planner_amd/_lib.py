@@ -13,14 +13,14 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 730  # FXJPS_VERSION of include/fxjps.h
+VERSION = 740  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
            "fxjps_plan_batch_csr", "fxjps_last_cells", "fxjps_last_timing", "fxjps_last_timing_device", "fxjps_comm_info", "fxjps_set_memory_share", "fxjps_selftest_sqrt", "fxjps_selftest_wavemin", "fxjps_selftest_openlist", "fxjps_debug_read_nbmask", "fxjps_debug_read_maps", "fxjps_debug_counters", "fxjps_debug_qstat",
            "fxjps_waypoint_st", "fxjps_waypoint_ccst", "fxjps_waypoint_ccst_batch", "fxjps_waypoint_st_batch",
            "fxjps_set_grid_slot", "fxjps_get_grid_slot", "fxjps_plan_batch_slots_csr", "fxjps_debug_read_slot_maps", "fxjps_debug_read_sets",
-           "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch")
+           "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch", "fxjps_publish_slots", "fxjps_slot_publish_size")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 
 
@@ -37,6 +37,12 @@ class SlotJob(C.Structure):
     _fields_ = [("raw", C.c_void_p), ("slot", C.c_int32), ("layout", C.c_int32), ("W0", C.c_int32), ("H0", C.c_int32),
                 ("ifa", C.c_int32), ("variant", C.c_int32), ("start_xy", C.c_int32 * 2), ("goal_xy", C.c_int32 * 2),
                 ("W", C.c_int32), ("H", C.c_int32), ("map_d", C.c_int32 * 2), ("end_occu", C.c_int32), ("status", C.c_int32)]
+
+
+class SlotPublish(C.Structure):
+    """fxjps_slot_publish_t: one slot's map on its way out as a message and / or a snapshot image (fxjps_publish_slots)."""
+    _fields_ = [("msg_data", C.c_void_p), ("image", C.c_void_p), ("slot", C.c_int32), ("channels", C.c_int32), ("W", C.c_int32),
+                ("H", C.c_int32)]
 
 
 class FxjpsError(RuntimeError):
@@ -86,6 +92,10 @@ def load():
     L.fxjps_slot_job_size.restype = C.c_int
     if L.fxjps_slot_job_size() != C.sizeof(SlotJob):
         raise FxjpsError(E_ARG, "%s has a %d-byte slot job; this binding's is %d bytes: rebuild it" % (LIB_PATH, L.fxjps_slot_job_size(), C.sizeof(SlotJob)))
+    L.fxjps_slot_publish_size.restype = C.c_int
+    if L.fxjps_slot_publish_size() != C.sizeof(SlotPublish):
+        raise FxjpsError(E_ARG, "%s has a %d-byte slot publish job; this binding's is %d bytes: rebuild it"
+                         % (LIB_PATH, L.fxjps_slot_publish_size(), C.sizeof(SlotPublish)))
     L.fxjps_last_timing_sized.restype = C.c_int
     L.fxjps_last_timing_sized.argtypes = [vp, vp, C.c_int64]
     L.fxjps_rank_preflight.restype = C.c_int
@@ -140,6 +150,8 @@ def load():
                                              C.c_int64, p_i32, p_f64, p_f64]
     L.fxjps_prepare_slots.restype = C.c_int
     L.fxjps_prepare_slots.argtypes = [vp, C.POINTER(SlotJob), C.c_int32]
+    L.fxjps_publish_slots.restype = C.c_int
+    L.fxjps_publish_slots.argtypes = [vp, C.POINTER(SlotPublish), C.c_int32]
     L.fxjps_debug_read_slot_maps.restype = C.c_int
     L.fxjps_debug_read_slot_maps.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, p_i64]
     L.fxjps_debug_read_sets.restype = C.c_int

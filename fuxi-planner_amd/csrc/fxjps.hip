@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -188,6 +189,9 @@ struct DevCtx : GridBufs {
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
     DBuf<int32_t> d_slots_res;
+    // fxjps_publish_slots: the call's job table (fx::PubTable) and all its outputs, pinned and on the device
+    HBuf<uint8_t> h_pub_in, h_pub_out;
+    DBuf<uint8_t> d_pub_in, d_pub_out;
     // a slots batch in progress: its grid ids (the caller's array) and the largest extents of the slots it names, which
     // size the scratch, the watchdog and the far band's form in place of the resident grid's
     const int32_t* mg_ids = nullptr;
@@ -1724,6 +1728,10 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_slots_in.release();
         d.h_slots_res.release();
         d.d_slots_res.release();
+        d.h_pub_in.release();
+        d.h_pub_out.release();
+        d.d_pub_in.release();
+        d.d_pub_out.release();
         if (d.ev_upd) (void)hipEventDestroy(d.ev_upd);
         if (d.ev_stage) (void)hipEventDestroy(d.ev_stage);
         d.h_occ_stage.release();
@@ -2521,6 +2529,83 @@ int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) {
         jb.map_d[1] = (int32_t)p.dy;
         jb.end_occu = res[(size_t)j * fx::SLOT_RES + 2];
         jb.status = res[(size_t)j * fx::SLOT_RES + 3] != 0 ? FXJPS_E_ARG : FXJPS_OK;
+    }
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ many slots' maps published, one call
+int fxjps_slot_publish_size(void) { return (int)sizeof(fxjps_slot_publish_t); }
+
+int fxjps_publish_slots(fxjps_t* h, fxjps_slot_publish_t* jobs, int32_t n) {
+    if (!h) return FXJPS_E_ARG;
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
+    if (int rr = refuse_on_rank_handle(h, "fxjps_publish_slots")) return rr;
+    // everything the host can judge, for every job, before anything is queued or written
+    constexpr size_t OUT_MAX = (size_t)1 << 30;
+    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    size_t out_bytes = 0;
+    for (int j = 0; j < n; j++) {
+        const fxjps_slot_publish_t& jb = jobs[j];
+        if (!slot_in_use(h, jb.slot)) return fail(h, FXJPS_E_ARG, "job %d: grid slot %d is empty or out of range", j, (int)jb.slot);
+        if (jb.image && jb.channels != 1 && jb.channels != 3) return fail(h, FXJPS_E_ARG, "job %d: channels = %d, must be 1 (L) or 3 (RGB)", j, (int)jb.channels);
+        const GridBufs& g = h->devs[0].slots[(size_t)jb.slot];
+        const size_t cells = (size_t)g.W * (size_t)g.H;  // (at most 8190^2: no overflow below)
+        if (jb.msg_data) out_bytes += up16(cells);
+        if (jb.image) out_bytes += up16(cells * (size_t)jb.channels);
+        if (out_bytes > OUT_MAX) return fail(h, FXJPS_E_ARG, "job %d: the call's outputs exceed 2^30 bytes", j);
+    }
+    DevCtx& d = h->devs[0];
+    for (int j = 0; j < n; j++) {
+        const GridBufs& g = d.slots[(size_t)jobs[j].slot];
+        jobs[j].W = g.W;
+        jobs[j].H = g.H;
+    }
+    if (out_bytes == 0) return FXJPS_OK;  // (extents only)
+    HIPCHK(h, hipSetDevice(d.dev));
+    // (no host wait in front: every earlier call of this one has waited for its copy out of these buffers)
+    const size_t in_bytes = offsetof(fx::PubTable, job) + (size_t)n * sizeof(fx::PubJobDev);
+    HIPCHK(h, d.h_pub_in.ensure(sizeof(fx::PubTable)));
+    HIPCHK(h, d.d_pub_in.ensure(sizeof(fx::PubTable)));
+    HIPCHK(h, d.h_pub_out.ensure(out_bytes));
+    HIPCHK(h, d.d_pub_out.ensure(out_bytes));
+    fx::PubTable& T = *reinterpret_cast<fx::PubTable*>(d.h_pub_in.p);
+    uint32_t at = 0;
+    size_t off = 0;
+    for (int j = 0; j < n; j++) {
+        const fxjps_slot_publish_t& jb = jobs[j];
+        const GridBufs& g = d.slots[(size_t)jb.slot];
+        const size_t cells = (size_t)g.W * (size_t)g.H;
+        fx::PubJobDev& J = T.job[j];
+        J.occ = g.occ.p;
+        J.W = g.W;
+        J.H = g.H;
+        J.nty = (g.H + 31) / 32;
+        J.ch = jb.image ? jb.channels : 1;
+        J.msg_off = J.img_off = -1;
+        if (jb.msg_data) {
+            J.msg_off = (long long)off;
+            off += up16(cells);
+        }
+        if (jb.image) {
+            J.img_off = (long long)off;
+            off += up16(cells * (size_t)jb.channels);
+        }
+        T.first[j] = at;
+        if (jb.msg_data || jb.image) at += (uint32_t)(((g.W + 31) / 32) * J.nty);  // (at most 2^30 / 2^10 tiles in all)
+    }
+    T.first[n] = at;
+    HIPCHK(h, hipMemcpyAsync(d.d_pub_in.p, d.h_pub_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+    hipLaunchKernelGGL(fx::k_publish_slots, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<const fx::PubTable*>(d.d_pub_in.p), (int)n, d.d_pub_out.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_pub_out.p, d.d_pub_out.p, out_bytes, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    for (int j = 0; j < n; j++) {
+        const fxjps_slot_publish_t& jb = jobs[j];
+        const fx::PubJobDev& J = T.job[j];
+        const size_t cells = (size_t)J.W * (size_t)J.H;
+        if (jb.msg_data) memcpy(jb.msg_data, d.h_pub_out.p + J.msg_off, cells);
+        if (jb.image) memcpy(jb.image, d.h_pub_out.p + J.img_off, cells * (size_t)jb.channels);
     }
     return FXJPS_OK;
 }

@@ -882,6 +882,58 @@ __global__ __launch_bounds__(256) void k_transpose_map(const uint8_t* __restrict
     }
 }
 
+// ---- Many slots' maps on their way out in one call (fxjps_publish_slots, DESIGN.md section 3.10): the two grid -> wire
+// adapters above (TM_OCC_TO_MSG, and TM_OCC_TO_GRAY with the rows flipped) for every job of the call in ONE launch.  Its
+// blocks are the 32 x 32 tiles of job 0, then those of job 1, ...: PubTable::first[j] is the first block of job j
+// (first[n] the grid size), found by the block-uniform search of section 3.8 (slot_job_of).  A block reads its tile of
+// occ[x][y] once and writes from it whichever outputs its job asked for; both land in one output buffer, each at the
+// 16-byte aligned offset the host chose.  Everything per job is block-uniform: it is loaded once, into scalar registers.
+struct PubJobDev {
+    const uint8_t* occ;  // [W][H] the slot's grid
+    int32_t W, H;
+    int32_t nty;         // tiles along y: (H + 31) / 32
+    int32_t ch;          // channels of the image
+    long long msg_off;   // of data[] [H][W] in the output buffer; < 0: not asked for
+    long long img_off;   // of the image [H][W][ch]; < 0: not asked for
+};
+struct PubTable {
+    uint32_t first[SLOT_JOBS_MAX + 1];
+    uint32_t pad_[3];    // (the jobs start at a 16-byte boundary)
+    PubJobDev job[SLOT_JOBS_MAX];
+};
+__global__ __launch_bounds__(256) void k_publish_slots(const PubTable* __restrict__ T, int n, uint8_t* __restrict__ out) {
+    __shared__ uint8_t tile[32][33];
+    const int j = slot_job_of(T->first, n, blockIdx.x);
+    const PubJobDev& J = T->job[j];
+    const uint8_t* __restrict__ occ = J.occ;
+    const int W = J.W, H = J.H, nty = J.nty, ch = J.ch;
+    const long long msg_off = J.msg_off, img_off = J.img_off;
+    const int t = (int)(blockIdx.x - T->first[j]);
+    const int x0 = (t / nty) * 32, y0 = (t % nty) * 32;
+    const int tx = (int)(threadIdx.x & 31u), ty = (int)(threadIdx.x >> 5);
+    for (int r = ty; r < 32; r += 8) {  // rows of occ: x; contiguous: y
+        const int x = x0 + r, y = y0 + tx;
+        tile[r][tx] = (x < W && y < H) ? occ[(size_t)x * H + y] : (uint8_t)0;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {  // rows of both outputs: y; contiguous: x
+        const int y = y0 + r, x = x0 + tx;
+        if (x < W && y < H) {
+            const uint8_t u = tile[tx][r];
+            if (msg_off >= 0) out[(size_t)msg_off + (size_t)y * W + x] = u ? 100 : 0;  // data.T, 1 -> 100   st:103,114
+            if (img_off >= 0) {                                                        // 0 -> 255, else 0; mapsave.T[::-1]   st:368-371
+                const size_t o = (size_t)img_off + ((size_t)(H - 1 - y) * W + x) * (size_t)ch;
+                const uint8_t v = u == 0 ? 255 : 0;
+                out[o] = v;
+                if (ch == 3) {  // (the host let nothing but 1 and 3 through)
+                    out[o + 1] = v;
+                    out[o + 2] = v;
+                }
+            }
+        }
+    }
+}
+
 // A cell that a list names more than once takes the value of its LAST entry (what `grid[xs, ys] = vals` does on the
 // host): every entry leaves its index, by atomic maximum, in owner[cell] (all -1 at rest), and only the entry that
 // finds its own index there applies its value -- and puts the -1 back.

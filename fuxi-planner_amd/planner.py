@@ -341,6 +341,35 @@ class Planner(object):
         return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy[0], j.goal_xy[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
                  j.status == 0) for j in arr[:len(jobs)]]
 
+    def publish_slots(self, slots, msg=True, image_channels=None):
+        """The fleet's publishing quarter of a tick in ONE call (fxjps_publish_slots): for every slot named what publish_map
+        and / or snapshot_image would return were it the resident grid.  msg (bool) and image_channels (None, 1 or 3) are
+        one value for all slots or one per slot.  -> per slot (data int8[W*H] or None, (W, H), image uint8 [H, W] /
+        [H, W, 3] or None).  Two C calls: the extents, then the data.  A slot may be named more than once."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        msgs = list(msg) if isinstance(msg, (list, tuple, np.ndarray)) else [msg] * n
+        chans = list(image_channels) if isinstance(image_channels, (list, tuple, np.ndarray)) else [image_channels] * n
+        if len(msgs) != n or len(chans) != n:
+            raise ValueError("msg and image_channels must be one value or one per slot")
+        arr = (_lib.SlotPublish * max(n, 1))()
+        for j, s in zip(arr, slots):
+            j.slot = s
+        self._chk(self._L.fxjps_publish_slots(self._h, arr, n))
+        out = []
+        for j, m, c in zip(arr, msgs, chans):
+            data = np.empty(j.W * j.H, dtype=np.int8) if m else None
+            img = None
+            if c is not None:
+                c = int(c)
+                img = np.empty((j.H, j.W) if c == 1 else (j.H, j.W, c), dtype=np.uint8)
+                j.image, j.channels = img.ctypes.data, c
+            if data is not None:
+                j.msg_data = data.ctypes.data
+            out.append((data, (j.W, j.H), img))
+        self._chk(self._L.fxjps_publish_slots(self._h, arr, n))
+        return out
+
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
         """plan_batch with a grid per query: query q runs on the grid of slot grid_ids[q].  -> (offsets, cells, cost,
         status) as plan_batch.  max_path_len=None: the default slot of the largest grid named, grown when a path needs it."""

@@ -81,8 +81,10 @@ typedef struct fxjps fxjps_t;
  *        and host waits do not depend on n), fxjps_slot_job_size.
  *   730  fxjps_waypoint_slots_batch (both waypoint rules over a grid-slots batch in one call: a rule, a slot, a resolution
  *        and an origin per query).
+ *   740  fxjps_publish_slots (the message and / or snapshot image of every named grid slot by one call whose launches and
+ *        host waits do not depend on n), fxjps_slot_publish_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 730
+#define FXJPS_VERSION 740
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -288,6 +290,32 @@ typedef struct fxjps_slot_job {
 } fxjps_slot_job_t;
 int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n);
 int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was built (cf. fxjps_timing_size) */
+
+/* ---- Many slots' maps published in one call (the last quarter of a fleet tick: every vehicle's prepared map leaves the
+ * device as the message and / or the snapshot image a node publishes).  Job by job the results are those of
+ * fxjps_publish_map (msg_data) and fxjps_snapshot_image (image) with "the resident grid" replaced by "slot `slot`" AS IT
+ * IS WHEN THIS CALL RUNS: the work is queued on the context's stream, behind any fxjps_prepare_slots / fxjps_set_grid_slot
+ * that came before.  The number of kernel launches, copies and host waits of a call does not depend on n: one staged copy
+ * of a job table in, ONE launch that reads every 32 x 32 tile of every named slot once and writes from it whichever
+ * outputs its job asked for, one copy of all outputs into pinned memory, one wait; the host then copies each job's bytes
+ * into the caller's arrays.
+ *   A job with both pointers NULL only gets its extents; a call whose jobs are all such jobs queues nothing (callers size
+ * their buffers with it).  A slot may be named by more than one job.  Nothing is written to a slot; the resident grid,
+ * stored replan results and the last batch's resident paths are not touched.  A handle with several contexts reads
+ * context 0's copy of the slot.
+ *   Whole-call errors (FXJPS_E_ARG, nothing queued, nothing written -- W and H included -- and fxjps_last_error names the
+ * first offending job): n outside 0 .. FXJPS_MAX_GRID_SLOTS, a slot out of range or empty, channels not 1 or 3 with a
+ * non-NULL image, more than 2^30 bytes of output in all (every output counted up to the next multiple of 16 bytes).  A rank
+ * handle (fxjps_create_rank, world > 1) refuses with FXJPS_E_ARG. */
+typedef struct fxjps_slot_publish {
+    int8_t* msg_data;     /* in: NULL, or room for W*H int8: nav_msgs/OccupancyGrid data[], row-major [y][x], 100 = occupied */
+    uint8_t* image;       /* in: NULL, or room for H*W*channels bytes: the snapshot convention (mapsave.T[::-1]) */
+    int32_t slot;         /* in: 0 .. FXJPS_MAX_GRID_SLOTS - 1 */
+    int32_t channels;     /* in: 1 (L) or 3 (RGB); read only when image != NULL */
+    int32_t W, H;         /* out: the slot's extents (info.width = W, info.height = H; image rows = H, cols = W) */
+} fxjps_slot_publish_t;
+int fxjps_publish_slots(fxjps_t* h, fxjps_slot_publish_t* jobs, int32_t n);
+int fxjps_slot_publish_size(void); /* sizeof(fxjps_slot_publish_t) as the library was built (cf. fxjps_slot_job_size) */
 
 /* Measurement hooks (bench.py, tests). */
 typedef struct fxjps_timing {

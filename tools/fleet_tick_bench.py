@@ -17,7 +17,14 @@ select_st, or get_grid_slot + select_ccst.  batch: ONE select_slots_batch on the
 compared byte for byte before anything is timed; the first batch call (it fills the table of angles) is reported apart.
 For information the whole tick of three calls, and the same with the loop as its last third.  The bar: batch / loop <= 1/2
 at n = 64 on `synth`.  With --trace-call N: prepare, plan, one warm batch call, a pause of 50 ms, then ONE batch call.
-Usage: python tools/fleet_tick_bench.py [--stage maps|waypoints] [--reps 5] [--ns 16 64 256]"""
+
+--stage publish: the publishing quarter of the tick, every vehicle's prepared map out of its slot
+as the nav_msgs/OccupancyGrid data[] the nodes publish.  new: ONE publish_slots call, messages only.  loop: what a fleet host
+writes without it, per vehicle get_grid_slot + the numpy lines of the reference's publish_map.  Both sides' outputs are
+compared byte for byte before anything is timed.  At n = 64 also messages plus RGB snapshots both ways, and the whole tick
+of four calls against the same tick with the loop as its last quarter and against the per-vehicle tick (all four stages
+per vehicle).  The bar: new / loop <= 1/2 at n = 64 on `synth`.  The JSON line is also written to --out.
+Usage: python tools/fleet_tick_bench.py [--stage maps|waypoints|publish] [--reps 5] [--ns 16 64 256]"""
 import argparse
 import json
 import os
@@ -150,6 +157,76 @@ def waypoint_stage(p, a):
     print(json.dumps(out))
 
 
+def publish_loop(p, n, rgb=False):
+    """The per-vehicle loop: get_grid_slot, then publish_map (global_planner_st.py:103,109-115) and, with rgb, the snapshot
+    (st:368-372) in numpy.  -> [(data int8[W*H], (W, H), image or None)]"""
+    out = []
+    for v in range(n):
+        g = p.get_grid_slot(v)
+        d = np.where(g == 1, 100, 0).astype(np.int8)
+        img = None
+        if rgb:
+            img = np.where(g == 0, 255, 0).astype(np.uint8).T[::-1]
+            img = np.repeat(img[:, :, None], 3, axis=2)
+        out.append((d.T.reshape(-1), (g.shape[0], g.shape[1]), img))
+    return out
+
+
+def same_published(a, b):
+    return len(a) == len(b) and all(x[0].tobytes() == y[0].tobytes() and tuple(x[1]) == tuple(y[1]) and (x[2] is None) == (y[2] is None)
+                                    and (x[2] is None or (x[2].shape == y[2].shape and x[2].tobytes() == y[2].tobytes())) for x, y in zip(a, b))
+
+
+def publish_stage(p, a):
+    from fuxi_planner_amd import waypoints
+    ms = lambda ts: round(float(np.median(ts)) * 1e3, 4)
+    spread = lambda ts: [round(min(ts) * 1e3, 4), round(max(ts) * 1e3, 4)]
+    out = {"tool": "fleet_tick_bench", "stage": "publish", "reps": a.reps, "window_s": WINDOW_S, "ifa": 1, "cases": []}
+    for shape in a.shapes:
+        for n in a.ns:
+            jobs = fleet(shape, n)
+            outs = side_new(p, jobs)
+            assert all(o[5] for o in outs), (shape, n)
+            slots = list(range(n))
+            assert same_published(p.publish_slots(slots), publish_loop(p, n)), (shape, n)
+            sides = {"new": lambda: p.publish_slots(slots), "loop": lambda: publish_loop(p, n)}
+            if n == 64:
+                assert same_published(p.publish_slots(slots, True, 3), publish_loop(p, n, True)), (shape, n)
+                ids = np.arange(n, dtype=np.int32)
+                starts, goals = [o[0] for o in outs], [o[1] for o in outs]
+                inp = waypoint_inputs(jobs, outs)
+                three = lambda: (side_new(p, jobs), p.plan_batch_slots(ids, starts, goals, 2), waypoints.select_slots_batch(p, **inp))
+                sides.update({"new_rgb": lambda: p.publish_slots(slots, True, 3), "loop_rgb": lambda: publish_loop(p, n, True),
+                              "tick_new": lambda: (three(), p.publish_slots(slots)), "tick_publish_loop": lambda: (three(), publish_loop(p, n)),
+                              "tick_per_vehicle": lambda: (side_today(p, jobs), waypoints_loop(p, p.plan_batch_slots(ids, starts, goals, 2), inp),
+                                                           publish_loop(p, n))})
+            t, per = windows(sides, a.reps)
+            cells = [o[3][0] * o[3][1] for o in outs]
+            case = {"shape": shape, "n": n, "prepared_cells_min_max": [min(cells), max(cells)], "message_bytes": int(sum(cells)),
+                    "calls_per_window": per, "new_ms": ms(t["new"]), "loop_ms": ms(t["loop"]),
+                    "ratio": round(float(np.median(t["new"]) / np.median(t["loop"])), 4), "spread_new_ms": spread(t["new"]),
+                    "spread_loop_ms": spread(t["loop"]), "new_us_per_vehicle": round(float(np.median(t["new"])) * 1e6 / n, 2),
+                    "loop_us_per_vehicle": round(float(np.median(t["loop"])) * 1e6 / n, 2)}
+            if n == 64:
+                case.update({"new_rgb_ms": ms(t["new_rgb"]), "loop_rgb_ms": ms(t["loop_rgb"]),
+                             "ratio_rgb": round(float(np.median(t["new_rgb"]) / np.median(t["loop_rgb"])), 4),
+                             "spread_new_rgb_ms": spread(t["new_rgb"]), "spread_loop_rgb_ms": spread(t["loop_rgb"])})
+                for k in ("tick_new", "tick_publish_loop", "tick_per_vehicle"):
+                    case[k + "_ms"] = ms(t[k])
+                    case["spread_" + k + "_ms"] = spread(t[k])
+                case["publish_share_of_tick_new"] = round(float(np.median(t["new"]) / np.median(t["tick_new"])), 4)
+                case["publish_loop_share_of_its_tick"] = round(float(np.median(t["loop"]) / np.median(t["tick_publish_loop"])), 4)
+                if shape == "synth":
+                    case["bar_half_met"] = bool(np.median(t["new"]) <= 0.5 * np.median(t["loop"]))
+            out["cases"].append(case)
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def windows(sides, reps):
     """sides: {name: fn}.  -> {name: [seconds per call, one per window]}; the sides alternate window by window."""
     per = {}
@@ -175,11 +252,16 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=["synth", "png"])
     ap.add_argument("--trace-call", type=int, default=0)
     ap.add_argument("--shape", default="synth")
-    ap.add_argument("--stage", choices=["maps", "waypoints"], default="maps")
+    ap.add_argument("--stage", choices=["maps", "waypoints", "publish"], default="maps")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_publish_bench.json"), help="--stage publish: where the JSON line is written too")
     a = ap.parse_args()
     import fuxi_planner_amd as fx
 
     p = fx.Planner([0])
+    if a.stage == "publish":
+        publish_stage(p, a)
+        p.close()
+        return
     if a.stage == "waypoints":
         if a.trace_call:
             from fuxi_planner_amd import waypoints
