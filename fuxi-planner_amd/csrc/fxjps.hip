@@ -3011,13 +3011,27 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
 // context's own slot records (d.slots, the records every other slot call keeps): its record carries the occupancy pointer
 // and the extents, so there is no second table on the device that could fall behind fxjps_set_grid_slot /
 // fxjps_prepare_slots, and fx::GridDev stays as it is.
-int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
-                               const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
-                               const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
-                               const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
-                               int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads) {
+//
+// fxjps_tick_outputs_slots is the same call with `K` set: the record of a query grows by its home position,
+// the result by the Point and the direct path's length, the output buffer by the two world-frame sections, and the launch
+// is k_tick_outputs_slots.  With K == nullptr every byte staged, launched and copied is what it was before that call existed.
+struct TickIO {
+    const double* home_xy;
+    double* out_point;
+    double* out_path_xyz;
+    int64_t path_capacity;
+    double* out_dir_xyz;
+    int32_t* out_dir_n;
+    int32_t* out_dir_back;
+    int64_t dir_capacity;
+};
+static int wp_slots_call(fxjps_t* h, const char* fn, const TickIO* K, int64_t nq, const int64_t* offsets, const int32_t* cells_xy,
+                         const int32_t* grid_ids, const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin,
+                         const double* pos, const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre,
+                         const double* prev_wp, const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
+                         int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads) {
     if (!h) return FXJPS_E_ARG;
-    if (int rr = refuse_on_rank_handle(h, "fxjps_waypoint_slots_batch")) return rr;
+    if (int rr = refuse_on_rank_handle(h, fn)) return rr;
     if (nq < 0 || (nq > 0 && (!rule || !reso || !origin || !pos || !goal || !out_wp))) return fail(h, FXJPS_E_ARG, "bad waypoint arguments");
     if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
     if ((prev_wp != nullptr) != (prev_dim != nullptr)) return fail(h, FXJPS_E_ARG, "prev_wp and prev_dim go together");
@@ -3026,6 +3040,7 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
     if (resident && (nq != h->last_nq || (int64_t)h->last_slot_ids.size() != nq))
         return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
     if (nq == 0) return FXJPS_OK;
+    if (K && K->out_point && !K->home_xy) return fail(h, FXJPS_E_ARG, "query 0: out_point needs home_xy");
     // ---- everything the host can judge, for every query, before anything is queued
     const int32_t* ids = grid_ids ? grid_ids : (resident ? h->last_slot_ids.data() : nullptr);
     int64_t n_st = 0;
@@ -3069,8 +3084,27 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
             kept_base += d.h_offsets.p[d.nq];
         }
     }
-    if (out_kept_cells && kept_capacity < kept_base)
+    // the first query whose range would not fit (query q ends at end(q) [+ 2 (q + 1)])
+    const auto first_over = [&](int64_t cap, int64_t per_q) -> int64_t {
+        for (auto& P : parts)
+            for (int64_t i = 0; i < P.n; i++)
+                if (P.kept_at + P.h_off[i + 1] + per_q * (P.q0 + i + 1) > cap) return P.q0 + i;
+        return -1;
+    };
+    if (out_kept_cells && kept_capacity < kept_base) {
+        if (K)
+            return fail(h, FXJPS_E_ARG, "query %lld: out_kept_cells holds %lld pairs, the paths have %lld", (long long)first_over(kept_capacity, 0),
+                        (long long)kept_capacity, (long long)kept_base);
         return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)kept_base);
+    }
+    if (K) {
+        if (K->out_path_xyz && K->path_capacity < kept_base)
+            return fail(h, FXJPS_E_ARG, "query %lld: out_path_xyz holds %lld triples, the paths have %lld", (long long)first_over(K->path_capacity, 0),
+                        (long long)K->path_capacity, (long long)kept_base);
+        if (K->out_dir_xyz && K->dir_capacity < kept_base + 2 * nq)
+            return fail(h, FXJPS_E_ARG, "query %lld: out_dir_xyz holds %lld triples, the direct paths need %lld", (long long)first_over(K->dir_capacity, 2),
+                        (long long)K->dir_capacity, (long long)(kept_base + 2 * nq));
+    }
     // path q on the host (the st rule's host form)
     const auto path_of = [&](int64_t q, const int32_t** c) -> int64_t {
         if (!resident) {
@@ -3083,6 +3117,13 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
                 return P.h_off[q - P.q0 + 1] - P.h_off[q - P.q0];
             }
         *c = nullptr;
+        return 0;
+    };
+    // ... and where its triples start in the caller's arrays
+    const auto path_at = [&](int64_t q) -> int64_t {
+        if (!resident) return offsets[q];
+        for (auto& P : parts)
+            if (q >= P.q0 && q < P.q0 + P.n) return P.kept_at + P.h_off[q - P.q0];
         return 0;
     };
     // ---- the st rule's table of angles: the range of (cell + 1 - map_start) over the st queries of the call (resident paths
@@ -3114,23 +3155,34 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
     }
     // ---- queue every context, then collect
     static_assert(sizeof(fx::WpSlotQuery) % 8 == 0 && sizeof(fx::WpSlotResult) % 8 == 0, "the offsets and cells behind the records stay aligned");
+    static_assert(sizeof(fx::TickQuery) % 8 == 0 && sizeof(fx::TickResult) % 8 == 0 && offsetof(fx::TickQuery, s) == 0 && offsetof(fx::TickResult, r) == 0,
+                  "a tick record begins with the waypoint record, and the doubles behind the records stay aligned");
     int rc = [&]() -> int {
         for (auto& P : parts) {
             DevCtx& d = *P.d;
             HIPCHK(h, hipSetDevice(d.dev));
             const size_t n = (size_t)P.n, tot = (size_t)P.total;
-            const size_t in_off = n * sizeof(fx::WpSlotQuery), in_cells = in_off + (n + 1) * sizeof(long long);
+            const size_t rec = K ? sizeof(fx::TickQuery) : sizeof(fx::WpSlotQuery);
+            const size_t in_off = n * rec, in_cells = in_off + (n + 1) * sizeof(long long);
             const size_t in_bytes = resident ? in_off : in_cells + tot * 2 * sizeof(int32_t);
-            const size_t out_kept = n * sizeof(fx::WpSlotResult), out_bytes = out_kept + std::max<size_t>(tot, 1) * 2 * sizeof(int32_t);
+            // out: the records | (K: path3 triples | direct-path triples |) the kept cells
+            const size_t out_path = n * (K ? sizeof(fx::TickResult) : sizeof(fx::WpSlotResult));
+            const size_t out_dir = out_path + (K ? tot * 3 * sizeof(double) : 0);
+            const size_t out_kept = out_dir + (K ? (tot + 2 * n) * 3 * sizeof(double) : 0);
+            const size_t out_bytes = out_kept + std::max<size_t>(tot, 1) * 2 * sizeof(int32_t);
             HIPCHK(h, d.h_wps_in.ensure(in_bytes));
             HIPCHK(h, d.d_wps_in.ensure(in_bytes));
             HIPCHK(h, d.h_wps_out.ensure(out_bytes));
             HIPCHK(h, d.d_wps_out.ensure(out_bytes));
-            fx::WpSlotQuery* Q = reinterpret_cast<fx::WpSlotQuery*>(d.h_wps_in.p);
             for (size_t i = 0; i < n; i++) {
                 const int64_t q = P.q0 + (int64_t)i;
-                fx::WpSlotQuery& r = Q[i];
+                fx::WpSlotQuery& r = *reinterpret_cast<fx::WpSlotQuery*>(d.h_wps_in.p + i * rec);  // (a TickQuery begins with one)
                 r = fx::WpSlotQuery{};
+                if (K) {
+                    fx::TickQuery& t = *reinterpret_cast<fx::TickQuery*>(d.h_wps_in.p + i * rec);
+                    t.hx = K->home_xy ? K->home_xy[2 * q] : 0.0;
+                    t.hy = K->home_xy ? K->home_xy[2 * q + 1] : 0.0;
+                }
                 r.rule = rule[q];
                 if (r.rule == 1) {
                     const GridBufs& g = d.slots[(size_t)ids[q]];
@@ -3160,21 +3212,41 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
                 if (tot > 0) memcpy(d.h_wps_in.p + in_cells, cells_xy, tot * 2 * sizeof(int32_t));
             }
             HIPCHK(h, hipMemcpyAsync(d.d_wps_in.p, d.h_wps_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
-            fx::WaypointSlotsArgs A;
-            A.in = reinterpret_cast<const fx::WpSlotQuery*>(d.d_wps_in.p);
-            A.out = reinterpret_cast<fx::WpSlotResult*>(d.d_wps_out.p);
-            A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
-            A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
-            A.len = resident ? d.d_len.p : nullptr;
-            A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
-            A.nq = (long long)P.n;
-            A.dis_wp_tre = dis_wp_tre;
-            A.ang_wp_tre = ang_wp_tre;
-            A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
-            hipLaunchKernelGGL(fx::k_waypoint_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            size_t back = out_path;  // the copy back ends after the last section the caller asked for
+            if (!K) {
+                fx::WaypointSlotsArgs A;
+                A.in = reinterpret_cast<const fx::WpSlotQuery*>(d.d_wps_in.p);
+                A.out = reinterpret_cast<fx::WpSlotResult*>(d.d_wps_out.p);
+                A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
+                A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
+                A.len = resident ? d.d_len.p : nullptr;
+                A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
+                A.nq = (long long)P.n;
+                A.dis_wp_tre = dis_wp_tre;
+                A.ang_wp_tre = ang_wp_tre;
+                A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
+                hipLaunchKernelGGL(fx::k_waypoint_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            } else {
+                fx::TickOutputsArgs A;
+                A.in = reinterpret_cast<const fx::TickQuery*>(d.d_wps_in.p);
+                A.out = reinterpret_cast<fx::TickResult*>(d.d_wps_out.p);
+                A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
+                A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
+                A.len = resident ? d.d_len.p : nullptr;
+                A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
+                A.path_xyz = reinterpret_cast<double*>(d.d_wps_out.p + out_path);
+                A.dir_xyz = reinterpret_cast<double*>(d.d_wps_out.p + out_dir);
+                A.nq = (long long)P.n;
+                A.dis_wp_tre = dis_wp_tre;
+                A.ang_wp_tre = ang_wp_tre;
+                A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
+                hipLaunchKernelGGL(fx::k_tick_outputs_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+                if (K->out_path_xyz) back = out_dir;
+                if (K->out_dir_xyz) back = out_kept;
+            }
             HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpyAsync(d.h_wps_out.p, d.d_wps_out.p, out_kept_cells ? out_kept + tot * 2 * sizeof(int32_t) : out_kept,
-                                     hipMemcpyDeviceToHost, d.stream));
+            if (out_kept_cells) back = out_kept + tot * 2 * sizeof(int32_t);
+            HIPCHK(h, hipMemcpyAsync(d.h_wps_out.p, d.d_wps_out.p, back, hipMemcpyDeviceToHost, d.stream));
         }
         return FXJPS_OK;
     }();
@@ -3209,6 +3281,23 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
                 if (out_n_kept) out_n_kept[q] = 0;
                 if (out_goal)
                     for (int k = 0; k < 3; k++) out_goal[3 * q + k] = gl[k];
+                if (K) {  // st:292-298, 335, 356-359 for the paths the host walked, by the functions the kernel calls
+                    if (K->out_point) {
+                        K->out_point[3 * q] = out_wp[3 * q];
+                        K->out_point[3 * q + 1] = out_wp[3 * q + 1];
+                        K->out_point[3 * q + 2] = fx::tick_point_z(out_wp[3 * q], out_wp[3 * q + 1], gl[0], gl[1], gl[2], K->home_xy[2 * q], K->home_xy[2 * q + 1]);
+                    }
+                    if (K->out_dir_n) K->out_dir_n[q] = 0;
+                    if (K->out_dir_back) K->out_dir_back[q] = 0;
+                    if (K->out_path_xyz && n > 0) {
+                        double* p3 = K->out_path_xyz + 3 * path_at(q);
+                        for (int64_t i = 0; i < n; i++) {
+                            p3[3 * i] = fx::wp_world(c[2 * i] + 1, reso[q], origin[2 * q]);
+                            p3[3 * i + 1] = fx::wp_world(c[2 * i + 1] + 1, reso[q], origin[2 * q + 1]);
+                            p3[3 * i + 2] = 0.0;
+                        }
+                    }
+                }
             }
             return 0;
         });
@@ -3220,12 +3309,29 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
     if (rc) return rc;
     if (bad_q >= 0) return fail(h, FXJPS_E_ARG, "query %d: fxjps_waypoint_st failed on its path", bad_q);
     for (auto& P : parts) {
-        const fx::WpSlotResult* R = reinterpret_cast<const fx::WpSlotResult*>(P.d->h_wps_out.p);
-        const int32_t* kept = reinterpret_cast<const int32_t*>(P.d->h_wps_out.p + (size_t)P.n * sizeof(fx::WpSlotResult));
+        const size_t n = (size_t)P.n, tot = (size_t)P.total;
+        const size_t rec = K ? sizeof(fx::TickResult) : sizeof(fx::WpSlotResult);
+        const uint8_t* base = P.d->h_wps_out.p;
+        const double* path3 = reinterpret_cast<const double*>(base + n * rec);
+        const double* dir = path3 + (K ? tot * 3 : 0);
+        const int32_t* kept = reinterpret_cast<const int32_t*>(dir + (K ? (tot + 2 * n) * 3 : 0));
         for (int64_t i = 0; i < P.n; i++) {
             const int64_t q = P.q0 + i;
             if (rule[q] == 0 && st_on_host) continue;
-            const fx::WpSlotResult& r = R[i];
+            const fx::WpSlotResult& r = *reinterpret_cast<const fx::WpSlotResult*>(base + (size_t)i * rec);  // (a TickResult begins with one)
+            if (K) {
+                const fx::TickResult& t = *reinterpret_cast<const fx::TickResult*>(base + (size_t)i * rec);
+                const int64_t len = P.h_off[i + 1] - P.h_off[i];
+                if (K->out_point)
+                    for (int k = 0; k < 3; k++) K->out_point[3 * q + k] = t.point[k];
+                if (K->out_dir_n) K->out_dir_n[q] = t.dir_n;
+                if (K->out_dir_back) K->out_dir_back[q] = t.dir_back;
+                if (K->out_path_xyz && len > 0)
+                    memcpy(K->out_path_xyz + 3 * (P.kept_at + P.h_off[i]), path3 + 3 * P.h_off[i], (size_t)len * 3 * sizeof(double));
+                if (K->out_dir_xyz && t.dir_n > 0)
+                    memcpy(K->out_dir_xyz + 3 * (P.kept_at + P.h_off[i] + 2 * q), dir + 3 * (P.h_off[i] + 2 * i),
+                           (size_t)std::min<int64_t>(t.dir_n, len + 2) * 3 * sizeof(double));
+            }
             for (int k = 0; k < 3; k++) out_wp[3 * q + k] = r.wp[k];
             if (out_goal)
                 for (int k = 0; k < 3; k++) out_goal[3 * q + k] = r.goal[k];
@@ -3237,6 +3343,29 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
         }
     }
     return FXJPS_OK;
+}
+
+int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                               const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
+                               const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
+                               const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
+                               int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads) {
+    return wp_slots_call(h, "fxjps_waypoint_slots_batch", nullptr, nq, offsets, cells_xy, grid_ids, rule, map_start, reso, origin, pos, goal, end_occu,
+                         dis_wp_tre, ang_wp_tre, prev_wp, prev_dim, out_wp, out_dim, out_goal, out_ang_wp, out_n_kept, out_kept_cells, kept_capacity,
+                         nthreads);
+}
+
+int fxjps_tick_outputs_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                             const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
+                             const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
+                             const int32_t* prev_dim, const double* home_xy, double* out_wp, int32_t* out_dim, double* out_goal,
+                             double* out_ang_wp, int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, double* out_point,
+                             double* out_path_xyz, int64_t path_capacity, double* out_dir_xyz, int32_t* out_dir_n, int32_t* out_dir_back,
+                             int64_t dir_capacity, int32_t nthreads) {
+    const TickIO K{home_xy, out_point, out_path_xyz, path_capacity, out_dir_xyz, out_dir_n, out_dir_back, dir_capacity};
+    return wp_slots_call(h, "fxjps_tick_outputs_slots", &K, nq, offsets, cells_xy, grid_ids, rule, map_start, reso, origin, pos, goal, end_occu,
+                         dis_wp_tre, ang_wp_tre, prev_wp, prev_dim, out_wp, out_dim, out_goal, out_ang_wp, out_n_kept, out_kept_cells, kept_capacity,
+                         nthreads);
 }
 
 int fxjps_last_timing(fxjps_t* h, fxjps_timing_t* out) {

@@ -1372,3 +1372,128 @@ __global__ __launch_bounds__(256) void k_waypoint_slots(WaypointSlotsArgs A) {
         R.nkept = S.m;
     }
 }
+
+// ---------------------------------------------------------------- a fleet tick's outgoing messages (DESIGN.md section 3.11)
+// fxjps_tick_outputs_slots: k_waypoint_slots' selection, and from the registers it leaves what each node publishes after
+// its waypoint block -- /jps_path (path3: every jump point in the world frame, st:292-298 / ccst:487-494),
+// /direct_jps_path (ccst: path4, the world-frame points of the cells the rule just kept, ccst:495-521; without a path the
+// two poses [pos, wp], ccst:485) and the Point of /goal_global (st:335, 356-359 / ccst:559-562, 590-593).  The record of a
+// query is k_waypoint_slots' with the vehicle's home position behind it; the rules are the very functions above.
+// The world-frame expression and the 2-norm are the ones the rules use for path3 and uav2next_wp, written once here for
+// the stores (IEEE multiply, add, divide and sqrt; -ffp-contract=off).
+struct TickQuery {
+    WpSlotQuery s;
+    double hx, hy;  // (xo, yo): the vehicle's position on its first tick
+};
+struct TickResult {
+    WpSlotResult r;
+    double point[3];
+    int32_t dir_n, dir_back;
+};
+struct TickOutputsArgs {
+    const TickQuery* in;      // [nq]
+    TickResult* out;          // [nq]
+    const int32_t* cells;     // CSR paths: (x, y) pairs
+    const long long* offsets; // [nq + 1]
+    const int32_t* len;       // > 0: jump points of the path, else no path; nullptr: offsets[q + 1] - offsets[q]
+    int32_t* kept;            // CSR with the offsets of the paths (ccst queries only)
+    double* path_xyz;         // [cells][3]: path3 of query q at triple offsets[q]
+    double* dir_xyz;          // [cells + 2 nq][3]: the direct path of query q at triple offsets[q] + 2 q
+    long long nq;
+    double dis_wp_tre, ang_wp_tre;
+    WpAtab T;
+};
+// (host and device: the st rule's host form in fxjps.hip calls the same three functions)
+__host__ __device__ __forceinline__ double wp_world(int c, double reso, double o) { return (double)c * reso + o; }
+__host__ __device__ __forceinline__ double wp_norm2(double x, double y) { return sqrt(x * x + y * y); }
+// st:335 / ccst:562 with Python's min(r, 1): 1 iff 1 < r, so a NaN (0 / 0) stays and x / 0 gives 1
+__host__ __device__ __forceinline__ double tick_point_z(double wx, double wy, double gx, double gy, double gz, double hx, double hy) {
+    const double r = wp_norm2(wx - hx, wy - hy) / wp_norm2(gx - hx, gy - hy);
+    const double r1 = 1.0 < r ? 1.0 : r;
+    return 1.0 + r1 * (gz - 1.0);
+}
+__global__ __launch_bounds__(256) void k_tick_outputs_slots(TickOutputsArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= A.nq) return;
+    const WpSlotQuery& Q = A.in[q].s;
+    const int rule = rfli(Q.rule);
+    if (rule != 0 && rule != 1) return;
+    const long long off = (long long)rfl64((uint64_t)A.offsets[q]);
+    const long long room = (long long)rfl64((uint64_t)A.offsets[q + 1]) - off;  // the query's own range: no store goes past it
+    const int n = A.len ? rfli(A.len[q]) : rfli((int)min(room, 0x7FFFFFFFll));
+    const WpView V{reinterpret_cast<const uint8_t*>(rfl64((uint64_t)Q.occ)), rfli(Q.W), rfli(Q.H), rfld(Q.reso), rfld(Q.ox), rfld(Q.oy),
+                   rfli(Q.msx), rfli(Q.msy)};
+    const int eo = rfli(Q.eo);
+    const double px = rfld(Q.pos[0]), py = rfld(Q.pos[1]), pz = rfld(Q.pos[2]);
+    const double gx = rfld(Q.goal[0]), gy = rfld(Q.goal[1]), gz = rfld(Q.goal[2]);
+    const int2* c = reinterpret_cast<const int2*>(A.cells) + (n > 0 ? off : 0);
+    int2* kept = reinterpret_cast<int2*>(A.kept) + (n > 0 ? off : 0);
+    WpSel S;
+    if (rule == 1) {
+        S = wp_rule_ccst(V, c, kept, n, px, py, pz, gx, gy, gz, eo, lane);
+    } else {
+        S = wp_rule_st(V, A.T, c, n, px, py, pz, gx, gy, gz, eo, rfli(Q.pdim), Q.prev, A.dis_wp_tre, A.ang_wp_tre, lane);
+    }
+    // ---- /jps_path: path2 = path + (1, 1) (st) or + (1, 0) (ccst), path3 = path2 * map_reso + map_o, z = 0
+    const int np = (int)min((long long)max(n, 0), room);
+    const int yplus = rule == 1 ? 0 : 1;
+    double* p3 = A.path_xyz + 3 * off;
+    for (int i = lane; i < np; i += WAVE) {
+        const int2 p = c[i];
+        p3[3 * i] = wp_world(p.x + 1, V.reso, V.ox);
+        p3[3 * i + 1] = wp_world(p.y + yplus, V.reso, V.oy);
+        p3[3 * i + 2] = 0.0;
+    }
+    RECONV();
+    // ---- /direct_jps_path (ccst): the kept cells in the world frame, or the two poses
+    int dir_n = 0, dir_back = 0;
+    if (rule == 1) {
+        double* d4 = A.dir_xyz + 3 * (off + 2 * q);  // (room + 2 triples are this query's)
+        if (n > 0) {
+            dir_n = S.m;
+            __threadfence_block();  // lane 0 wrote the cells the pruning kept
+            const int nd = min(S.m, np);
+            for (int i = lane; i < nd; i += WAVE) {
+                const int2 p = kept[i];
+                d4[3 * i] = wp_world(p.x + 1, V.reso, V.ox);
+                d4[3 * i + 1] = wp_world(p.y, V.reso, V.oy);
+                d4[3 * i + 2] = 0.0;
+            }
+            RECONV();
+        } else {
+            dir_n = 2;
+            dir_back = 100;
+            if (lane == 0) {
+                d4[0] = px;
+                d4[1] = py;
+                d4[2] = pz;
+                d4[3] = S.wx;
+                d4[4] = S.wy;
+                d4[5] = S.wz;
+            }
+            RECONV();
+        }
+    }
+    // ---- /goal_global
+    const double hx = rfld(A.in[q].hx), hy = rfld(A.in[q].hy);
+    double z = tick_point_z(S.wx, S.wy, S.ogx, S.ogy, S.ogz, hx, hy);
+    if (rule == 1 && (wp_norm2(S.ogx - px, S.ogy - py) < 0.5 || eo != 0)) z = 0.0;
+    if (lane == 0) {
+        TickResult& R = A.out[q];
+        R.r.wp[0] = S.wx;
+        R.r.wp[1] = S.wy;
+        R.r.wp[2] = S.wz;
+        R.r.goal[0] = S.ogx;
+        R.r.goal[1] = S.ogy;
+        R.r.goal[2] = S.ogz;
+        R.r.ang = S.ang;
+        R.r.dim = S.dim;
+        R.r.nkept = S.m;
+        R.point[0] = S.wx;
+        R.point[1] = S.wy;
+        R.point[2] = z;
+        R.dir_n = dir_n;
+        R.dir_back = dir_back;
+    }
+}

@@ -370,6 +370,51 @@ class Planner(object):
         self._chk(self._L.fxjps_publish_slots(self._h, arr, n))
         return out
 
+    def fleet_tick(self, jobs, pos, global_goals, home, map_reso, map_o, prev_wp=None, prev_dim=None, publish=True, image_channels=None):
+        """One tick of a fleet, raw maps in, every node's outgoing messages out: prepare_slots, plan_batch_slots,
+        waypoints.tick_outputs_slots on the resident paths and publish_slots, composed as INTEGRATION.md section 3d
+        composes them.  jobs: as prepare_slots takes them, vehicle v in jobs[v]; pos, global_goals (n x 3), home (n x 2),
+        map_reso (a scalar or n) and map_o (one pair or n x 2: the origin of the RAW map) per vehicle; prev_wp (n x 3) /
+        prev_dim (n) as select_slots_batch takes them.  publish: bring out each live slot's OccupancyGrid data;
+        image_channels: None, 1 or 3.  A vehicle whose job failed (the goal's row and column are fully occupied) is left out
+        of the three later calls.  -> one dict per vehicle: ok, and when ok: status, cost, start, goal, map_d, shape,
+        end_occu, origin (the shifted origin), wp, dim, goal_out, ang_wp, n_kept, point, path, dir_path, dir_back, msg,
+        image; when not ok the other values are None."""
+        from . import waypoints
+        jobs = list(jobs)
+        n = len(jobs)
+        pos = np.asarray(pos, dtype=np.float64).reshape(n, 3)
+        goals = np.asarray(global_goals, dtype=np.float64).reshape(n, 3)
+        home = np.broadcast_to(np.asarray(home, dtype=np.float64), (n, 2))
+        reso = np.broadcast_to(np.asarray(map_reso, dtype=np.float64), (n,))
+        orig = np.broadcast_to(np.asarray(map_o, dtype=np.float64), (n, 2))
+        keys = ("status", "cost", "start", "goal", "map_d", "shape", "end_occu", "origin", "wp", "dim", "goal_out", "ang_wp", "n_kept", "point",
+                "path", "dir_path", "dir_back", "msg", "image")
+        recs = [dict({"ok": False}, **{k: None for k in keys}) for _ in range(n)]
+        outs = self.prepare_slots(jobs)
+        live = [v for v in range(n) if outs[v][5]]
+        if not live:
+            return recs
+        slots = [int(jobs[v][0]) for v in live]
+        offsets, _, cost, status = self.plan_batch_slots(slots, [outs[v][0] for v in live], [outs[v][1] for v in live], 2)
+        origin = [Planner.shifted_origin(orig[v], outs[v][2], reso[v]) for v in live]
+        pw = pd = None
+        if prev_wp is not None:
+            pw = np.asarray(prev_wp, dtype=np.float64).reshape(n, 3)[live]
+            pd = np.asarray(prev_dim, dtype=np.int32).reshape(n)[live]
+        wp, dim, gout, ang, nk, point, paths, dirs, back = waypoints.tick_outputs_slots(
+            self, [jobs[v][5] for v in live], [outs[v][0] for v in live], reso[live], origin, pos[live], goals[live], home[live],
+            [outs[v][4] for v in live], pw, pd, offsets=offsets)
+        pub = self.publish_slots(slots, msg=publish, image_channels=image_channels) if (publish or image_channels is not None) else None
+        for i, v in enumerate(live):
+            o = outs[v]
+            recs[v].update(ok=True, status=int(status[i]), cost=float(cost[i]), start=o[0], goal=o[1], map_d=o[2], shape=o[3], end_occu=o[4],
+                           origin=origin[i], wp=wp[i, :dim[i]], dim=int(dim[i]), goal_out=gout[i], ang_wp=float(ang[i]), n_kept=int(nk[i]),
+                           point=point[i], path=paths[i], dir_path=dirs[i], dir_back=int(back[i]))
+            if pub is not None:
+                recs[v].update(msg=pub[i][0], image=pub[i][2])
+        return recs
+
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
         """plan_batch with a grid per query: query q runs on the grid of slot grid_ids[q].  -> (offsets, cells, cost,
         status) as plan_batch.  max_path_len=None: the default slot of the largest grid named, grown when a path needs it."""

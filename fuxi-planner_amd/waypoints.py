@@ -93,10 +93,13 @@ def _batch_vec(v, n):
 
 
 def _batch_paths(planner, paths, n_hint):
-    """paths: None (the planner's most recent batch, resident on the device) or (offsets, cells) as plan_batch returns."""
+    """paths: None (the planner's most recent batch, resident on the device) or (offsets, cells) as plan_batch returns;
+    (offsets, None), where the caller says so: the resident paths again, with the offsets their batch returned."""
     if paths is None:
         return n_hint, None, None
     off = np.ascontiguousarray(paths[0], dtype=np.int64)
+    if paths[1] is None:
+        return len(off) - 1, off, None
     cells = np.ascontiguousarray(np.asarray(paths[1], dtype=np.int32).reshape(-1, 2))
     return len(off) - 1, off, cells
 
@@ -158,7 +161,8 @@ def select_slots_batch(planner, rule, map_start, map_reso, map_o, pos, global_go
     global_planner_st.py:292-327; 1 / "ccst": global_planner_ccst.py:487-544 against the grid of slot grid_ids[q] as it is
     now) with its own map_start[q], map_reso[q] and map_o[q].  paths=None: the paths of the planner's last plan_batch_slots,
     resident on the device (len(rule) of them; grid_ids=None: the slots that batch named); else (offsets, cells), and
-    grid_ids is needed as soon as one query uses the ccst rule.  map_reso: a scalar or nq values; map_o: one pair or
+    grid_ids is needed as soon as one query uses the ccst rule; (offsets, None): the resident paths, `offsets` being what
+    that plan_batch_slots returned (return_kept needs them to place the kept cells).  map_reso: a scalar or nq values; map_o: one pair or
     nq x 2; map_start: one pair or nq x 2 (None when no query uses the st rule); pos / global_goal: one (x, y, z) or nq x 3.
     -> (wp float64[nq, 3], dim int32[nq] (2 or 3 valid components; ccst: 3), global_goal float64[nq, 3], ang_wp float64[nq]
     (ccst: 0.0), n_kept int32[nq] (st: 0)) [+ kept cells int32[total, 2], aligned with the offsets of the paths, when
@@ -190,10 +194,67 @@ def select_slots_batch(planner, rule, map_start, map_reso, map_o, pos, global_go
     def opt(a, t):
         return None if a is None else _lib.ptr(a, t)
     planner._chk(planner._L.fxjps_waypoint_slots_batch(
-        planner._h, nq, opt(off, C.c_int64), opt(cells, C.c_int32), opt(ids, C.c_int32), _lib.ptr(r, C.c_int32), opt(ms, C.c_int32),
+        planner._h, nq, None if cells is None else _lib.ptr(off, C.c_int64), opt(cells, C.c_int32), opt(ids, C.c_int32), _lib.ptr(r, C.c_int32), opt(ms, C.c_int32),
         _lib.ptr(reso, C.c_double), _lib.ptr(o, C.c_double), _lib.ptr(p, C.c_double), _lib.ptr(g, C.c_double), opt(eo, C.c_int32),
         float(dis_wp_tre), float(ang_wp_tre), opt(pw, C.c_double), opt(pd, C.c_int32), _lib.ptr(wp, C.c_double), _lib.ptr(dim, C.c_int32),
         _lib.ptr(gout, C.c_double), _lib.ptr(ang, C.c_double), _lib.ptr(nk, C.c_int32), opt(kept, C.c_int32), cap, int(nthreads)))
     if return_kept:
         return wp, dim, gout, ang, nk, kept[:cap]
     return wp, dim, gout, ang, nk
+
+
+def tick_outputs_slots(planner, rule, map_start, map_reso, map_o, pos, global_goal, home, end_occu=None, prev_wp=None, prev_dim=None,
+                       grid_ids=None, paths=None, offsets=None, return_kept=False, dis_wp_tre=2.0, ang_wp_tre=math.pi / 4, nthreads=0):
+    """What both nodes send out per tick, for every query of a grid-slots batch in one call (fxjps_tick_outputs_slots):
+    select_slots_batch's selection, and from the same launch the Point of /goal_global (x, y of the waypoint, z by
+    global_planner_st.py:335 or global_planner_ccst.py:559-562 with `home` = (xo, yo), one pair or nq x 2), /jps_path (path3,
+    st:292-298 / ccst:487-494) and the ccst node's /direct_jps_path (path4 of ccst:495-521 with time_b 0; without a path the two
+    poses [pos, wp] with time_b 100; st: empty).  The other arguments are select_slots_batch's.  With paths=None
+    (the resident paths of the planner's last plan_batch_slots) `offsets` are the offsets that call returned: they place
+    the triples.
+    -> (wp, dim, goal_out, ang_wp, n_kept, point float64[nq, 3], paths, dir_paths, dir_back int32[nq]); paths and dir_paths
+    are lists of nq float64 [m, 3] views [+ kept cells int32[total, 2], aligned with the offsets of the paths, when
+    return_kept]."""
+    r = np.ascontiguousarray([{"st": 0, "ccst": 1}[x] if isinstance(x, str) else int(x) for x in np.asarray(rule, dtype=object).ravel()],
+                             dtype=np.int32)
+    nq, off, cells = _batch_paths(planner, paths, len(r))
+    if len(r) != nq:
+        raise ValueError("%d rules for %d paths" % (len(r), nq))
+    c_off = None if cells is None else off
+    if off is None:
+        if offsets is None:
+            raise ValueError("resident paths need offsets= (what plan_batch_slots returned): they place the triples")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if len(off) != nq + 1:
+            raise ValueError("%d offsets for %d paths" % (len(off), nq))
+    reso = np.ascontiguousarray(np.broadcast_to(np.asarray(map_reso, dtype=np.float64), (nq,)))
+    o = np.ascontiguousarray(np.broadcast_to(np.asarray(map_o, dtype=np.float64), (nq, 2)))
+    p, g = _batch_vec(pos, nq), _batch_vec(global_goal, nq)
+    hm = np.ascontiguousarray(np.broadcast_to(np.asarray(home, dtype=np.float64), (nq, 2)))
+    ms = None if map_start is None else np.ascontiguousarray(np.broadcast_to(np.asarray(map_start, dtype=np.int32), (nq, 2)))
+    eo = None if end_occu is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_occu, dtype=np.int32), (nq,)))
+    ids = None if grid_ids is None else np.ascontiguousarray(np.broadcast_to(np.asarray(grid_ids, dtype=np.int32), (nq,)))
+    pw = pd = None
+    if prev_wp is not None:
+        pw = np.ascontiguousarray(np.asarray(prev_wp, dtype=np.float64).reshape(nq, 3))
+        pd = np.ascontiguousarray(np.asarray(prev_dim, dtype=np.int32).reshape(nq))
+    wp, gout, dim, ang, nk = np.zeros((nq, 3)), np.zeros((nq, 3)), np.zeros(nq, dtype=np.int32), np.zeros(nq), np.zeros(nq, dtype=np.int32)
+    total = int(off[-1]) if nq else 0
+    point, dn, db = np.zeros((nq, 3)), np.zeros(nq, dtype=np.int32), np.zeros(nq, dtype=np.int32)
+    pxyz, dxyz = np.zeros((max(total, 1), 3)), np.zeros((total + 2 * nq + 1, 3))
+    kept = np.zeros((max(total, 1), 2), dtype=np.int32) if return_kept else None
+
+    def opt(a, t):
+        return None if a is None else _lib.ptr(a, t)
+    planner._chk(planner._L.fxjps_tick_outputs_slots(
+        planner._h, nq, opt(c_off, C.c_int64), opt(cells, C.c_int32), opt(ids, C.c_int32), _lib.ptr(r, C.c_int32), opt(ms, C.c_int32),
+        _lib.ptr(reso, C.c_double), _lib.ptr(o, C.c_double), _lib.ptr(p, C.c_double), _lib.ptr(g, C.c_double), opt(eo, C.c_int32),
+        float(dis_wp_tre), float(ang_wp_tre), opt(pw, C.c_double), opt(pd, C.c_int32), _lib.ptr(hm, C.c_double), _lib.ptr(wp, C.c_double),
+        _lib.ptr(dim, C.c_int32), _lib.ptr(gout, C.c_double), _lib.ptr(ang, C.c_double), _lib.ptr(nk, C.c_int32), opt(kept, C.c_int32), total,
+        _lib.ptr(point, C.c_double), _lib.ptr(pxyz, C.c_double), total, _lib.ptr(dxyz, C.c_double), _lib.ptr(dn, C.c_int32),
+        _lib.ptr(db, C.c_int32), total + 2 * nq, int(nthreads)))
+    paths_out = [pxyz[int(off[q]):int(off[q + 1])] for q in range(nq)]
+    dir_out = [dxyz[int(off[q]) + 2 * q:int(off[q]) + 2 * q + int(dn[q])] for q in range(nq)]
+    if return_kept:
+        return wp, dim, gout, ang, nk, point, paths_out, dir_out, db, kept[:total]
+    return wp, dim, gout, ang, nk, point, paths_out, dir_out, db

@@ -83,8 +83,10 @@ typedef struct fxjps fxjps_t;
  *        and an origin per query).
  *   740  fxjps_publish_slots (the message and / or snapshot image of every named grid slot by one call whose launches and
  *        host waits do not depend on n), fxjps_slot_publish_size.
+ *   750  fxjps_tick_outputs_slots (fxjps_waypoint_slots_batch plus what each node sends out per tick: the goal Point, the
+ *        world-frame path and the ccst node's direct path of every query, in the same one launch).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 740
+#define FXJPS_VERSION 750
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -524,6 +526,44 @@ int fxjps_waypoint_slots_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, c
                                const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
                                const int32_t* prev_dim, double* out_wp, int32_t* out_dim, double* out_goal, double* out_ang_wp,
                                int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, int32_t nthreads);
+
+/* ---- A fleet tick's outgoing messages, one call (version 750): fxjps_waypoint_slots_batch above, and from the same launch
+ * what each node publishes after its waypoint block.  Inputs, the shared outputs (out_wp .. out_kept_cells), their meaning,
+ * the st rule's host form and every refusal are those of fxjps_waypoint_slots_batch; that call is unchanged.  New:
+ *
+ * home_xy (nq x 2): (xo, yo) of each vehicle, its position on its first tick.  Required iff out_point is given.
+ * out_point (nq x 3): the Point of /goal_global.  x, y = wp[0], wp[1] of the waypoint THIS call selects.  z, with
+ *   r = norm(wp[0:2] - home) / norm(goal[0:2] - home), `goal` being the goal AFTER the block (out_goal: the vehicle's position
+ *   where end_occu replaced it) and norm(v) = sqrt(v0 * v0 + v1 * v1):
+ *     st   (global_planner_st.py:335):        1 + min(r, 1) * (goal[2] - 1)
+ *     ccst (global_planner_ccst.py:559-562):  0 if norm(goal[0:2] - pos[0:2]) < 0.5 or end_occu != 0, else the st expression
+ *   min is Python's: 1 iff 1 < r, else r.  A goal equal to home gives r = x / 0 = inf -> 1, or 0 / 0 = NaN, which stays NaN
+ *   (both are legal input; the NaN is the one IEEE division returns, sign bit set, as on the host).
+ * out_path_xyz (path_capacity triples >= the cells of the paths): /jps_path.  path3 of query q, (x, y, 0.0) per jump point
+ *   with x = (cx + 1) * reso + origin[0], y = (cy + 1) * reso + origin[1] for st (st:292-298) and y = cy * reso + origin[1] for
+ *   ccst (ccst:487-494), at triple offsets[q] .. offsets[q + 1].  A query without a path writes nothing.
+ * out_dir_xyz (dir_capacity triples >= cells + 2 * nq), out_dir_n (nq), out_dir_back (nq): /direct_jps_path.  The direct
+ *   path of query q starts at triple offsets[q] + 2 * q:
+ *     ccst with a path:     n_kept points, path4 = the world-frame points of the kept cells (ccst:495-521), back 0
+ *     ccst without a path:  2 points, [pos, wp] (ccst:485), back 100 (the `time_b` the node sends with it)
+ *     st:                   0 points, back 0, nothing written
+ * With resident paths `offsets` are the out_offsets of the fxjps_plan_batch_slots_csr call; the library uses its own copy.
+ * Every output but out_wp may be NULL; the copy back from the device ends after the last section the caller asked for.
+ *
+ * Per query every output is bit-identical to the cited lines of the node run on that query's path with that query's reso
+ * and origin.  The ccst node's branch that skips planning when map_start lies beyond the map (ccst:471-475) is the
+ * host's decision and not part of this call.
+ *
+ * Refused with FXJPS_E_ARG besides what fxjps_waypoint_slots_batch refuses: out_point without home_xy, a path_capacity,
+ * dir_capacity or kept_capacity that is too small.  Everything is judged before anything is queued or written.  The call
+ * changes neither a slot, nor the resident grid, nor the stored results of fxjps_replan_frame, nor the resident paths. */
+int fxjps_tick_outputs_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                             const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin, const double* pos,
+                             const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre, const double* prev_wp,
+                             const int32_t* prev_dim, const double* home_xy, double* out_wp, int32_t* out_dim, double* out_goal,
+                             double* out_ang_wp, int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, double* out_point,
+                             double* out_path_xyz, int64_t path_capacity, double* out_dir_xyz, int32_t* out_dir_n, int32_t* out_dir_back,
+                             int64_t dir_capacity, int32_t nthreads);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

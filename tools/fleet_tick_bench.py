@@ -24,7 +24,14 @@ writes without it, per vehicle get_grid_slot + the numpy lines of the reference'
 compared byte for byte before anything is timed.  At n = 64 also messages plus RGB snapshots both ways, and the whole tick
 of four calls against the same tick with the loop as its last quarter and against the per-vehicle tick (all four stages
 per vehicle).  The bar: new / loop <= 1/2 at n = 64 on `synth`.  The JSON line is also written to --out.
-Usage: python tools/fleet_tick_bench.py [--stage maps|waypoints|publish] [--reps 5] [--ns 16 64 256]"""
+
+--stage outputs: what every node sends out per tick besides its map: the Point of /goal_global,
+/jps_path and the ccst node's /direct_jps_path.  new: ONE tick_outputs_slots call on the resident paths.  loop: what a fleet
+host writes without it, select_slots_batch on the same resident paths (with the kept cells) and then per vehicle the numpy lines of the nodes
+(st:292-298, 335, 356-359; ccst:485, 487-495, 559-562, 590-593).  Both sides are compared byte for byte before anything is timed.
+Also the whole tick of four calls both ways.  No bar is fixed; the JSON line is also written to --out.  With --trace-call N:
+prepare, plan, one warm call, a pause of 50 ms, then ONE call.
+Usage: python tools/fleet_tick_bench.py [--stage maps|waypoints|publish|outputs] [--reps 5] [--ns 16 64 256]"""
 import argparse
 import json
 import os
@@ -227,6 +234,86 @@ def publish_stage(p, a):
     print(line)
 
 
+def outputs_loop(p, plan, inp, home):
+    """select_slots_batch, then the nodes' own numpy lines per vehicle.  -> (wp, dim, goal_out, point [n, 3], paths, dir_paths, dir_back)"""
+    from fuxi_planner_amd import waypoints
+    off, cells, cost, st = plan
+    n = len(st)
+    wps, dim, gout, ang, nk, kept = waypoints.select_slots_batch(p, paths=(off, None), return_kept=True, **inp)  # (the resident paths, as the tick runs it)
+    point, paths, dirs, back = np.zeros((n, 3)), [], [], np.zeros(n, np.int32)
+    with np.errstate(all="ignore"):
+        for v in range(n):
+            map_reso, map_o, ccst = inp["map_reso"][v], list(inp["map_o"][v]), inp["rule"][v] == 1
+            px, py, pz = inp["pos"][v]
+            xo, yo = home[v]
+            wp, global_goal = wps[v, :dim[v]], gout[v]
+            path3 = np.zeros((0, 3))
+            path4 = None
+            if st[v] > 0:
+                path2 = cells[off[v]:off[v + 1]] + (np.array([1, 0]) if ccst else np.array([1, 1]))
+                path3 = path2 * map_reso + map_o
+                path3 = np.c_[path3, np.zeros([len(path3), 1])]
+                if ccst:
+                    path4 = (kept[off[v]:off[v] + nk[v]] + np.array([1, 0])) * map_reso + map_o
+                    path4 = np.c_[path4, np.zeros([len(path4), 1])]
+            elif ccst:
+                path4 = np.array([[px, py, pz], wp])
+                back[v] = 100
+            if ccst and (np.linalg.norm(global_goal[0:2] - np.array([px, py])) < 0.5 or inp["end_occu"][v]):
+                z = 0
+            else:
+                z = 1 + min(np.linalg.norm(wp[0:2] - np.array([xo, yo])) / np.linalg.norm(global_goal[0:2] - np.array([xo, yo])), 1) * (global_goal[2] - 1)
+            point[v] = (wp[0], wp[1], z)
+            paths.append(path3)
+            dirs.append(np.zeros((0, 3)) if path4 is None else path4)
+    return wps, dim, gout, point, paths, dirs, back
+
+
+def outputs_stage(p, a):
+    from fuxi_planner_amd import waypoints
+    ms = lambda ts: round(float(np.median(ts)) * 1e3, 4)
+    spread = lambda ts: [round(min(ts) * 1e3, 4), round(max(ts) * 1e3, 4)]
+    out = {"tool": "fleet_tick_bench", "stage": "outputs", "reps": a.reps, "window_s": WINDOW_S, "ifa": 1, "cases": []}
+    for shape in a.shapes:
+        for n in a.ns:
+            jobs = fleet(shape, n)
+            outs = side_new(p, jobs)
+            assert all(o[5] for o in outs), (shape, n)
+            ids = np.arange(n, dtype=np.int32)
+            slots = list(range(n))
+            starts, goals = [o[0] for o in outs], [o[1] for o in outs]
+            plan = p.plan_batch_slots(ids, starts, goals, 2)
+            inp = waypoint_inputs(jobs, outs)
+            home = inp["pos"][:, :2] + np.random.default_rng(n + 1).normal(0, 3.0, (n, 2))
+            new = lambda off=plan[0]: waypoints.tick_outputs_slots(p, home=home, offsets=off, **inp)
+            got, want = new(), outputs_loop(p, plan, inp, home)
+            flat = lambda wp, dim, gout, point, paths, dirs, back: [wp, dim, gout, point, back] + list(paths) + list(dirs)
+            a_, b_ = flat(got[0], got[1], got[2], got[5], got[6], got[7], got[8]), flat(*want)
+            assert len(a_) == len(b_) and all(x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a_, b_)), (shape, n)
+            two = lambda: (side_new(p, jobs), p.plan_batch_slots(ids, starts, goals, 2))
+            sides = {"new": new, "loop": lambda: outputs_loop(p, plan, inp, home),
+                     "tick_new": lambda: (new(two()[1][0]), p.publish_slots(slots)),
+                     "tick_loop": lambda: (outputs_loop(p, two()[1], inp, home), p.publish_slots(slots)),
+                     "tick_without_outputs": lambda: (two(), waypoints.select_slots_batch(p, **inp), p.publish_slots(slots))}
+            t, per = windows(sides, a.reps)
+            case = {"shape": shape, "n": n, "planned": int((plan[3] > 0).sum()), "ccst": int((inp["rule"] == 1).sum()),
+                    "path_points": int(plan[0][-1]), "calls_per_window": per, "new_ms": ms(t["new"]), "loop_ms": ms(t["loop"]),
+                    "ratio": round(float(np.median(t["new"]) / np.median(t["loop"])), 4), "spread_new_ms": spread(t["new"]),
+                    "spread_loop_ms": spread(t["loop"]), "new_us_per_vehicle": round(float(np.median(t["new"])) * 1e6 / n, 2),
+                    "loop_us_per_vehicle": round(float(np.median(t["loop"])) * 1e6 / n, 2)}
+            for k in ("tick_new", "tick_loop", "tick_without_outputs"):
+                case[k + "_ms"] = ms(t[k])
+                case["spread_" + k + "_ms"] = spread(t[k])
+            case["new_faster_than_loop"] = bool(np.median(t["new"]) < np.median(t["loop"]))
+            out["cases"].append(case)
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def windows(sides, reps):
     """sides: {name: fn}.  -> {name: [seconds per call, one per window]}; the sides alternate window by window."""
     per = {}
@@ -252,14 +339,33 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=["synth", "png"])
     ap.add_argument("--trace-call", type=int, default=0)
     ap.add_argument("--shape", default="synth")
-    ap.add_argument("--stage", choices=["maps", "waypoints", "publish"], default="maps")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_publish_bench.json"), help="--stage publish: where the JSON line is written too")
+    ap.add_argument("--stage", choices=["maps", "waypoints", "publish", "outputs"], default="maps")
+    ap.add_argument("--out", default=None, help="--stage publish / outputs: where the JSON line is written too (profiles/fleet_<stage>_bench.json)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "fleet_%s_bench.json" % a.stage)
     import fuxi_planner_amd as fx
 
     p = fx.Planner([0])
     if a.stage == "publish":
         publish_stage(p, a)
+        p.close()
+        return
+    if a.stage == "outputs":
+        if a.trace_call:
+            from fuxi_planner_amd import waypoints
+            jobs = fleet(a.shape, a.trace_call)
+            outs = side_new(p, jobs)
+            plan = p.plan_batch_slots(np.arange(a.trace_call, dtype=np.int32), [o[0] for o in outs], [o[1] for o in outs], 2)
+            inp = waypoint_inputs(jobs, outs)
+            home = inp["pos"][:, :2] + 1.0
+            waypoints.tick_outputs_slots(p, home=home, offsets=plan[0], **inp)
+            time.sleep(0.05)
+            got = waypoints.tick_outputs_slots(p, home=home, offsets=plan[0], **inp)
+            print(json.dumps({"tool": "fleet_tick_bench", "stage": "outputs", "trace_call": a.trace_call, "shape": a.shape,
+                              "planned": int((plan[3] > 0).sum()), "dir_points": int(sum(len(d) for d in got[7]))}))
+        else:
+            outputs_stage(p, a)
         p.close()
         return
     if a.stage == "waypoints":
