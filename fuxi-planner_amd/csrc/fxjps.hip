@@ -183,8 +183,8 @@ struct DevCtx : GridBufs {
     std::vector<GridDev> h_slot_desc;
     DBuf<GridDev> d_slot_desc;
     DBuf<int32_t> d_grid_ids;
-    // fxjps_prepare_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw maps), pinned and
-    // on the device, and the per-job results of k_slots_goal
+    // fxjps_prepare_slots / fxjps_refresh_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw
+    // maps | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal / k_refresh_goal
     HBuf<uint8_t> h_slots_in;
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
@@ -2367,9 +2367,11 @@ struct SlotPlan {
 constexpr size_t SLOTS_IN_DESC = (sizeof(fx::SlotTable) + 15) & ~(size_t)15;
 constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS + 15) & ~(size_t)15;
 
-// One context's part of fxjps_prepare_slots: everything is queued on d.stream behind ONE copy in, and waited for ONCE,
-// whatever n is.  The results are left in d.h_slots_res.
-int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes) {
+// One context's part of fxjps_prepare_slots / fxjps_refresh_slots: everything is queued on d.stream behind ONE copy in, and
+// waited for ONCE, whatever n is.  The results are left in d.h_slots_res.  refresh: a job whose slot holds a grid of the
+// prepared extents is compared with it byte by byte while it is gathered, and built only if a byte differed (DESIGN.md
+// section 3.12); the n `changed` words travel in behind the raws and come back behind the results, in the same two copies.
+int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh) {
     HIPCHK(h, hipSetDevice(d.dev));
     if (d.slots.empty()) {
         d.slots.resize(FXJPS_MAX_GRID_SLOTS);
@@ -2378,17 +2380,24 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
     }
     // (no host wait in front: every call of the library that reads a slot has returned; a buffer that grows is freed by
     // hipFree, which waits for the device itself)
+    const size_t flags_off = in_bytes, n_res = (size_t)n * (fx::SLOT_RES + (refresh ? 1 : 0));
+    if (refresh) in_bytes += (size_t)n * sizeof(uint32_t);  // (every raw's room is a multiple of 16 bytes: the words are aligned)
     HIPCHK(h, d.h_slots_in.ensure(in_bytes));
     HIPCHK(h, d.d_slots_in.ensure(in_bytes));
-    HIPCHK(h, d.h_slots_res.ensure((size_t)n * fx::SLOT_RES));
-    HIPCHK(h, d.d_slots_res.ensure((size_t)n * fx::SLOT_RES));
+    HIPCHK(h, d.h_slots_res.ensure(n_res));
+    HIPCHK(h, d.d_slots_res.ensure(n_res));
     fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
+    uint32_t* h_changed = reinterpret_cast<uint32_t*>(d.h_slots_in.p + flags_off);
+    uint32_t* d_changed = reinterpret_cast<uint32_t*>(d.d_slots_in.p + flags_off);
     uint32_t at[fx::SL_LAUNCHES] = {};
     bool any_large = false;
     for (int j = 0; j < n; j++) {
         const fxjps_slot_job_t& jb = jobs[j];
         const SlotPlan& p = plan[(size_t)j];
         GridBufs& g = d.slots[(size_t)jb.slot];
+        // (what this context's copy of the slot holds now; a grid beyond the fused build is built by the host below, which
+        // cannot know the device's word without a wait: it always builds)
+        const bool compare = refresh && g.W > 0 && g.W == p.W1 && g.H == p.H1 && p.W1 * p.H1 <= (1ll << 18);
         d.h_slot_desc[(size_t)jb.slot] = GridDev{};
         int e = alloc_grid_bufs(h, g, (int)p.W1, (int)p.H1);  // (a slot that has room allocates nothing)
         if (e) return e;
@@ -2407,6 +2416,8 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
         J.layout = jb.layout;
         J.gx = (int32_t)p.ngx;
         J.gy = (int32_t)p.ngy;
+        J.compare = compare ? 1 : 0;
+        if (refresh) h_changed[j] = compare ? 0u : 1u;  // (written anew by every call: nothing of the call before is read)
         memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
         // the blocks derive_maps would launch for this grid alone (the fused build: at most 2^18 cells)
         const long long ncell = p.W1 * p.H1, npad = (long long)g.PW * g.PH;
@@ -2428,9 +2439,20 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
     memcpy(d.h_slots_in.p + SLOTS_IN_DESC, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS);
     HIPCHK(h, hipMemcpyAsync(d.d_slots_in.p, d.h_slots_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
     const fx::SlotTable* dT = reinterpret_cast<const fx::SlotTable*>(d.d_slots_in.p);
-    hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
-    hipLaunchKernelGGL(fx::k_slots_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p);
-    if (at[fx::SL_BUILD_1] > 0) {
+    if (refresh) {
+        hipLaunchKernelGGL(fx::k_refresh_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, d_changed);
+        hipLaunchKernelGGL(fx::k_refresh_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p, n, d_changed);
+        if (at[fx::SL_BUILD_1] > 0) {
+            hipLaunchKernelGGL(fx::k_refresh_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n, d_changed);
+            hipLaunchKernelGGL(fx::k_refresh_build_2, dim3(at[fx::SL_BUILD_2]), dim3(256), 0, d.stream, dT, n, d_changed);
+            hipLaunchKernelGGL(fx::k_refresh_build_3, dim3(at[fx::SL_BUILD_3]), dim3(1024), 0, d.stream, dT, n, d_changed);
+            hipLaunchKernelGGL(fx::k_refresh_derive_jd, dim3(at[fx::SL_JD]), dim3(256), 0, d.stream, dT, n, d_changed);
+        }
+    } else {
+        hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
+        hipLaunchKernelGGL(fx::k_slots_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p);
+    }
+    if (!refresh && at[fx::SL_BUILD_1] > 0) {
         hipLaunchKernelGGL(fx::k_slots_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n);
         hipLaunchKernelGGL(fx::k_slots_build_2, dim3(at[fx::SL_BUILD_2]), dim3(256), 0, d.stream, dT, n);
         hipLaunchKernelGGL(fx::k_slots_build_3, dim3(at[fx::SL_BUILD_3]), dim3(1024), 0, d.stream, dT, n);
@@ -2444,7 +2466,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
                 if (e) return e;
             }
     HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p, d.h_slots_in.p + SLOTS_IN_DESC, sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice, d.stream));
-    HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d.d_slots_res.p, (size_t)n * fx::SLOT_RES * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d.d_slots_res.p, n_res * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     // a goal with no free cell in its row or column: that slot stays empty (its buffers keep their room)
     for (int j = 0; j < n; j++)
@@ -2458,11 +2480,14 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
 }
 }  // namespace
 
-int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) {
+namespace {
+// fxjps_prepare_slots (out_kept == nullptr, refresh false) and fxjps_refresh_slots: the checks, the call on every context
+// and the outputs are the same code.
+int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what) {
     if (!h) return FXJPS_E_ARG;
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
     if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
-    if (int rr = refuse_on_rank_handle(h, "fxjps_prepare_slots")) return rr;
+    if (int rr = refuse_on_rank_handle(h, what)) return rr;
     // everything the host can judge, for every job, before anything is queued or any slot is touched
     std::vector<SlotPlan> plan((size_t)n);
     std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
@@ -2501,7 +2526,7 @@ int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) {
     }
     if (n == 0) return FXJPS_OK;
     // every context prepares every job from the caller's raws (host copies, no collective, as fxjps_set_grid_slot)
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes); });
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh); });
     if (rc) {
         drain_all(h);
         for (auto& d : h->devs)  // (slots of a call that failed on one context are released on all of them)
@@ -2529,8 +2554,17 @@ int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) {
         jb.map_d[1] = (int32_t)p.dy;
         jb.end_occu = res[(size_t)j * fx::SLOT_RES + 2];
         jb.status = res[(size_t)j * fx::SLOT_RES + 3] != 0 ? FXJPS_E_ARG : FXJPS_OK;
+        // kept: no byte of context 0's copy differed, so nothing was built (a job that failed has an empty slot: not kept)
+        if (out_kept) out_kept[j] = refresh && jb.status == FXJPS_OK && res[(size_t)n * fx::SLOT_RES + (size_t)j] == 0 ? 1 : 0;
     }
     return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) { return slots_call(h, jobs, n, false, nullptr, "fxjps_prepare_slots"); }
+
+int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept) {
+    return slots_call(h, jobs, n, true, out_kept, "fxjps_refresh_slots");
 }
 
 // ------------------------------------------------------------------ many slots' maps published, one call
@@ -3617,6 +3651,23 @@ int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* bu
     DevCtx& d = h->devs[0];
     HIPCHK(h, hipSetDevice(d.dev));
     return read_maps(h, d, d.slots[(size_t)slot], which, buf, capacity_bytes, out_bytes);
+}
+
+int fxjps_debug_read_slot_context(fxjps_t* h, int32_t context, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes) {
+    if (!h) return FXJPS_E_ARG;
+    if (context < 0 || (size_t)context >= h->devs.size()) return fail(h, FXJPS_E_ARG, "context %d is not in 0 .. %zu", (int)context, h->devs.size() - 1);
+    if (!slot_in_use(h, slot)) return fail(h, FXJPS_E_ARG, "grid slot %d is empty or out of range", (int)slot);
+    DevCtx& d = h->devs[(size_t)context];
+    const GridBufs& g = d.slots[(size_t)slot];
+    HIPCHK(h, hipSetDevice(d.dev));
+    if (which != -1) return read_maps(h, d, g, which, buf, capacity_bytes, out_bytes);
+    const size_t bytes = (size_t)g.W * g.H;  // the occupancy bytes [W][H]
+    if (out_bytes) *out_bytes = (int64_t)bytes;
+    if (!buf) return FXJPS_OK;
+    if (capacity_bytes < (int64_t)bytes) return fail(h, FXJPS_E_ARG, "buffer holds %lld bytes, the grid has %zu", (long long)capacity_bytes, bytes);
+    HIPCHK(h, hipMemcpyAsync(buf, g.occ.p, bytes, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    return FXJPS_OK;
 }
 
 

@@ -697,6 +697,7 @@ struct SlotJobDev {
     int32_t W0, H0, dx, dy, ifa, variant, layout;
     int32_t gx, gy;      // the shifted goal (inside the prepared grid: the host checked)
     uint32_t nb_rows, nb_cols, nb_ci, nb_diag;  // k_build_1 .. 3: where the kinds of blocks change within the job's part
+    int32_t compare;     // fxjps_refresh_slots: the slot holds a grid of these extents, store only the bytes that differ
 };
 struct SlotTable {
     uint32_t first[SL_LAUNCHES][SLOT_JOBS_MAX + 1];
@@ -715,13 +716,8 @@ __device__ __forceinline__ int slot_job_of(const uint32_t* __restrict__ first, i
 }
 
 // k_prepare_grid's gather, for every output cell of every job.
-__global__ __launch_bounds__(256) void k_prepare_slots(const SlotTable* __restrict__ T, int n) {
-    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
-    const SlotJobDev& J = T->job[j];
-    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
-    const uint8_t* __restrict__ raw = J.raw;
-    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    if (i >= (long long)W1 * H1) return;
+__device__ __forceinline__ uint8_t slot_prepared_byte(const uint8_t* __restrict__ raw, int W0, int H0, int dx, int dy, int ifa, int variant, int msg_layout,
+                                                      int H1, long long i) {
     const int x = (int)(i / H1), y = (int)(i % H1);
     const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
     uint8_t v = 0;
@@ -734,7 +730,16 @@ __global__ __launch_bounds__(256) void k_prepare_slots(const SlotTable* __restri
                 if (o) v = 1;
             }
         }
-    J.occ[i] = v;
+    return v;
+}
+__global__ __launch_bounds__(256) void k_prepare_slots(const SlotTable* __restrict__ T, int n) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const uint8_t* __restrict__ raw = J.raw;
+    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
+    if (i >= (long long)W1 * H1) return;
+    J.occ[i] = slot_prepared_byte(raw, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
 }
 
 // The free cell of line[0], line[stride], .. (n cells) nearest to index c, the lower index of two equally near ones
@@ -757,8 +762,7 @@ __device__ __forceinline__ int slot_nearest_free(const uint8_t* __restrict__ lin
 // One wavefront per job: what prepare_grid_impl does on the host with blocking row / column copies -- the goal moved off
 // an obstacle (st:268-272 / ccst:454-458), end_occu (st:273 / ccst:461-464 with numpy's slice rules: a negative bound
 // counts from the end, everything is clipped to the array).
-__global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res) {
-    const int j = (int)blockIdx.x, lane = (int)threadIdx.x;
+__device__ __forceinline__ void slots_goal_job(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int j, int lane) {
     const SlotJobDev& J = T->job[j];
     const int W1 = J.G.W, H1 = J.G.H, ifa = J.ifa, variant = J.variant;
     const uint8_t* __restrict__ occ = J.occ;
@@ -790,11 +794,13 @@ __global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__
         res[j * SLOT_RES + 3] = status;
     }
 }
+__global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res) {
+    slots_goal_job(T, res, (int)blockIdx.x, (int)threadIdx.x);
+}
 
 // k_build_1 .. 3 and k_derive_jd over all jobs whose grid takes the fused build (at most 2^18 cells; the others have no
 // blocks here and are built by derive_maps behind these launches).
-__global__ __launch_bounds__(256) void k_slots_build_1(const SlotTable* __restrict__ T, int n) {
-    const int j = slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x);
+__device__ __forceinline__ void slots_build_1_block(const SlotTable* __restrict__ T, int j) {
     const SlotJobDev& J = T->job[j];
     const GridDev G = J.G;
     const uint8_t* __restrict__ occ = J.occ;
@@ -814,8 +820,7 @@ __global__ __launch_bounds__(256) void k_slots_build_1(const SlotTable* __restri
     b -= nb_cols;
     ccl_init_item(occ, (long long)G.W * G.H, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_slots_build_2(const SlotTable* __restrict__ T, int n) {
-    const int j = slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x);
+__device__ __forceinline__ void slots_build_2_block(const SlotTable* __restrict__ T, int j) {
     const SlotJobDev& J = T->job[j];
     const GridDev G = J.G;
     const uint8_t* __restrict__ occ = J.occ;
@@ -830,8 +835,7 @@ __global__ __launch_bounds__(256) void k_slots_build_2(const SlotTable* __restri
     b -= nb_ci;
     ccl_merge_item(occ, G.W, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(1024) void k_slots_build_3(const SlotTable* __restrict__ T, int n) {
-    const int j = slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x);
+__device__ __forceinline__ void slots_build_3_block(const SlotTable* __restrict__ T, int j) {
     const SlotJobDev& J = T->job[j];
     const GridDev G = J.G;
     const uint8_t* __restrict__ occ = J.occ;
@@ -845,11 +849,75 @@ __global__ __launch_bounds__(1024) void k_slots_build_3(const SlotTable* __restr
     b -= nb_diag;
     ccl_flatten_item((long long)G.W * G.H, const_cast<int*>(G.comp), (long long)b * 1024 + threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_slots_derive_jd(const SlotTable* __restrict__ T, int n) {
-    const int j = slot_job_of(T->first[SL_JD], n, blockIdx.x);
+__device__ __forceinline__ void slots_derive_jd_block(const SlotTable* __restrict__ T, int j) {
     const GridDev G = T->job[j].G;
     const DiagRange whole{1, 0, 0, 0, 0};
     derive_jd_item(G, const_cast<uint16_t*>(G.jd), whole, (long long)(blockIdx.x - T->first[SL_JD][j]) * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_slots_build_1(const SlotTable* __restrict__ T, int n) {
+    slots_build_1_block(T, slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x));
+}
+__global__ __launch_bounds__(256) void k_slots_build_2(const SlotTable* __restrict__ T, int n) {
+    slots_build_2_block(T, slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x));
+}
+__global__ __launch_bounds__(1024) void k_slots_build_3(const SlotTable* __restrict__ T, int n) {
+    slots_build_3_block(T, slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x));
+}
+__global__ __launch_bounds__(256) void k_slots_derive_jd(const SlotTable* __restrict__ T, int n) {
+    slots_derive_jd_block(T, slot_job_of(T->first[SL_JD], n, blockIdx.x));
+}
+
+// ---- The same call for a tick whose maps mostly did not change (fxjps_refresh_slots, DESIGN.md section 3.12).  A vehicle
+// hands in the raw map of the tick before far more often than a new one, and then the prepared grid is byte for byte what
+// its slot holds.  `changed` has one word per job, set by the host for every call: 1 for a job that must build (an empty
+// slot, other extents, a grid beyond the fused build), 0 for a job whose slot holds a grid of the prepared extents
+// (SlotJobDev::compare).  The gather of such a job reads the slot's byte at the index it would write, stores only where
+// the two differ and raises the job's word when any byte of the block did; a thread touches its own cell alone.  The four
+// build launches and the jump-distance launch then return at once in every block of a job whose word is still 0 -- the
+// six derived arrays of that slot are already those of these bytes.  The goal launch runs for every job (the goal may
+// have moved on an unchanged map) and hands the words to the host beside its results: res[n * SLOT_RES + j].
+__global__ __launch_bounds__(256) void k_refresh_slots(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const uint8_t* __restrict__ raw = J.raw;
+    uint8_t* __restrict__ occ = J.occ;
+    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
+    const bool inside = i < (long long)W1 * H1;
+    const uint8_t v = inside ? slot_prepared_byte(raw, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
+    if (!J.compare) {  // (block-uniform) a job that builds whatever the bytes are: its word is 1 already
+        if (inside) occ[i] = v;
+        return;
+    }
+    const bool differs = inside && occ[i] != v;  // bytes, not truthiness: a slot set to 7 where this is 1 is rewritten
+    if (differs) occ[i] = v;
+    // (every thread of the block reaches the barrier: none has returned above)
+    if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+}
+__global__ __launch_bounds__(64) void k_refresh_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int n, const uint32_t* __restrict__ changed) {
+    const int j = (int)blockIdx.x;
+    slots_goal_job(T, res, j, (int)threadIdx.x);
+    if (threadIdx.x == 0) res[n * SLOT_RES + j] = (int32_t)changed[j];
+}
+__global__ __launch_bounds__(256) void k_refresh_build_1(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x);
+    if (changed[j] == 0u) return;  // (block-uniform: one scalar load)
+    slots_build_1_block(T, j);
+}
+__global__ __launch_bounds__(256) void k_refresh_build_2(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x);
+    if (changed[j] == 0u) return;
+    slots_build_2_block(T, j);
+}
+__global__ __launch_bounds__(1024) void k_refresh_build_3(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x);
+    if (changed[j] == 0u) return;
+    slots_build_3_block(T, j);
+}
+__global__ __launch_bounds__(256) void k_refresh_derive_jd(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_JD], n, blockIdx.x);
+    if (changed[j] == 0u) return;
+    slots_derive_jd_block(T, j);
 }
 
 // Wire / on-disk adapters (SURVEY.md 8f, N3): one tiled byte transpose with a value map.

@@ -317,8 +317,30 @@ class Planner(object):
         (W, H), end_occu, ok); ok False: the goal's row and column are fully occupied (the reference raises there) and
         that slot is empty.  The resident grid is not touched."""
         jobs = list(jobs)
+        arr, keep = self._slot_jobs(jobs)  # (keep: the raws, alive until the call has returned)
+        self._chk(self._L.fxjps_prepare_slots(self._h, arr, len(jobs)))
+        del keep
+        return self._slot_outs(arr, len(jobs))
+
+    def refresh_slots(self, jobs):
+        """prepare_slots for the tick after (fxjps_refresh_slots): the same jobs, the same slots and outputs afterwards, but
+        a job whose prepared grid is byte for byte what its slot already holds keeps the slot's maps and costs no build
+        work.  -> per job (start', goal', map_d, (W, H), end_occu, ok, kept); kept False: the slot was built (it was
+        empty, its extents or a byte differed, the prepared grid has more than 2^18 cells, or the job failed)."""
+        jobs = list(jobs)
+        arr, keep = self._slot_jobs(jobs)
+        n = len(jobs)
+        kept = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.fxjps_refresh_slots(self._h, arr, n, _lib.ptr(kept, C.c_int32)))
+        del keep
+        return [o + (bool(k),) for o, k in zip(self._slot_outs(arr, n), kept[:n])]
+
+    @staticmethod
+    def _slot_jobs(jobs):
+        """-> the fxjps_slot_job_t array of prepare_slots' jobs, and the raws it points into (the caller holds them until the
+        C call has returned)."""
         arr = (_lib.SlotJob * max(len(jobs), 1))()
-        keep = []  # (the raws, alive until the call has returned)
+        keep = []
         for j, (slot, raw, start, goal, ifa, variant) in zip(arr, jobs):
             if isinstance(raw, tuple):
                 data, width, height = raw
@@ -337,9 +359,12 @@ class Planner(object):
             j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
             j.start_xy[0], j.start_xy[1] = int(start[0]), int(start[1])
             j.goal_xy[0], j.goal_xy[1] = int(goal[0]), int(goal[1])
-        self._chk(self._L.fxjps_prepare_slots(self._h, arr, len(jobs)))
+        return arr, keep
+
+    @staticmethod
+    def _slot_outs(arr, n):
         return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy[0], j.goal_xy[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
-                 j.status == 0) for j in arr[:len(jobs)]]
+                 j.status == 0) for j in arr[:n]]
 
     def publish_slots(self, slots, msg=True, image_channels=None):
         """The fleet's publishing quarter of a tick in ONE call (fxjps_publish_slots): for every slot named what publish_map
@@ -380,6 +405,15 @@ class Planner(object):
         of the three later calls.  -> one dict per vehicle: ok, and when ok: status, cost, start, goal, map_d, shape,
         end_occu, origin (the shifted origin), wp, dim, goal_out, ang_wp, n_kept, point, path, dir_path, dir_back, msg,
         image; when not ok the other values are None."""
+        return self._fleet_tick(False, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels)
+
+    def fleet_tick_refresh(self, jobs, pos, global_goals, home, map_reso, map_o, prev_wp=None, prev_dim=None, publish=True, image_channels=None):
+        """fleet_tick for the tick after: the maps are prepared through refresh_slots, so a vehicle whose prepared map is
+        what its slot already holds keeps the slot's maps.  The same arguments, the same records, and in every live
+        vehicle's record a further key, kept (bool)."""
+        return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels)
+
+    def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels):
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -391,7 +425,7 @@ class Planner(object):
         keys = ("status", "cost", "start", "goal", "map_d", "shape", "end_occu", "origin", "wp", "dim", "goal_out", "ang_wp", "n_kept", "point",
                 "path", "dir_path", "dir_back", "msg", "image")
         recs = [dict({"ok": False}, **{k: None for k in keys}) for _ in range(n)]
-        outs = self.prepare_slots(jobs)
+        outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
         live = [v for v in range(n) if outs[v][5]]
         if not live:
             return recs
@@ -413,6 +447,8 @@ class Planner(object):
                            point=point[i], path=paths[i], dir_path=dirs[i], dir_back=int(back[i]))
             if pub is not None:
                 recs[v].update(msg=pub[i][0], image=pub[i][2])
+            if refresh:
+                recs[v]["kept"] = o[6]
         return recs
 
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
@@ -602,6 +638,18 @@ class Planner(object):
         self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), None, C.byref(W), C.byref(H)))
         return self._read_maps(W.value, H.value,
                                lambda which, buf, cap, nb: self._L.fxjps_debug_read_slot_maps(self._h, int(slot), which, buf, cap, nb))
+
+    def debug_slot_context(self, context, slot):
+        """The copy of grid slot `slot` on context `context` (fxjps_debug_read_slot_context): -> (uint8 [W][H] occupancy,
+        the derived maps as debug_maps() returns them)."""
+        W, H = C.c_int32(), C.c_int32()
+        self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), None, C.byref(W), C.byref(H)))
+        occ = np.empty((W.value, H.value), dtype=np.uint8)
+        nb = C.c_int64(0)
+        self._chk(self._L.fxjps_debug_read_slot_context(self._h, int(context), int(slot), -1, occ.ctypes.data_as(C.c_void_p), occ.nbytes, C.byref(nb)))
+        assert nb.value == occ.nbytes, (nb.value, occ.nbytes)
+        return occ, self._read_maps(W.value, H.value, lambda which, buf, cap, n_: self._L.fxjps_debug_read_slot_context(
+            self._h, int(context), int(slot), which, buf, cap, n_))
 
     def _read_maps(self, W, H, read):
         PW, PH = W + 2, H + 2

@@ -85,8 +85,10 @@ typedef struct fxjps fxjps_t;
  *        host waits do not depend on n), fxjps_slot_publish_size.
  *   750  fxjps_tick_outputs_slots (fxjps_waypoint_slots_batch plus what each node sends out per tick: the goal Point, the
  *        world-frame path and the ccst node's direct path of every query, in the same one launch).
+ *   760  fxjps_refresh_slots (fxjps_prepare_slots for a tick whose maps mostly did not change: a job whose prepared grid is
+ *        byte for byte what its slot holds keeps the slot's maps and runs no build work), fxjps_debug_read_slot_context.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 750
+#define FXJPS_VERSION 760
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -292,6 +294,21 @@ typedef struct fxjps_slot_job {
 } fxjps_slot_job_t;
 int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n);
 int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was built (cf. fxjps_timing_size) */
+/* fxjps_prepare_slots for the tick after: the same jobs, the same checks and refusals, the same outputs job by job, and
+ * afterwards every named slot holds exactly the bytes and the derived maps fxjps_prepare_slots would leave.  The
+ * difference: a job whose prepared grid has the extents of the grid its slot holds, and the same value in every byte
+ * (bytes are compared, not truthiness), when the call runs on that context, keeps the slot's maps -- none of the build
+ * launches does any work for it -- and is reported with out_kept[j] = 1.  Every other job is built as fxjps_prepare_slots
+ * builds it and reports 0: an empty slot, other extents, any byte that differs, a job that failed (status = FXJPS_E_ARG,
+ * its slot is empty).  The goal relocation and end_occu are computed anew on every call: the goal may have moved on an
+ * unchanged map.  Jobs whose prepared grid has more than 2^18 cells are always built and report 0 (their maps are built
+ * by host-driven launches behind the shared ones, and the host does not know the device's answer without a wait).
+ *   The compare happens inside the gather: a thread reads the slot's byte where it would write, and writes only if the two
+ * differ.  Launches, copies and host waits do not depend on n and are those of fxjps_prepare_slots; the n answers travel
+ * behind the staged raws on the way in and behind the results on the way out.  A handle with several contexts compares
+ * on every context against that context's own copy; out_kept reports context 0's.  out_kept may be NULL; it is not
+ * written when the call is refused (nor for n = 0). */
+int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept);
 
 /* ---- Many slots' maps published in one call (the last quarter of a fleet tick: every vehicle's prepared map leaves the
  * device as the message and / or the snapshot image a node publishes).  Job by job the results are those of
@@ -419,6 +436,10 @@ int fxjps_debug_read_nbmask(fxjps_t* h, uint8_t* buf);
 int fxjps_debug_read_maps(fxjps_t* h, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
 /* Like fxjps_debug_read_maps, for a slot (tests compare it byte for byte with a fresh fxjps_set_grid). */
 int fxjps_debug_read_slot_maps(fxjps_t* h, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes, int64_t* out_bytes);
+/* ... and for the copy of a slot that context `context` of a handle with several contexts holds; which = -1: the slot's
+ * occupancy bytes [W][H] (fxjps_get_grid_slot reads context 0's). */
+int fxjps_debug_read_slot_context(fxjps_t* h, int32_t context, int32_t slot, int32_t which, void* buf, int64_t capacity_bytes,
+                                  int64_t* out_bytes);
 /* The read sets of the stored results of fxjps_replan_frame (tests check them against the cells the reference reads): the
  * grid is covered by tiles of (1 << tsh) cells a side, tsh the least shift with (max(W, H) - 1) >> tsh <= 63; for query
  * q (the order of fxjps_set_queries) out[q * 128 + ty] has bit tx set and / or out[q * 128 + 64 + tx] bit ty set for
