@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 760  # FXJPS_VERSION of include/fxjps.h
+VERSION = 770  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -21,7 +21,7 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_waypoint_st", "fxjps_waypoint_ccst", "fxjps_waypoint_ccst_batch", "fxjps_waypoint_st_batch",
            "fxjps_set_grid_slot", "fxjps_get_grid_slot", "fxjps_plan_batch_slots_csr", "fxjps_debug_read_slot_maps", "fxjps_debug_read_sets",
            "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch", "fxjps_publish_slots", "fxjps_slot_publish_size",
-           "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context")
+           "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context", "fxjps_replan_slots")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 
 
@@ -149,6 +149,9 @@ def load():
     L.fxjps_plan_batch_slots_csr.restype = C.c_int
     L.fxjps_plan_batch_slots_csr.argtypes = [vp, p_i32, p_i32, p_i32, C.c_int64, C.c_int32, C.c_int32, p_i64, p_i32,
                                              C.c_int64, p_i32, p_f64, p_f64]
+    L.fxjps_replan_slots.restype = C.c_int
+    L.fxjps_replan_slots.argtypes = [vp, p_i32, p_i32, p_i32, C.c_int64, C.c_int32, C.c_int32, p_i64, p_i32,
+                                     C.c_int64, p_i32, p_f64, p_i32, p_f64]
     L.fxjps_prepare_slots.restype = C.c_int
     L.fxjps_prepare_slots.argtypes = [vp, C.POINTER(SlotJob), C.c_int32]
     L.fxjps_refresh_slots.restype = C.c_int

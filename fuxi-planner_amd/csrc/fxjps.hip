@@ -214,6 +214,12 @@ struct DevCtx : GridBufs {
     DBuf<long long> d_offsets;
     DBuf<unsigned int> d_next;
     DBuf<unsigned long long> d_counters, d_qstat, d_qread;
+    // fxjps_replan_slots: the previous full batch's results (the set that d_len / d_cost / d_offsets / d_cells flip with), the
+    // sub-batch's lengths and costs, and which of the two each query of the full batch takes (fx::ReplanSrc::src)
+    DBuf<int32_t> p_len, p_cells, s_len, d_rs_src;
+    DBuf<double> p_cost, s_cost;
+    DBuf<long long> p_offsets;
+    HBuf<int32_t> h_rs_src;
     std::vector<unsigned long long> h_qread;  // read sets of the resident results (streaming replan)
     std::vector<uint8_t> h_sel;   // mode 2: which queries of the shard are searched again this frame
     int mode = 0;                 // 0 plain batch, 1 search everything and record read sets, 2 the same for h_sel only
@@ -294,6 +300,15 @@ struct fxjps {
     // true while the device result buffers and the host read sets of every device describe the stored queries on the
     // resident grid: then a frame only searches the queries whose read set its cell updates touch
     bool q_results_valid = false;
+    // fxjps_replan_slots: the previous such call's arguments, the generation of each query's slot then, and its per-query
+    // codes; rs_valid while the device buffers of context 0 still hold that batch (whatever drops q_results_valid drops it)
+    std::vector<int32_t> rs_ids, rs_starts, rs_goals, rs_len;
+    std::vector<uint64_t> rs_gen;
+    int64_t rs_nq = 0;
+    int rs_hchoice = 0, rs_max_len = 0;
+    bool rs_valid = false;
+    // per-slot generation: bumped by every call that writes a slot's bytes or maps on any context (a release included)
+    uint64_t slot_gen[FXJPS_MAX_GRID_SLOTS] = {};
     // RCCL (only for n_dev > 1), resolved with dlopen so that a single-GPU
     // deployment does not need librccl at load time
     void* rccl = nullptr;
@@ -988,9 +1003,9 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
     return FXJPS_OK;
 }
 
-// Second half: wait for the search, retry overflowed queries with the large
-// pool, pack to CSR, copy len/cost/offsets back.
-int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
+// Second half, first part: wait for the search and retry overflowed queries with the large pool.  Leaves the lengths (internal
+// codes included) in d.h_len.
+int finish_search(fxjps* h, DevCtx& d, int hchoice, int max_len) {
     HIPCHK(h, hipSetDevice(d.dev));
     const int64_t nq = d.nq;
     if (nq == 0) return FXJPS_OK;
@@ -1034,7 +1049,16 @@ int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
         HIPCHK(h, hipEventElapsedTime(&ms, d.ev0, d.ev1));
         d.kernel_ms += ms;
     }
-    DBG("kernel %.3f ms, %zu to redo; scan", d.kernel_ms, redo.size());
+    DBG("kernel %.3f ms, %zu to redo", d.kernel_ms, redo.size());
+    return FXJPS_OK;
+}
+
+// Second half: wait for the search, retry overflowed queries with the large
+// pool, pack to CSR, copy len/cost/offsets back.
+int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
+    const int64_t nq = d.nq;
+    if (nq == 0) return FXJPS_OK;
+    if (int rc = finish_search(h, d, hchoice, max_len)) return rc;
     hipLaunchKernelGGL(fx::k_scan_len, dim3(1), dim3(1024), 0, d.stream, d.d_len.p, (long long)nq, d.d_offsets.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(d.h_offsets.p, d.d_offsets.p, ((size_t)nq + 1) * sizeof(long long), hipMemcpyDeviceToHost, d.stream));
@@ -1152,6 +1176,7 @@ int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals
 
 int update_cells_async(fxjps* h, const int32_t* xy, const uint8_t* val, int64_t n, bool derive);  // (below, with the streaming entry points)
 void drain_all(fxjps* h);
+void collect_timing(fxjps* h);
 
 // grid_ids != nullptr: a slots batch (fxjps_plan_batch_slots_csr, which checked the ids and set every context's mg_* fields)
 int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len, int mode = 0,
@@ -1177,7 +1202,7 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
         h->devs[r].nq = nq * (r + 1) / nd - h->devs[r].q0;
         h->devs[r].mode = mode;
     }
-    h->q_results_valid = false;  // (fxjps_replan_frame sets it again once its frame is complete)
+    h->q_results_valid = h->rs_valid = false;  // (fxjps_replan_frame sets it again once its frame is complete)
     int rc = FXJPS_OK;
     h->last_on_host = false;
     static const bool single_ok = !(getenv("FXJPS_SINGLE") && atoi(getenv("FXJPS_SINGLE")) == 0) && !getenv("FXJPS_QSTAT");  // (0: test / measurement aid)
@@ -1210,6 +1235,12 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
         for (auto& d : h->devs) d.nq = 0;  // (no shard holds a result)
         return rc;
     }
+    collect_timing(h);
+    return FXJPS_OK;
+}
+
+// the handle's timing record out of what every context's last batch left
+void collect_timing(fxjps* h) {
     fxjps_timing_t& T = h->timing;
     T.search_kernel_ms = 0;
     T.search_launches = 0;
@@ -1244,7 +1275,6 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
             if (d.cfg[0].direct_ly > 0) T.table_direct = 1;
         }
     }
-    return FXJPS_OK;
 }
 
 typedef int (*nccl_init_all_t)(void**, int, const int*);
@@ -1595,7 +1625,7 @@ int fxjps_reserve_grid(fxjps_t* h, int32_t W, int32_t H) {
     if (!h) return FXJPS_E_ARG;
     if (W < 1 || H < 1 || W > 8190 || H > 8190) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
     h->have_grid = false;  // (the buffers of the resident grid may have been replaced)
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     for (auto& d : h->devs) {
         int rc = alloc_grid(h, d, W, H);
         if (rc) return rc;
@@ -1640,7 +1670,7 @@ int fxjps_set_grid_rank(fxjps_t* h, const uint8_t* occ, int32_t W, int32_t H) {
     if (h->world < 1) return fail(h, FXJPS_E_ARG, "fxjps_set_grid_rank on a handle that fxjps_create_rank did not make");
     if (W < 1 || H < 1 || W > 8190 || H > 8190 || (h->rank == 0 && !occ)) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side (rank 0 passes it)");
     h->have_grid = false;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     DevCtx& d0 = h->devs[0];
     int rc = alloc_grid(h, d0, W, H);
     if (rc) return rc;
@@ -1683,6 +1713,14 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_order.release();
         d.d_redo.release();
         d.d_offsets.release();
+        d.p_len.release();
+        d.p_cells.release();
+        d.p_cost.release();
+        d.p_offsets.release();
+        d.s_len.release();
+        d.s_cost.release();
+        d.d_rs_src.release();
+        d.h_rs_src.release();
         d.d_next.release();
         d.d_counters.release();
         d.d_qstat.release();
@@ -1758,7 +1796,7 @@ int fxjps_set_grid(fxjps_t* h, const uint8_t* occ, int32_t W, int32_t H) {
     if (!occ || W < 1 || H < 1 || W > 8190 || H > 8190) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
     if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid")) return rr;
     h->have_grid = false;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     for (auto& d : h->devs) {
         int rc = alloc_grid(h, d, W, H);
         if (rc) return rc;
@@ -1795,7 +1833,7 @@ int fxjps_set_grid_device(fxjps_t* h, const void* d_occ, int32_t W, int32_t H) {
     if (!d_occ || W < 1 || H < 1 || W > 8190 || H > 8190) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
     if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid_device")) return rr;
     h->have_grid = false;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     for (auto& d : h->devs) {
         int rc = alloc_grid(h, d, W, H);
         if (rc) return rc;
@@ -1825,7 +1863,7 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
     const long long H1 = std::max<long long>(std::max<long long>(H0, gy), sy) + dy + 4ll * ifa;
     if (W1 > 8190 || H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", W1, H1);
     h->have_grid = false;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     for (auto& d : h->devs) {
         HIPCHK(h, hipSetDevice(d.dev));
         HIPCHK(h, d.d_raw.ensure((size_t)W0 * H0));
@@ -1969,7 +2007,7 @@ int fxjps_set_grid_image(fxjps_t* h, const uint8_t* gray, int32_t rows, int32_t 
     if (!gray || rows < 1 || cols < 1 || rows > 8190 || cols > 8190) return fail(h, FXJPS_E_ARG, "image must be 1..8190 pixels a side");
     if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid_image")) return rr;
     h->have_grid = false;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     const size_t n = (size_t)rows * cols;
     for (auto& d : h->devs) {
         int rc = alloc_grid(h, d, cols, rows);  // map_pre = img[::-1].T: W = image columns, H = image rows   :182
@@ -2159,7 +2197,7 @@ static int emit_csr(fxjps_t* h, int64_t nq, int64_t* out_offsets, int32_t* out_c
 
 int fxjps_update_cells(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n) {
     if (!h) return FXJPS_E_ARG;
-    h->q_results_valid = false;  // the grid changes behind the stored results
+    h->q_results_valid = h->rs_valid = false;  // the grid changes behind the stored results
     int rc = update_cells_async(h, xy, val, n, true);
     if (rc) return rc;
     for (auto& d : h->devs) {
@@ -2171,7 +2209,7 @@ int fxjps_update_cells(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
 
 int fxjps_update_cells_deferred(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n) {
     if (!h) return FXJPS_E_ARG;
-    h->q_results_valid = false;  // the grid changes behind the stored results
+    h->q_results_valid = h->rs_valid = false;  // the grid changes behind the stored results
     return update_cells_async(h, xy, val, n, false);  // queued; the next planning call (or fxjps_update_cells) rebuilds the maps
 }
 
@@ -2186,7 +2224,7 @@ int fxjps_set_queries(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals
     h->q_hchoice = hchoice;
     h->q_max_len = max_path_len;
     h->q_set = true;
-    h->q_results_valid = false;
+    h->q_results_valid = h->rs_valid = false;
     return FXJPS_OK;
 }
 
@@ -2246,7 +2284,7 @@ int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
     }
     // the frame's map update is queued in front of the search on the same streams: the first host wait of the frame
     // is the one for the search results
-    h->q_results_valid = false;  // (set again below, once the frame is complete)
+    h->q_results_valid = h->rs_valid = false;  // (set again below, once the frame is complete)
     int rc = update_cells_async(h, xy, val, n, true);
     if (rc) {
         drain_all(h);  // the devices in front of the failing one have the update queued
@@ -2288,6 +2326,7 @@ int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W,
     if (slot < 0 || slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "slot %d is not in 0 .. %d", (int)slot, FXJPS_MAX_GRID_SLOTS - 1);
     if (occ && (W < 1 || H < 1 || W > 8190 || H > 8190)) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
     if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid_slot")) return rr;
+    h->slot_gen[(size_t)slot]++;  // (whatever becomes of the call: the slot's bytes are about to be written or released)
     // Every context gets its own copy from the host (no collective), builds the maps on its own streams, and refreshes its
     // table of slot descriptors.  The resident grid and its update state are not touched.
     int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int {
@@ -2538,6 +2577,7 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
                 if (hipSetDevice(d.dev) == hipSuccess) (void)hipMemcpy(d.d_slot_desc.p + s, &d.h_slot_desc[s], sizeof(GridDev), hipMemcpyHostToDevice);
             }
         (void)hipGetLastError();
+        for (int j = 0; j < n; j++) h->slot_gen[(size_t)jobs[j].slot]++;  // (released)
         return rc;
     }
     const int32_t* res = h->devs[0].h_slots_res.p;  // (every context computed the same)
@@ -2555,7 +2595,9 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
         jb.end_occu = res[(size_t)j * fx::SLOT_RES + 2];
         jb.status = res[(size_t)j * fx::SLOT_RES + 3] != 0 ? FXJPS_E_ARG : FXJPS_OK;
         // kept: no byte of context 0's copy differed, so nothing was built (a job that failed has an empty slot: not kept)
-        if (out_kept) out_kept[j] = refresh && jb.status == FXJPS_OK && res[(size_t)n * fx::SLOT_RES + (size_t)j] == 0 ? 1 : 0;
+        const bool kept = refresh && jb.status == FXJPS_OK && res[(size_t)n * fx::SLOT_RES + (size_t)j] == 0;
+        if (out_kept) out_kept[j] = kept ? 1 : 0;
+        if (!kept) h->slot_gen[(size_t)jb.slot]++;  // (built, or left empty; a prepare always builds)
     }
     return FXJPS_OK;
 }
@@ -2644,6 +2686,29 @@ int fxjps_publish_slots(fxjps_t* h, fxjps_slot_publish_t* jobs, int32_t n) {
     return FXJPS_OK;
 }
 
+namespace {
+// A slots batch's ids, every one checked before anything is queued; the batch is sized by the largest extents among the
+// slots it names.
+int slots_batch_extents(fxjps_t* h, const int32_t* grid_ids, int64_t nq, int& mw, int& mh, uint64_t& mc) {
+    mw = mh = 1;
+    mc = 1;
+    std::vector<uint8_t> seen(FXJPS_MAX_GRID_SLOTS, 0);
+    for (int64_t q = 0; q < nq; q++) {
+        const int32_t id = grid_ids[q];
+        if (!slot_in_use(h, id))
+            return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)id,
+                        id < 0 || id >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
+        if (seen[(size_t)id]) continue;
+        seen[(size_t)id] = 1;
+        const GridBufs& g = h->devs[0].slots[(size_t)id];
+        mw = std::max(mw, g.W);
+        mh = std::max(mh, g.H);
+        mc = std::max(mc, (uint64_t)g.W * (uint64_t)g.H);
+    }
+    return FXJPS_OK;
+}
+}  // namespace
+
 int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
                                int32_t hchoice, int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy,
                                int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
@@ -2651,24 +2716,9 @@ int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_
     if (!h) return FXJPS_E_ARG;
     if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
     if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
-    // every id checked before anything is queued; the batch is sized by the largest extents among the slots it names
     int mw = 1, mh = 1;
     uint64_t mc = 1;
-    {
-        std::vector<uint8_t> seen(FXJPS_MAX_GRID_SLOTS, 0);
-        for (int64_t q = 0; q < nq; q++) {
-            const int32_t id = grid_ids[q];
-            if (!slot_in_use(h, id))
-                return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)id,
-                            id < 0 || id >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
-            if (seen[(size_t)id]) continue;
-            seen[(size_t)id] = 1;
-            const GridBufs& g = h->devs[0].slots[(size_t)id];
-            mw = std::max(mw, g.W);
-            mh = std::max(mh, g.H);
-            mc = std::max(mc, (uint64_t)g.W * (uint64_t)g.H);
-        }
-    }
+    if (int rc = slots_batch_extents(h, grid_ids, nq, mw, mh, mc)) return rc;
     static const int32_t no_ids = 0;  // (an empty batch may pass no array: it is a slots batch all the same)
     const int32_t* ids = grid_ids ? grid_ids : &no_ids;
     for (auto& d : h->devs) {
@@ -2683,6 +2733,177 @@ int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_
     h->last_slots_W = mw;
     h->last_slots_H = mh;
     h->last_slot_ids.assign(ids, ids + nq);
+    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
+    h->timing.total_ms = (now_s() - t0) * 1e3;
+    if (out_seconds_total) *out_seconds_total = now_s() - t0;
+    return rc;
+}
+
+namespace {
+// fxjps_replan_slots on a handle with one context.  The arguments are checked; `searched` lists the
+// queries to search, in query order.  Runs them as a sub-batch through run_shard / finish_search, then assembles the full
+// batch on the device: one copy in (the source table), one scan launch, one gather launch, the copies out, one wait.
+int replan_slots_assemble(fxjps* h, DevCtx& d, const int32_t* grid_ids, const int32_t* starts, const int32_t* goals, int64_t nq,
+                          const std::vector<int64_t>& searched, int hchoice, int max_len, int mw, int mh, uint64_t mc) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    const int64_t nsub = (int64_t)searched.size();
+    // the previous batch's results become the other set: what was `previous` before is written anew
+    std::swap(d.d_len, d.p_len);
+    std::swap(d.d_cost, d.p_cost);
+    std::swap(d.d_offsets, d.p_offsets);
+    std::swap(d.d_cells, d.p_cells);
+    std::vector<int32_t> sub_len((size_t)nsub);
+    d.q0 = 0;
+    d.nq = nsub;
+    d.mode = 0;
+    if (nsub > 0) {
+        std::vector<int32_t> ids((size_t)nsub), st((size_t)nsub * 2), go((size_t)nsub * 2);
+        for (int64_t k = 0; k < nsub; k++) {
+            const int64_t q = searched[(size_t)k];
+            ids[(size_t)k] = grid_ids[q];
+            st[(size_t)2 * k] = starts[2 * q];
+            st[(size_t)2 * k + 1] = starts[2 * q + 1];
+            go[(size_t)2 * k] = goals[2 * q];
+            go[(size_t)2 * k + 1] = goals[2 * q + 1];
+        }
+        d.mg_ids = ids.data();  // (the full batch's extents: the scratch is configured as the whole batch would configure it)
+        d.mg_W = mw;
+        d.mg_H = mh;
+        d.mg_cells = mc;
+        int rc = run_shard(h, d, st.data(), go.data(), hchoice, max_len);
+        if (!rc) rc = finish_search(h, d, hchoice, max_len);  // (waits: the pageable arrays above have been read)
+        d.mg_ids = nullptr;
+        if (rc) return rc;
+        memcpy(sub_len.data(), d.h_len.p, (size_t)nsub * sizeof(int32_t));
+        std::swap(d.d_len, d.s_len);  // the sub-batch's lengths and costs step aside for the full batch's
+        std::swap(d.d_cost, d.s_cost);
+    } else {
+        d.kernel_ms = 0;
+        d.launches = 0;
+        d.retried = 0;
+        d.nrun = 0;
+        d.waves_used = 0;
+        d.waves_short = false;
+        d.had_solo = false;
+        d.head_ms = d.batch_ms = 0;
+    }
+    if (nq == 0) return FXJPS_OK;
+    // every length is known to the host (the stored codes; the sub-batch's, which finish_search brought back): the cells'
+    // room is sized before anything is queued, and nothing below waits but the last line
+    HIPCHK(h, d.h_rs_src.ensure((size_t)nq));
+    HIPCHK(h, d.d_rs_src.ensure((size_t)nq));
+    long long total = 0;
+    {
+        int64_t k = 0;
+        for (int64_t q = 0; q < nq; q++) {
+            const bool s = k < nsub && searched[(size_t)k] == q;
+            const int32_t n = s ? sub_len[(size_t)k] : h->rs_len[(size_t)q];
+            d.h_rs_src.p[q] = s ? (int32_t)k : -1;
+            if (s) k++;
+            total += n > 0 ? n : 0;
+        }
+    }
+    HIPCHK(h, d.d_len.ensure((size_t)nq));
+    HIPCHK(h, d.d_cost.ensure((size_t)nq));
+    HIPCHK(h, d.d_offsets.ensure((size_t)nq + 1));
+    HIPCHK(h, d.h_len.ensure((size_t)nq));
+    HIPCHK(h, d.h_cost.ensure((size_t)nq));
+    HIPCHK(h, d.h_offsets.ensure((size_t)nq + 1));
+    HIPCHK(h, d.h_counters.ensure(64));
+    if (total > 0) {
+        if (d.d_cells.ensure((size_t)total * 2) != hipSuccess) {  // (the search is over: its scratch can go)
+            (void)hipGetLastError();
+            release_pool0(d);
+            HIPCHK(h, d.d_cells.ensure((size_t)total * 2));
+        }
+        HIPCHK(h, d.h_cells.ensure((size_t)total * 2));
+    }
+    HIPCHK(h, hipMemcpyAsync(d.d_rs_src.p, d.h_rs_src.p, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    const fx::ReplanSrc R{d.d_rs_src.p, d.p_len.p, d.p_cost.p, d.p_offsets.p, d.p_cells.p, d.s_len.p, d.s_cost.p, d.d_path.p, max_len};
+    hipLaunchKernelGGL(fx::k_replan_scan, dim3(1), dim3(1024), 0, d.stream, R, (long long)nq, d.d_len.p, d.d_cost.p, d.d_offsets.p);
+    if (total > 0)
+        hipLaunchKernelGGL(fx::k_replan_gather, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, d.stream, R, d.d_len.p, d.d_offsets.p, (long long)nq,
+                           d.d_cells.p, total);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.h_offsets.p, d.d_offsets.p, ((size_t)nq + 1) * sizeof(long long), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.h_cost.p, d.d_cost.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    if (nsub > 0) HIPCHK(h, hipMemcpyAsync(d.h_counters.p, d.d_counters.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    if (total > 0) HIPCHK(h, hipMemcpyAsync(d.h_cells.p, d.d_cells.p, (size_t)total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    if (nsub == 0) memset(d.h_counters.p, 0, 64 * sizeof(unsigned long long));  // (nothing was searched)
+    d.nq = nq;
+    if (d.h_offsets.p[nq] != total) return fail(h, FXJPS_E_HIP, "the assembled batch has %lld cells, the host counted %lld", (long long)d.h_offsets.p[nq], total);
+    for (int64_t i = 0; i < nq; i++)  // internal codes must not leak
+        if (d.h_len.p[i] <= fx::QI_TABLE_FULL) d.h_len.p[i] = FXJPS_Q_CAPACITY;
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq, int32_t hchoice,
+                       int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len,
+                       double* out_cost, int32_t* out_reused, double* out_seconds_total) {
+    const double t0 = now_s();
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_replan_slots")) return rr;
+    if (h->devs.size() > 1) {  // several contexts: a plain slots batch (reuse across shards is not built)
+        if (out_reused && nq > 0) memset(out_reused, 0, (size_t)nq * sizeof(int32_t));
+        return fxjps_plan_batch_slots_csr(h, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, out_offsets, out_cells_xy, cells_capacity,
+                                          out_len, out_cost, out_seconds_total);
+    }
+    // the refusals of fxjps_plan_batch_slots_csr and of plan_core, all of them before the stored results are touched
+    if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
+    if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
+    int mw = 1, mh = 1;
+    uint64_t mc = 1;
+    if (int rc = slots_batch_extents(h, grid_ids, nq, mw, mh, mc)) return rc;
+    if (nq < 0 || (nq > 0 && (!starts_xy || !goals_xy))) return fail(h, FXJPS_E_ARG, "bad query arrays");
+    if (hchoice != 1 && hchoice != 2) return fail(h, FXJPS_E_ARG, "hchoice must be 1 or 2 (the reference raises TypeError, jps1.py:188)");
+    if (max_path_len < 1 || max_path_len > (1 << 20)) return fail(h, FXJPS_E_ARG, "max_path_len out of range");
+    if (nq > 0x7FFFFFF0ll) return fail(h, FXJPS_E_ARG, "too many queries in one batch");
+    // ---- which queries are searched: plain compares of the arguments against the stored ones, before anything is queued
+    static const bool allow_reuse = !(getenv("FXJPS_REPLAN_REUSE") && atoi(getenv("FXJPS_REPLAN_REUSE")) == 0);
+    const bool stored = allow_reuse && h->rs_valid && h->rs_nq == nq && h->rs_hchoice == hchoice && h->rs_max_len == max_path_len;
+    std::vector<int64_t> searched;
+    std::vector<uint64_t> gen((size_t)nq);
+    for (int64_t q = 0; q < nq; q++) {
+        const size_t i = (size_t)q;
+        gen[i] = h->slot_gen[(size_t)grid_ids[q]];
+        const bool reuse = stored && h->rs_ids[i] == grid_ids[q] && h->rs_gen[i] == gen[i] && h->rs_len[i] != FXJPS_Q_CAPACITY &&
+                           h->rs_starts[2 * i] == starts_xy[2 * q] && h->rs_starts[2 * i + 1] == starts_xy[2 * q + 1] &&
+                           h->rs_goals[2 * i] == goals_xy[2 * q] && h->rs_goals[2 * i + 1] == goals_xy[2 * q + 1];
+        if (!reuse) searched.push_back(q);
+    }
+    // (as plan_core: until this batch is complete no earlier batch is "the last batch")
+    h->last_nq = 0;
+    h->last_slots = true;
+    h->last_on_host = false;
+    h->q_results_valid = h->rs_valid = false;
+    DevCtx& d = h->devs[0];
+    int rc = replan_slots_assemble(h, d, grid_ids, starts_xy, goals_xy, nq, searched, hchoice, max_path_len, mw, mh, mc);
+    if (rc) {
+        drain_all(h);  // before the error leaves the library
+        d.nq = 0;      // (the context holds no result)
+        return rc;
+    }
+    collect_timing(h);
+    h->timing.reused = nq - (int64_t)searched.size();
+    h->last_slots_W = mw;
+    h->last_slots_H = mh;
+    h->last_slot_ids.assign(grid_ids, grid_ids + nq);
+    h->rs_ids = h->last_slot_ids;
+    h->rs_starts.assign(starts_xy, starts_xy + 2 * nq);
+    h->rs_goals.assign(goals_xy, goals_xy + 2 * nq);
+    h->rs_len.assign(d.h_len.p, d.h_len.p + nq);
+    h->rs_gen.swap(gen);
+    h->rs_nq = nq;
+    h->rs_hchoice = hchoice;
+    h->rs_max_len = max_path_len;
+    h->rs_valid = true;
+    if (out_reused) {
+        for (int64_t q = 0; q < nq; q++) out_reused[q] = 1;
+        for (int64_t q : searched) out_reused[q] = 0;
+    }
     rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
     h->timing.total_ms = (now_s() - t0) * 1e3;
     if (out_seconds_total) *out_seconds_total = now_s() - t0;

@@ -10,6 +10,7 @@
 //                                                       (heuristic; read-set recording; visited table indexed by the cell;
 //                                                       each query on the grid of its own slot)
 //   k_scan_len / k_gather_paths                         dense per-query path slots -> CSR
+//   k_replan_scan / k_replan_gather                     a batch's CSR out of the previous batch's and a sub-batch's results
 //   k_waypoint_ccst                                     the ccst node's waypoint selection, one wavefront per path
 //   k_sqrt_selftest / k_selftest_wavemin / k_selftest_openlist   arithmetic and open-list proofs used by the tests
 //
@@ -3322,6 +3323,105 @@ __global__ __launch_bounds__(256) void k_gather_paths(const uint32_t* __restrict
     for (int i = lane; i < n; i += WAVE) {
         const uint32_t v = src[i];
         dst[i] = make_int2((int)(v >> 16), (int)(v & 0xFFFFu));
+    }
+}
+
+// ---- fxjps_replan_slots: the full batch's resident CSR out of two sources (DESIGN.md section 3.13).  src[q] < 0: query q
+// was not searched, its length, cost and cells are the previous batch's at index q; else they are the sub-batch's at index
+// src[q] (lengths and costs as k_search left them, cells still in the dense slots of max_len packed words).
+struct ReplanSrc {
+    const int32_t* src;
+    const int32_t* p_len;  // the previous batch
+    const double* p_cost;
+    const long long* p_off;
+    const int32_t* p_cells;
+    const int32_t* s_len;  // the sub-batch
+    const double* s_cost;
+    const uint32_t* s_path;
+    int max_len;
+};
+
+// Lengths and costs of the full batch, and the exclusive scan of max(len, 0) into offsets[0 .. nq]; one block (k_scan_len's
+// scan, reading each length through the source table).
+__global__ __launch_bounds__(1024) void k_replan_scan(ReplanSrc R, long long nq, int32_t* __restrict__ len, double* __restrict__ cost,
+                                                      long long* __restrict__ offsets) {
+    __shared__ long long s_part[1024];
+    const int tid = threadIdx.x;
+    const long long per = (nq + 1023) / 1024;
+    const long long lo = (long long)tid * per, hi = min(lo + per, nq);
+    long long sum = 0;
+    for (long long i = lo; i < hi; i++) {
+        const int32_t s = R.src[i];
+        const int32_t n = s < 0 ? R.p_len[i] : R.s_len[s];
+        len[i] = n;
+        cost[i] = s < 0 ? R.p_cost[i] : R.s_cost[s];
+        sum += n > 0 ? n : 0;
+    }
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        long long v = tid >= o ? s_part[tid - o] : 0;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    long long run = tid ? s_part[tid - 1] : 0;
+    for (long long i = lo; i < hi; i++) {  // (each thread reads back what it wrote itself)
+        offsets[i] = run;
+        const int32_t n = len[i];
+        run += n > 0 ? n : 0;
+    }
+    if (tid == 1023) offsets[nq] = s_part[1023];
+}
+
+// One wavefront per query: its cells to their CSR offset, from the previous batch's cells or from the sub-batch's dense slot.
+// A cell is 8 bytes, so an odd offset leaves the destination 8 bytes off a 16-byte boundary: that one cell goes out alone,
+// the rest in pairs (16-byte stores; 16-byte loads too when the previous batch's offset has the same parity), an odd one
+// at the end alone again.
+__global__ __launch_bounds__(256) void k_replan_gather(ReplanSrc R, const int32_t* __restrict__ len, const long long* __restrict__ offsets,
+                                                       long long nq, int32_t* __restrict__ cells, long long cells_cap) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const int n = len[q];
+    if (n <= 0) return;
+    const long long off = offsets[q];
+    if (off + n > cells_cap) return;
+    int2* dst = reinterpret_cast<int2*>(cells) + off;
+    const int head = (int)(off & 1), pairs = (n - head) >> 1, tail = head + 2 * pairs;  // tail == n or n - 1
+    const int32_t s = R.src[q];
+    if (s >= 0) {
+        const uint32_t* sp = R.s_path + (size_t)s * (size_t)R.max_len;
+        const auto cell = [](uint32_t v) { return make_int2((int)(v >> 16), (int)(v & 0xFFFFu)); };
+        if (lane == 0 && head) dst[0] = cell(sp[0]);
+        if (lane == 1 && tail < n) dst[tail] = cell(sp[tail]);
+        const bool al = ((((size_t)s * (size_t)R.max_len) + (size_t)head) & 1u) == 0;  // the words of a pair in one 8-byte load
+        for (int k = lane; k < pairs; k += WAVE) {
+            const int i = head + 2 * k;
+            uint32_t a, b;
+            if (al) {
+                const uint2 v = *reinterpret_cast<const uint2*>(sp + i);
+                a = v.x;
+                b = v.y;
+            } else {
+                a = sp[i];
+                b = sp[i + 1];
+            }
+            *reinterpret_cast<int4*>(dst + i) = make_int4((int)(a >> 16), (int)(a & 0xFFFFu), (int)(b >> 16), (int)(b & 0xFFFFu));
+        }
+    } else {
+        const long long poff = R.p_off[q];
+        const int2* pp = reinterpret_cast<const int2*>(R.p_cells) + poff;
+        if (((poff ^ off) & 1) == 0) {
+            if (lane == 0 && head) dst[0] = pp[0];
+            if (lane == 1 && tail < n) dst[tail] = pp[tail];
+            for (int k = lane; k < pairs; k += WAVE) {
+                const int i = head + 2 * k;
+                *reinterpret_cast<int4*>(dst + i) = *reinterpret_cast<const int4*>(pp + i);
+            }
+        } else {
+            for (int i = lane; i < n; i += WAVE) dst[i] = pp[i];
+        }
     }
 }
 

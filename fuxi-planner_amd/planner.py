@@ -407,13 +407,16 @@ class Planner(object):
         image; when not ok the other values are None."""
         return self._fleet_tick(False, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels)
 
-    def fleet_tick_refresh(self, jobs, pos, global_goals, home, map_reso, map_o, prev_wp=None, prev_dim=None, publish=True, image_channels=None):
+    def fleet_tick_refresh(self, jobs, pos, global_goals, home, map_reso, map_o, prev_wp=None, prev_dim=None, publish=True, image_channels=None,
+                           reuse=False):
         """fleet_tick for the tick after: the maps are prepared through refresh_slots, so a vehicle whose prepared map is
         what its slot already holds keeps the slot's maps.  The same arguments, the same records, and in every live
-        vehicle's record a further key, kept (bool)."""
-        return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels)
+        vehicle's record a further key, kept (bool).  reuse=True: the batch is planned through replan_slots, so a vehicle
+        whose slot was kept and whose start and goal cells did not move is not searched again; its record says so in a
+        further key, reused (bool).  Every other value is what reuse=False gives."""
+        return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse)
 
-    def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels):
+    def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False):
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -430,7 +433,7 @@ class Planner(object):
         if not live:
             return recs
         slots = [int(jobs[v][0]) for v in live]
-        offsets, _, cost, status = self.plan_batch_slots(slots, [outs[v][0] for v in live], [outs[v][1] for v in live], 2)
+        offsets, _, cost, status, reused = self._plan_slots(reuse, slots, [outs[v][0] for v in live], [outs[v][1] for v in live], 2, None)
         origin = [Planner.shifted_origin(orig[v], outs[v][2], reso[v]) for v in live]
         pw = pd = None
         if prev_wp is not None:
@@ -449,11 +452,23 @@ class Planner(object):
                 recs[v].update(msg=pub[i][0], image=pub[i][2])
             if refresh:
                 recs[v]["kept"] = o[6]
+            if reuse:
+                recs[v]["reused"] = bool(reused[i])
         return recs
 
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
         """plan_batch with a grid per query: query q runs on the grid of slot grid_ids[q].  -> (offsets, cells, cost,
         status) as plan_batch.  max_path_len=None: the default slot of the largest grid named, grown when a path needs it."""
+        return self._plan_slots(False, grid_ids, starts, goals, hchoice, max_path_len)[:4]
+
+    def replan_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
+        """plan_batch_slots for the tick after (fxjps_replan_slots): a query whose slot, start and goal are those of the
+        previous replan_slots call, on a slot nothing has written since, hands back its stored path without a search.
+        -> (offsets, cells, cost, status, reused); reused: one bool per query.  The results are byte for byte those of
+        plan_batch_slots.  A max_path_len that grows makes that retry a full search."""
+        return self._plan_slots(True, grid_ids, starts, goals, hchoice, max_path_len)
+
+    def _plan_slots(self, replan, grid_ids, starts, goals, hchoice, max_path_len):
         ids = np.ascontiguousarray(grid_ids, dtype=np.int32).reshape(-1)
         starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 2)
         goals = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
@@ -478,9 +493,16 @@ class Planner(object):
             status = np.zeros(n, dtype=np.int32)
             cost = np.zeros(n, dtype=np.float64)
             secs = C.c_double(0.0)
-            self._chk(self._L.fxjps_plan_batch_slots_csr(self._h, _lib.ptr(ids, C.c_int32), _lib.ptr(starts, C.c_int32),
-                                                         _lib.ptr(goals, C.c_int32), n, int(hchoice), mpl, _lib.ptr(offsets, C.c_int64),
-                                                         None, 0, _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double), C.byref(secs)))
+            reused = np.zeros(n, dtype=np.int32)
+            if replan:
+                self._chk(self._L.fxjps_replan_slots(self._h, _lib.ptr(ids, C.c_int32), _lib.ptr(starts, C.c_int32),
+                                                     _lib.ptr(goals, C.c_int32), n, int(hchoice), mpl, _lib.ptr(offsets, C.c_int64),
+                                                     None, 0, _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double),
+                                                     _lib.ptr(reused, C.c_int32), C.byref(secs)))
+            else:
+                self._chk(self._L.fxjps_plan_batch_slots_csr(self._h, _lib.ptr(ids, C.c_int32), _lib.ptr(starts, C.c_int32),
+                                                             _lib.ptr(goals, C.c_int32), n, int(hchoice), mpl, _lib.ptr(offsets, C.c_int64),
+                                                             None, 0, _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double), C.byref(secs)))
             cells = np.empty((int(offsets[n]), 2), dtype=np.int32)
             if offsets[n] > 0:
                 self._chk(self._L.fxjps_last_cells(self._h, _lib.ptr(cells, C.c_int32), int(offsets[n])))
@@ -489,7 +511,7 @@ class Planner(object):
                 continue
             break
         self.last_seconds = secs.value
-        return offsets, cells, cost, status
+        return offsets, cells, cost, status, reused.astype(bool)
 
     # -- streaming replan (persistent goals, one call per frame)
     def set_queries(self, starts, goals, hchoice=2, max_path_len=None):

@@ -87,8 +87,10 @@ typedef struct fxjps fxjps_t;
  *        world-frame path and the ccst node's direct path of every query, in the same one launch).
  *   760  fxjps_refresh_slots (fxjps_prepare_slots for a tick whose maps mostly did not change: a job whose prepared grid is
  *        byte for byte what its slot holds keeps the slot's maps and runs no build work), fxjps_debug_read_slot_context.
+ *   770  fxjps_replan_slots (fxjps_plan_batch_slots_csr for the tick after: a query whose slot, start and goal did not
+ *        change since the previous such call hands back its stored path without a search).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 760
+#define FXJPS_VERSION 770
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -309,6 +311,33 @@ int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was bu
  * on every context against that context's own copy; out_kept reports context 0's.  out_kept may be NULL; it is not
  * written when the call is refused (nor for n = 0). */
 int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept);
+/* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
+ * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
+ * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
+ * fxjps_tick_outputs_slots without explicit paths behave as after fxjps_plan_batch_slots_csr).  The difference: query q
+ * is not searched -- its stored result is handed back, out_reused[q] = 1 -- iff
+ *   - the handle's previous batch call was a fxjps_replan_slots with the same nq, hchoice and max_path_len (calls that
+ *     touch neither the resident paths nor the stored results may lie in between: fxjps_prepare_slots, fxjps_refresh_slots,
+ *     fxjps_publish_slots, the waypoint and tick-output calls, fxjps_set_grid_slot; every other batch call and every change
+ *     of the resident grid drops the stored results, as it drops those of fxjps_replan_frame),
+ *   - grid_ids[q], the start and the goal equal that call's values for q,
+ *   - the slot's generation is the one recorded then (a counter per slot, kept by the library: fxjps_set_grid_slot and
+ *     fxjps_prepare_slots bump it for every slot they name, fxjps_refresh_slots for every job it did not report kept), and
+ *   - q's stored code is not FXJPS_Q_CAPACITY (every other outcome is a function of the grid and the query).
+ * The host decides this with plain compares before anything is queued.  The queries to search run as a sub-batch through
+ * the search path of fxjps_plan_batch_slots_csr; behind it one scan launch and one gather launch assemble the full
+ * batch's lengths, costs, offsets and cells on the device from the previous batch's buffers and the sub-batch's results.
+ * Launches, copies and host waits do not depend on nq or on how many queries are reused; when nothing is searched no search
+ * launch is queued (fxjps_timing_t.search_launches == 0).  fxjps_timing_t.reused counts the queries that were not
+ * searched; pops, pushes and the other search counters describe the searched ones only.
+ *   A refused call (FXJPS_E_ARG: a bad argument, an empty slot named) queues nothing and leaves the stored results as they
+ * were.  A handle with several contexts runs the call as a plain fxjps_plan_batch_slots_csr (nothing is reused); a rank
+ * handle (fxjps_create_rank, world > 1) refuses with FXJPS_E_ARG.  FXJPS_REPLAN_REUSE=0 in the environment turns the reuse
+ * off.  out_reused (nq flags) may be NULL. */
+int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
+                       int32_t hchoice, int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy,
+                       int64_t cells_capacity, int32_t* out_len, double* out_cost, int32_t* out_reused,
+                       double* out_seconds_total);
 
 /* ---- Many slots' maps published in one call (the last quarter of a fleet tick: every vehicle's prepared map leaves the
  * device as the message and / or the snapshot image a node publishes).  Job by job the results are those of
@@ -348,7 +377,7 @@ typedef struct fxjps_timing {
     int64_t far_refills;     /* open-list refills from the global-memory tier */
     int64_t slow_pops;       /* pops taken straight from the global-memory tier (> 256 entries tied at the minimum key) */
     int64_t table_wipes;     /* visited-table wipes after a wavefront's generation counter wrapped (every 63 searches) */
-    int64_t reused;          /* fxjps_replan_frame: stored results returned without a search (their read set was untouched) */
+    int64_t reused;          /* fxjps_replan_frame / fxjps_replan_slots: stored results returned without a search */
     int64_t table_direct;    /* 1: the last batch ran on visited tables indexed by the cell (grids of up to 2^20 slots), 0: on
                                 hashed tables of 4-slot buckets (larger grids; FXJPS_DIRECT=0) */
     int64_t waves;           /* resident wavefronts (= queries in flight) the last batch ran with, summed over the contexts */
