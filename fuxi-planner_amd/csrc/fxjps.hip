@@ -184,11 +184,17 @@ struct DevCtx : GridBufs {
     DBuf<GridDev> d_slot_desc;
     DBuf<int32_t> d_grid_ids;
     // fxjps_prepare_slots / fxjps_refresh_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw
-    // maps | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal / k_refresh_goal
+    // maps | a world-frame call's fx::WorldSrcDev records | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal / k_refresh_goal
     HBuf<uint8_t> h_slots_in;
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
     DBuf<int32_t> d_slots_res;
+    // prior maps (fxjps_set_prior_map): [W][H] bytes the world-frame calls gather from; W == 0: not set
+    struct PriorBuf {
+        DBuf<uint8_t> occ;
+        int W = 0, H = 0;
+    };
+    std::vector<PriorBuf> priors;  // [FXJPS_MAX_PRIOR_MAPS] once the first prior is set
     // fxjps_publish_slots: the call's job table (fx::PubTable) and all its outputs, pinned and on the device
     HBuf<uint8_t> h_pub_in, h_pub_out;
     DBuf<uint8_t> d_pub_in, d_pub_out;
@@ -1756,6 +1762,7 @@ void fxjps_destroy(fxjps_t* h) {
         d.h_upd_xy.release();
         d.h_path1.release();
         for (auto& g : d.slots) g.release();
+        for (auto& pr : d.priors) pr.occ.release();
         d.d_slot_desc.release();
         d.d_grid_ids.release();
         d.h_slots_in.release();
@@ -2402,6 +2409,17 @@ struct SlotPlan {
     long long dx, dy, W1, H1, nsx, nsy, ngx, ngy;
     size_t raw_off;  // of its raw map inside the staged input
 };
+// A world-frame job's two sources, in canvas cells (fxjps_prepare_slots_world): the job handed to slots_call has the canvas
+// extents as W0 / H0 and the detected map as raw.
+struct WorldSrc {
+    int prior;           // -1: none
+    int rW, rH, rx, ry;  // the detected map: its extents, where it lies
+    int px, py;          // where the prior lies
+};
+struct WorldCall {
+    const WorldSrc* src;
+    size_t off;  // of the fx::WorldSrcDev records inside the staged input
+};
 // The staged input of a call: the job table, the context's 256 slot descriptors as they will be, then the raw maps.
 constexpr size_t SLOTS_IN_DESC = (sizeof(fx::SlotTable) + 15) & ~(size_t)15;
 constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS + 15) & ~(size_t)15;
@@ -2410,7 +2428,8 @@ constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GR
 // waited for ONCE, whatever n is.  The results are left in d.h_slots_res.  refresh: a job whose slot holds a grid of the
 // prepared extents is compared with it byte by byte while it is gathered, and built only if a byte differed (DESIGN.md
 // section 3.12); the n `changed` words travel in behind the raws and come back behind the results, in the same two copies.
-int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh) {
+int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh,
+                     const WorldCall* world) {
     HIPCHK(h, hipSetDevice(d.dev));
     if (d.slots.empty()) {
         d.slots.resize(FXJPS_MAX_GRID_SLOTS);
@@ -2428,6 +2447,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
     fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
     uint32_t* h_changed = reinterpret_cast<uint32_t*>(d.h_slots_in.p + flags_off);
     uint32_t* d_changed = reinterpret_cast<uint32_t*>(d.d_slots_in.p + flags_off);
+    fx::WorldSrcDev* h_world = world ? reinterpret_cast<fx::WorldSrcDev*>(d.h_slots_in.p + world->off) : nullptr;
     uint32_t at[fx::SL_LAUNCHES] = {};
     bool any_large = false;
     for (int j = 0; j < n; j++) {
@@ -2457,7 +2477,22 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
         J.gy = (int32_t)p.ngy;
         J.compare = compare ? 1 : 0;
         if (refresh) h_changed[j] = compare ? 0u : 1u;  // (written anew by every call: nothing of the call before is read)
-        memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
+        if (world) {  // (only the detected map is staged: the prior's bytes are on the device already)
+            const WorldSrc& w = world->src[j];
+            fx::WorldSrcDev& S = h_world[j];
+            S = fx::WorldSrcDev{nullptr, 0, 0, 0, 0, w.rW, w.rH, w.rx, w.ry};
+            if (w.prior >= 0) {
+                const DevCtx::PriorBuf& pr = d.priors[(size_t)w.prior];
+                S.prior = pr.occ.p;
+                S.pW = pr.W;
+                S.pH = pr.H;
+                S.px = w.px;
+                S.py = w.py;
+            }
+            memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)w.rW * (size_t)w.rH);
+        } else {
+            memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
+        }
         // the blocks derive_maps would launch for this grid alone (the fused build: at most 2^18 cells)
         const long long ncell = p.W1 * p.H1, npad = (long long)g.PW * g.PH;
         const bool fused = ncell <= (1ll << 18);
@@ -2479,7 +2514,11 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
     HIPCHK(h, hipMemcpyAsync(d.d_slots_in.p, d.h_slots_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
     const fx::SlotTable* dT = reinterpret_cast<const fx::SlotTable*>(d.d_slots_in.p);
     if (refresh) {
-        hipLaunchKernelGGL(fx::k_refresh_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, d_changed);
+        if (world)
+            hipLaunchKernelGGL(fx::k_refresh_world, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT,
+                               reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off), n, d_changed);
+        else
+            hipLaunchKernelGGL(fx::k_refresh_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, d_changed);
         hipLaunchKernelGGL(fx::k_refresh_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p, n, d_changed);
         if (at[fx::SL_BUILD_1] > 0) {
             hipLaunchKernelGGL(fx::k_refresh_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n, d_changed);
@@ -2488,7 +2527,11 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
             hipLaunchKernelGGL(fx::k_refresh_derive_jd, dim3(at[fx::SL_JD]), dim3(256), 0, d.stream, dT, n, d_changed);
         }
     } else {
-        hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
+        if (world)
+            hipLaunchKernelGGL(fx::k_prepare_world, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT,
+                               reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off), n);
+        else
+            hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
         hipLaunchKernelGGL(fx::k_slots_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p);
     }
     if (!refresh && at[fx::SL_BUILD_1] > 0) {
@@ -2522,7 +2565,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
 namespace {
 // fxjps_prepare_slots (out_kept == nullptr, refresh false) and fxjps_refresh_slots: the checks, the call on every context
 // and the outputs are the same code.
-int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what) {
+int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const WorldSrc* world_src = nullptr) {
     if (!h) return FXJPS_E_ARG;
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
     if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
@@ -2561,11 +2604,15 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
         if (p.ngx < 0 || p.ngy < 0 || p.ngx >= p.W1 || p.ngy >= p.H1)
             return fail(h, FXJPS_E_ARG, "job %d: goal (%lld, %lld) outside the prepared grid %lldx%lld", j, p.ngx, p.ngy, p.W1, p.H1);
         p.raw_off = in_bytes;
-        in_bytes += ((size_t)jb.W0 * (size_t)jb.H0 + 15) & ~(size_t)15;
+        const size_t raw_bytes = world_src ? (size_t)world_src[j].rW * (size_t)world_src[j].rH : (size_t)jb.W0 * (size_t)jb.H0;
+        in_bytes += (raw_bytes + 15) & ~(size_t)15;
     }
     if (n == 0) return FXJPS_OK;
+    WorldCall wc{world_src, in_bytes};
+    const WorldCall* world = world_src ? &wc : nullptr;
+    if (world) in_bytes += ((size_t)n * sizeof(fx::WorldSrcDev) + 15) & ~(size_t)15;
     // every context prepares every job from the caller's raws (host copies, no collective, as fxjps_set_grid_slot)
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh); });
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world); });
     if (rc) {
         drain_all(h);
         for (auto& d : h->devs)  // (slots of a call that failed on one context are released on all of them)
@@ -2607,6 +2654,173 @@ int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) { return 
 
 int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept) {
     return slots_call(h, jobs, n, true, out_kept, "fxjps_refresh_slots");
+}
+
+// ------------------------------------------------------------------ the same two calls from world-frame jobs
+int fxjps_world_job_size(void) { return (int)sizeof(fxjps_world_job_t); }
+
+int fxjps_set_prior_map(fxjps_t* h, int32_t prior, const uint8_t* occ, int32_t W, int32_t H) {
+    if (!h) return FXJPS_E_ARG;
+    if (prior < 0 || prior >= FXJPS_MAX_PRIOR_MAPS) return fail(h, FXJPS_E_ARG, "prior %d is not in 0 .. %d", (int)prior, FXJPS_MAX_PRIOR_MAPS - 1);
+    if (occ && (W < 1 || H < 1 || W > 8190 || H > 8190)) return fail(h, FXJPS_E_ARG, "a prior map must be 1..8190 cells a side");
+    if (int rr = refuse_on_rank_handle(h, "fxjps_set_prior_map")) return rr;
+    // every context gets its own copy from the host, as a slot does; no slot, generation or stored result is touched
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int {
+        DevCtx& d = h->devs[r];
+        HIPCHK(h, hipSetDevice(d.dev));
+        if (d.priors.empty()) d.priors.resize(FXJPS_MAX_PRIOR_MAPS);
+        DevCtx::PriorBuf& pr = d.priors[(size_t)prior];
+        HIPCHK(h, hipStreamSynchronize(d.stream));  // (whatever is queued may still read the prior's bytes)
+        pr.W = pr.H = 0;
+        if (!occ) {
+            pr.occ.release();
+            return FXJPS_OK;
+        }
+        HIPCHK(h, pr.occ.ensure((size_t)W * H));
+        HIPCHK(h, hipMemcpyAsync(pr.occ.p, occ, (size_t)W * H, hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+        pr.W = W;
+        pr.H = H;
+        return FXJPS_OK;
+    });
+    if (rc) {
+        drain_all(h);
+        for (auto& d : h->devs)  // (a prior that failed on one context is released on all of them)
+            if ((size_t)prior < d.priors.size()) {
+                if (hipSetDevice(d.dev) == hipSuccess) d.priors[(size_t)prior].occ.release();
+                d.priors[(size_t)prior].W = d.priors[(size_t)prior].H = 0;
+            }
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+int fxjps_get_prior_map(fxjps_t* h, int32_t prior, uint8_t* out, int32_t* W, int32_t* H) {
+    if (!h) return FXJPS_E_ARG;
+    DevCtx& d = h->devs[0];
+    if (prior < 0 || prior >= FXJPS_MAX_PRIOR_MAPS || (size_t)prior >= d.priors.size() || d.priors[(size_t)prior].W <= 0)
+        return fail(h, FXJPS_E_ARG, "prior %d is not set or out of range", (int)prior);
+    const DevCtx::PriorBuf& pr = d.priors[(size_t)prior];
+    if (W) *W = pr.W;
+    if (H) *H = pr.H;
+    if (out) {
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, hipMemcpyAsync(out, pr.occ.p, (size_t)pr.W * pr.H, hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+    }
+    return FXJPS_OK;
+}
+
+namespace {
+// numpy's .astype(int) / Python's int() of a float64 quotient, for quotients whose truncation is an int32
+bool trunc_i32(double q, long long& out) {
+    if (!(q > -2147483649.0 && q < 2147483648.0)) return false;  // (NaN fails both)
+    out = (long long)q;
+    return true;
+}
+
+// The conversion in front of slots_call: the reference's lines between the map callback and the preparation
+// (global_planner_st.py:210-227 / global_planner_ccst.py:395-412), in float64 with the reference's operations in the
+// reference's order (the library is built with -ffp-contract=off).  Each world job becomes the fxjps_slot_job_t whose raw is
+// the canvas -- which only the gather ever sees, through WorldSrc -- and slots_call does the rest.
+int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what) {
+    if (!h) return FXJPS_E_ARG;
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
+    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    std::vector<fxjps_slot_job_t> sj((size_t)n);
+    std::vector<WorldSrc> src((size_t)n);
+    std::vector<double> co((size_t)n * 2);
+    const DevCtx& d0 = h->devs[0];
+    for (int j = 0; j < n; j++) {
+        const fxjps_world_job_t& wj = jobs[j];
+        if (!wj.raw) return fail(h, FXJPS_E_ARG, "job %d: NULL raw", j);
+        if (wj.W0 < 1 || wj.H0 < 1 || wj.W0 > 8190 || wj.H0 > 8190)
+            return fail(h, FXJPS_E_ARG, "job %d: bad arguments (W0 %d, H0 %d): the detected map must be 1..8190 cells a side", j, (int)wj.W0, (int)wj.H0);
+        if (wj.prior < -1 || wj.prior >= FXJPS_MAX_PRIOR_MAPS)
+            return fail(h, FXJPS_E_ARG, "job %d: prior %d is not in -1 .. %d", j, (int)wj.prior, FXJPS_MAX_PRIOR_MAPS - 1);
+        const bool with_prior = wj.prior >= 0;
+        if (with_prior && ((size_t)wj.prior >= d0.priors.size() || d0.priors[(size_t)wj.prior].W <= 0))
+            return fail(h, FXJPS_E_ARG, "job %d: prior %d is not set", j, (int)wj.prior);
+        const double reso = wj.map_reso;
+        if (!std::isfinite(reso) || !(reso > 0.0)) return fail(h, FXJPS_E_ARG, "job %d: map_reso %g must be finite and > 0", j, reso);
+        for (int k = 0; k < 2; k++)
+            if (!std::isfinite(wj.map_o[k]) || !std::isfinite(wj.pos_xy[k]) || !std::isfinite(wj.goal_xy[k]) ||
+                (with_prior && (!std::isfinite(wj.map_t[k]) || !std::isfinite(wj.ori_pre[k]))))
+                return fail(h, FXJPS_E_ARG, "job %d: a non-finite map_o / map_t / pos_xy / goal_xy / ori_pre", j);
+        WorldSrc& w = src[(size_t)j];
+        w = WorldSrc{wj.prior, wj.W0, wj.H0, 0, 0, 0, 0};
+        long long canvas[2] = {wj.W0, wj.H0};
+        double* o = &co[(size_t)j * 2];
+        o[0] = wj.map_o[0];
+        o[1] = wj.map_o[1];
+        if (with_prior) {
+            const DevCtx::PriorBuf& pr = d0.priors[(size_t)wj.prior];
+            const long long l[2] = {pr.W, pr.H}, rl[2] = {wj.W0, wj.H0};
+            long long rpos[2], ppos[2];
+            for (int k = 0; k < 2; k++) {
+                const double t_pre = wj.ori_pre[k] + reso * (double)l[k];          // st:187
+                o[k] = std::min(wj.map_o[k], wj.ori_pre[k]);                       // st:212 (the first of two equal ones, as min())
+                const double top = std::max(t_pre, wj.map_t[k]);                   // st:215-216 (likewise)
+                if (!trunc_i32((wj.map_o[k] - o[k]) / reso, rpos[k]) || !trunc_i32((wj.ori_pre[k] - o[k]) / reso, ppos[k]) ||
+                    !trunc_i32((top - o[k]) / reso, canvas[k]))
+                    return fail(h, FXJPS_E_ARG, "job %d: a placement index or a canvas extent is outside int32", j);
+                // the reference's slice assignment raises here (st:219-220); where a side of 1 clipped to 0 would broadcast,
+                // the library refuses all the same
+                if (canvas[k] < 1 || rpos[k] < 0 || ppos[k] < 0 || rpos[k] + rl[k] > canvas[k] || ppos[k] + l[k] > canvas[k])
+                    return fail(h, FXJPS_E_ARG, "job %d: axis %d: the detected map (%lld + %lld) or the prior (%lld + %lld) sticks out of the canvas of %lld cells",
+                                j, k, rpos[k], rl[k], ppos[k], l[k], canvas[k]);
+            }
+            w.rx = (int)rpos[0];
+            w.ry = (int)rpos[1];
+            w.px = (int)ppos[0];
+            w.py = (int)ppos[1];
+        }
+        long long sc[2], gc[2];
+        for (int k = 0; k < 2; k++)  // st:226-227
+            if (!trunc_i32((wj.goal_xy[k] - o[k]) / reso, gc[k]) || !trunc_i32((wj.pos_xy[k] - o[k]) / reso, sc[k]))
+                return fail(h, FXJPS_E_ARG, "job %d: a start or goal cell is outside int32", j);
+        fxjps_slot_job_t& s = sj[(size_t)j];
+        s = fxjps_slot_job_t{};
+        s.raw = wj.raw;
+        s.slot = wj.slot;
+        s.layout = wj.layout;
+        s.W0 = (int32_t)canvas[0];
+        s.H0 = (int32_t)canvas[1];
+        s.ifa = wj.ifa;
+        s.variant = wj.variant;
+        s.start_xy[0] = (int32_t)sc[0];
+        s.start_xy[1] = (int32_t)sc[1];
+        s.goal_xy[0] = (int32_t)gc[0];
+        s.goal_xy[1] = (int32_t)gc[1];
+    }
+    int rc = slots_call(h, sj.data(), n, refresh, out_kept, what, src.data());
+    if (rc) return rc;
+    for (int j = 0; j < n; j++) {
+        fxjps_world_job_t& wj = jobs[j];
+        const fxjps_slot_job_t& s = sj[(size_t)j];
+        for (int k = 0; k < 2; k++) {
+            wj.start_xy[k] = s.start_xy[k];
+            wj.goal_xy_cell[k] = s.goal_xy[k];
+            wj.map_d[k] = s.map_d[k];
+            wj.canvas_o[k] = co[(size_t)j * 2 + k];
+            wj.origin[k] = (double)(-(long long)s.map_d[k]) * wj.map_reso + wj.canvas_o[k];  // st:236: map_o2 * map_reso + map_o
+        }
+        wj.W = s.W;
+        wj.H = s.H;
+        wj.end_occu = s.end_occu;
+        wj.status = s.status;
+        wj.canvas_W = s.W0;
+        wj.canvas_H = s.H0;
+    }
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_prepare_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n) { return world_call(h, jobs, n, false, nullptr, "fxjps_prepare_slots_world"); }
+
+int fxjps_refresh_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept) {
+    return world_call(h, jobs, n, true, out_kept, "fxjps_refresh_slots_world");
 }
 
 // ------------------------------------------------------------------ many slots' maps published, one call

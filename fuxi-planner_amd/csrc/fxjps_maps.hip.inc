@@ -920,6 +920,68 @@ __global__ __launch_bounds__(256) void k_refresh_derive_jd(const SlotTable* __re
     slots_derive_jd_block(T, j);
 }
 
+// ---- The same two calls from world-frame jobs (fxjps_prepare_slots_world / fxjps_refresh_slots_world, DESIGN.md section
+// 3.14).  The raw map of such a job is a CANVAS that nobody assembles: the detected map pasted over a prior map that lives
+// on the device (global_planner_st.py:210-225 / global_planner_ccst.py:395-409).  SlotJobDev stays as it is, W0 / H0 being
+// the canvas extents; a WorldSrcDev per job, staged behind the raws, says where the two sources lie in the canvas.  The
+// gather reads a canvas cell from the detected map inside its rectangle (it overwrites: a free detected cell clears an
+// occupied prior cell), else from the prior inside the prior's rectangle, else it is 0.  Block mapping, compare-while-gather
+// and the `changed` word are those of k_prepare_slots / k_refresh_slots; every later launch is the existing one.
+struct WorldSrcDev {
+    const uint8_t* prior;  // [pW][pH] non-zero = occupied, resident on this context; nullptr: the job has no prior
+    int32_t pW, pH, px, py;  // the prior's extents and where its cell (0, 0) lies in the canvas
+    int32_t rW, rH, rx, ry;  // the detected map's (SlotJobDev::raw, SlotJobDev::layout)
+};
+__device__ __forceinline__ uint8_t world_prepared_byte(const uint8_t* __restrict__ raw, const WorldSrcDev& S, int W0, int H0, int dx, int dy, int ifa,
+                                                       int variant, int msg_layout, int H1, long long i) {
+    const int x = (int)(i / H1), y = (int)(i % H1);
+    const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
+    const uint8_t* __restrict__ prior = S.prior;
+    const int pW = S.pW, pH = S.pH, px = S.px, py = S.py, rW = S.rW, rH = S.rH, rx = S.rx, ry = S.ry;
+    uint8_t v = 0;
+    for (int a = -ifa; a <= ifa; a += step)
+        for (int b = -ifa; b <= ifa; b += step) {
+            const int sx = x - dx - a, sy = y - dy - b;
+            if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
+                const int ux = sx - rx, uy = sy - ry, qx = sx - px, qy = sy - py;
+                bool o = false;
+                if (ux >= 0 && uy >= 0 && ux < rW && uy < rH)
+                    o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)uy * rW + ux] > 0) : (raw[(size_t)ux * rH + uy] != 0);
+                else if (qx >= 0 && qy >= 0 && qx < pW && qy < pH)  // (pW == 0 without a prior)
+                    o = prior[(size_t)qx * pH + qy] != 0;
+                if (o) v = 1;
+            }
+        }
+    return v;
+}
+__global__ __launch_bounds__(256) void k_prepare_world(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const uint8_t* __restrict__ raw = J.raw;
+    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
+    if (i >= (long long)W1 * H1) return;
+    J.occ[i] = world_prepared_byte(raw, S[j], W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
+}
+__global__ __launch_bounds__(256) void k_refresh_world(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
+                                                      uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const uint8_t* __restrict__ raw = J.raw;
+    uint8_t* __restrict__ occ = J.occ;
+    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
+    const bool inside = i < (long long)W1 * H1;
+    const uint8_t v = inside ? world_prepared_byte(raw, S[j], W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
+    if (!J.compare) {  // (block-uniform, as in k_refresh_slots)
+        if (inside) occ[i] = v;
+        return;
+    }
+    const bool differs = inside && occ[i] != v;
+    if (differs) occ[i] = v;
+    if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+}
+
 // Wire / on-disk adapters (SURVEY.md 8f, N3): one tiled byte transpose with a value map.
 //   dst[(fb ? B-1-b : b)][(fa ? A-1-a : a)][0..ch) = map(src[a][b])      src [A][B], dst [B][A][ch]
 // TM_OCC_TO_MSG   grid -> nav_msgs/OccupancyGrid data[] (global_planner_st.py:103,115: 1 -> 100, data.T)

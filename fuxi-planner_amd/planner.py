@@ -366,6 +366,109 @@ class Planner(object):
         return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy[0], j.goal_xy[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
                  j.status == 0) for j in arr[:n]]
 
+    # -- world-frame ticks: a prior map on the device, positions instead of cells (fxjps_prepare_slots_world)
+    def set_prior_map(self, prior, matrix):
+        """Upload `matrix` ([x][y], > 0 = occupied: a map known before the flight, st:176-187) as prior map `prior`
+        (0 .. _lib.MAX_PRIOR_MAPS - 1).  Once per flight; no slot and not the resident grid is touched."""
+        occ = np.ascontiguousarray(np.asarray(matrix) > 0, dtype=np.uint8)
+        if occ.ndim != 2:
+            raise ValueError("a prior map must be 2-D")
+        self._chk(self._L.fxjps_set_prior_map(self._h, int(prior), _lib.ptr(occ, C.c_uint8), occ.shape[0], occ.shape[1]))
+
+    def set_prior_image(self, prior, gray):
+        """set_prior_map from a decoded 8-bit grey image (rows x cols) with the loader convention of
+        global_planner_st.py:179-182: > 200 free, else occupied, map = img[::-1].T."""
+        from . import worldprep
+        self.set_prior_map(prior, worldprep.prior_from_image(gray))
+
+    def get_prior_map(self, prior):
+        """The uint8 [W][H] bytes of prior map `prior` (non-zero = occupied)."""
+        W, H = C.c_int32(), C.c_int32()
+        self._chk(self._L.fxjps_get_prior_map(self._h, int(prior), None, C.byref(W), C.byref(H)))
+        out = np.empty((W.value, H.value), dtype=np.uint8)
+        self._chk(self._L.fxjps_get_prior_map(self._h, int(prior), _lib.ptr(out, C.c_uint8), None, None))
+        return out
+
+    def clear_prior_map(self, prior):
+        """Release prior map `prior` (a world job that names it is refused)."""
+        self._chk(self._L.fxjps_set_prior_map(self._h, int(prior), None, 0, 0))
+
+    def prepare_slots_world(self, jobs):
+        """prepare_slots from what a node holds at the top of its tick (fxjps_prepare_slots_world): the prior-map merge
+        (st:210-225 / ccst:395-409) and the world -> cell conversion (st:226-227) happen in the call, the prior stays on the
+        device and only the detected map is staged.  A job is (slot, raw or (data, width, height), map_o, map_reso, pos_xy,
+        goal_xy, ifa, variant[, prior=None[, ori_pre=(-15, -15)[, map_t=None]]]); map_t None: map_o + extent * map_reso
+        (st:24).  -> per job prepare_slots' tuple followed by origin (the origin after the padding, st:236),
+        canvas_shape and canvas_o (the merged origin).  worldprep.merge_host is the same conversion on the host."""
+        jobs = list(jobs)
+        arr, keep = self._world_jobs(jobs)
+        self._chk(self._L.fxjps_prepare_slots_world(self._h, arr, len(jobs)))
+        del keep
+        return [o + w for o, w in zip(self._slot_outs_world(arr, len(jobs)), self._world_outs(arr, len(jobs)))]
+
+    def refresh_slots_world(self, jobs):
+        """refresh_slots from world-frame jobs (fxjps_refresh_slots_world): -> per job refresh_slots' tuple (kept last)
+        followed by origin, canvas_shape, canvas_o."""
+        jobs = list(jobs)
+        arr, keep = self._world_jobs(jobs)
+        n = len(jobs)
+        kept = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.fxjps_refresh_slots_world(self._h, arr, n, _lib.ptr(kept, C.c_int32)))
+        del keep
+        return [o + (bool(k),) + w for o, k, w in zip(self._slot_outs_world(arr, n), kept[:n], self._world_outs(arr, n))]
+
+    @staticmethod
+    def _world_jobs(jobs):
+        """-> the fxjps_world_job_t array of prepare_slots_world's jobs, and the raws it points into."""
+        from . import worldprep
+        arr = (_lib.WorldJob * max(len(jobs), 1))()
+        keep = []
+        for j, job in zip(arr, jobs):
+            slot, raw, map_o, map_reso, pos_xy, goal_xy, ifa, variant = job[:8]
+            prior, ori_pre, map_t = (tuple(job[8:]) + (None, (-15, -15), None)[len(job) - 8:])[:3]
+            if isinstance(raw, tuple):
+                data, width, height = raw
+                a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+                if a.size != width * height:
+                    raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+                j.layout, j.W0, j.H0 = 1, int(width), int(height)
+            else:
+                a = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
+                if a.ndim != 2:
+                    raise ValueError("grid must be 2-D")
+                j.layout, j.W0, j.H0 = 0, a.shape[0], a.shape[1]
+            keep.append(a)
+            j.raw = a.ctypes.data
+            j.slot, j.ifa = int(slot), int(ifa)
+            j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+            j.prior = -1 if prior is None else int(prior)
+            j.map_reso = float(map_reso)
+            if map_t is None:
+                map_t = worldprep.map_top(map_o, (j.W0, j.H0), map_reso)
+            for k in range(2):
+                j.map_o[k], j.map_t[k], j.pos_xy[k] = float(map_o[k]), float(map_t[k]), float(pos_xy[k])
+                j.goal_xy[k], j.ori_pre[k] = float(goal_xy[k]), float(ori_pre[k])
+        return arr, keep
+
+    @staticmethod
+    def _slot_outs_world(arr, n):
+        return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy_cell[0], j.goal_xy_cell[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
+                 j.status == 0) for j in arr[:n]]
+
+    @staticmethod
+    def _world_outs(arr, n):
+        return [([j.origin[0], j.origin[1]], (j.canvas_W, j.canvas_H), [j.canvas_o[0], j.canvas_o[1]]) for j in arr[:n]]
+
+    def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
+                         reuse=False):
+        """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
+        prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
+        job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
+        (reuse=True plans through replan_slots)."""
+        jobs = list(jobs)
+        return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
+                                image_channels, reuse, world=True)
+
     def publish_slots(self, slots, msg=True, image_channels=None):
         """The fleet's publishing quarter of a tick in ONE call (fxjps_publish_slots): for every slot named what publish_map
         and / or snapshot_image would return were it the resident grid.  msg (bool) and image_channels (None, 1 or 3) are
@@ -416,7 +519,8 @@ class Planner(object):
         further key, reused (bool).  Every other value is what reuse=False gives."""
         return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse)
 
-    def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False):
+    def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
+                    world=False):
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -424,23 +528,27 @@ class Planner(object):
         goals = np.asarray(global_goals, dtype=np.float64).reshape(n, 3)
         home = np.broadcast_to(np.asarray(home, dtype=np.float64), (n, 2))
         reso = np.broadcast_to(np.asarray(map_reso, dtype=np.float64), (n,))
-        orig = np.broadcast_to(np.asarray(map_o, dtype=np.float64), (n, 2))
+        orig = None if world else np.broadcast_to(np.asarray(map_o, dtype=np.float64), (n, 2))
         keys = ("status", "cost", "start", "goal", "map_d", "shape", "end_occu", "origin", "wp", "dim", "goal_out", "ang_wp", "n_kept", "point",
                 "path", "dir_path", "dir_back", "msg", "image")
         recs = [dict({"ok": False}, **{k: None for k in keys}) for _ in range(n)]
-        outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
+        if world:  # (the call's own origin, canvas_shape and canvas_o lie behind the existing tuple)
+            outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
+        else:
+            outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
+        variant_at = 7 if world else 5
         live = [v for v in range(n) if outs[v][5]]
         if not live:
             return recs
         slots = [int(jobs[v][0]) for v in live]
         offsets, _, cost, status, reused = self._plan_slots(reuse, slots, [outs[v][0] for v in live], [outs[v][1] for v in live], 2, None)
-        origin = [Planner.shifted_origin(orig[v], outs[v][2], reso[v]) for v in live]
+        origin = [outs[v][-3] if world else Planner.shifted_origin(orig[v], outs[v][2], reso[v]) for v in live]
         pw = pd = None
         if prev_wp is not None:
             pw = np.asarray(prev_wp, dtype=np.float64).reshape(n, 3)[live]
             pd = np.asarray(prev_dim, dtype=np.int32).reshape(n)[live]
         wp, dim, gout, ang, nk, point, paths, dirs, back = waypoints.tick_outputs_slots(
-            self, [jobs[v][5] for v in live], [outs[v][0] for v in live], reso[live], origin, pos[live], goals[live], home[live],
+            self, [jobs[v][variant_at] for v in live], [outs[v][0] for v in live], reso[live], origin, pos[live], goals[live], home[live],
             [outs[v][4] for v in live], pw, pd, offsets=offsets)
         pub = self.publish_slots(slots, msg=publish, image_channels=image_channels) if (publish or image_channels is not None) else None
         for i, v in enumerate(live):

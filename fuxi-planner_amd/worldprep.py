@@ -1,0 +1,98 @@
+"""What each planner node does between the map callback and the grid preparation, per vehicle, in plain numpy: the
+prior-map merge (global_planner_st.py:210-225 / global_planner_ccst.py:395-409) and the world -> cell conversion
+(st:226-227 / ccst:411-412).
+
+This is the host form of Planner.prepare_slots_world for callers without a device, and what the tests compare the device
+against: the same float64 operations in the same order, truncation toward zero where the reference's .astype(int) /
+int() truncate, and a ValueError where the library refuses.  Pinned by tests/golden/worldprep.json, whose expected
+values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).
+"""
+import math
+
+import numpy as np
+
+I32_LO, I32_HI = -2147483649.0, 2147483648.0  # a quotient strictly between them truncates to an int32
+
+
+def matrix_from_msg(data, width, height):
+    """The matrix map_callback (st:15-20) makes of a nav_msgs/OccupancyGrid: [x][y], 100 -> 1, -1 -> 0."""
+    a = np.asarray(data, dtype=np.int8).reshape(-1)
+    if a.size != width * height:
+        raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+    m = a.reshape(height, width).T.copy()
+    m[m == 100] = 1
+    m[m == -1] = 0
+    return m
+
+
+def prior_from_image(gray):
+    """The loader convention of st:179-182 on a decoded 8-bit grey image (rows x cols): > 200 free, else occupied, the
+    map is img[::-1].T.  -> uint8 [cols][rows]."""
+    gray = np.asarray(gray, dtype=np.uint8)
+    if gray.ndim != 2:
+        raise ValueError("image must be 2-D (convert('L'))")
+    return np.ascontiguousarray(np.where(gray > 200, 0, 1).astype(np.uint8)[::-1].T)
+
+
+def map_top(map_o, extent, map_reso):
+    """self.map_t as map_callback computes it (st:24)."""
+    return [float(map_o[0]) + int(extent[0]) * float(map_reso), float(map_o[1]) + int(extent[1]) * float(map_reso)]
+
+
+def _trunc(q, what):
+    if not (I32_LO < q < I32_HI):  # (NaN and the infinities fail)
+        raise ValueError("%s: the quotient %r does not truncate to an int32" % (what, q))
+    return int(q)
+
+
+def _pair(v, what):
+    a, b = float(v[0]), float(v[1])
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError("%s is not finite" % what)
+    return [a, b]
+
+
+def merge_host(raw, map_o, map_reso, pos_xy, goal_xy, prior=None, ori_pre=(-15, -15), map_t=None):
+    """raw: the detected map, a matrix [x][y] (> 0 = occupied) or (data, width, height) of an OccupancyGrid; prior: the
+    prior map as a matrix [x][y] (> 0 = occupied) at world origin ori_pre, or None; map_t None: map_o + extent * map_reso.
+    -> (canvas uint8 [W][H] of 0 / 1, (W, H), canvas_o [x, y], start (x, y), goal (x, y)): the merged map, its origin and
+    the vehicle's and the goal's cell in it -- what Planner.prepare_slots / oracle-style preparation take as raw, start
+    and goal.  The detected map OVERWRITES the prior (a free detected cell clears an occupied prior cell)."""
+    m = matrix_from_msg(*raw) if isinstance(raw, tuple) else np.asarray(raw)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError("the detected map must be 2-D and not empty")
+    ext = [int(m.shape[0]), int(m.shape[1])]
+    reso = float(map_reso)
+    if not (math.isfinite(reso) and reso > 0.0):
+        raise ValueError("map_reso %r must be finite and > 0" % (map_reso,))
+    o = _pair(map_o, "map_o")
+    pos = _pair(pos_xy, "pos_xy")
+    goal = _pair(goal_xy, "goal_xy")
+    canvas = np.ascontiguousarray(m > 0, dtype=np.uint8)
+    if prior is not None:
+        pre = np.asarray(prior)
+        if pre.ndim != 2 or pre.shape[0] < 1 or pre.shape[1] < 1:
+            raise ValueError("the prior map must be 2-D and not empty")
+        op = _pair(ori_pre, "ori_pre")
+        top = _pair(map_t, "map_t") if map_t is not None else map_top(o, ext, reso)
+        if not (math.isfinite(top[0]) and math.isfinite(top[1])):
+            raise ValueError("map_t is not finite")
+        o1, at_raw, at_pre, size = [0.0, 0.0], [0, 0], [0, 0], [0, 0]
+        for k in range(2):
+            t_pre = op[k] + reso * int(pre.shape[k])            # st:187
+            o1[k] = min(o[k], op[k])                            # st:212
+            at_raw[k] = _trunc((o[k] - o1[k]) / reso, "the detected map's index")   # st:213
+            at_pre[k] = _trunc((op[k] - o1[k]) / reso, "the prior's index")         # st:214
+            size[k] = _trunc((max(t_pre, top[k]) - o1[k]) / reso, "the canvas extent")  # st:215-216
+            # the reference's slice assignment raises when a rectangle is clipped (st:219-220); a side of 1 clipped to 0
+            # would broadcast there: refused here as well, like the library
+            if size[k] < 1 or at_raw[k] < 0 or at_pre[k] < 0 or at_raw[k] + ext[k] > size[k] or at_pre[k] + int(pre.shape[k]) > size[k]:
+                raise ValueError("axis %d: the detected map (%d + %d) or the prior (%d + %d) sticks out of the canvas of %d cells"
+                                 % (k, at_raw[k], ext[k], at_pre[k], pre.shape[k], size[k]))
+        merged = np.zeros(size, dtype=np.uint8)
+        merged[at_pre[0]:at_pre[0] + pre.shape[0], at_pre[1]:at_pre[1] + pre.shape[1]] = pre > 0
+        merged[at_raw[0]:at_raw[0] + ext[0], at_raw[1]:at_raw[1] + ext[1]] = canvas
+        canvas, o = merged, o1
+    g = tuple(_trunc((goal[k] - o[k]) / reso, "the goal's cell") for k in range(2))   # st:226
+    s = tuple(_trunc((pos[k] - o[k]) / reso, "the start's cell") for k in range(2))   # st:227
+    return canvas, (int(canvas.shape[0]), int(canvas.shape[1])), o, s, g

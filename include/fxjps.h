@@ -89,8 +89,11 @@ typedef struct fxjps fxjps_t;
  *        byte for byte what its slot holds keeps the slot's maps and runs no build work), fxjps_debug_read_slot_context.
  *   770  fxjps_replan_slots (fxjps_plan_batch_slots_csr for the tick after: a query whose slot, start and goal did not
  *        change since the previous such call hands back its stored path without a search).
+ *   780  fxjps_prepare_slots_world, fxjps_refresh_slots_world (the two calls from world-frame jobs: the detected map is
+ *        merged over a prior map that lives on the device, positions become cells, in the same launches),
+ *        fxjps_set_prior_map, fxjps_get_prior_map, fxjps_world_job_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 770
+#define FXJPS_VERSION 780
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -311,6 +314,61 @@ int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was bu
  * on every context against that context's own copy; out_kept reports context 0's.  out_kept may be NULL; it is not
  * written when the call is refused (nor for n = 0). */
 int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept);
+/* ---- The same two calls from world-frame jobs (version 780): what each node does in front of the preparation on every
+ * tick (global_planner_st.py:210-227 / global_planner_ccst.py:395-412) moves into the call.
+ *   Prior maps: a map known before the flight (st:176-187), uploaded once and held on every context like a slot (host
+ * copies, no collective).  occ is [W][H], non-zero = occupied, 1..8190 a side; occ == NULL releases the prior.  Setting or
+ * releasing a prior touches no slot, no slot generation, no stored result and not the resident grid.  A rank handle
+ * (fxjps_create_rank, world > 1) refuses.  fxjps_get_prior_map: out == NULL returns the extents only; FXJPS_E_ARG for a
+ * prior that is not set. */
+#define FXJPS_MAX_PRIOR_MAPS 16
+int fxjps_set_prior_map(fxjps_t* h, int32_t prior, const uint8_t* occ, int32_t W, int32_t H);
+int fxjps_get_prior_map(fxjps_t* h, int32_t prior, uint8_t* out, int32_t* W, int32_t* H);
+/*   The job.  With a prior of l1 x l2 cells the raw map of fxjps_prepare_slots is replaced by a CANVAS, computed with the
+ * reference's float64 operations in the reference's order, truncating toward zero where .astype(int) / int() do:
+ *     t_pre   = ori_pre + map_reso * l                      (st:187)
+ *     map_o1  = min(map_o, ori_pre) per axis                (st:212)   -> canvas_o
+ *     the detected map lies at ((map_o - map_o1) / map_reso), the prior at ((ori_pre - map_o1) / map_reso)   (st:213-214)
+ *     canvas_W / canvas_H = int((max(t_pre, map_t) - map_o1) / map_reso)                                     (st:215-216)
+ * and a canvas cell is the detected cell inside the detected rectangle (it overwrites: a free detected cell clears an
+ * occupied prior cell), else the prior's cell inside the prior's rectangle, else 0 (st:217-220).  Without a prior
+ * (prior = -1) the canvas is the raw map and canvas_o = map_o.  start and goal cells are ((xy - canvas_o) / map_reso)
+ * truncated (st:226-227); from there on the job is a fxjps_slot_job_t whose raw is the canvas.  The canvas is never
+ * assembled: the prepare launch gathers from two sources, and only the detected map is staged.
+ *   Whole-call refusals besides those of fxjps_prepare_slots: a prior id outside -1 .. FXJPS_MAX_PRIOR_MAPS - 1 or not set;
+ * a non-finite map_o / map_t / pos_xy / goal_xy / ori_pre; map_reso not finite or <= 0; a truncated quotient outside
+ * int32; either rectangle not lying wholly inside the canvas.  The reference's slice assignment raises in the last case,
+ * except where a side of 1 is clipped to 0 and numpy's broadcasting lets it go on: the library refuses there too (a stated
+ * deviation).  Slot generations, out_kept, the 2^18 rule, several contexts and the failed-job outcome are those of the
+ * existing two calls; so are the launches, copies and host waits. */
+typedef struct fxjps_world_job {
+    const void* raw;       /* in: the detected map, as fxjps_slot_job_t::raw */
+    int32_t slot;          /* in */
+    int32_t layout;        /* in: 0 / 1 */
+    int32_t W0, H0;        /* in: extents of the detected map (map_c, map_r) */
+    int32_t ifa;           /* in: 0 .. 64 */
+    int32_t variant;       /* in: 0 st, 1 ccst */
+    int32_t prior;         /* in: 0 .. FXJPS_MAX_PRIOR_MAPS - 1, or -1: none */
+    int32_t status;        /* out: as fxjps_slot_job_t::status */
+    double map_o[2];       /* in: the node's self.map_o */
+    double map_t[2];       /* in: self.map_t (st:24); read only with a prior */
+    double map_reso;       /* in: self.map_reso */
+    double pos_xy[2];      /* in: the vehicle's position, world */
+    double goal_xy[2];     /* in: the goal, world */
+    double ori_pre[2];     /* in: the prior's world origin; read only with a prior */
+    double canvas_o[2];    /* out: map_o1, or map_o without a prior */
+    double origin[2];      /* out: the origin after the padding (st:236 / ccst:421): -map_d * map_reso + canvas_o */
+    int32_t start_xy[2];   /* out: the start cell in the prepared grid */
+    int32_t goal_xy_cell[2]; /* out: the goal cell in the prepared grid, moved off an obstacle */
+    int32_t W, H;          /* out: extents of the prepared grid */
+    int32_t map_d[2];      /* out: the low-side padding */
+    int32_t end_occu;      /* out */
+    int32_t canvas_W, canvas_H; /* out */
+    int32_t reserved_;     /* (keeps the size a multiple of 8 on every ABI) */
+} fxjps_world_job_t;
+int fxjps_prepare_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n);
+int fxjps_refresh_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept);
+int fxjps_world_job_size(void); /* sizeof(fxjps_world_job_t) as the library was built (cf. fxjps_slot_job_size) */
 /* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
  * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
  * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
