@@ -184,7 +184,7 @@ struct DevCtx : GridBufs {
     DBuf<GridDev> d_slot_desc;
     DBuf<int32_t> d_grid_ids;
     // fxjps_prepare_slots / fxjps_refresh_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw
-    // maps | a world-frame call's fx::WorldSrcDev records | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal / k_refresh_goal
+    // maps | a world-frame call's fx::WorldSrcDev records | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal
     HBuf<uint8_t> h_slots_in;
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
@@ -1852,6 +1852,35 @@ int fxjps_set_grid_device(fxjps_t* h, const void* d_occ, int32_t W, int32_t H) {
     return finish_set_grid(h, W, H);
 }
 
+namespace {
+// What the host derives from a raw map's extents, the start and the goal before anything is queued: the padding, the
+// prepared extents and the shifted start and goal.  The callers judge the result (extents over 8190, a goal outside).
+struct SlotPlan {
+    long long dx, dy, W1, H1, nsx, nsy, ngx, ngy;
+    size_t raw_off;  // (fxjps_prepare_slots) of the job's raw map inside the staged input
+};
+SlotPlan prepared_geometry(long long W0, long long H0, long long ifa, int variant, const int32_t* start_xy, const int32_t* goal_xy) {
+    const long long sx = start_xy[0], sy = start_xy[1], gx = goal_xy[0], gy = goal_xy[1];
+    SlotPlan p{};
+    // global_planner_st.py:230-235 / global_planner_ccst.py:415-420
+    long long o2x = -2 * ifa, o2y = -2 * ifa;
+    if (gx < 0 || sx < 0) o2x += std::min(gx, sx);
+    if (gy < 0 || sy < 0) o2y += std::min(gy, sy);
+    p.dx = std::llabs(o2x);
+    p.dy = std::llabs(o2y);
+    // :246-247 / :431-432
+    p.W1 = std::max(std::max(W0, gx), sx) + p.dx + 4 * ifa;
+    p.H1 = std::max(std::max(H0, gy), sy) + p.dy + 4 * ifa;
+    // :266-267 (st: + map_d - 1) / :452-453 (ccst: + map_d)
+    const long long sh = variant == 0 ? 1 : 0;
+    p.nsx = sx + p.dx - sh;
+    p.nsy = sy + p.dy - sh;
+    p.ngx = gx + p.dx - sh;
+    p.ngy = gy + p.dy - sh;
+    return p;
+}
+}  // namespace
+
 static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
                              int msg_layout, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
                              int32_t* out_map_d, int32_t* out_end_occu) {
@@ -1859,15 +1888,9 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
     if (!raw || !start_xy || !goal_xy || W0 < 1 || H0 < 1 || ifa < 0 || ifa > 64 || (variant != 0 && variant != 1))
         return fail(h, FXJPS_E_ARG, "bad prepare_grid arguments");
     if (int rr = refuse_on_rank_handle(h, "fxjps_prepare_grid")) return rr;
-    const long long sx = start_xy[0], sy = start_xy[1], gx = goal_xy[0], gy = goal_xy[1];
-    // global_planner_st.py:230-235 / global_planner_ccst.py:415-420
-    long long o2x = -2ll * ifa, o2y = -2ll * ifa;
-    if (gx < 0 || sx < 0) o2x += std::min(gx, sx);
-    if (gy < 0 || sy < 0) o2y += std::min(gy, sy);
-    const long long dx = std::llabs(o2x), dy = std::llabs(o2y);
-    // :246-247 / :431-432
-    const long long W1 = std::max<long long>(std::max<long long>(W0, gx), sx) + dx + 4ll * ifa;
-    const long long H1 = std::max<long long>(std::max<long long>(H0, gy), sy) + dy + 4ll * ifa;
+    const SlotPlan p = prepared_geometry(W0, H0, ifa, variant, start_xy, goal_xy);
+    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1, nsx = p.nsx, nsy = p.nsy;
+    long long ngx = p.ngx, ngy = p.ngy;
     if (W1 > 8190 || H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", W1, H1);
     h->have_grid = false;
     h->q_results_valid = h->rs_valid = false;
@@ -1891,9 +1914,6 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
     }
     h->have_grid = true;
     h->maps_stale = false;
-    // :266-267 (st: + map_d - 1) / :452-453 (ccst: + map_d)
-    const long long sh = variant == 0 ? 1 : 0;
-    long long nsx = sx + dx - sh, nsy = sy + dy - sh, ngx = gx + dx - sh, ngy = gy + dy - sh;
     if (ngx < 0 || ngy < 0 || ngx >= W1 || ngy >= H1) return fail(h, FXJPS_E_ARG, "goal outside the prepared grid");
     // :268-272 / :454-458: a goal on an obstacle moves to the nearest free cell of its row, else of its column
     DevCtx& d0 = h->devs[0];
@@ -2326,6 +2346,27 @@ bool slot_in_use(fxjps_t* h, int32_t slot) {
     const DevCtx& d0 = h->devs[0];
     return slot >= 0 && slot < FXJPS_MAX_GRID_SLOTS && (size_t)slot < d0.slots.size() && d0.slots[(size_t)slot].W > 0;
 }
+// A context's slot tables, created by the first call that sets a slot (the context is current).
+int ensure_slot_tables(fxjps_t* h, DevCtx& d) {
+    if (d.slots.empty()) {
+        d.slots.resize(FXJPS_MAX_GRID_SLOTS);
+        d.h_slot_desc.assign(FXJPS_MAX_GRID_SLOTS, GridDev{});
+        HIPCHK(h, d.d_slot_desc.ensure(FXJPS_MAX_GRID_SLOTS));
+    }
+    return FXJPS_OK;
+}
+// A slot whose call failed on one context is released on all of them, and every context's descriptor says so.
+void release_slot_everywhere(fxjps_t* h, int32_t slot) {
+    const size_t s = (size_t)slot;
+    for (auto& d : h->devs) {
+        if (d.slots.empty()) continue;
+        const bool current = hipSetDevice(d.dev) == hipSuccess;
+        if (current) d.slots[s].release();
+        d.slots[s].W = 0;
+        d.h_slot_desc[s] = GridDev{};
+        if (current) (void)hipMemcpy(d.d_slot_desc.p + s, &d.h_slot_desc[s], sizeof(GridDev), hipMemcpyHostToDevice);
+    }
+}
 }  // namespace
 
 int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W, int32_t H) {
@@ -2339,11 +2380,7 @@ int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W,
     int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int {
         DevCtx& d = h->devs[r];
         HIPCHK(h, hipSetDevice(d.dev));
-        if (d.slots.empty()) {
-            d.slots.resize(FXJPS_MAX_GRID_SLOTS);
-            d.h_slot_desc.assign(FXJPS_MAX_GRID_SLOTS, GridDev{});
-            HIPCHK(h, d.d_slot_desc.ensure(FXJPS_MAX_GRID_SLOTS));
-        }
+        if (int e = ensure_slot_tables(h, d)) return e;
         GridBufs& g = d.slots[(size_t)slot];
         HIPCHK(h, hipStreamSynchronize(d.stream));  // (whatever is queued may still read the slot's buffers)
         if (!occ) {
@@ -2371,14 +2408,7 @@ int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W,
     });
     if (rc) {
         drain_all(h);
-        for (auto& d : h->devs)  // (a slot that failed on one context is released on all of them)
-            if ((size_t)slot < d.slots.size()) {
-                if (hipSetDevice(d.dev) == hipSuccess) d.slots[(size_t)slot].release();
-                d.slots[(size_t)slot].W = 0;
-                d.h_slot_desc[(size_t)slot] = GridDev{};
-                if (hipSetDevice(d.dev) == hipSuccess)
-                    (void)hipMemcpy(d.d_slot_desc.p + slot, &d.h_slot_desc[(size_t)slot], sizeof(GridDev), hipMemcpyHostToDevice);
-            }
+        release_slot_everywhere(h, slot);
         (void)hipGetLastError();
     }
     return rc;
@@ -2404,11 +2434,6 @@ int fxjps_slot_job_size(void) { return (int)sizeof(fxjps_slot_job_t); }
 
 namespace {
 static_assert(fx::SLOT_JOBS_MAX == FXJPS_MAX_GRID_SLOTS, "the job table of fxjps_prepare_slots holds one job per slot");
-// What the host derives from a job before anything is queued (prepare_grid_impl's arithmetic, with its line citations).
-struct SlotPlan {
-    long long dx, dy, W1, H1, nsx, nsy, ngx, ngy;
-    size_t raw_off;  // of its raw map inside the staged input
-};
 // A world-frame job's two sources, in canvas cells (fxjps_prepare_slots_world): the job handed to slots_call has the canvas
 // extents as W0 / H0 and the detected map as raw.
 struct WorldSrc {
@@ -2431,11 +2456,7 @@ constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GR
 int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh,
                      const WorldCall* world) {
     HIPCHK(h, hipSetDevice(d.dev));
-    if (d.slots.empty()) {
-        d.slots.resize(FXJPS_MAX_GRID_SLOTS);
-        d.h_slot_desc.assign(FXJPS_MAX_GRID_SLOTS, GridDev{});
-        HIPCHK(h, d.d_slot_desc.ensure(FXJPS_MAX_GRID_SLOTS));
-    }
+    if (int e = ensure_slot_tables(h, d)) return e;
     // (no host wait in front: every call of the library that reads a slot has returned; a buffer that grows is freed by
     // hipFree, which waits for the device itself)
     const size_t flags_off = in_bytes, n_res = (size_t)n * (fx::SLOT_RES + (refresh ? 1 : 0));
@@ -2513,33 +2534,24 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
     memcpy(d.h_slots_in.p + SLOTS_IN_DESC, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS);
     HIPCHK(h, hipMemcpyAsync(d.d_slots_in.p, d.h_slots_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
     const fx::SlotTable* dT = reinterpret_cast<const fx::SlotTable*>(d.d_slots_in.p);
-    if (refresh) {
-        if (world)
-            hipLaunchKernelGGL(fx::k_refresh_world, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT,
-                               reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off), n, d_changed);
-        else
-            hipLaunchKernelGGL(fx::k_refresh_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, d_changed);
-        hipLaunchKernelGGL(fx::k_refresh_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p, n, d_changed);
-        if (at[fx::SL_BUILD_1] > 0) {
-            hipLaunchKernelGGL(fx::k_refresh_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n, d_changed);
-            hipLaunchKernelGGL(fx::k_refresh_build_2, dim3(at[fx::SL_BUILD_2]), dim3(256), 0, d.stream, dT, n, d_changed);
-            hipLaunchKernelGGL(fx::k_refresh_build_3, dim3(at[fx::SL_BUILD_3]), dim3(1024), 0, d.stream, dT, n, d_changed);
-            hipLaunchKernelGGL(fx::k_refresh_derive_jd, dim3(at[fx::SL_JD]), dim3(256), 0, d.stream, dT, n, d_changed);
-        }
-    } else {
-        if (world)
-            hipLaunchKernelGGL(fx::k_prepare_world, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT,
-                               reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off), n);
-        else
-            hipLaunchKernelGGL(fx::k_prepare_slots, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n);
-        hipLaunchKernelGGL(fx::k_slots_goal, dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p);
-    }
-    if (!refresh && at[fx::SL_BUILD_1] > 0) {
-        hipLaunchKernelGGL(fx::k_slots_build_1, dim3(at[fx::SL_BUILD_1]), dim3(256), 0, d.stream, dT, n);
-        hipLaunchKernelGGL(fx::k_slots_build_2, dim3(at[fx::SL_BUILD_2]), dim3(256), 0, d.stream, dT, n);
-        hipLaunchKernelGGL(fx::k_slots_build_3, dim3(at[fx::SL_BUILD_3]), dim3(1024), 0, d.stream, dT, n);
-        hipLaunchKernelGGL(fx::k_slots_derive_jd, dim3(at[fx::SL_JD]), dim3(256), 0, d.stream, dT, n);
-    }
+    // the instantiation of each launch by (world, refresh); the forms that do not read the sources or the words get nullptr
+    using GatherFn = void (*)(const fx::SlotTable*, const fx::WorldSrcDev*, int, uint32_t*);
+    using GoalFn = void (*)(const fx::SlotTable*, int32_t*, int, const uint32_t*);
+    using StageFn = void (*)(const fx::SlotTable*, int, const uint32_t*);
+    static const GatherFn gather[2][2] = {{fx::k_slots_gather<false, false>, fx::k_slots_gather<false, true>},
+                                          {fx::k_slots_gather<true, false>, fx::k_slots_gather<true, true>}};
+    static const GoalFn goal[2] = {fx::k_slots_goal<false>, fx::k_slots_goal<true>};
+    static const StageFn stage[2][4] = {
+        {fx::k_slots_stage<fx::SL_BUILD_1, false>, fx::k_slots_stage<fx::SL_BUILD_2, false>, fx::k_slots_stage<fx::SL_BUILD_3, false>, fx::k_slots_stage<fx::SL_JD, false>},
+        {fx::k_slots_stage<fx::SL_BUILD_1, true>, fx::k_slots_stage<fx::SL_BUILD_2, true>, fx::k_slots_stage<fx::SL_BUILD_3, true>, fx::k_slots_stage<fx::SL_JD, true>}};
+    const fx::WorldSrcDev* dS = world ? reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off) : nullptr;
+    uint32_t* dC = refresh ? d_changed : nullptr;
+    hipLaunchKernelGGL(gather[world ? 1 : 0][refresh ? 1 : 0], dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, dS, n, dC);
+    hipLaunchKernelGGL(goal[refresh ? 1 : 0], dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p, n, (const uint32_t*)dC);
+    if (at[fx::SL_BUILD_1] > 0)
+        for (int l = fx::SL_BUILD_1; l <= fx::SL_JD; l++)
+            hipLaunchKernelGGL(stage[refresh ? 1 : 0][l - fx::SL_BUILD_1], dim3(at[l]), dim3(l == fx::SL_BUILD_3 ? 1024 : 256), 0, d.stream, dT, n,
+                               (const uint32_t*)dC);
     HIPCHK(h, hipGetLastError());
     if (any_large)  // (grids beyond the fused build: their maps one by one, as fxjps_set_grid_slot builds them)
         for (int j = 0; j < n; j++)
@@ -2583,24 +2595,9 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
         if (jb.W0 < 1 || jb.H0 < 1 || jb.ifa < 0 || jb.ifa > 64 || (jb.variant != 0 && jb.variant != 1) || (jb.layout != 0 && jb.layout != 1))
             return fail(h, FXJPS_E_ARG, "job %d: bad arguments (W0 %d, H0 %d, ifa %d, variant %d, layout %d)", j, (int)jb.W0, (int)jb.H0, (int)jb.ifa,
                         (int)jb.variant, (int)jb.layout);
-        const long long sx = jb.start_xy[0], sy = jb.start_xy[1], gx = jb.goal_xy[0], gy = jb.goal_xy[1], ifa = jb.ifa;
         SlotPlan& p = plan[(size_t)j];
-        // global_planner_st.py:230-235 / global_planner_ccst.py:415-420
-        long long o2x = -2 * ifa, o2y = -2 * ifa;
-        if (gx < 0 || sx < 0) o2x += std::min(gx, sx);
-        if (gy < 0 || sy < 0) o2y += std::min(gy, sy);
-        p.dx = std::llabs(o2x);
-        p.dy = std::llabs(o2y);
-        // :246-247 / :431-432
-        p.W1 = std::max<long long>(std::max<long long>(jb.W0, gx), sx) + p.dx + 4 * ifa;
-        p.H1 = std::max<long long>(std::max<long long>(jb.H0, gy), sy) + p.dy + 4 * ifa;
+        p = prepared_geometry(jb.W0, jb.H0, jb.ifa, jb.variant, jb.start_xy, jb.goal_xy);
         if (p.W1 > 8190 || p.H1 > 8190) return fail(h, FXJPS_E_ARG, "job %d: prepared grid %lldx%lld exceeds 8190 cells a side", j, p.W1, p.H1);
-        // :266-267 (st: + map_d - 1) / :452-453 (ccst: + map_d)
-        const long long sh = jb.variant == 0 ? 1 : 0;
-        p.nsx = sx + p.dx - sh;
-        p.nsy = sy + p.dy - sh;
-        p.ngx = gx + p.dx - sh;
-        p.ngy = gy + p.dy - sh;
         if (p.ngx < 0 || p.ngy < 0 || p.ngx >= p.W1 || p.ngy >= p.H1)
             return fail(h, FXJPS_E_ARG, "job %d: goal (%lld, %lld) outside the prepared grid %lldx%lld", j, p.ngx, p.ngy, p.W1, p.H1);
         p.raw_off = in_bytes;
@@ -2615,16 +2612,11 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
     int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world); });
     if (rc) {
         drain_all(h);
-        for (auto& d : h->devs)  // (slots of a call that failed on one context are released on all of them)
-            for (int j = 0; j < n && !d.slots.empty(); j++) {
-                const size_t s = (size_t)jobs[j].slot;
-                if (hipSetDevice(d.dev) == hipSuccess) d.slots[s].release();
-                d.slots[s].W = 0;
-                d.h_slot_desc[s] = GridDev{};
-                if (hipSetDevice(d.dev) == hipSuccess) (void)hipMemcpy(d.d_slot_desc.p + s, &d.h_slot_desc[s], sizeof(GridDev), hipMemcpyHostToDevice);
-            }
+        for (int j = 0; j < n; j++) {  // (slots of a call that failed on one context are released on all of them)
+            release_slot_everywhere(h, jobs[j].slot);
+            h->slot_gen[(size_t)jobs[j].slot]++;
+        }
         (void)hipGetLastError();
-        for (int j = 0; j < n; j++) h->slot_gen[(size_t)jobs[j].slot]++;  // (released)
         return rc;
     }
     const int32_t* res = h->devs[0].h_slots_res.p;  // (every context computed the same)

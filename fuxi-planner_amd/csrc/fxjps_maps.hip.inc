@@ -618,11 +618,14 @@ __global__ void k_ccl_flatten(long long n, int* __restrict__ lab) { ccl_flatten_
 // co-resident grid -- an agent-scope release / acquire between blocks on different XCDs writes back and invalidates their
 // L2s: 170 - 240 us per build whatever the barrier's form; and the eight launches as a HIP graph -- the runtime ran the
 // graph's two branches one after the other, with the same gaps.)
-__global__ __launch_bounds__(256) void k_build_1(const uint8_t* __restrict__ occ, GridDev G, uint8_t* __restrict__ nb8, BmWord* __restrict__ bm,
-                                                int* __restrict__ lab, unsigned nb_rows, unsigned nb_cols) {
+// One function per launch: block b of the launch's grid, for one grid.  k_build_1 .. 3 below call them for the handle's
+// grid, k_slots_stage (further down) for every job of a fleet call.  (No __restrict__ on their own parameters: the kernels'
+// and the item functions' qualifiers are the ones the compiler had before the bodies were shared, and with a third layer
+// of them k_build_2 came out with two more SGPRs than profiles/prepare_slots_resource_usage.json records.)
+__device__ __forceinline__ void build_1_block(const uint8_t* occ, const GridDev& G, uint8_t* nb8, BmWord* bm,
+                                              int* lab, unsigned nb_rows, unsigned nb_cols, unsigned b) {
     const int lane = (int)(threadIdx.x & 63);
     const MapRange rr{0, G.PW - 1, 0, G.WORDS - 1}, rc{0, G.PH - 1, 0, G.WORDS - 1};
-    unsigned b = blockIdx.x;
     if (b < nb_rows) {
         derive_rows_item(occ, G, nb8, bm, rr, (long long)b * 4 + (threadIdx.x >> 6), lane);
         return;
@@ -635,8 +638,8 @@ __global__ __launch_bounds__(256) void k_build_1(const uint8_t* __restrict__ occ
     b -= nb_cols;
     ccl_init_item(occ, (long long)G.W * G.H, G.H, lab, (long long)b * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_build_2(const uint8_t* __restrict__ occ, GridDev G, uint16_t* __restrict__ ci, int* __restrict__ lab, unsigned nb_ci) {
-    unsigned b = blockIdx.x;
+__device__ __forceinline__ void build_2_block(const uint8_t* occ, const GridDev& G, uint16_t* ci, int* lab,
+                                              unsigned nb_ci, unsigned b) {
     if (b < nb_ci) {
         const ChangeOut none{nullptr, nullptr, nullptr, 0u, MapRange{1, 0, 1, 0}};
         derive_cellinfo_item(G, ci, MapRange{0, G.PW - 1, 0, G.PH - 1}, MapRange{1, 0, 1, 0}, none, (long long)b * 256 + threadIdx.x, (int)(threadIdx.x & 63));
@@ -645,8 +648,8 @@ __global__ __launch_bounds__(256) void k_build_2(const uint8_t* __restrict__ occ
     b -= nb_ci;
     ccl_merge_item(occ, G.W, G.H, lab, (long long)b * 256 + threadIdx.x);
 }
-__global__ __launch_bounds__(1024) void k_build_3(const uint8_t* __restrict__ occ, GridDev G, BmWord* __restrict__ dbm, int* __restrict__ lab, unsigned nb_diag) {
-    unsigned b = blockIdx.x;
+__device__ __forceinline__ void build_3_block(const uint8_t* occ, const GridDev& G, BmWord* dbm, int* lab,
+                                              unsigned nb_diag, unsigned b) {
     if (b < nb_diag) {
         const DiagRange whole{1, 0, 0, 0, 0};
         derive_diag_item(occ, G, dbm, whole, (long long)b * 16 + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
@@ -654,6 +657,16 @@ __global__ __launch_bounds__(1024) void k_build_3(const uint8_t* __restrict__ oc
     }
     b -= nb_diag;
     ccl_flatten_item((long long)G.W * G.H, lab, (long long)b * 1024 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_build_1(const uint8_t* __restrict__ occ, GridDev G, uint8_t* __restrict__ nb8, BmWord* __restrict__ bm,
+                                                int* __restrict__ lab, unsigned nb_rows, unsigned nb_cols) {
+    build_1_block(occ, G, nb8, bm, lab, nb_rows, nb_cols, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_build_2(const uint8_t* __restrict__ occ, GridDev G, uint16_t* __restrict__ ci, int* __restrict__ lab, unsigned nb_ci) {
+    build_2_block(occ, G, ci, lab, nb_ci, blockIdx.x);
+}
+__global__ __launch_bounds__(1024) void k_build_3(const uint8_t* __restrict__ occ, GridDev G, BmWord* __restrict__ dbm, int* __restrict__ lab, unsigned nb_diag) {
+    build_3_block(occ, G, dbm, lab, nb_diag, blockIdx.x);
 }
 
 // Callers' grid preparation (SURVEY.md 8f, N1): zero-pad by map_d on the low side, dilate every occupied cell
@@ -663,23 +676,48 @@ __global__ __launch_bounds__(1024) void k_build_3(const uint8_t* __restrict__ oc
 // msg_layout != 0: `raw` is the int8 data[] of a nav_msgs/OccupancyGrid (row-major [y][x], 100 = occupied,
 // -1 = unknown), i.e. the transpose/threshold of map_callback (global_planner_st.py:16-20) is fused in:
 // after 100 -> 1 and -1 -> 0 a cell counts as occupied for the dilation iff its value is > 0.
-__global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict__ raw, int W0, int H0, int dx, int dy, int ifa,
-                                                     int variant, int msg_layout, int W1, int H1, uint8_t* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)W1 * H1) return;
+// WORLD (fxjps_prepare_slots_world, DESIGN.md section 3.14): the W0 x H0 source is a CANVAS that nobody assembles, the
+// detected map `raw` pasted over a prior map that lives on the device (global_planner_st.py:210-225 /
+// global_planner_ccst.py:395-409).  A canvas cell is read from the detected map inside its rectangle (it overwrites: a
+// free detected cell clears an occupied prior cell), else from the prior inside the prior's rectangle, else it is 0.
+struct WorldSrcDev {
+    const uint8_t* prior;  // [pW][pH] non-zero = occupied, resident on this context; nullptr: the job has no prior
+    int32_t pW, pH, px, py;  // the prior's extents and where its cell (0, 0) lies in the canvas
+    int32_t rW, rH, rx, ry;  // the detected map's (SlotJobDev::raw, SlotJobDev::layout)
+};
+template <bool WORLD>  // (S is read only when WORLD)
+__device__ __forceinline__ uint8_t prepared_byte(const uint8_t* __restrict__ raw, const WorldSrcDev* __restrict__ S, int W0, int H0, int dx, int dy, int ifa,
+                                                 int variant, int msg_layout, int H1, long long i) {
     const int x = (int)(i / H1), y = (int)(i % H1);
     const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
+    // (block-uniform: loaded once, into scalar registers.  With the fields read inside the loop the gather had two VGPRs less
+    // and the world calls took 1 - 5 % longer: profiles/slot_kernel_family_bench.json)
+    const WorldSrcDev W = WORLD ? *S : WorldSrcDev{};
     uint8_t v = 0;
     for (int a = -ifa; a <= ifa; a += step)
         for (int b = -ifa; b <= ifa; b += step) {
             const int sx = x - dx - a, sy = y - dy - b;
             if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
-                const bool o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * W0 + sx] > 0)
-                                          : (raw[(size_t)sx * H0 + sy] != 0);
+                bool o = false;  // canvas cell (sx, sy)
+                if constexpr (WORLD) {
+                    const int ux = sx - W.rx, uy = sy - W.ry, qx = sx - W.px, qy = sy - W.py;
+                    if (ux >= 0 && uy >= 0 && ux < W.rW && uy < W.rH)
+                        o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)uy * W.rW + ux] > 0) : (raw[(size_t)ux * W.rH + uy] != 0);
+                    else if (qx >= 0 && qy >= 0 && qx < W.pW && qy < W.pH)  // (pW == 0 without a prior)
+                        o = W.prior[(size_t)qx * W.pH + qy] != 0;
+                } else {
+                    o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * W0 + sx] > 0) : (raw[(size_t)sx * H0 + sy] != 0);
+                }
                 if (o) v = 1;
             }
         }
-    out[i] = v;
+    return v;
+}
+__global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict__ raw, int W0, int H0, int dx, int dy, int ifa,
+                                                     int variant, int msg_layout, int W1, int H1, uint8_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)W1 * H1) return;
+    out[i] = prepared_byte<false>(raw, nullptr, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
 }
 
 // ---- Many raw maps into grid slots in one call (fxjps_prepare_slots, DESIGN.md section 3.8): the preparation above, the
@@ -687,7 +725,23 @@ __global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict_
 // the single-grid kernel would run for job 0, then those for job 1, ...: SlotTable::first[launch][j] is the first block
 // of job j (first[launch][n] the grid size), and a block finds its job by a block-uniform binary search of that row (jobs
 // differ in size: a 2-D grid padded to the largest job would waste most of its blocks).  Everything per item is the
-// single-grid code: the *_item functions are called as they stand.
+// single-grid code: prepared_byte, build_1 .. 3_block and derive_jd_item are called as they stand.
+//
+// Three kernel templates make the launches of the four calls of this family; what differs between the calls is a template
+// parameter, never a run-time flag (the compare form has a barrier and its LDS, which the plain form must not acquire):
+//   REFRESH (fxjps_refresh_slots, DESIGN.md section 3.12): a tick whose maps mostly did not change.  A vehicle hands in the
+//     raw map of the tick before far more often than a new one, and then the prepared grid is byte for byte what its slot
+//     holds.  `changed` has one word per job, set by the host for every call: 1 for a job that must build (an empty slot,
+//     other extents, a grid beyond the fused build), 0 for a job whose slot holds a grid of the prepared extents
+//     (SlotJobDev::compare).  The gather of such a job reads the slot's byte at the index it would write, stores only where
+//     the two differ and raises the job's word when any byte of the block did; a thread touches its own cell alone.  The
+//     stage launches then return at once in every block of a job whose word is still 0 -- the six derived arrays of that
+//     slot are already those of these bytes.  The goal launch runs for every job (the goal may have moved on an unchanged
+//     map) and hands the words to the host beside its results: res[n * SLOT_RES + j].
+//   WORLD (fxjps_prepare_slots_world / fxjps_refresh_slots_world, DESIGN.md section 3.14): SlotJobDev stays as it is, W0 / H0
+//     being the canvas extents; a WorldSrcDev per job, staged behind the raws, says where the two sources lie in the canvas.
+//     Only the gather knows: every later launch is the plain one.
+// The forms that do not read `S` or `changed` are handed nullptr.
 constexpr int SLOT_JOBS_MAX = 256;  // FXJPS_MAX_GRID_SLOTS
 enum { SL_PREPARE = 0, SL_BUILD_1, SL_BUILD_2, SL_BUILD_3, SL_JD, SL_LAUNCHES };
 struct SlotJobDev {
@@ -696,7 +750,7 @@ struct SlotJobDev {
     const uint8_t* raw;  // this job's raw map inside the staged input
     int32_t W0, H0, dx, dy, ifa, variant, layout;
     int32_t gx, gy;      // the shifted goal (inside the prepared grid: the host checked)
-    uint32_t nb_rows, nb_cols, nb_ci, nb_diag;  // k_build_1 .. 3: where the kinds of blocks change within the job's part
+    uint32_t nb_rows, nb_cols, nb_ci, nb_diag;  // build_1 .. 3_block: where the kinds of blocks change within the job's part
     int32_t compare;     // fxjps_refresh_slots: the slot holds a grid of these extents, store only the bytes that differ
 };
 struct SlotTable {
@@ -716,30 +770,31 @@ __device__ __forceinline__ int slot_job_of(const uint32_t* __restrict__ first, i
 }
 
 // k_prepare_grid's gather, for every output cell of every job.
-__device__ __forceinline__ uint8_t slot_prepared_byte(const uint8_t* __restrict__ raw, int W0, int H0, int dx, int dy, int ifa, int variant, int msg_layout,
-                                                      int H1, long long i) {
-    const int x = (int)(i / H1), y = (int)(i % H1);
-    const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
-    uint8_t v = 0;
-    for (int a = -ifa; a <= ifa; a += step)
-        for (int b = -ifa; b <= ifa; b += step) {
-            const int sx = x - dx - a, sy = y - dy - b;
-            if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
-                const bool o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * W0 + sx] > 0)
-                                          : (raw[(size_t)sx * H0 + sy] != 0);
-                if (o) v = 1;
-            }
-        }
-    return v;
-}
-__global__ __launch_bounds__(256) void k_prepare_slots(const SlotTable* __restrict__ T, int n) {
+template <bool WORLD, bool REFRESH>
+__global__ __launch_bounds__(256) void k_slots_gather(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
+                                                     uint32_t* __restrict__ changed) {
     const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
     const SlotJobDev& J = T->job[j];
     const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
     const uint8_t* __restrict__ raw = J.raw;
+    uint8_t* __restrict__ occ = J.occ;
     const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    if (i >= (long long)W1 * H1) return;
-    J.occ[i] = slot_prepared_byte(raw, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
+    const bool inside = i < (long long)W1 * H1;
+    const WorldSrcDev* __restrict__ Sj = WORLD ? S + j : nullptr;
+    if constexpr (!REFRESH) {
+        if (!inside) return;
+        occ[i] = prepared_byte<WORLD>(raw, Sj, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
+    } else {
+        const uint8_t v = inside ? prepared_byte<WORLD>(raw, Sj, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
+        if (!J.compare) {  // (block-uniform) a job that builds whatever the bytes are: its word is 1 already
+            if (inside) occ[i] = v;
+            return;
+        }
+        const bool differs = inside && occ[i] != v;  // bytes, not truthiness: a slot set to 7 where this is 1 is rewritten
+        if (differs) occ[i] = v;
+        // (every thread of the block reaches the barrier: none has returned above)
+        if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+    }
 }
 
 // The free cell of line[0], line[stride], .. (n cells) nearest to index c, the lower index of two equally near ones
@@ -794,192 +849,34 @@ __device__ __forceinline__ void slots_goal_job(const SlotTable* __restrict__ T, 
         res[j * SLOT_RES + 3] = status;
     }
 }
-__global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res) {
-    slots_goal_job(T, res, (int)blockIdx.x, (int)threadIdx.x);
-}
-
-// k_build_1 .. 3 and k_derive_jd over all jobs whose grid takes the fused build (at most 2^18 cells; the others have no
-// blocks here and are built by derive_maps behind these launches).
-__device__ __forceinline__ void slots_build_1_block(const SlotTable* __restrict__ T, int j) {
-    const SlotJobDev& J = T->job[j];
-    const GridDev G = J.G;
-    const uint8_t* __restrict__ occ = J.occ;
-    const unsigned nb_rows = J.nb_rows, nb_cols = J.nb_cols;
-    const int lane = (int)(threadIdx.x & 63);
-    const MapRange rr{0, G.PW - 1, 0, G.WORDS - 1}, rc{0, G.PH - 1, 0, G.WORDS - 1};
-    unsigned b = blockIdx.x - T->first[SL_BUILD_1][j];
-    if (b < nb_rows) {
-        derive_rows_item(occ, G, const_cast<uint8_t*>(G.nb8), const_cast<BmWord*>(G.bm), rr, (long long)b * 4 + (threadIdx.x >> 6), lane);
-        return;
-    }
-    b -= nb_rows;
-    if (b < nb_cols) {
-        derive_cols_item<true>(occ, G, const_cast<BmWord*>(G.bm), rc, (long long)b * 4 + (threadIdx.x >> 6), lane);
-        return;
-    }
-    b -= nb_cols;
-    ccl_init_item(occ, (long long)G.W * G.H, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
-}
-__device__ __forceinline__ void slots_build_2_block(const SlotTable* __restrict__ T, int j) {
-    const SlotJobDev& J = T->job[j];
-    const GridDev G = J.G;
-    const uint8_t* __restrict__ occ = J.occ;
-    const unsigned nb_ci = J.nb_ci;
-    unsigned b = blockIdx.x - T->first[SL_BUILD_2][j];
-    if (b < nb_ci) {
-        const ChangeOut none{nullptr, nullptr, nullptr, 0u, MapRange{1, 0, 1, 0}};
-        derive_cellinfo_item(G, const_cast<uint16_t*>(G.ci), MapRange{0, G.PW - 1, 0, G.PH - 1}, MapRange{1, 0, 1, 0}, none, (long long)b * 256 + threadIdx.x,
-                             (int)(threadIdx.x & 63));
-        return;
-    }
-    b -= nb_ci;
-    ccl_merge_item(occ, G.W, G.H, const_cast<int*>(G.comp), (long long)b * 256 + threadIdx.x);
-}
-__device__ __forceinline__ void slots_build_3_block(const SlotTable* __restrict__ T, int j) {
-    const SlotJobDev& J = T->job[j];
-    const GridDev G = J.G;
-    const uint8_t* __restrict__ occ = J.occ;
-    const unsigned nb_diag = J.nb_diag;
-    unsigned b = blockIdx.x - T->first[SL_BUILD_3][j];
-    if (b < nb_diag) {
-        const DiagRange whole{1, 0, 0, 0, 0};
-        derive_diag_item(occ, G, const_cast<BmWord*>(G.bm) + (size_t)4 * G.LINES * G.WORDS, whole, (long long)b * 16 + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
-        return;
-    }
-    b -= nb_diag;
-    ccl_flatten_item((long long)G.W * G.H, const_cast<int*>(G.comp), (long long)b * 1024 + threadIdx.x);
-}
-__device__ __forceinline__ void slots_derive_jd_block(const SlotTable* __restrict__ T, int j) {
-    const GridDev G = T->job[j].G;
-    const DiagRange whole{1, 0, 0, 0, 0};
-    derive_jd_item(G, const_cast<uint16_t*>(G.jd), whole, (long long)(blockIdx.x - T->first[SL_JD][j]) * 256 + threadIdx.x);
-}
-__global__ __launch_bounds__(256) void k_slots_build_1(const SlotTable* __restrict__ T, int n) {
-    slots_build_1_block(T, slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x));
-}
-__global__ __launch_bounds__(256) void k_slots_build_2(const SlotTable* __restrict__ T, int n) {
-    slots_build_2_block(T, slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x));
-}
-__global__ __launch_bounds__(1024) void k_slots_build_3(const SlotTable* __restrict__ T, int n) {
-    slots_build_3_block(T, slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x));
-}
-__global__ __launch_bounds__(256) void k_slots_derive_jd(const SlotTable* __restrict__ T, int n) {
-    slots_derive_jd_block(T, slot_job_of(T->first[SL_JD], n, blockIdx.x));
-}
-
-// ---- The same call for a tick whose maps mostly did not change (fxjps_refresh_slots, DESIGN.md section 3.12).  A vehicle
-// hands in the raw map of the tick before far more often than a new one, and then the prepared grid is byte for byte what
-// its slot holds.  `changed` has one word per job, set by the host for every call: 1 for a job that must build (an empty
-// slot, other extents, a grid beyond the fused build), 0 for a job whose slot holds a grid of the prepared extents
-// (SlotJobDev::compare).  The gather of such a job reads the slot's byte at the index it would write, stores only where
-// the two differ and raises the job's word when any byte of the block did; a thread touches its own cell alone.  The four
-// build launches and the jump-distance launch then return at once in every block of a job whose word is still 0 -- the
-// six derived arrays of that slot are already those of these bytes.  The goal launch runs for every job (the goal may
-// have moved on an unchanged map) and hands the words to the host beside its results: res[n * SLOT_RES + j].
-__global__ __launch_bounds__(256) void k_refresh_slots(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
-    const SlotJobDev& J = T->job[j];
-    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
-    const uint8_t* __restrict__ raw = J.raw;
-    uint8_t* __restrict__ occ = J.occ;
-    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    const bool inside = i < (long long)W1 * H1;
-    const uint8_t v = inside ? slot_prepared_byte(raw, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
-    if (!J.compare) {  // (block-uniform) a job that builds whatever the bytes are: its word is 1 already
-        if (inside) occ[i] = v;
-        return;
-    }
-    const bool differs = inside && occ[i] != v;  // bytes, not truthiness: a slot set to 7 where this is 1 is rewritten
-    if (differs) occ[i] = v;
-    // (every thread of the block reaches the barrier: none has returned above)
-    if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
-}
-__global__ __launch_bounds__(64) void k_refresh_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int n, const uint32_t* __restrict__ changed) {
+template <bool REFRESH>
+__global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int n, const uint32_t* __restrict__ changed) {
     const int j = (int)blockIdx.x;
     slots_goal_job(T, res, j, (int)threadIdx.x);
-    if (threadIdx.x == 0) res[n * SLOT_RES + j] = (int32_t)changed[j];
-}
-__global__ __launch_bounds__(256) void k_refresh_build_1(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_BUILD_1], n, blockIdx.x);
-    if (changed[j] == 0u) return;  // (block-uniform: one scalar load)
-    slots_build_1_block(T, j);
-}
-__global__ __launch_bounds__(256) void k_refresh_build_2(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_BUILD_2], n, blockIdx.x);
-    if (changed[j] == 0u) return;
-    slots_build_2_block(T, j);
-}
-__global__ __launch_bounds__(1024) void k_refresh_build_3(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_BUILD_3], n, blockIdx.x);
-    if (changed[j] == 0u) return;
-    slots_build_3_block(T, j);
-}
-__global__ __launch_bounds__(256) void k_refresh_derive_jd(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_JD], n, blockIdx.x);
-    if (changed[j] == 0u) return;
-    slots_derive_jd_block(T, j);
+    if constexpr (REFRESH)
+        if (threadIdx.x == 0) res[n * SLOT_RES + j] = (int32_t)changed[j];
 }
 
-// ---- The same two calls from world-frame jobs (fxjps_prepare_slots_world / fxjps_refresh_slots_world, DESIGN.md section
-// 3.14).  The raw map of such a job is a CANVAS that nobody assembles: the detected map pasted over a prior map that lives
-// on the device (global_planner_st.py:210-225 / global_planner_ccst.py:395-409).  SlotJobDev stays as it is, W0 / H0 being
-// the canvas extents; a WorldSrcDev per job, staged behind the raws, says where the two sources lie in the canvas.  The
-// gather reads a canvas cell from the detected map inside its rectangle (it overwrites: a free detected cell clears an
-// occupied prior cell), else from the prior inside the prior's rectangle, else it is 0.  Block mapping, compare-while-gather
-// and the `changed` word are those of k_prepare_slots / k_refresh_slots; every later launch is the existing one.
-struct WorldSrcDev {
-    const uint8_t* prior;  // [pW][pH] non-zero = occupied, resident on this context; nullptr: the job has no prior
-    int32_t pW, pH, px, py;  // the prior's extents and where its cell (0, 0) lies in the canvas
-    int32_t rW, rH, rx, ry;  // the detected map's (SlotJobDev::raw, SlotJobDev::layout)
-};
-__device__ __forceinline__ uint8_t world_prepared_byte(const uint8_t* __restrict__ raw, const WorldSrcDev& S, int W0, int H0, int dx, int dy, int ifa,
-                                                       int variant, int msg_layout, int H1, long long i) {
-    const int x = (int)(i / H1), y = (int)(i % H1);
-    const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
-    const uint8_t* __restrict__ prior = S.prior;
-    const int pW = S.pW, pH = S.pH, px = S.px, py = S.py, rW = S.rW, rH = S.rH, rx = S.rx, ry = S.ry;
-    uint8_t v = 0;
-    for (int a = -ifa; a <= ifa; a += step)
-        for (int b = -ifa; b <= ifa; b += step) {
-            const int sx = x - dx - a, sy = y - dy - b;
-            if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
-                const int ux = sx - rx, uy = sy - ry, qx = sx - px, qy = sy - py;
-                bool o = false;
-                if (ux >= 0 && uy >= 0 && ux < rW && uy < rH)
-                    o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)uy * rW + ux] > 0) : (raw[(size_t)ux * rH + uy] != 0);
-                else if (qx >= 0 && qy >= 0 && qx < pW && qy < pH)  // (pW == 0 without a prior)
-                    o = prior[(size_t)qx * pH + qy] != 0;
-                if (o) v = 1;
-            }
-        }
-    return v;
-}
-__global__ __launch_bounds__(256) void k_prepare_world(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n) {
-    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+// k_build_1 .. 3 and k_derive_jd (L = SL_BUILD_1 .. SL_JD) over all jobs whose grid takes the fused build (at most 2^18
+// cells; the others have no blocks here and are built by derive_maps behind these launches).
+template <int L, bool REFRESH>
+__global__ __launch_bounds__(L == SL_BUILD_3 ? 1024 : 256) void k_slots_stage(const SlotTable* __restrict__ T, int n, const uint32_t* __restrict__ changed) {
+    static_assert(L >= SL_BUILD_1 && L <= SL_JD, "a build stage");
+    const int j = slot_job_of(T->first[L], n, blockIdx.x);
+    if constexpr (REFRESH)
+        if (changed[j] == 0u) return;  // (block-uniform: one scalar load)
     const SlotJobDev& J = T->job[j];
-    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
-    const uint8_t* __restrict__ raw = J.raw;
-    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    if (i >= (long long)W1 * H1) return;
-    J.occ[i] = world_prepared_byte(raw, S[j], W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
-}
-__global__ __launch_bounds__(256) void k_refresh_world(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
-                                                      uint32_t* __restrict__ changed) {
-    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
-    const SlotJobDev& J = T->job[j];
-    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
-    const uint8_t* __restrict__ raw = J.raw;
-    uint8_t* __restrict__ occ = J.occ;
-    const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    const bool inside = i < (long long)W1 * H1;
-    const uint8_t v = inside ? world_prepared_byte(raw, S[j], W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
-    if (!J.compare) {  // (block-uniform, as in k_refresh_slots)
-        if (inside) occ[i] = v;
-        return;
-    }
-    const bool differs = inside && occ[i] != v;
-    if (differs) occ[i] = v;
-    if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+    const GridDev G = J.G;
+    const uint8_t* __restrict__ occ = J.occ;
+    const unsigned b = blockIdx.x - T->first[L][j];
+    if constexpr (L == SL_BUILD_1)
+        build_1_block(occ, G, const_cast<uint8_t*>(G.nb8), const_cast<BmWord*>(G.bm), const_cast<int*>(G.comp), J.nb_rows, J.nb_cols, b);
+    else if constexpr (L == SL_BUILD_2)
+        build_2_block(occ, G, const_cast<uint16_t*>(G.ci), const_cast<int*>(G.comp), J.nb_ci, b);
+    else if constexpr (L == SL_BUILD_3)
+        build_3_block(occ, G, const_cast<BmWord*>(G.bm) + (size_t)4 * G.LINES * G.WORDS, const_cast<int*>(G.comp), J.nb_diag, b);
+    else
+        derive_jd_item(G, const_cast<uint16_t*>(G.jd), DiagRange{1, 0, 0, 0, 0}, (long long)b * 256 + threadIdx.x);
 }
 
 // Wire / on-disk adapters (SURVEY.md 8f, N3): one tiled byte transpose with a value map.

@@ -336,34 +336,41 @@ class Planner(object):
         return [o + (bool(k),) for o, k in zip(self._slot_outs(arr, n), kept[:n])]
 
     @staticmethod
+    def _job_raw(j, slot, raw, ifa, variant):
+        """Fill what fxjps_slot_job_t and fxjps_world_job_t share -- raw, layout, W0, H0, slot, ifa, variant -- from a job's
+        raw[x][y] or (data, width, height).  -> the array j.raw points into."""
+        if isinstance(raw, tuple):
+            data, width, height = raw
+            a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+            if a.size != width * height:
+                raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+            j.layout, j.W0, j.H0 = 1, int(width), int(height)
+        else:
+            a = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
+            if a.ndim != 2:
+                raise ValueError("grid must be 2-D")
+            j.layout, j.W0, j.H0 = 0, a.shape[0], a.shape[1]
+        j.raw = a.ctypes.data
+        j.slot, j.ifa = int(slot), int(ifa)
+        j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+        return a
+
+    @staticmethod
     def _slot_jobs(jobs):
         """-> the fxjps_slot_job_t array of prepare_slots' jobs, and the raws it points into (the caller holds them until the
         C call has returned)."""
         arr = (_lib.SlotJob * max(len(jobs), 1))()
         keep = []
         for j, (slot, raw, start, goal, ifa, variant) in zip(arr, jobs):
-            if isinstance(raw, tuple):
-                data, width, height = raw
-                a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
-                if a.size != width * height:
-                    raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
-                j.layout, j.W0, j.H0 = 1, int(width), int(height)
-            else:
-                a = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
-                if a.ndim != 2:
-                    raise ValueError("grid must be 2-D")
-                j.layout, j.W0, j.H0 = 0, a.shape[0], a.shape[1]
-            keep.append(a)
-            j.raw = a.ctypes.data
-            j.slot, j.ifa = int(slot), int(ifa)
-            j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+            keep.append(Planner._job_raw(j, slot, raw, ifa, variant))
             j.start_xy[0], j.start_xy[1] = int(start[0]), int(start[1])
             j.goal_xy[0], j.goal_xy[1] = int(goal[0]), int(goal[1])
         return arr, keep
 
     @staticmethod
-    def _slot_outs(arr, n):
-        return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy[0], j.goal_xy[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
+    def _slot_outs(arr, n, goal="goal_xy"):
+        """(goal: the field of the goal's cell -- goal_xy_cell in a fxjps_world_job_t, whose goal_xy is the position)"""
+        return [((j.start_xy[0], j.start_xy[1]), tuple(getattr(j, goal)), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
                  j.status == 0) for j in arr[:n]]
 
     # -- world-frame ticks: a prior map on the device, positions instead of cells (fxjps_prepare_slots_world)
@@ -404,7 +411,7 @@ class Planner(object):
         arr, keep = self._world_jobs(jobs)
         self._chk(self._L.fxjps_prepare_slots_world(self._h, arr, len(jobs)))
         del keep
-        return [o + w for o, w in zip(self._slot_outs_world(arr, len(jobs)), self._world_outs(arr, len(jobs)))]
+        return [o + w for o, w in zip(self._slot_outs(arr, len(jobs), "goal_xy_cell"), self._world_outs(arr, len(jobs)))]
 
     def refresh_slots_world(self, jobs):
         """refresh_slots from world-frame jobs (fxjps_refresh_slots_world): -> per job refresh_slots' tuple (kept last)
@@ -415,7 +422,7 @@ class Planner(object):
         kept = np.zeros(max(n, 1), dtype=np.int32)
         self._chk(self._L.fxjps_refresh_slots_world(self._h, arr, n, _lib.ptr(kept, C.c_int32)))
         del keep
-        return [o + (bool(k),) + w for o, k, w in zip(self._slot_outs_world(arr, n), kept[:n], self._world_outs(arr, n))]
+        return [o + (bool(k),) + w for o, k, w in zip(self._slot_outs(arr, n, "goal_xy_cell"), kept[:n], self._world_outs(arr, n))]
 
     @staticmethod
     def _world_jobs(jobs):
@@ -426,21 +433,7 @@ class Planner(object):
         for j, job in zip(arr, jobs):
             slot, raw, map_o, map_reso, pos_xy, goal_xy, ifa, variant = job[:8]
             prior, ori_pre, map_t = (tuple(job[8:]) + (None, (-15, -15), None)[len(job) - 8:])[:3]
-            if isinstance(raw, tuple):
-                data, width, height = raw
-                a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
-                if a.size != width * height:
-                    raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
-                j.layout, j.W0, j.H0 = 1, int(width), int(height)
-            else:
-                a = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
-                if a.ndim != 2:
-                    raise ValueError("grid must be 2-D")
-                j.layout, j.W0, j.H0 = 0, a.shape[0], a.shape[1]
-            keep.append(a)
-            j.raw = a.ctypes.data
-            j.slot, j.ifa = int(slot), int(ifa)
-            j.variant = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+            keep.append(Planner._job_raw(j, slot, raw, ifa, variant))
             j.prior = -1 if prior is None else int(prior)
             j.map_reso = float(map_reso)
             if map_t is None:
@@ -449,11 +442,6 @@ class Planner(object):
                 j.map_o[k], j.map_t[k], j.pos_xy[k] = float(map_o[k]), float(map_t[k]), float(pos_xy[k])
                 j.goal_xy[k], j.ori_pre[k] = float(goal_xy[k]), float(ori_pre[k])
         return arr, keep
-
-    @staticmethod
-    def _slot_outs_world(arr, n):
-        return [((j.start_xy[0], j.start_xy[1]), (j.goal_xy_cell[0], j.goal_xy_cell[1]), (j.map_d[0], j.map_d[1]), (j.W, j.H), j.end_occu,
-                 j.status == 0) for j in arr[:n]]
 
     @staticmethod
     def _world_outs(arr, n):

@@ -14,7 +14,9 @@ from test_grid_slots_host import HIPCC, _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("fxjps_prepare_slots", "fxjps_slot_job_size")
-KERNELS = ("k_prepare_slots", "k_slots_goal", "k_slots_build_1", "k_slots_build_2", "k_slots_build_3", "k_slots_derive_jd")
+# (template instantiations, as they are spelled inside a mangled name: gather <WORLD, REFRESH>, goal <REFRESH>, stage <L, REFRESH>)
+KERNELS = ("k_slots_gatherILb0ELb0EE", "k_slots_goalILb0EE", "k_slots_stageILi1ELb0EE", "k_slots_stageILi2ELb0EE", "k_slots_stageILi3ELb0EE",
+           "k_slots_stageILi4ELb0EE")
 
 
 def test_declared_exported_and_bound():
@@ -54,7 +56,7 @@ def test_library_reports_the_job_size_the_binding_has():
 def test_kernels_exist_without_scratch_and_the_shared_ones_are_unchanged():
     rows = _resource_usage()
     for k in KERNELS:
-        hit = [v for name, v in rows.items() if re.search(r"\d+%sE" % k, name)]
+        hit = [v for name, v in rows.items() if re.search(r"\d+%sEv" % k, name)]
         assert len(hit) == 1, (k, sorted(rows))
         assert int(hit[0]["ScratchSize [bytes/lane]"]) == 0 and int(hit[0]["VGPRs Spill"]) == 0, (k, hit[0])
     with open(os.path.join(ROOT, "profiles", "prepare_slots_resource_usage.json")) as f:

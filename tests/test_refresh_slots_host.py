@@ -14,9 +14,12 @@ from test_grid_slots_host import HIPCC, _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("fxjps_refresh_slots", "fxjps_debug_read_slot_context")
-REFRESH_KERNELS = ("k_refresh_slots", "k_refresh_goal", "k_refresh_build_1", "k_refresh_build_2", "k_refresh_build_3", "k_refresh_derive_jd")
+# (template instantiations, as they are spelled inside a mangled name: gather <WORLD, REFRESH>, goal <REFRESH>, stage <L, REFRESH>)
+REFRESH_KERNELS = ("k_slots_gatherILb0ELb1EE", "k_slots_goalILb1EE", "k_slots_stageILi1ELb1EE", "k_slots_stageILi2ELb1EE", "k_slots_stageILi3ELb1EE",
+                   "k_slots_stageILi4ELb1EE")
 # (changed: their bodies moved into functions the refresh kernels call too)
-PREPARE_KERNELS = ("k_prepare_slots", "k_slots_goal", "k_slots_build_1", "k_slots_build_2", "k_slots_build_3", "k_slots_derive_jd")
+PREPARE_KERNELS = ("k_slots_gatherILb0ELb0EE", "k_slots_goalILb0EE", "k_slots_stageILi1ELb0EE", "k_slots_stageILi2ELb0EE", "k_slots_stageILi3ELb0EE",
+                   "k_slots_stageILi4ELb0EE")
 
 
 def test_declared_exported_and_bound():
@@ -68,7 +71,7 @@ def test_library_exports_the_call():
 def test_new_and_changed_kernels_exist_without_scratch():
     rows = _resource_usage()
     for k in REFRESH_KERNELS + PREPARE_KERNELS:
-        hit = [v for name, v in rows.items() if re.search(r"\d+%sE" % k, name)]
+        hit = [v for name, v in rows.items() if re.search(r"\d+%sEv" % k, name)]
         assert len(hit) == 1, (k, sorted(rows))
         assert int(hit[0]["ScratchSize [bytes/lane]"]) == 0 and int(hit[0]["VGPRs Spill"]) == 0, (k, hit[0])
         assert int(hit[0].get("SGPRs Spill", 0)) == 0, (k, hit[0])

@@ -17,7 +17,7 @@ from worldprep_cases import cases, merge_args, placements, unpack
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size")
-KERNELS = ("k_prepare_world", "k_refresh_world")
+KERNELS = ("k_slots_gatherILb1ELb0EE", "k_slots_gatherILb1ELb1EE")  # k_slots_gather<WORLD = true, REFRESH> inside a mangled name
 CTYPES = {"const void*": C.c_void_p, "int32_t": C.c_int32, "double": C.c_double}
 
 
@@ -36,7 +36,7 @@ def test_declared_exported_bound_and_in_the_changelog():
         assert name in _lib.SYMBOLS
     src = open(os.path.join(ROOT, "fuxi-planner_amd", "csrc", "fxjps_maps.hip.inc")).read()
     for k in KERNELS:
-        assert "k_search" not in k and re.search(r"__global__[^\n]*\bvoid %s\(" % k, src), k
+        assert "k_search" not in k and re.search(r"__global__[^\n]*\bvoid %s\(" % k.split("I")[0], src), k
 
 
 def test_ctypes_mirror_matches_the_header_field_by_field():
@@ -185,7 +185,7 @@ def test_prior_image_numpy_agrees_with_the_loader_cases():
 def test_new_kernels_compile_without_scratch_or_spills():
     rows = _resource_usage()
     for k in KERNELS:
-        hit = [v for name, v in rows.items() if re.search(r"\d+%sE" % k, name)]
+        hit = [v for name, v in rows.items() if re.search(r"\d+%sEv" % k, name)]
         assert len(hit) == 1, (k, sorted(rows))
         assert int(hit[0]["ScratchSize [bytes/lane]"]) == 0 and int(hit[0]["VGPRs Spill"]) == 0, (k, hit[0])
     assert len([n for n in rows if "k_search" in n]) == 12

@@ -11,6 +11,9 @@ repetition is a window of as many calls as make a side run >= 0.2 s, medians of 
                      git worktree add /tmp/parent HEAD~1 && make -C /tmp/parent/fuxi-planner_amd libfxjps.so
     world_call, parent, this   the C call alone on arrays filled beforehand: fxjps_prepare_slots_world, and fxjps_prepare_slots
                  of the parent's and of this library on the same canvases
+    world_refresh_call   fxjps_refresh_slots_world on the same jobs call after call: every slot is compared and kept
+    parent_world_call, parent_world_refresh_call   the two world calls of the parent's library, where it has them (a change
+                 that leaves the calls as they are -- a refactor -- is measured against these sides)
 Before anything is timed every slot's bytes and the per-job outputs are compared across the three handles, and the six
 derived arrays between the two handles of this library.  Bars: world <= 1.0 x host_parent; this <= 1.05 x parent.
 --trace-call N --side world|canvas: ONE call of N jobs and nothing else (for rocprofv3 --kernel-trace --stats).
@@ -49,6 +52,11 @@ class Parent(object):
         L.fxjps_last_error.argtypes = [vp]
         L.fxjps_prepare_slots.argtypes = [vp, C.POINTER(_lib.SlotJob), i32]
         L.fxjps_get_grid_slot.argtypes = [vp, i32, vp, vp, vp]
+        self.has_world = hasattr(L, "fxjps_prepare_slots_world") and L.fxjps_world_job_size() == C.sizeof(_lib.WorldJob)
+        if self.has_world:
+            L.fxjps_set_prior_map.argtypes = [vp, i32, vp, i32, i32]
+            L.fxjps_prepare_slots_world.argtypes = [vp, C.POINTER(_lib.WorldJob), i32]
+            L.fxjps_refresh_slots_world.argtypes = [vp, C.POINTER(_lib.WorldJob), i32, C.POINTER(i32)]
         assert L.fxjps_slot_job_size() == C.sizeof(_lib.SlotJob), lib_path
         self.version = L.fxjps_version()
         self.h = vp()
@@ -58,6 +66,9 @@ class Parent(object):
 
     def prepare(self, arr, n):
         assert self.L.fxjps_prepare_slots(self.h, arr, n) == 0, self.L.fxjps_last_error(self.h)
+
+    def set_prior(self, prior, occ):
+        assert self.L.fxjps_set_prior_map(self.h, prior, occ.ctypes.data_as(C.c_void_p), occ.shape[0], occ.shape[1]) == 0, self.L.fxjps_last_error(self.h)
 
     def slot(self, s):
         W, H = C.c_int32(), C.c_int32()
@@ -137,7 +148,11 @@ def main():
         ap.error("--parent-lib is required")
     _lib.load()
     world, this, parent = fx.Planner([0]), fx.Planner([0]), Parent(a.parent_lib)
-    assert parent.version < _lib.VERSION, (parent.version, _lib.VERSION)
+    assert parent.version <= _lib.VERSION, (parent.version, _lib.VERSION)
+    # (the world calls of the parent and the two refreshing sides: handles of their own, so that every side's slots hold what its own calls left)
+    parent_world = Parent(a.parent_lib) if parent.has_world else None
+    parent_world_refresh = Parent(a.parent_lib) if parent.has_world else None
+    world_refresh = fx.Planner([0])
     out = {"tool": "world_slots_bench", "n": N, "reps": a.reps, "window_s": ftb.WINDOW_S, "ifa": 1, "map_reso": R,
            "parent_version": parent.version, "version": _lib.VERSION, "cases": []}
     ms = lambda ts: round(float(np.median(ts)) * 1e3, 4)
@@ -145,6 +160,10 @@ def main():
     for shape in a.shapes:
         prior, wjobs = world_fleet(shape, N)
         world.set_prior_map(PRIOR, prior)
+        world_refresh.set_prior_map(PRIOR, prior)
+        for p in (parent_world, parent_world_refresh):
+            if p is not None:
+                p.set_prior(PRIOR, np.ascontiguousarray(prior > 0, dtype=np.uint8))
         hjobs = host_jobs(wjobs, prior)
         # the same slots three ways, byte for byte, before anything is timed
         o_world = world.prepare_slots_world(wjobs)
@@ -184,7 +203,33 @@ def main():
                  "world_call": lambda: c_call(world._L.fxjps_prepare_slots_world, world._h, warr),
                  "parent": lambda: canvas_call("parent", parent.L.fxjps_prepare_slots, parent.h),
                  "this": lambda: canvas_call("this", this._L.fxjps_prepare_slots, this._h)}
+        kept = np.zeros(N, np.int32)
+        p_kept = kept.ctypes.data_as(C.POINTER(C.c_int32))
+
+        def refresh_call(fn, h, arr):
+            assert fn(h, arr, N, p_kept) == 0 and int(kept.sum()) == N
+
+        # the refreshing sides and the parent's world calls, each on a job array of its own
+        extra = {"world_refresh_call": (world_refresh._L, world_refresh._h)}
+        if parent.has_world:
+            extra["parent_world_refresh_call"] = (parent_world_refresh.L, parent_world_refresh.h)
+            extra["parent_world_call"] = (parent_world.L, parent_world.h)
+        rarr = {}
+        for k, (L, h) in extra.items():
+            rarr[k], keep_k = fx.Planner._world_jobs(wjobs)
+            wkeep = wkeep + keep_k
+            if k == "parent_world_call":
+                sides[k] = lambda k=k, L=L, h=h: c_call(L.fxjps_prepare_slots_world, h, rarr[k])
+                continue
+            assert L.fxjps_refresh_slots_world(h, rarr[k], N, p_kept) == 0, (shape, k)  # (the first call builds what differs)
+            assert [tuple(j.goal_xy_cell) + (j.W, j.H, j.end_occu, j.status) for j in rarr[k]] == \
+                [tuple(j.goal_xy) + (j.W, j.H, j.end_occu, j.status) for j in first], (shape, k)
+            sides[k] = lambda k=k, L=L, h=h: refresh_call(L.fxjps_refresh_slots_world, h, rarr[k])
         t, per = ftb.windows(sides, a.reps)
+        if parent.has_world:
+            for v in range(N):  # what the parent's world calls left in their slots is what this library's left
+                g = world.get_grid_slot(v).tobytes()
+                assert g == world_refresh.get_grid_slot(v).tobytes() == parent_world.slot(v).tobytes() == parent_world_refresh.slot(v).tobytes(), (shape, v)
         med = {k: float(np.median(t[k])) for k in sides}
         cells = [o[3][0] * o[3][1] for o in o_this]
         case = {"shape": shape, "prior_shape": list(prior.shape), "prepared_cells_min_max": [min(cells), max(cells)],
@@ -196,15 +241,18 @@ def main():
         case["world_over_host_parent"] = round(med["world"] / med["host_parent"], 4)
         case["this_over_parent"] = round(med["this"] / med["parent"], 4)
         case["world_call_over_parent"] = round(med["world_call"] / med["parent"], 4)
+        if parent.has_world:
+            case["world_call_over_parent_world_call"] = round(med["world_call"] / med["parent_world_call"], 4)
+            case["world_refresh_call_over_parent"] = round(med["world_refresh_call"] / med["parent_world_refresh_call"], 4)
         case["bar_world_1_00_met"] = bool(med["world"] <= 1.0 * med["host_parent"])
         case["bar_this_1_05_met"] = bool(med["this"] <= 1.05 * med["parent"])
         out["cases"].append(case)
     for spec in a.fold_trace:
         name, d = spec.split("=", 1)
         out.setdefault("trace_us", {})[name] = fold_trace(d)
-    world.close()
-    this.close()
-    parent.close()
+    for p in (world, this, parent, world_refresh, parent_world, parent_world_refresh):
+        if p is not None:
+            p.close()
     line = json.dumps(out)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
