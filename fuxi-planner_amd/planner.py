@@ -796,6 +796,15 @@ class Planner(object):
         self._chk(self._L.fxjps_debug_read_sets(self._h, _lib.ptr(out, C.c_uint64), self._nq, C.byref(tsh)))
         return out, tsh.value
 
+    def debug_qstat(self, nq):
+        """The per-query diagnostics of the last batch on the first context (fxjps_debug_qstat; FXJPS_QSTAT=1 must be in
+        the environment before the first planning call of the process): -> uint64[nq, 4], per query start, end (100 MHz
+        ticks), pops, wavefront (low 24 bits) | shader-clock cycles of the search << 24.  A query that was not searched
+        has a zero row."""
+        out = np.zeros((int(nq), 4), dtype=np.uint64)
+        self._chk(self._L.fxjps_debug_qstat(self._h, _lib.ptr(out, C.c_uint64), int(nq)))
+        return out
+
     def debug_nbmask(self):
         W, H = self.shape
         buf = np.empty((W + 2, H + 2), dtype=np.uint8)

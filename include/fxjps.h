@@ -430,8 +430,13 @@ typedef struct fxjps_timing {
     int64_t search_launches; /* kernel launches that made up search_kernel_ms (a batch of 4 096 .. 32 768 queries is two
                                 overlapping launches: its longest queries on CUs of their own, the rest beside them) */
     int64_t retried;         /* queries re-run with large scratch */
-    int64_t pops;            /* open-list pops executed by the last batch (all devices) */
-    int64_t pushes;
+    int64_t pops;            /* open-list pops of the last batch (all devices): for a query that is searched -- start in the
+                                grid, start != goal, goal in the grid and free, and the start occupied or in the goal's
+                                4-connected component of free cells -- exactly the heappop calls of jps1.py:198 on that
+                                query; a query answered without a search adds nothing.  A query that is run again with
+                                large scratch (`retried`) starts over: its abandoned attempt is counted as well */
+    int64_t pushes;          /* ... and its open-list pushes: the heappush calls of jps1.py:228 -- the reference's count less
+                                the one push of the start (jps1.py:192), which goes straight into the register tier */
     int64_t far_refills;     /* open-list refills from the global-memory tier */
     int64_t slow_pops;       /* pops taken straight from the global-memory tier (> 256 entries tied at the minimum key) */
     int64_t table_wipes;     /* visited-table wipes after a wavefront's generation counter wrapped (every 63 searches) */

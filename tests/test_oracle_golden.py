@@ -97,6 +97,25 @@ def test_batch_api_matches_single(oracle):
                 assert [tuple(x) for x in cells[q, :ln[q]]] == path and cost[q] == c
 
 
+def test_fast_mode_counts_equal_the_literal_ones(oracle):
+    """The non-literal mode (stale duplicates of closed nodes skipped as the no-ops they are) is what the GPU tests take
+    their expected pops and pushes from; only the literal mode's counts are pinned to jps1.py above.  Same pops, pushes
+    and open_peak -- and the same paths and costs -- on the inputs of test_search_work_gpu and on synth1024."""
+    from fuxi_planner_amd import synth
+    cases = [(synth.synth_grid(96, 80, 7, 0.25), 3, 600), (synth.synth_grid(300, 200, 11, 0.02), 11, 400)]
+    g = load_golden("synth1024.json")
+    cases.append((oracle.synth_grid(g["W"], g["H"], g["grid_seed"], g["p"]), g["qseed"], 24))
+    for occ, qseed, n in cases:
+        s, t = synth.synth_queries(occ, qseed, n)
+        for h in (2, 1):
+            lit = oracle.plan_batch(occ, s, t, h, literal=True, max_len=1024, nthreads=8, want_stats=True)
+            fast = oracle.plan_batch(occ, s, t, h, literal=False, max_len=1024, nthreads=8, want_stats=True)
+            for k in ("pops", "pushes", "open_peak"):
+                assert np.array_equal(lit[3][k], fast[3][k]), (occ.shape, h, k)
+            assert lit[3]["pops"].sum() > 0 and (lit[3]["cells"] >= fast[3]["cells"]).all()
+            assert np.array_equal(lit[1], fast[1]) and lit[2].tobytes() == fast[2].tobytes() and np.array_equal(lit[0], fast[0])
+
+
 def test_generators_agree(oracle):
     from fuxi_planner_amd import synth
     for W, H, seed, p in [(1024, 1024, 1, 0.2), (100, 37, 5, 0.33), (3, 3, 9, 0.5)]:

@@ -3,19 +3,17 @@
 each search's wall time (s_memrealtime, 100 MHz) and its shader-clock cycles (s_memtime): cycles / microsecond is the
 clock the wavefront saw.  A query that takes longer inside the batch at the SAME number of cycles ran at a lower clock
 (the chip under load); more cycles mean waiting (memory, a shared CU).   python tools/clock_probe.py [workload=c2] [n=6]"""
-import ctypes as C, json, os, sys
+import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["FXJPS_QSTAT"] = "1"
 import fuxi_planner_amd as fx
-from fuxi_planner_amd import synth, _lib
+from fuxi_planner_amd import synth
 wname = sys.argv[1] if len(sys.argv) > 1 else "c2"
 ntop = int(sys.argv[2]) if len(sys.argv) > 2 else 6
 wl = json.load(open(os.path.join(ROOT, "fuxi-planner_amd", "workloads.json")))[wname]
 p = fx.Planner([0])
-L = _lib.load()
-L.fxjps_debug_qstat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]
 occ = synth.synth_grid(wl["W"], wl["H"], wl["grid_seed"], wl["p"])
 p.set_grid_occ(occ)
 nq = wl["nq"]
@@ -25,8 +23,7 @@ s, g = synth.synth_queries(occ, wl["qseed"], nq)
 def stats(ss, gg):
     for rep in range(2):
         p.plan_batch(ss, gg, wl["hchoice"], wl["max_path_len"])
-    q = np.zeros((len(ss), 4), dtype=np.uint64)
-    assert L.fxjps_debug_qstat(p._h, q.ctypes.data_as(C.POINTER(C.c_uint64)), len(ss)) == 0
+    q = p.debug_qstat(len(ss))
     us = (q[:, 1] - q[:, 0]).astype(float) / 100.0
     return us, (q[:, 3] >> np.uint64(24)).astype(float), q[:, 2].astype(float)
 

@@ -1,17 +1,15 @@
 #!/usr/bin/env python3
 """How long does the query that ends config 2 (9206) take by the company it keeps?  Its own start / end inside each batch
 (FXJPS_QSTAT), for batches made of: the query alone; the 16 queries of the head launch; those + n of the others."""
-import ctypes as C, json, os, sys
+import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["FXJPS_QSTAT"] = "1"
 import fuxi_planner_amd as fx
-from fuxi_planner_amd import synth, _lib
+from fuxi_planner_amd import synth
 wl = json.load(open(os.path.join(ROOT, "fuxi-planner_amd", "workloads.json")))["c2"]
 p = fx.Planner([0])
-L = _lib.load()
-L.fxjps_debug_qstat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]
 occ = synth.synth_grid(wl["W"], wl["H"], wl["grid_seed"], wl["p"])
 p.set_grid_occ(occ)
 s, g = synth.synth_queries(occ, wl["qseed"], wl["nq"])
@@ -28,8 +26,7 @@ for name, ids in sets:
     for rep in range(2):
         p.plan_batch(s[ids], g[ids], 2, 1024)
     tm = p.timing()
-    q = np.zeros((len(ids), 4), dtype=np.uint64)
-    assert L.fxjps_debug_qstat(p._h, q.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids)) == 0
+    q = p.debug_qstat(len(ids))
     i = int(np.flatnonzero(ids == 9206)[0])
     t0 = q[q[:, 2] > 0, 0].min()
     print("%-28s kernel %.2f ms | 9206: start %.2f ms, runs %.2f ms, %d pops" % (name, tm["search_kernel_ms"], (q[i, 0] - t0) / 1e5, (q[i, 1] - q[i, 0]) / 1e5, q[i, 2]), flush=True)

@@ -15,7 +15,10 @@ for d in glob.glob(out + "/pmc_*/"):
                 vals[r["Counter_Name"]] = float(r["Counter_Value"])
                 vals["_vgpr"], vals["_sgpr"], vals["_lds"] = r.get("VGPR_Count"), r.get("SGPR_Count"), r.get("LDS_Block_Size")
 wl = json.load(open("fuxi-planner_amd/workloads.json"))["c2"]
-pops = 332391044.0  # pops the kernel executes on config 2 (stale duplicates of one batch are committed together)
+# the reference's pops (jps1.py:198, stale duplicates included) over the 9 958 config-2 queries that are searched, which
+# is exactly what the kernel executes (tests/test_search_work_gpu.py); the 343 995 318 of workloads.json count the 42
+# queries as well whose goal lies in another component and which the kernel answers from the component labels
+pops = 332391044.0
 print("regs vgpr %s sgpr %s lds %s" % (vals.get("_vgpr"), vals.get("_sgpr"), vals.get("_lds")))
 for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"):
     if k in vals:

@@ -2,18 +2,16 @@
 """Per-query timeline of one batch (FXJPS_QSTAT diagnostics): when each query started and ended, how many pops it
 made, on which wavefront -- the per-pop rate as a function of how busy the chip is.
 Usage: python tools/qstat.py [workload=c2] [FXJPS_WAVES=...]"""
-import ctypes as C, json, os, sys
+import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["FXJPS_QSTAT"] = "1"
 import fuxi_planner_amd as fx
-from fuxi_planner_amd import synth, _lib
+from fuxi_planner_amd import synth
 wname = sys.argv[1] if len(sys.argv) > 1 else "c2"
 wl = json.load(open(os.path.join(ROOT, "fuxi-planner_amd", "workloads.json")))[wname]
 p = fx.Planner([0])
-L = _lib.load()
-L.fxjps_debug_qstat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]
 occ = synth.synth_grid(wl["W"], wl["H"], wl["grid_seed"], wl["p"])
 p.set_grid_occ(occ)
 nq = wl["nq"]
@@ -21,8 +19,7 @@ s, g = synth.synth_queries(occ, wl["qseed"], nq)
 for rep in range(2):
     off, cells, cost, st = p.plan_batch(s, g, wl["hchoice"], wl["max_path_len"])
 tm = p.timing()
-q = np.zeros((nq, 4), dtype=np.uint64)
-assert L.fxjps_debug_qstat(p._h, q.ctypes.data_as(C.POINTER(C.c_uint64)), nq) == 0
+q = p.debug_qstat(nq)
 ran = q[:, 2] > 0
 t0 = q[ran, 0].min()
 ts, te, pops = (q[ran, 0] - t0) / 100.0, (q[ran, 1] - t0) / 100.0, q[ran, 2].astype(float)  # microseconds
