@@ -231,18 +231,30 @@ struct DevCtx : GridBufs {
     int mode = 0;                 // 0 plain batch, 1 search everything and record read sets, 2 the same for h_sel only
     int64_t nrun = 0;             // queries handed to the search kernel
     DBuf<uint8_t> d_raw, d_img;
-    // waypoint selection over a batch (fxjps_waypoint_ccst_batch)
-    DBuf<double> d_wp_in, d_wp_out;
-    DBuf<int32_t> d_wp_eo, d_wp_nkept, d_wp_kept, d_wp_cells, d_wp_len;
-    DBuf<long long> d_wp_off;
-    // ... the st rule (fxjps_waypoint_st_batch): per-query inputs / outputs, and the host libm's atan2 of integer pairs
-    DBuf<int32_t> d_wp_ms, d_wp_pdim, d_wp_dim;
-    DBuf<double> d_wp_prev, d_wp_ang, d_atab;
-    int atab_a = -1, atab_b = -1;  // d_atab holds atan2(a, b) for a in [0, atab_a], b in [-atab_b, atab_b]
-    // ... both rules over a slots batch (fxjps_waypoint_slots_batch): the call's staged input (fx::WpSlotQuery per query |
-    // the caller's offsets | cells) and output (fx::WpSlotResult per query | the kept cells), pinned and on the device
-    HBuf<uint8_t> h_wps_in, h_wps_out;
-    DBuf<uint8_t> d_wps_in, d_wps_out;
+    struct Waypoints {
+        // waypoint selection over a batch (fxjps_waypoint_ccst_batch)
+        DBuf<double> d_in, d_out;
+        DBuf<int32_t> d_eo, d_nkept, d_kept, d_cells, d_len;
+        DBuf<long long> d_off;
+        // ... the st rule (fxjps_waypoint_st_batch): per-query inputs / outputs, and the host libm's atan2 of integer pairs
+        DBuf<int32_t> d_ms, d_pdim, d_dim;
+        DBuf<double> d_prev, d_ang, d_atab;
+        int atab_a = -1, atab_b = -1;  // d_atab holds atan2(a, b) for a in [0, atab_a], b in [-atab_b, atab_b]
+        // ... both rules over a slots batch (fxjps_waypoint_slots_batch): the call's staged input (fx::WpSlotQuery per query |
+        // the caller's offsets | cells) and output (fx::WpSlotResult per query | the kept cells), pinned and on the device
+        HBuf<uint8_t> h_recs_in, h_recs_out;
+        DBuf<uint8_t> d_recs_in, d_recs_out;
+        void release() {
+            for (DBuf<double>* b : {&d_in, &d_out, &d_prev, &d_ang, &d_atab}) b->release();
+            for (DBuf<int32_t>* b : {&d_eo, &d_nkept, &d_kept, &d_cells, &d_len, &d_ms, &d_pdim, &d_dim}) b->release();
+            d_off.release();
+            atab_a = atab_b = -1;
+            h_recs_in.release();
+            h_recs_out.release();
+            d_recs_in.release();
+            d_recs_out.release();
+        }
+    } wp;
     DBuf<int32_t> d_upd_xy;
     DBuf<uint8_t> d_upd_chg;
     DBuf<int> d_owner;        // [W][H], -1 at rest: which entry of an update list decides a cell it names several times
@@ -1408,69 +1420,152 @@ void drain_all(fxjps* h) {
     h->err = keep;
 }
 
-// ---- waypoint selection over a batch: where the paths are.  The caller's CSR (device 0 takes all of them), or the last
-// batch's, resident shard by shard on the devices that planned them.
-struct WpPart {
-    DevCtx* d;
-    int64_t q0, n;
-    const long long* d_off;
-    const int32_t *d_cells, *d_len;
-    long long total;
-};
-int wp_gather_parts(fxjps* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, bool nonneg, std::vector<WpPart>& parts,
-                    std::vector<int64_t>& kept_at, int64_t& kept_base) {
-    kept_base = 0;
-    if (cells_xy) {
-        for (int64_t q = 0; q < nq; q++)
-            if (offsets[q + 1] < offsets[q]) return fail(h, FXJPS_E_ARG, "offsets must ascend");
-        if (offsets[0] != 0) return fail(h, FXJPS_E_ARG, "offsets[0] must be 0");
-        if (nonneg)
-            for (int64_t i = 0; i < 2 * offsets[nq]; i++)
-                if (cells_xy[i] < 0) return fail(h, FXJPS_E_ARG, "negative cell");
-        DevCtx& d = h->devs[0];
-        HIPCHK(h, hipSetDevice(d.dev));
-        const long long total = offsets[nq];
-        HIPCHK(h, d.d_wp_off.ensure((size_t)nq + 1));
-        HIPCHK(h, d.d_wp_len.ensure((size_t)nq));
-        HIPCHK(h, d.d_wp_cells.ensure((size_t)std::max<long long>(total, 1) * 2));
-        std::vector<int32_t> len((size_t)nq);
-        for (int64_t q = 0; q < nq; q++) len[(size_t)q] = (int32_t)std::min<int64_t>(offsets[q + 1] - offsets[q], 0x7FFFFFFF);
-        static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
-        HIPCHK(h, hipMemcpyAsync(d.d_wp_off.p, offsets, ((size_t)nq + 1) * sizeof(long long), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(h, hipMemcpyAsync(d.d_wp_len.p, len.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-        if (total > 0) HIPCHK(h, hipMemcpyAsync(d.d_wp_cells.p, cells_xy, (size_t)total * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(h, hipStreamSynchronize(d.stream));  // (`len` is pageable host memory)
-        parts.push_back(WpPart{&d, 0, nq, d.d_wp_off.p, d.d_wp_cells.p, d.d_wp_len.p, total});
-        kept_at.push_back(0);
-        kept_base = total;
-    } else {
-        for (auto& d : h->devs) {
-            if (d.nq == 0) continue;
-            const long long total = d.h_offsets.p[d.nq];
-            parts.push_back(WpPart{&d, d.q0, d.nq, d.d_offsets.p, d.d_cells.p, d.d_len.p, total});
-            kept_at.push_back(kept_base);
-            kept_base += total;
+// ---- waypoint selection over a batch: where the paths are.  The caller's CSR (context 0 takes all of them), the last
+// batch's, resident shard by shard on the contexts that planned them, or a single call's, which is in the pinned host
+// buffers only and is handed over like a caller's CSR.
+struct WpPaths {
+    struct Part {
+        DevCtx* d;
+        int64_t q0, n, total, kept_at;    // kept_at: where the part's cells begin among the call's (the caller's kept cells and triples)
+        const long long* h_off;           // the part's offsets on the host (local: h_off[0] == 0) ...
+        const int32_t* h_cells;           // ... and the cells they index
+        const long long* d_off;           // the same on the device: a resident shard's, or what upload() left there (nullptr:
+        const int32_t *d_cells, *d_len;   // an explicit CSR not uploaded -- the slots call stages it behind its records)
+    };
+    std::vector<Part> parts;
+    int64_t total = 0;      // cells of all parts
+    bool resident = false;  // the parts are the last batch's shards
+
+    // nonneg(q): path q's cells are read as grid cells (the ccst rule) and may not be negative.  name_query: the slots calls'
+    // refusals name the query.
+    template <typename F>
+    int resolve(fxjps* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, bool name_query, F&& nonneg) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
+        if (!cells_xy && h->last_on_host) {
+            offsets = reinterpret_cast<const int64_t*>(h->devs[0].h_offsets.p);
+            cells_xy = h->devs[0].h_cells.p;
         }
+        resident = !cells_xy;
+        if (resident) {
+            for (auto& d : h->devs) {
+                if (d.nq == 0) continue;
+                const long long t = d.h_offsets.p[d.nq];
+                parts.push_back(Part{&d, d.q0, d.nq, t, total, d.h_offsets.p, d.h_cells.p, d.d_offsets.p, d.d_cells.p, d.d_len.p});
+                total += t;
+            }
+            return FXJPS_OK;
+        }
+        char pre[32] = "";
+        const auto at = [&](int64_t q) -> const char* {
+            if (name_query) snprintf(pre, sizeof(pre), "query %lld: ", (long long)q);
+            return pre;
+        };
+        if (offsets[0] != 0) return fail(h, FXJPS_E_ARG, "%soffsets[0] must be 0", at(0));
+        for (int64_t q = 0; q < nq; q++) {
+            if (offsets[q + 1] < offsets[q]) return fail(h, FXJPS_E_ARG, "%soffsets must ascend", at(q));
+            if (nonneg(q))
+                for (int64_t i = 2 * offsets[q]; i < 2 * offsets[q + 1]; i++)
+                    if (cells_xy[i] < 0) return fail(h, FXJPS_E_ARG, "%snegative cell", at(q));
+        }
+        total = offsets[nq];
+        parts.push_back(Part{&h->devs[0], 0, nq, total, 0, reinterpret_cast<const long long*>(offsets), cells_xy, nullptr, nullptr, nullptr});
+        return FXJPS_OK;
     }
-    return FXJPS_OK;
+    const Part* part_of(int64_t q) const {
+        for (auto& P : parts)
+            if (q >= P.q0 && q < P.q0 + P.n) return &P;
+        return nullptr;
+    }
+    // path q on the host: its cells and their number ...
+    int64_t path_of(int64_t q, const int32_t** c) const {
+        const Part* P = part_of(q);
+        *c = P ? P->h_cells + 2 * P->h_off[q - P->q0] : nullptr;
+        return P ? P->h_off[q - P->q0 + 1] - P->h_off[q - P->q0] : 0;
+    }
+    // ... and where they begin among the call's
+    int64_t path_at(int64_t q) const {
+        const Part* P = part_of(q);
+        return P ? P->kept_at + P->h_off[q - P->q0] : 0;
+    }
+    // an explicit CSR onto context 0 as it is (offsets | lengths | cells), for the single-grid kernels
+    int upload(fxjps* h) {
+        if (resident) return FXJPS_OK;
+        Part& P = parts[0];
+        DevCtx& d = *P.d;
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, d.wp.d_off.ensure((size_t)P.n + 1));
+        HIPCHK(h, d.wp.d_len.ensure((size_t)P.n));
+        HIPCHK(h, d.wp.d_cells.ensure((size_t)std::max<long long>(P.total, 1) * 2));
+        std::vector<int32_t> len((size_t)P.n);
+        for (int64_t q = 0; q < P.n; q++) len[(size_t)q] = (int32_t)std::min<int64_t>(P.h_off[q + 1] - P.h_off[q], 0x7FFFFFFF);
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_off.p, P.h_off, ((size_t)P.n + 1) * sizeof(long long), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_len.p, len.data(), (size_t)P.n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+        if (P.total > 0) HIPCHK(h, hipMemcpyAsync(d.wp.d_cells.p, P.h_cells, (size_t)P.total * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));  // (`len` is pageable host memory)
+        P.d_off = d.wp.d_off.p;
+        P.d_cells = d.wp.d_cells.p;
+        P.d_len = d.wp.d_len.p;
+        return FXJPS_OK;
+    }
+};
+
+// Queue every part's copies and launch (queue(P) -> int), run `beside` on the host while the devices work, then collect.
+template <typename F, typename G>
+int wp_queue_then_collect(fxjps* h, WpPaths& S, F&& queue, G&& beside) {
+    int rc = FXJPS_OK;
+    for (auto& P : S.parts)
+        if ((rc = queue(P)) != FXJPS_OK) {  // copies of the contexts in front of the failing one are still queued on the caller's buffers
+            drain_all(h);
+            return rc;
+        }
+    beside();
+    for (auto& P : S.parts)
+        if (hipSetDevice(P.d->dev) != hipSuccess || hipStreamSynchronize(P.d->stream) != hipSuccess) rc = fail(h, FXJPS_E_HIP, "waypoint kernel failed");
+    return rc;
 }
 
 // The st rule's table of angles (fx::WpAtab): atan2(a, b) by the HOST's libm for a in [0, am], b in [-bm, bm], on every
-// device of `parts` -- grown to the largest range seen on each device, filled once per range by `nthreads` host threads.
+// context of the call -- grown to the largest range seen on each, filled once per range by `nthreads` host threads.
 constexpr long long ATAB_MAX = 1ll << 27;  // entries (1 GiB): a map_start far off the grid takes the host form of the rule
 bool wp_atab_fits(long long am, long long bm) { return (am + 1) * (2 * bm + 1) <= ATAB_MAX && am < (1ll << 30) && bm < (1ll << 30); }
-int wp_ensure_atab(fxjps* h, std::vector<WpPart>& parts, long long am, long long bm, int nthreads) {
-    // the table: grown to the largest range seen on each device, filled by the host's libm
+
+// The range of (cell + 1 - map_start) over the st queries of a call (rule == nullptr: every query), which decides whether
+// the table fits: exactly, cell by cell, for paths the host sees; resident paths lie on the grid their batch was planned
+// on, a slots batch's within the largest slot it named.
+void wp_st_range(const fxjps* h, const WpPaths& S, int64_t nq, const int32_t* rule, const int32_t* map_start, long long& am, long long& bm) {
+    am = bm = 0;
+    const long long W = h->last_slots ? h->last_slots_W : h->devs[0].W, H = h->last_slots ? h->last_slots_H : h->devs[0].H;
+    for (int64_t q = 0; q < nq; q++) {
+        if (rule && rule[q] != 0) continue;
+        const long long mx = map_start[2 * q], my = map_start[2 * q + 1];
+        if (S.resident) {
+            am = std::max(am, std::max(std::llabs(1 - mx), std::llabs(W - mx)));
+            bm = std::max(bm, std::max(std::llabs(1 - my), std::llabs(H - my)));
+            continue;
+        }
+        const int32_t* c = nullptr;
+        const int64_t n = S.path_of(q, &c);
+        for (int64_t i = 0; i < n; i++) {
+            am = std::max(am, std::llabs((long long)c[2 * i] + 1 - mx));
+            bm = std::max(bm, std::llabs((long long)c[2 * i + 1] + 1 - my));
+        }
+    }
+}
+
+// -> FXJPS_OK: every context of the call holds a table that covers [0, am] x [-bm, bm]; 1: no table (a context has no memory
+// for it: the caller takes the host form); else the error.  A context's atab_a / atab_b describe its table only while the
+// table is there and whole.
+int wp_ensure_atab(fxjps* h, WpPaths& S, long long am, long long bm, int nthreads) {
     std::vector<double> tab;
     int ta = -1, tb = -1;
-    for (auto& P : parts) {
+    for (auto& P : S.parts) {
         DevCtx& d = *P.d;
-        if (d.atab_a >= (int)am && d.atab_b >= (int)bm) continue;
-        const int na = std::max<int>((int)am, d.atab_a), nb = std::max<int>((int)bm, d.atab_b);
-        if ((long long)(na + 1) * (2ll * nb + 1) > ATAB_MAX) {  // (the union of two ranges may not fit: start over with this one)
-            d.atab_a = d.atab_b = -1;
+        if (d.wp.atab_a >= (int)am && d.wp.atab_b >= (int)bm) continue;
+        int wa = std::max<int>((int)am, d.wp.atab_a), wb = std::max<int>((int)bm, d.wp.atab_b);
+        if ((long long)(wa + 1) * (2ll * wb + 1) > ATAB_MAX) {  // (the union of two ranges may not fit: start over with this one)
+            wa = (int)am;
+            wb = (int)bm;
         }
-        const int wa = d.atab_a < 0 ? (int)am : na, wb = d.atab_b < 0 ? (int)bm : nb;
         if (ta != wa || tb != wb) {
             ta = wa;
             tb = wb;
@@ -1486,13 +1581,114 @@ int wp_ensure_atab(fxjps* h, std::vector<WpPart>& parts, long long am, long long
             });
         }
         HIPCHK(h, hipSetDevice(d.dev));
-        HIPCHK(h, d.d_atab.ensure(tab.size()));
-        HIPCHK(h, hipMemcpyAsync(d.d_atab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        d.wp.atab_a = d.wp.atab_b = -1;  // (ensure frees the old table before it allocates, and the copy may fail)
+        if (d.wp.d_atab.ensure(tab.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            return 1;
+        }
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_atab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));  // (`tab` is pageable and dies with this call)
-        d.atab_a = ta;
-        d.atab_b = tb;
+        d.wp.atab_a = ta;
+        d.wp.atab_b = tb;
     }
     return FXJPS_OK;
+}
+
+// Where the st queries of a call run (rule == nullptr: every query is one).  -> FXJPS_OK: on the device -- every context of
+// the call holds a table of angles for them and, with `upload`, the explicit CSR; 1: on host threads (wp_st_on_host) -- the
+// table would not fit or could not be had, or FXJPS_WAYPOINT_ST_HOST=1 (test / measurement aid, read per call); else the error
+int wp_st_place(fxjps* h, WpPaths& S, int64_t nq, const int32_t* rule, const int32_t* map_start, int nthreads, bool upload) {
+    if (getenv("FXJPS_WAYPOINT_ST_HOST") && atoi(getenv("FXJPS_WAYPOINT_ST_HOST")) != 0) return 1;
+    long long am = 0, bm = 0;
+    wp_st_range(h, S, nq, rule, map_start, am, bm);
+    if (!wp_atab_fits(am, bm)) return 1;  // (a map_start far off the grid)
+    if (upload)
+        if (int rc = S.upload(h)) return rc;
+    return wp_ensure_atab(h, S, am, bm, nthreads);
+}
+
+// What only fxjps_tick_outputs_slots takes and writes
+struct TickIO {
+    const double* home_xy;
+    double* out_point;
+    double* out_path_xyz;
+    int64_t path_capacity;
+    double* out_dir_xyz;
+    int32_t* out_dir_n;
+    int32_t* out_dir_back;
+    int64_t dir_capacity;
+};
+
+// The st rule on host threads, by fxjps_waypoint_st: a table of angles that would not fit or could not be had, or
+// FXJPS_WAYPOINT_ST_HOST=1.  For the st queries of the call (rule == nullptr: every query); per_query: reso and origin are
+// arrays with one entry per query, not one value for all.  out_wp apart, an output that is nullptr is not written.
+// -> the first query fxjps_waypoint_st refused, -1: none
+struct WpStHost {
+    const int32_t *rule, *map_start;
+    const double *reso, *origin;
+    bool per_query;
+    const double *pos, *goal;
+    const int32_t* end_occu;
+    double dis_wp_tre, ang_wp_tre;
+    const double* prev_wp;
+    const int32_t* prev_dim;
+    double* out_wp;
+    int32_t* out_dim;
+    double *out_goal, *out_ang_wp;
+    int32_t* out_n_kept;
+    const TickIO* K;
+};
+int64_t wp_st_on_host(const WpPaths& S, int64_t nq, int nthreads, const WpStHost& A) {
+    int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 256));
+    nt = (int)std::min<int64_t>(nt, std::max<int64_t>(nq / 256, 1));
+    std::vector<int64_t> bad((size_t)nt, -1);
+    const TickIO* K = A.K;
+    (void)run_side_by_side((size_t)nt, [&](size_t t) {
+        for (int64_t q = nq * (int64_t)t / nt; q < nq * (int64_t)(t + 1) / nt; q++) {
+            if (A.rule && A.rule[q] != 0) continue;
+            const double reso = A.reso[A.per_query ? q : 0], *origin = A.origin + (A.per_query ? 2 * q : 0);
+            double* wp = A.out_wp + 3 * q;
+            const int32_t* c = nullptr;
+            const int64_t n = S.path_of(q, &c);
+            double gl[3] = {A.goal[3 * q], A.goal[3 * q + 1], A.goal[3 * q + 2]}, ang = 0.0;
+            int32_t dim = 3;
+            if (n <= 0) {  // no path: wp = global_goal    global_planner_st.py:287-290
+                for (int k = 0; k < 3; k++) wp[k] = gl[k];
+            } else {
+                const bool hp = A.prev_wp && (A.prev_dim[q] == 2 || A.prev_dim[q] == 3);
+                if (fxjps_waypoint_st(c, (int32_t)std::min<int64_t>(n, 0x7FFFFFFF), A.map_start + 2 * q, reso, origin, A.pos + 3 * q, A.goal + 3 * q,
+                                      A.end_occu ? A.end_occu[q] : 0, A.dis_wp_tre, A.ang_wp_tre, hp ? A.prev_wp + 3 * q : nullptr,
+                                      hp ? A.prev_dim[q] : 0, wp, &dim, gl, &ang) != FXJPS_OK && bad[t] < 0)
+                    bad[t] = q;
+            }
+            if (A.out_dim) A.out_dim[q] = dim;
+            if (A.out_ang_wp) A.out_ang_wp[q] = ang;
+            if (A.out_n_kept) A.out_n_kept[q] = 0;
+            if (A.out_goal)
+                for (int k = 0; k < 3; k++) A.out_goal[3 * q + k] = gl[k];
+            if (!K) continue;
+            // st:292-298, 335, 356-359 for the paths the host walked, by the functions the kernel calls
+            if (K->out_point) {
+                K->out_point[3 * q] = wp[0];
+                K->out_point[3 * q + 1] = wp[1];
+                K->out_point[3 * q + 2] = fx::tick_point_z(wp[0], wp[1], gl[0], gl[1], gl[2], K->home_xy[2 * q], K->home_xy[2 * q + 1]);
+            }
+            if (K->out_dir_n) K->out_dir_n[q] = 0;
+            if (K->out_dir_back) K->out_dir_back[q] = 0;
+            if (K->out_path_xyz && n > 0) {
+                double* p3 = K->out_path_xyz + 3 * S.path_at(q);
+                for (int64_t i = 0; i < n; i++) {
+                    p3[3 * i] = fx::wp_world(c[2 * i] + 1, reso, origin[0]);
+                    p3[3 * i + 1] = fx::wp_world(c[2 * i + 1] + 1, reso, origin[1]);
+                    p3[3 * i + 2] = 0.0;
+                }
+            }
+        }
+        return 0;
+    });
+    for (int64_t b : bad)
+        if (b >= 0) return b;
+    return -1;
 }
 
 }  // namespace
@@ -1733,20 +1929,7 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_qread.release();
         d.d_raw.release();
         d.d_img.release();
-        d.d_wp_in.release();
-        d.d_wp_out.release();
-        d.d_wp_eo.release();
-        d.d_wp_nkept.release();
-        d.d_wp_kept.release();
-        d.d_wp_cells.release();
-        d.d_wp_len.release();
-        d.d_wp_off.release();
-        d.d_wp_ms.release();
-        d.d_wp_pdim.release();
-        d.d_wp_dim.release();
-        d.d_wp_prev.release();
-        d.d_wp_ang.release();
-        d.d_atab.release();
+        d.wp.release();
         d.d_upd_xy.release();
         d.d_upd_chg.release();
         d.d_owner.release();
@@ -1766,10 +1949,6 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_slot_desc.release();
         d.d_grid_ids.release();
         d.h_slots_in.release();
-        d.h_wps_in.release();
-        d.h_wps_out.release();
-        d.d_wps_in.release();
-        d.d_wps_out.release();
         d.d_slots_in.release();
         d.h_slots_res.release();
         d.d_slots_res.release();
@@ -3239,39 +3418,28 @@ int fxjps_waypoint_ccst_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, co
     if (!cells_xy && nq != h->last_nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
     if (!cells_xy && h->last_slots)  // (the line tests read the resident grid: those paths were planned on other grids)
         return fail(h, FXJPS_E_ARG, "the last batch ran on grid slots: pass its paths explicitly");
-    if (!cells_xy && h->last_on_host) {  // (a single call leaves its path in the pinned host buffers: handed over like a caller's CSR)
-        static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
-        offsets = reinterpret_cast<const int64_t*>(h->devs[0].h_offsets.p);
-        cells_xy = h->devs[0].h_cells.p;
-    }
     if (h->maps_stale) {  // (the grid is what the line test reads; deferred updates are queued on the same streams anyway)
         int rc = update_cells_async(h, nullptr, nullptr, 0, true);
         if (rc) return rc;
     }
     if (nq == 0) return FXJPS_OK;
-    // the paths: the caller's CSR (device 0 takes all of them), or the last batch's, resident shard by shard
-    std::vector<WpPart> parts;
-    int64_t kept_base = 0;
-    std::vector<int64_t> kept_at;
-    {
-        int rc = wp_gather_parts(h, nq, offsets, cells_xy, true, parts, kept_at, kept_base);
-        if (rc) return rc;
-    }
-    if (out_kept_cells && kept_capacity < kept_base)
-        return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)kept_base);
-    int rc = [&]() -> int {
-    for (auto& P : parts) {  // queue every device, then collect
+    WpPaths S;
+    if (int rc = S.resolve(h, nq, offsets, cells_xy, false, [](int64_t) { return true; })) return rc;
+    if (out_kept_cells && kept_capacity < S.total)
+        return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)S.total);
+    if (int rc = S.upload(h)) return rc;
+    const auto queue = [&](WpPaths::Part& P) -> int {
         DevCtx& d = *P.d;
         HIPCHK(h, hipSetDevice(d.dev));
         const size_t n = (size_t)P.n;
-        HIPCHK(h, d.d_wp_in.ensure(n * 6));
-        HIPCHK(h, d.d_wp_out.ensure(n * 6));
-        HIPCHK(h, d.d_wp_eo.ensure(n));
-        HIPCHK(h, d.d_wp_nkept.ensure(n));
-        HIPCHK(h, d.d_wp_kept.ensure((size_t)std::max<long long>(P.total, 1) * 2));
-        HIPCHK(h, hipMemcpyAsync(d.d_wp_in.p, pos + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(h, hipMemcpyAsync(d.d_wp_in.p + n * 3, goal + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        if (end_occu) HIPCHK(h, hipMemcpyAsync(d.d_wp_eo.p, end_occu + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, d.wp.d_in.ensure(n * 6));
+        HIPCHK(h, d.wp.d_out.ensure(n * 6));
+        HIPCHK(h, d.wp.d_eo.ensure(n));
+        HIPCHK(h, d.wp.d_nkept.ensure(n));
+        HIPCHK(h, d.wp.d_kept.ensure((size_t)std::max<long long>(P.total, 1) * 2));
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_in.p, pos + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_in.p + n * 3, goal + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        if (end_occu) HIPCHK(h, hipMemcpyAsync(d.wp.d_eo.p, end_occu + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
         fx::WaypointArgs A;
         A.occ = d.occ.p;
         A.W = d.W;
@@ -3283,32 +3451,23 @@ int fxjps_waypoint_ccst_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, co
         A.reso = reso;
         A.ox = origin[0];
         A.oy = origin[1];
-        A.pos = d.d_wp_in.p;
-        A.goal = d.d_wp_in.p + n * 3;
-        A.end_occu = end_occu ? d.d_wp_eo.p : nullptr;
-        A.out_wp = d.d_wp_out.p;
-        A.out_goal = d.d_wp_out.p + n * 3;
-        A.out_nkept = d.d_wp_nkept.p;
-        A.kept = d.d_wp_kept.p;
+        A.pos = d.wp.d_in.p;
+        A.goal = d.wp.d_in.p + n * 3;
+        A.end_occu = end_occu ? d.wp.d_eo.p : nullptr;
+        A.out_wp = d.wp.d_out.p;
+        A.out_goal = d.wp.d_out.p + n * 3;
+        A.out_nkept = d.wp.d_nkept.p;
+        A.kept = d.wp.d_kept.p;
         hipLaunchKernelGGL(fx::k_waypoint_ccst, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(out_wp + 3 * P.q0, d.d_wp_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        if (out_goal) HIPCHK(h, hipMemcpyAsync(out_goal + 3 * P.q0, d.d_wp_out.p + n * 3, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        if (out_n_kept) HIPCHK(h, hipMemcpyAsync(out_n_kept + P.q0, d.d_wp_nkept.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipMemcpyAsync(out_wp + 3 * P.q0, d.wp.d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (out_goal) HIPCHK(h, hipMemcpyAsync(out_goal + 3 * P.q0, d.wp.d_out.p + n * 3, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (out_n_kept) HIPCHK(h, hipMemcpyAsync(out_n_kept + P.q0, d.wp.d_nkept.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
         if (out_kept_cells && P.total > 0)
-            HIPCHK(h, hipMemcpyAsync(out_kept_cells + 2 * kept_at[(size_t)(&P - parts.data())], d.d_wp_kept.p, (size_t)P.total * 2 * sizeof(int32_t),
-                                     hipMemcpyDeviceToHost, d.stream));
-    }
-    return FXJPS_OK;
-    }();
-    if (rc) {  // copies of the devices in front of the failing one are still queued on the caller's buffers
-        drain_all(h);
-        return rc;
-    }
-    for (auto& P : parts) {
-        if (hipSetDevice(P.d->dev) != hipSuccess || hipStreamSynchronize(P.d->stream) != hipSuccess) rc = fail(h, FXJPS_E_HIP, "waypoint kernel failed");
-    }
-    return rc;
+            HIPCHK(h, hipMemcpyAsync(out_kept_cells + 2 * P.kept_at, d.wp.d_kept.p, (size_t)P.total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+        return FXJPS_OK;
+    };
+    return wp_queue_then_collect(h, S, queue, [] {});
 }
 
 int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* map_start, double reso,
@@ -3322,147 +3481,68 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
     if ((prev_wp != nullptr) != (prev_dim != nullptr)) return fail(h, FXJPS_E_ARG, "prev_wp and prev_dim go together");
     if (!cells_xy && nq != h->last_nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
     if (nq == 0) return FXJPS_OK;
+    WpPaths S;
+    if (int rc = S.resolve(h, nq, offsets, cells_xy, false, [](int64_t) { return false; })) return rc;
     // ---- on the device (round 6): one wavefront per path, the angles out of a table of the HOST's atan2 over the integer
     // pairs this batch can ask for.  The table is filled once per range (threads of this call) and stays on the device.
-    if (!(getenv("FXJPS_WAYPOINT_ST_HOST") && atoi(getenv("FXJPS_WAYPOINT_ST_HOST")) != 0)) {  // (1: the host form, test / measurement aid)
-        if (!cells_xy && h->last_on_host) {  // (a single call's path is in the pinned host buffers: handed over like a caller's CSR)
-            static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
-            offsets = reinterpret_cast<const int64_t*>(h->devs[0].h_offsets.p);
-            cells_xy = h->devs[0].h_cells.p;
-        }
-        // the range of (cell + 1 - map_start) over the batch
-        long long cx0 = 0, cx1 = 0, cy0 = 0, cy1 = 0;
-        if (cells_xy) {
-            if (offsets[nq] > 0) {
-                cx0 = cx1 = cells_xy[0];
-                cy0 = cy1 = cells_xy[1];
+    const int place = wp_st_place(h, S, nq, nullptr, map_start, nthreads, true);
+    if (place < 0) return place;
+    if (place == FXJPS_OK) {
+        const auto queue = [&](WpPaths::Part& P) -> int {
+            DevCtx& d = *P.d;
+            HIPCHK(h, hipSetDevice(d.dev));
+            const size_t n = (size_t)P.n;
+            HIPCHK(h, d.wp.d_in.ensure(n * 6));
+            HIPCHK(h, d.wp.d_out.ensure(n * 6));
+            HIPCHK(h, d.wp.d_eo.ensure(n));
+            HIPCHK(h, d.wp.d_ms.ensure(n * 2));
+            HIPCHK(h, d.wp.d_prev.ensure(n * 3));
+            HIPCHK(h, d.wp.d_pdim.ensure(n));
+            HIPCHK(h, d.wp.d_dim.ensure(n));
+            HIPCHK(h, d.wp.d_ang.ensure(n));
+            HIPCHK(h, hipMemcpyAsync(d.wp.d_in.p, pos + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            HIPCHK(h, hipMemcpyAsync(d.wp.d_in.p + n * 3, goal + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            HIPCHK(h, hipMemcpyAsync(d.wp.d_ms.p, map_start + 2 * P.q0, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+            if (end_occu) HIPCHK(h, hipMemcpyAsync(d.wp.d_eo.p, end_occu + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+            if (prev_wp) {
+                HIPCHK(h, hipMemcpyAsync(d.wp.d_prev.p, prev_wp + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
+                HIPCHK(h, hipMemcpyAsync(d.wp.d_pdim.p, prev_dim + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
             }
-            for (int64_t i = 0; i < offsets[nq]; i++) {
-                cx0 = std::min<long long>(cx0, cells_xy[2 * i]);
-                cx1 = std::max<long long>(cx1, cells_xy[2 * i]);
-                cy0 = std::min<long long>(cy0, cells_xy[2 * i + 1]);
-                cy1 = std::max<long long>(cy1, cells_xy[2 * i + 1]);
-            }
-        } else {  // (resident paths lie on the grid; a slots batch's within the largest slot it named)
-            cx1 = (h->last_slots ? h->last_slots_W : h->devs[0].W) - 1;
-            cy1 = (h->last_slots ? h->last_slots_H : h->devs[0].H) - 1;
-        }
-        long long am = 0, bm = 0;
-        for (int64_t q = 0; q < nq; q++) {
-            const long long mx = map_start[2 * q], my = map_start[2 * q + 1];
-            am = std::max(am, std::max(std::llabs(cx0 + 1 - mx), std::llabs(cx1 + 1 - mx)));
-            bm = std::max(bm, std::max(std::llabs(cy0 + 1 - my), std::llabs(cy1 + 1 - my)));
-        }
-        if (wp_atab_fits(am, bm)) {  // (else: a map_start far off the grid takes the host form below)
-            std::vector<WpPart> parts;
-            std::vector<int64_t> kept_at;
-            int64_t kept_base = 0;
-            int rc = wp_gather_parts(h, nq, offsets, cells_xy, false, parts, kept_at, kept_base);
-            if (rc) return rc;
-            rc = wp_ensure_atab(h, parts, am, bm, nthreads);
-            if (rc) return rc;
-            rc = [&]() -> int {
-                for (auto& P : parts) {  // queue every device, then collect
-                    DevCtx& d = *P.d;
-                    HIPCHK(h, hipSetDevice(d.dev));
-                    const size_t n = (size_t)P.n;
-                    HIPCHK(h, d.d_wp_in.ensure(n * 6));
-                    HIPCHK(h, d.d_wp_out.ensure(n * 6));
-                    HIPCHK(h, d.d_wp_eo.ensure(n));
-                    HIPCHK(h, d.d_wp_ms.ensure(n * 2));
-                    HIPCHK(h, d.d_wp_prev.ensure(n * 3));
-                    HIPCHK(h, d.d_wp_pdim.ensure(n));
-                    HIPCHK(h, d.d_wp_dim.ensure(n));
-                    HIPCHK(h, d.d_wp_ang.ensure(n));
-                    HIPCHK(h, hipMemcpyAsync(d.d_wp_in.p, pos + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
-                    HIPCHK(h, hipMemcpyAsync(d.d_wp_in.p + n * 3, goal + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
-                    HIPCHK(h, hipMemcpyAsync(d.d_wp_ms.p, map_start + 2 * P.q0, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-                    if (end_occu) HIPCHK(h, hipMemcpyAsync(d.d_wp_eo.p, end_occu + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-                    if (prev_wp) {
-                        HIPCHK(h, hipMemcpyAsync(d.d_wp_prev.p, prev_wp + 3 * P.q0, n * 3 * sizeof(double), hipMemcpyHostToDevice, d.stream));
-                        HIPCHK(h, hipMemcpyAsync(d.d_wp_pdim.p, prev_dim + P.q0, n * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-                    }
-                    fx::WaypointStArgs A;
-                    A.cells = P.d_cells;
-                    A.offsets = P.d_off;
-                    A.len = P.d_len;
-                    A.nq = (long long)P.n;
-                    A.map_start = d.d_wp_ms.p;
-                    A.reso = reso;
-                    A.ox = origin[0];
-                    A.oy = origin[1];
-                    A.pos = d.d_wp_in.p;
-                    A.goal = d.d_wp_in.p + n * 3;
-                    A.end_occu = end_occu ? d.d_wp_eo.p : nullptr;
-                    A.dis_wp_tre = dis_wp_tre;
-                    A.ang_wp_tre = ang_wp_tre;
-                    A.prev_wp = prev_wp ? d.d_wp_prev.p : nullptr;
-                    A.prev_dim = prev_wp ? d.d_wp_pdim.p : nullptr;
-                    A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
-                    A.out_wp = d.d_wp_out.p;
-                    A.out_dim = d.d_wp_dim.p;
-                    A.out_goal = d.d_wp_out.p + n * 3;
-                    A.out_ang = d.d_wp_ang.p;
-                    hipLaunchKernelGGL(fx::k_waypoint_st, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
-                    HIPCHK(h, hipGetLastError());
-                    HIPCHK(h, hipMemcpyAsync(out_wp + 3 * P.q0, d.d_wp_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-                    HIPCHK(h, hipMemcpyAsync(out_goal + 3 * P.q0, d.d_wp_out.p + n * 3, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-                    HIPCHK(h, hipMemcpyAsync(out_dim + P.q0, d.d_wp_dim.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
-                    HIPCHK(h, hipMemcpyAsync(out_ang_wp + P.q0, d.d_wp_ang.p, n * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-                }
-                return FXJPS_OK;
-            }();
-            if (rc) {  // copies of the devices in front of the failing one are still queued on the caller's buffers
-                drain_all(h);
-                return rc;
-            }
-            for (auto& P : parts)
-                if (hipSetDevice(P.d->dev) != hipSuccess || hipStreamSynchronize(P.d->stream) != hipSuccess) rc = fail(h, FXJPS_E_HIP, "waypoint kernel failed");
-            return rc;
-        }
+            fx::WaypointStArgs A;
+            A.cells = P.d_cells;
+            A.offsets = P.d_off;
+            A.len = P.d_len;
+            A.nq = (long long)P.n;
+            A.map_start = d.wp.d_ms.p;
+            A.reso = reso;
+            A.ox = origin[0];
+            A.oy = origin[1];
+            A.pos = d.wp.d_in.p;
+            A.goal = d.wp.d_in.p + n * 3;
+            A.end_occu = end_occu ? d.wp.d_eo.p : nullptr;
+            A.dis_wp_tre = dis_wp_tre;
+            A.ang_wp_tre = ang_wp_tre;
+            A.prev_wp = prev_wp ? d.wp.d_prev.p : nullptr;
+            A.prev_dim = prev_wp ? d.wp.d_pdim.p : nullptr;
+            A.T = fx::WpAtab{d.wp.d_atab.p, d.wp.atab_a, d.wp.atab_b};
+            A.out_wp = d.wp.d_out.p;
+            A.out_dim = d.wp.d_dim.p;
+            A.out_goal = d.wp.d_out.p + n * 3;
+            A.out_ang = d.wp.d_ang.p;
+            hipLaunchKernelGGL(fx::k_waypoint_st, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(out_wp + 3 * P.q0, d.wp.d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(h, hipMemcpyAsync(out_goal + 3 * P.q0, d.wp.d_out.p + n * 3, n * 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(h, hipMemcpyAsync(out_dim + P.q0, d.wp.d_dim.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(h, hipMemcpyAsync(out_ang_wp + P.q0, d.wp.d_ang.p, n * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+            return FXJPS_OK;
+        };
+        return wp_queue_then_collect(h, S, queue, [] {});
     }
-    // ---- on host threads: a map_start so far off the grid that the table of angles would not fit (or FXJPS_WAYPOINT_ST_HOST=1)
-    // path q: its cells and their number (the last batch's paths are in the handle's pinned host buffers, shard by shard)
-    auto path_of = [&](int64_t q, const int32_t** c) -> int64_t {
-        if (cells_xy) {
-            *c = cells_xy + 2 * offsets[q];
-            return offsets[q + 1] - offsets[q];
-        }
-        for (auto& d : h->devs)
-            if (q >= d.q0 && q < d.q0 + d.nq) {
-                const int64_t i = q - d.q0;
-                *c = d.h_cells.p + 2 * d.h_offsets.p[i];
-                return d.h_offsets.p[i + 1] - d.h_offsets.p[i];
-            }
-        *c = nullptr;
-        return 0;
-    };
-    int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 256));
-    nt = (int)std::min<int64_t>(nt, std::max<int64_t>(nq / 256, 1));
-    std::vector<int> bad((size_t)nt, 0);
-    auto work = [&](int t) {
-        for (int64_t q = nq * t / nt; q < nq * (t + 1) / nt; q++) {
-            const int32_t* c = nullptr;
-            const int64_t n = path_of(q, &c);
-            if (n <= 0) {  // no path: wp = global_goal    global_planner_st.py:287-290
-                for (int k = 0; k < 3; k++) out_wp[3 * q + k] = out_goal[3 * q + k] = goal[3 * q + k];
-                out_dim[q] = 3;
-                out_ang_wp[q] = 0.0;
-                continue;
-            }
-            const bool hp = prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3);
-            if (fxjps_waypoint_st(c, (int32_t)n, map_start + 2 * q, reso, origin, pos + 3 * q, goal + 3 * q, end_occu ? end_occu[q] : 0, dis_wp_tre,
-                                  ang_wp_tre, hp ? prev_wp + 3 * q : nullptr, hp ? prev_dim[q] : 0, out_wp + 3 * q, out_dim + q, out_goal + 3 * q,
-                                  out_ang_wp + q) != FXJPS_OK)
-                bad[(size_t)t] = 1;
-        }
-    };
-    (void)run_side_by_side((size_t)nt, [&](size_t t) {
-        work((int)t);
-        return 0;
-    });
-    for (int b : bad)
-        if (b) return fail(h, FXJPS_E_ARG, "fxjps_waypoint_st failed on a path");
+    // ---- on host threads
+    const WpStHost A{nullptr, map_start, &reso, origin, false, pos, goal, end_occu, dis_wp_tre, ang_wp_tre, prev_wp, prev_dim,
+                     out_wp, out_dim, out_goal, out_ang_wp, nullptr, nullptr};
+    if (wp_st_on_host(S, nq, nthreads, A) >= 0) return fail(h, FXJPS_E_ARG, "fxjps_waypoint_st failed on a path");
     return FXJPS_OK;
 }
 
@@ -3476,16 +3556,6 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
 // fxjps_tick_outputs_slots is the same call with `K` set: the record of a query grows by its home position,
 // the result by the Point and the direct path's length, the output buffer by the two world-frame sections, and the launch
 // is k_tick_outputs_slots.  With K == nullptr every byte staged, launched and copied is what it was before that call existed.
-struct TickIO {
-    const double* home_xy;
-    double* out_point;
-    double* out_path_xyz;
-    int64_t path_capacity;
-    double* out_dir_xyz;
-    int32_t* out_dir_n;
-    int32_t* out_dir_back;
-    int64_t dir_capacity;
-};
 static int wp_slots_call(fxjps_t* h, const char* fn, const TickIO* K, int64_t nq, const int64_t* offsets, const int32_t* cells_xy,
                          const int32_t* grid_ids, const int32_t* rule, const int32_t* map_start, const double* reso, const double* origin,
                          const double* pos, const double* goal, const int32_t* end_occu, double dis_wp_tre, double ang_wp_tre,
@@ -3517,262 +3587,142 @@ static int wp_slots_call(fxjps_t* h, const char* fn, const TickIO* K, int64_t nq
                         ids[q] < 0 || ids[q] >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
     }
     if (n_st > 0 && !map_start) return fail(h, FXJPS_E_ARG, "the st rule needs map_start");
-    if (!resident) {
-        if (offsets[0] != 0) return fail(h, FXJPS_E_ARG, "query 0: offsets[0] must be 0");
-        for (int64_t q = 0; q < nq; q++) {
-            if (offsets[q + 1] < offsets[q]) return fail(h, FXJPS_E_ARG, "query %lld: offsets must ascend", (long long)q);
-            if (rule[q] == 1)
-                for (int64_t i = 2 * offsets[q]; i < 2 * offsets[q + 1]; i++)
-                    if (cells_xy[i] < 0) return fail(h, FXJPS_E_ARG, "query %lld: negative cell", (long long)q);
-        }
-    }
     // the paths: the caller's CSR (context 0 takes all of them, inside its staged input), or the last batch's, shard by shard
-    struct Part {
-        DevCtx* d;
-        int64_t q0, n, total, kept_at;
-        const long long* h_off;  // host copy of the part's offsets (local: h_off[0] == 0)
-    };
-    std::vector<Part> parts;
-    int64_t kept_base = 0;
-    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
-    if (!resident) {
-        parts.push_back(Part{&h->devs[0], 0, nq, offsets[nq], 0, reinterpret_cast<const long long*>(offsets)});
-        kept_base = offsets[nq];
-    } else {
-        for (auto& d : h->devs) {
-            if (d.nq == 0) continue;
-            parts.push_back(Part{&d, d.q0, d.nq, d.h_offsets.p[d.nq], kept_base, d.h_offsets.p});
-            kept_base += d.h_offsets.p[d.nq];
-        }
-    }
+    WpPaths S;
+    if (int rc = S.resolve(h, nq, offsets, cells_xy, true, [&](int64_t q) { return rule[q] == 1; })) return rc;
     // the first query whose range would not fit (query q ends at end(q) [+ 2 (q + 1)])
     const auto first_over = [&](int64_t cap, int64_t per_q) -> int64_t {
-        for (auto& P : parts)
+        for (auto& P : S.parts)
             for (int64_t i = 0; i < P.n; i++)
                 if (P.kept_at + P.h_off[i + 1] + per_q * (P.q0 + i + 1) > cap) return P.q0 + i;
         return -1;
     };
-    if (out_kept_cells && kept_capacity < kept_base) {
+    if (out_kept_cells && kept_capacity < S.total) {
         if (K)
             return fail(h, FXJPS_E_ARG, "query %lld: out_kept_cells holds %lld pairs, the paths have %lld", (long long)first_over(kept_capacity, 0),
-                        (long long)kept_capacity, (long long)kept_base);
-        return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)kept_base);
+                        (long long)kept_capacity, (long long)S.total);
+        return fail(h, FXJPS_E_ARG, "out_kept_cells holds %lld pairs, the paths have %lld", (long long)kept_capacity, (long long)S.total);
     }
     if (K) {
-        if (K->out_path_xyz && K->path_capacity < kept_base)
+        if (K->out_path_xyz && K->path_capacity < S.total)
             return fail(h, FXJPS_E_ARG, "query %lld: out_path_xyz holds %lld triples, the paths have %lld", (long long)first_over(K->path_capacity, 0),
-                        (long long)K->path_capacity, (long long)kept_base);
-        if (K->out_dir_xyz && K->dir_capacity < kept_base + 2 * nq)
+                        (long long)K->path_capacity, (long long)S.total);
+        if (K->out_dir_xyz && K->dir_capacity < S.total + 2 * nq)
             return fail(h, FXJPS_E_ARG, "query %lld: out_dir_xyz holds %lld triples, the direct paths need %lld", (long long)first_over(K->dir_capacity, 2),
-                        (long long)K->dir_capacity, (long long)(kept_base + 2 * nq));
+                        (long long)K->dir_capacity, (long long)(S.total + 2 * nq));
     }
-    // path q on the host (the st rule's host form)
-    const auto path_of = [&](int64_t q, const int32_t** c) -> int64_t {
-        if (!resident) {
-            *c = cells_xy + 2 * offsets[q];
-            return offsets[q + 1] - offsets[q];
-        }
-        for (auto& P : parts)
-            if (q >= P.q0 && q < P.q0 + P.n) {
-                *c = P.d->h_cells.p + 2 * P.h_off[q - P.q0];
-                return P.h_off[q - P.q0 + 1] - P.h_off[q - P.q0];
-            }
-        *c = nullptr;
-        return 0;
-    };
-    // ... and where its triples start in the caller's arrays
-    const auto path_at = [&](int64_t q) -> int64_t {
-        if (!resident) return offsets[q];
-        for (auto& P : parts)
-            if (q >= P.q0 && q < P.q0 + P.n) return P.kept_at + P.h_off[q - P.q0];
-        return 0;
-    };
-    // ---- the st rule's table of angles: the range of (cell + 1 - map_start) over the st queries of the call (resident paths
-    // lie within the largest slot their batch named)
-    bool st_on_host = n_st > 0 && getenv("FXJPS_WAYPOINT_ST_HOST") && atoi(getenv("FXJPS_WAYPOINT_ST_HOST")) != 0;
-    if (n_st > 0 && !st_on_host) {
-        long long am = 0, bm = 0;
-        for (int64_t q = 0; q < nq; q++) {
-            if (rule[q] != 0) continue;
-            const long long mx = map_start[2 * q], my = map_start[2 * q + 1];
-            if (resident) {
-                am = std::max(am, std::max(std::llabs(1 - mx), std::llabs((long long)h->last_slots_W - mx)));
-                bm = std::max(bm, std::max(std::llabs(1 - my), std::llabs((long long)h->last_slots_H - my)));
-            } else {
-                for (int64_t i = offsets[q]; i < offsets[q + 1]; i++) {
-                    am = std::max(am, std::llabs((long long)cells_xy[2 * i] + 1 - mx));
-                    bm = std::max(bm, std::llabs((long long)cells_xy[2 * i + 1] + 1 - my));
-                }
-            }
-        }
-        if (wp_atab_fits(am, bm)) {
-            std::vector<WpPart> tp;
-            for (auto& P : parts) tp.push_back(WpPart{P.d, P.q0, P.n, nullptr, nullptr, nullptr, 0});
-            int rc = wp_ensure_atab(h, tp, am, bm, nthreads);
-            if (rc) return rc;
-        } else {
-            st_on_host = true;
-        }
+    // ---- the st rule's table of angles, or the rule's host form
+    bool st_on_host = false;
+    if (n_st > 0) {
+        const int place = wp_st_place(h, S, nq, rule, map_start, nthreads, false);
+        if (place < 0) return place;
+        st_on_host = place != FXJPS_OK;
     }
     // ---- queue every context, then collect
     static_assert(sizeof(fx::WpSlotQuery) % 8 == 0 && sizeof(fx::WpSlotResult) % 8 == 0, "the offsets and cells behind the records stay aligned");
     static_assert(sizeof(fx::TickQuery) % 8 == 0 && sizeof(fx::TickResult) % 8 == 0 && offsetof(fx::TickQuery, s) == 0 && offsetof(fx::TickResult, r) == 0,
                   "a tick record begins with the waypoint record, and the doubles behind the records stay aligned");
-    int rc = [&]() -> int {
-        for (auto& P : parts) {
-            DevCtx& d = *P.d;
-            HIPCHK(h, hipSetDevice(d.dev));
-            const size_t n = (size_t)P.n, tot = (size_t)P.total;
-            const size_t rec = K ? sizeof(fx::TickQuery) : sizeof(fx::WpSlotQuery);
-            const size_t in_off = n * rec, in_cells = in_off + (n + 1) * sizeof(long long);
-            const size_t in_bytes = resident ? in_off : in_cells + tot * 2 * sizeof(int32_t);
-            // out: the records | (K: path3 triples | direct-path triples |) the kept cells
-            const size_t out_path = n * (K ? sizeof(fx::TickResult) : sizeof(fx::WpSlotResult));
-            const size_t out_dir = out_path + (K ? tot * 3 * sizeof(double) : 0);
-            const size_t out_kept = out_dir + (K ? (tot + 2 * n) * 3 * sizeof(double) : 0);
-            const size_t out_bytes = out_kept + std::max<size_t>(tot, 1) * 2 * sizeof(int32_t);
-            HIPCHK(h, d.h_wps_in.ensure(in_bytes));
-            HIPCHK(h, d.d_wps_in.ensure(in_bytes));
-            HIPCHK(h, d.h_wps_out.ensure(out_bytes));
-            HIPCHK(h, d.d_wps_out.ensure(out_bytes));
-            for (size_t i = 0; i < n; i++) {
-                const int64_t q = P.q0 + (int64_t)i;
-                fx::WpSlotQuery& r = *reinterpret_cast<fx::WpSlotQuery*>(d.h_wps_in.p + i * rec);  // (a TickQuery begins with one)
-                r = fx::WpSlotQuery{};
-                if (K) {
-                    fx::TickQuery& t = *reinterpret_cast<fx::TickQuery*>(d.h_wps_in.p + i * rec);
-                    t.hx = K->home_xy ? K->home_xy[2 * q] : 0.0;
-                    t.hy = K->home_xy ? K->home_xy[2 * q + 1] : 0.0;
-                }
-                r.rule = rule[q];
-                if (r.rule == 1) {
-                    const GridBufs& g = d.slots[(size_t)ids[q]];
-                    r.occ = g.occ.p;
-                    r.W = g.W;
-                    r.H = g.H;
-                } else {
-                    r.msx = map_start[2 * q];
-                    r.msy = map_start[2 * q + 1];
-                    if (prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3)) {
-                        r.pdim = prev_dim[q];
-                        for (int k = 0; k < 3; k++) r.prev[k] = prev_wp[3 * q + k];
-                    }
-                    if (st_on_host) r.rule = 2;  // (not the kernel's: fxjps_waypoint_st below, on host threads)
-                }
-                r.reso = reso[q];
-                r.ox = origin[2 * q];
-                r.oy = origin[2 * q + 1];
-                r.eo = end_occu ? end_occu[q] : 0;
-                for (int k = 0; k < 3; k++) {
-                    r.pos[k] = pos[3 * q + k];
-                    r.goal[k] = goal[3 * q + k];
-                }
+    const auto queue = [&](WpPaths::Part& P) -> int {
+        DevCtx& d = *P.d;
+        HIPCHK(h, hipSetDevice(d.dev));
+        const size_t n = (size_t)P.n, tot = (size_t)P.total;
+        const size_t rec = K ? sizeof(fx::TickQuery) : sizeof(fx::WpSlotQuery);
+        const size_t in_off = n * rec, in_cells = in_off + (n + 1) * sizeof(long long);
+        const size_t in_bytes = S.resident ? in_off : in_cells + tot * 2 * sizeof(int32_t);
+        // out: the records | (K: path3 triples | direct-path triples |) the kept cells
+        const size_t out_path = n * (K ? sizeof(fx::TickResult) : sizeof(fx::WpSlotResult));
+        const size_t out_dir = out_path + (K ? tot * 3 * sizeof(double) : 0);
+        const size_t out_kept = out_dir + (K ? (tot + 2 * n) * 3 * sizeof(double) : 0);
+        const size_t out_bytes = out_kept + std::max<size_t>(tot, 1) * 2 * sizeof(int32_t);
+        HIPCHK(h, d.wp.h_recs_in.ensure(in_bytes));
+        HIPCHK(h, d.wp.d_recs_in.ensure(in_bytes));
+        HIPCHK(h, d.wp.h_recs_out.ensure(out_bytes));
+        HIPCHK(h, d.wp.d_recs_out.ensure(out_bytes));
+        for (size_t i = 0; i < n; i++) {
+            const int64_t q = P.q0 + (int64_t)i;
+            fx::WpSlotQuery& r = *reinterpret_cast<fx::WpSlotQuery*>(d.wp.h_recs_in.p + i * rec);  // (a TickQuery begins with one)
+            r = fx::WpSlotQuery{};
+            if (K) {
+                fx::TickQuery& t = *reinterpret_cast<fx::TickQuery*>(d.wp.h_recs_in.p + i * rec);
+                t.hx = K->home_xy ? K->home_xy[2 * q] : 0.0;
+                t.hy = K->home_xy ? K->home_xy[2 * q + 1] : 0.0;
             }
-            if (!resident) {
-                memcpy(d.h_wps_in.p + in_off, offsets, (n + 1) * sizeof(long long));
-                if (tot > 0) memcpy(d.h_wps_in.p + in_cells, cells_xy, tot * 2 * sizeof(int32_t));
-            }
-            HIPCHK(h, hipMemcpyAsync(d.d_wps_in.p, d.h_wps_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
-            size_t back = out_path;  // the copy back ends after the last section the caller asked for
-            if (!K) {
-                fx::WaypointSlotsArgs A;
-                A.in = reinterpret_cast<const fx::WpSlotQuery*>(d.d_wps_in.p);
-                A.out = reinterpret_cast<fx::WpSlotResult*>(d.d_wps_out.p);
-                A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
-                A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
-                A.len = resident ? d.d_len.p : nullptr;
-                A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
-                A.nq = (long long)P.n;
-                A.dis_wp_tre = dis_wp_tre;
-                A.ang_wp_tre = ang_wp_tre;
-                A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
-                hipLaunchKernelGGL(fx::k_waypoint_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            r.rule = rule[q];
+            if (r.rule == 1) {
+                const GridBufs& g = d.slots[(size_t)ids[q]];
+                r.occ = g.occ.p;
+                r.W = g.W;
+                r.H = g.H;
             } else {
-                fx::TickOutputsArgs A;
-                A.in = reinterpret_cast<const fx::TickQuery*>(d.d_wps_in.p);
-                A.out = reinterpret_cast<fx::TickResult*>(d.d_wps_out.p);
-                A.cells = resident ? d.d_cells.p : reinterpret_cast<const int32_t*>(d.d_wps_in.p + in_cells);
-                A.offsets = resident ? d.d_offsets.p : reinterpret_cast<const long long*>(d.d_wps_in.p + in_off);
-                A.len = resident ? d.d_len.p : nullptr;
-                A.kept = reinterpret_cast<int32_t*>(d.d_wps_out.p + out_kept);
-                A.path_xyz = reinterpret_cast<double*>(d.d_wps_out.p + out_path);
-                A.dir_xyz = reinterpret_cast<double*>(d.d_wps_out.p + out_dir);
-                A.nq = (long long)P.n;
-                A.dis_wp_tre = dis_wp_tre;
-                A.ang_wp_tre = ang_wp_tre;
-                A.T = fx::WpAtab{d.d_atab.p, d.atab_a, d.atab_b};
-                hipLaunchKernelGGL(fx::k_tick_outputs_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
-                if (K->out_path_xyz) back = out_dir;
-                if (K->out_dir_xyz) back = out_kept;
+                r.msx = map_start[2 * q];
+                r.msy = map_start[2 * q + 1];
+                if (prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3)) {
+                    r.pdim = prev_dim[q];
+                    for (int k = 0; k < 3; k++) r.prev[k] = prev_wp[3 * q + k];
+                }
+                if (st_on_host) r.rule = 2;  // (not the kernel's: fxjps_waypoint_st below, on host threads)
             }
-            HIPCHK(h, hipGetLastError());
-            if (out_kept_cells) back = out_kept + tot * 2 * sizeof(int32_t);
-            HIPCHK(h, hipMemcpyAsync(d.h_wps_out.p, d.d_wps_out.p, back, hipMemcpyDeviceToHost, d.stream));
+            r.reso = reso[q];
+            r.ox = origin[2 * q];
+            r.oy = origin[2 * q + 1];
+            r.eo = end_occu ? end_occu[q] : 0;
+            for (int k = 0; k < 3; k++) {
+                r.pos[k] = pos[3 * q + k];
+                r.goal[k] = goal[3 * q + k];
+            }
         }
+        if (!S.resident) {
+            memcpy(d.wp.h_recs_in.p + in_off, P.h_off, (n + 1) * sizeof(long long));
+            if (tot > 0) memcpy(d.wp.h_recs_in.p + in_cells, P.h_cells, tot * 2 * sizeof(int32_t));
+        }
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_recs_in.p, d.wp.h_recs_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+        size_t back = out_path;  // the copy back ends after the last section the caller asked for
+        if (!K) {
+            fx::WaypointSlotsArgs A;
+            A.in = reinterpret_cast<const fx::WpSlotQuery*>(d.wp.d_recs_in.p);
+            A.out = reinterpret_cast<fx::WpSlotResult*>(d.wp.d_recs_out.p);
+            A.cells = S.resident ? P.d_cells : reinterpret_cast<const int32_t*>(d.wp.d_recs_in.p + in_cells);
+            A.offsets = S.resident ? P.d_off : reinterpret_cast<const long long*>(d.wp.d_recs_in.p + in_off);
+            A.len = S.resident ? P.d_len : nullptr;
+            A.kept = reinterpret_cast<int32_t*>(d.wp.d_recs_out.p + out_kept);
+            A.nq = (long long)P.n;
+            A.dis_wp_tre = dis_wp_tre;
+            A.ang_wp_tre = ang_wp_tre;
+            A.T = fx::WpAtab{d.wp.d_atab.p, d.wp.atab_a, d.wp.atab_b};
+            hipLaunchKernelGGL(fx::k_waypoint_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+        } else {
+            fx::TickOutputsArgs A;
+            A.in = reinterpret_cast<const fx::TickQuery*>(d.wp.d_recs_in.p);
+            A.out = reinterpret_cast<fx::TickResult*>(d.wp.d_recs_out.p);
+            A.cells = S.resident ? P.d_cells : reinterpret_cast<const int32_t*>(d.wp.d_recs_in.p + in_cells);
+            A.offsets = S.resident ? P.d_off : reinterpret_cast<const long long*>(d.wp.d_recs_in.p + in_off);
+            A.len = S.resident ? P.d_len : nullptr;
+            A.kept = reinterpret_cast<int32_t*>(d.wp.d_recs_out.p + out_kept);
+            A.path_xyz = reinterpret_cast<double*>(d.wp.d_recs_out.p + out_path);
+            A.dir_xyz = reinterpret_cast<double*>(d.wp.d_recs_out.p + out_dir);
+            A.nq = (long long)P.n;
+            A.dis_wp_tre = dis_wp_tre;
+            A.ang_wp_tre = ang_wp_tre;
+            A.T = fx::WpAtab{d.wp.d_atab.p, d.wp.atab_a, d.wp.atab_b};
+            hipLaunchKernelGGL(fx::k_tick_outputs_slots, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, d.stream, A);
+            if (K->out_path_xyz) back = out_dir;
+            if (K->out_dir_xyz) back = out_kept;
+        }
+        HIPCHK(h, hipGetLastError());
+        if (out_kept_cells) back = out_kept + tot * 2 * sizeof(int32_t);
+        HIPCHK(h, hipMemcpyAsync(d.wp.h_recs_out.p, d.wp.d_recs_out.p, back, hipMemcpyDeviceToHost, d.stream));
         return FXJPS_OK;
-    }();
-    if (rc) {
-        drain_all(h);
-        return rc;
-    }
-    // the st rule on host threads (a table of angles that would not fit, or FXJPS_WAYPOINT_ST_HOST=1), beside the device's work
-    int bad_q = -1;
-    if (st_on_host) {
-        int nt = std::max(1, std::min<int>(nthreads > 0 ? nthreads : (int)std::thread::hardware_concurrency(), 256));
-        nt = (int)std::min<int64_t>(nt, std::max<int64_t>(nq / 256, 1));
-        std::vector<int64_t> bad((size_t)nt, -1);
-        (void)run_side_by_side((size_t)nt, [&](size_t t) {
-            for (int64_t q = nq * (int64_t)t / nt; q < nq * (int64_t)(t + 1) / nt; q++) {
-                if (rule[q] != 0) continue;
-                const int32_t* c = nullptr;
-                const int64_t n = path_of(q, &c);
-                double gl[3], ang = 0.0;
-                int32_t dim = 3;
-                if (n <= 0) {  // no path: wp = global_goal    global_planner_st.py:287-290
-                    for (int k = 0; k < 3; k++) out_wp[3 * q + k] = gl[k] = goal[3 * q + k];
-                } else {
-                    const bool hp = prev_wp && (prev_dim[q] == 2 || prev_dim[q] == 3);
-                    if (fxjps_waypoint_st(c, (int32_t)std::min<int64_t>(n, 0x7FFFFFFF), map_start + 2 * q, reso[q], origin + 2 * q, pos + 3 * q,
-                                          goal + 3 * q, end_occu ? end_occu[q] : 0, dis_wp_tre, ang_wp_tre, hp ? prev_wp + 3 * q : nullptr,
-                                          hp ? prev_dim[q] : 0, out_wp + 3 * q, &dim, gl, &ang) != FXJPS_OK && bad[t] < 0)
-                        bad[t] = q;
-                }
-                if (out_dim) out_dim[q] = dim;
-                if (out_ang_wp) out_ang_wp[q] = ang;
-                if (out_n_kept) out_n_kept[q] = 0;
-                if (out_goal)
-                    for (int k = 0; k < 3; k++) out_goal[3 * q + k] = gl[k];
-                if (K) {  // st:292-298, 335, 356-359 for the paths the host walked, by the functions the kernel calls
-                    if (K->out_point) {
-                        K->out_point[3 * q] = out_wp[3 * q];
-                        K->out_point[3 * q + 1] = out_wp[3 * q + 1];
-                        K->out_point[3 * q + 2] = fx::tick_point_z(out_wp[3 * q], out_wp[3 * q + 1], gl[0], gl[1], gl[2], K->home_xy[2 * q], K->home_xy[2 * q + 1]);
-                    }
-                    if (K->out_dir_n) K->out_dir_n[q] = 0;
-                    if (K->out_dir_back) K->out_dir_back[q] = 0;
-                    if (K->out_path_xyz && n > 0) {
-                        double* p3 = K->out_path_xyz + 3 * path_at(q);
-                        for (int64_t i = 0; i < n; i++) {
-                            p3[3 * i] = fx::wp_world(c[2 * i] + 1, reso[q], origin[2 * q]);
-                            p3[3 * i + 1] = fx::wp_world(c[2 * i + 1] + 1, reso[q], origin[2 * q + 1]);
-                            p3[3 * i + 2] = 0.0;
-                        }
-                    }
-                }
-            }
-            return 0;
-        });
-        for (int64_t b : bad)
-            if (b >= 0 && bad_q < 0) bad_q = (int)b;
-    }
-    for (auto& P : parts)
-        if (hipSetDevice(P.d->dev) != hipSuccess || hipStreamSynchronize(P.d->stream) != hipSuccess) rc = fail(h, FXJPS_E_HIP, "waypoint kernel failed");
-    if (rc) return rc;
-    if (bad_q >= 0) return fail(h, FXJPS_E_ARG, "query %d: fxjps_waypoint_st failed on its path", bad_q);
-    for (auto& P : parts) {
+    };
+    // (the st rule on host threads runs beside the device's work)
+    int64_t bad_q = -1;
+    const WpStHost A{rule, map_start, reso, origin, true, pos, goal, end_occu, dis_wp_tre, ang_wp_tre, prev_wp, prev_dim,
+                     out_wp, out_dim, out_goal, out_ang_wp, out_n_kept, K};
+    if (int rc = wp_queue_then_collect(h, S, queue, [&] { bad_q = st_on_host ? wp_st_on_host(S, nq, nthreads, A) : -1; })) return rc;
+    if (bad_q >= 0) return fail(h, FXJPS_E_ARG, "query %d: fxjps_waypoint_st failed on its path", (int)bad_q);
+    for (auto& P : S.parts) {
         const size_t n = (size_t)P.n, tot = (size_t)P.total;
         const size_t rec = K ? sizeof(fx::TickResult) : sizeof(fx::WpSlotResult);
-        const uint8_t* base = P.d->h_wps_out.p;
+        const uint8_t* base = P.d->wp.h_recs_out.p;
         const double* path3 = reinterpret_cast<const double*>(base + n * rec);
         const double* dir = path3 + (K ? tot * 3 : 0);
         const int32_t* kept = reinterpret_cast<const int32_t*>(dir + (K ? (tot + 2 * n) * 3 : 0));

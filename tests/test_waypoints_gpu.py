@@ -209,3 +209,109 @@ def test_st_rule_on_the_device_equals_the_host_form(planner, monkeypatch):
         b = waypoints.select_st_batch(planner, 901, ms[:901], reso, origin, pos[:901], goal[:901], eo[:901], prev[:901], pdim[:901],
                                       paths=(res[0], res[1]))
         assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+ATAB_MAX = 1 << 27  # entries of the st rule's table of angles (fxjps.hip)
+
+
+def st_range(paths, map_start):
+    """The library's range rule for explicit paths, restated: (am, bm) = the largest |cell + 1 - map_start| per axis, and
+    the entries of the table that covers them."""
+    d = np.abs(np.concatenate([np.asarray(p, np.int64).reshape(-1, 2) for p in paths]) + 1 - np.asarray(map_start, np.int64))
+    am, bm = (int(d[:, 0].max()), int(d[:, 1].max())) if len(d) else (0, 0)
+    return am, bm, (am + 1) * (2 * bm + 1)
+
+
+def test_batch_calls_share_paths_table_and_host_walk(monkeypatch):
+    """The three batch entry points resolve their paths, size the table of angles and walk the st rule on host threads by
+    the same functions.  Seven explicit paths, map_start (1, 1): of 0, 1 and 2 points, of 64 and 65 (either side of one
+    wavefront's window), three points near (10000, 5) and three near (5, 10000).  (a) the same st inputs through
+    select_st_batch, select_slots_batch and tick_outputs_slots, on the device and with FXJPS_WAYPOINT_ST_HOST=1: byte-equal,
+    and equal to select_st per path; (b) the table grows, is reused, and starts over when the union of two ranges would not
+    fit; (c) a single call's path, left in the pinned host buffers, is handed over like a caller's CSR."""
+    import fuxi_planner_amd as fx
+    from fuxi_planner_amd import waypoints
+    def arc(n):  # (the bearing turns point by point, as in test_st_rule_on_the_device_equals_the_host_form)
+        phi = np.linspace(0.0, 1.1, n)
+        return np.stack([np.rint(100 * np.sin(phi)), np.rint(100 * np.cos(phi))], 1).astype(np.int32) + 7
+    paths = [np.zeros((0, 2), np.int32), np.array([(3, 4)], np.int32), np.array([(3, 4), (9, 12)], np.int32), arc(64), arc(65),
+             np.array([(9990, 3), (9996, 7), (10000, 10)], np.int32), np.array([(3, 9990), (7, 9996), (10, 10000)], np.int32)]
+    assert [len(p) for p in paths] == [0, 1, 2, 64, 65, 3, 3]
+    n = len(paths)
+    ms, reso, origin = (1, 1), 0.25, (1.5, -4.0)
+    rng = np.random.default_rng(5)
+    pos = np.c_[rng.uniform(0, 10, n), rng.uniform(0, 10, n), rng.choice([0.0, 1.0], n)]
+    goal = np.c_[rng.uniform(0, 3000, n), rng.uniform(0, 3000, n), np.full(n, 1.5)]
+    eo = np.array([0, 0, 0, 0, 1, 0, 0], np.int32)
+    prev = rng.uniform(-5, 50, (n, 3))
+    pdim = np.array([0, 2, 3, 2, 3, 0, 2], np.int32)
+    home = rng.uniform(-5, 5, (n, 2))
+    expect = []
+    for q, p in enumerate(paths):
+        if len(p) == 0:  # no path: wp = global_goal
+            expect.append((goal[q].copy(), goal[q].copy(), 0.0))
+            continue
+        expect.append(waypoints.select_st(p, ms, reso, origin, pos[q], goal[q], int(eo[q]), prev_wp=None if pdim[q] == 0 else prev[q, :pdim[q]]))
+
+    def csr(sel):
+        off = np.zeros(len(sel) + 1, np.int64)
+        off[1:] = np.cumsum([len(paths[q]) for q in sel])
+        return off, np.concatenate([paths[q] for q in sel]).astype(np.int32).reshape(-1, 2)
+
+    def equals_one_path(got, sel):
+        for i, q in enumerate(sel):
+            w1, g1, a1 = expect[q]
+            assert got[0][i, :got[1][i]].tobytes() == w1.tobytes() and not got[0][i, got[1][i]:].any(), q
+            assert got[2][i].tobytes() == g1.tobytes() and got[3][i] == a1, q
+
+    with fx.Planner([0]) as p:
+        occ = np.zeros((64, 64), np.uint8)
+        occ[20:44, 31] = 1
+        p.set_grid_occ(occ)
+
+        def st(sel):
+            return waypoints.select_st_batch(p, len(sel), ms, reso, origin, pos[sel], goal[sel], eo[sel], prev[sel], pdim[sel], paths=csr(sel))
+        # (b) first: this handle's table starts empty.  short paths; the path near (10000, 5) grows the table to 10001 x 21; the
+        # short paths fit the larger table; the path near (5, 10000) alone is 11 x 20001, the union 10001 x 20001 is too large
+        short, east, north = [0, 1, 2, 3, 4], [5], [6]
+        for sel, entries in ((short, None), (east, 10001 * 21), (short, None), (north, 11 * 20001)):
+            am, bm, size = st_range([paths[q] for q in sel], ms)
+            assert size <= ATAB_MAX and (entries is None or size == entries), (sel, am, bm, size)
+            equals_one_path(st(sel), sel)
+        assert st_range([paths[5]], ms)[0] == st_range([paths[6]], ms)[1] == 10000 and 10001 * 20001 > ATAB_MAX
+        # (a) all seven (their common range does not fit the table: the host walk by itself) and the first six (the device)
+        for sel in (list(range(n)), list(range(n - 1))):
+            assert (st_range([paths[q] for q in sel], ms)[2] > ATAB_MAX) == (len(sel) == n)
+            for host in (False, True):
+                if host:
+                    monkeypatch.setenv("FXJPS_WAYPOINT_ST_HOST", "1")
+                a = st(sel)
+                b = waypoints.select_slots_batch(p, [0] * len(sel), ms, reso, origin, pos[sel], goal[sel], eo[sel], prev[sel], pdim[sel], paths=csr(sel))
+                c = waypoints.tick_outputs_slots(p, [0] * len(sel), ms, reso, origin, pos[sel], goal[sel], home[sel], eo[sel], prev[sel], pdim[sel],
+                                                 paths=csr(sel))
+                if host:
+                    monkeypatch.delenv("FXJPS_WAYPOINT_ST_HOST")
+                for k in range(4):  # wp, dim, goal, ang
+                    assert a[k].tobytes() == b[k].tobytes() == c[k].tobytes(), (len(sel), host, k)
+                equals_one_path(a, sel)
+        # (c) a single call: its path is in the pinned host buffers only
+        status, cost, cells = p.plan_one((5, 30), (60, 33))
+        cells = cells.copy()
+        assert status > 2
+        one = (np.array([0, len(cells)], np.int64), cells)
+        for host in (False, True):
+            if host:
+                monkeypatch.setenv("FXJPS_WAYPOINT_ST_HOST", "1")
+            a = waypoints.select_st_batch(p, 1, (6, 31), reso, origin, pos[:1], goal[:1], eo[:1], prev[1:2], pdim[1:2])
+            b = waypoints.select_st_batch(p, 1, (6, 31), reso, origin, pos[:1], goal[:1], eo[:1], prev[1:2], pdim[1:2], paths=one)
+            if host:
+                monkeypatch.delenv("FXJPS_WAYPOINT_ST_HOST")
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+            w1, g1, a1 = waypoints.select_st(cells, (6, 31), reso, origin, pos[0], goal[0], int(eo[0]), prev_wp=prev[1, :2])
+            assert a[0][0, :a[1][0]].tobytes() == w1.tobytes() and a[2][0].tobytes() == g1.tobytes() and a[3][0] == a1
+        p.plan_one((5, 30), (60, 33))
+        a = waypoints.select_ccst_batch(p, 1, reso, origin, pos[:1], goal[:1], eo[:1])
+        b = waypoints.select_ccst_batch(p, 1, reso, origin, pos[:1], goal[:1], eo[:1], paths=one, return_kept=True)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b[:3]))
+        w1, k1, g1 = waypoints.select_ccst(cells, occ, reso, origin, pos[0], goal[0], int(eo[0]), return_goal=True)
+        assert a[0][0].tobytes() == w1.tobytes() and a[1][0].tobytes() == g1.tobytes() and np.array_equal(b[3][:b[2][0]], k1)
