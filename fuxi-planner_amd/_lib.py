@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 780  # FXJPS_VERSION of include/fxjps.h
+VERSION = 790  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -22,9 +22,11 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_set_grid_slot", "fxjps_get_grid_slot", "fxjps_plan_batch_slots_csr", "fxjps_debug_read_slot_maps", "fxjps_debug_read_sets",
            "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch", "fxjps_publish_slots", "fxjps_slot_publish_size",
            "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context", "fxjps_replan_slots",
-           "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size")
+           "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size",
+           "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
+JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
 
 
 class Timing(C.Structure):
@@ -52,6 +54,13 @@ class WorldJob(C.Structure):
                 ("start_xy", C.c_int32 * 2), ("goal_xy_cell", C.c_int32 * 2), ("W", C.c_int32), ("H", C.c_int32),
                 ("map_d", C.c_int32 * 2), ("end_occu", C.c_int32), ("canvas_W", C.c_int32), ("canvas_H", C.c_int32),
                 ("reserved_", C.c_int32)]
+
+
+class Crop(C.Structure):
+    """fxjps_crop_t: what remove_zero_rowscols (global_planner_ccst.py:36-63) makes of one map message
+    (fxjps_prepare_slots_cropped)."""
+    _fields_ = [("bbox", C.c_int32 * 4), ("start0", C.c_int32 * 2), ("lo", C.c_int32 * 2), ("win", C.c_int32 * 2),
+                ("map_o", C.c_double * 2), ("map_t", C.c_double * 2)]
 
 
 class SlotPublish(C.Structure):
@@ -115,6 +124,9 @@ def load():
     if L.fxjps_world_job_size() != C.sizeof(WorldJob):
         raise FxjpsError(E_ARG, "%s has a %d-byte world job; this binding's is %d bytes: rebuild it"
                          % (LIB_PATH, L.fxjps_world_job_size(), C.sizeof(WorldJob)))
+    L.fxjps_crop_size.restype = C.c_int
+    if L.fxjps_crop_size() != C.sizeof(Crop):
+        raise FxjpsError(E_ARG, "%s has a %d-byte crop record; this binding's is %d bytes: rebuild it" % (LIB_PATH, L.fxjps_crop_size(), C.sizeof(Crop)))
     L.fxjps_last_timing_sized.restype = C.c_int
     L.fxjps_last_timing_sized.argtypes = [vp, vp, C.c_int64]
     L.fxjps_rank_preflight.restype = C.c_int
@@ -182,6 +194,10 @@ def load():
     L.fxjps_prepare_slots_world.argtypes = [vp, C.POINTER(WorldJob), C.c_int32]
     L.fxjps_refresh_slots_world.restype = C.c_int
     L.fxjps_refresh_slots_world.argtypes = [vp, C.POINTER(WorldJob), C.c_int32, p_i32]
+    L.fxjps_prepare_slots_cropped.restype = C.c_int
+    L.fxjps_prepare_slots_cropped.argtypes = [vp, C.POINTER(WorldJob), C.c_int32, C.POINTER(Crop)]
+    L.fxjps_refresh_slots_cropped.restype = C.c_int
+    L.fxjps_refresh_slots_cropped.argtypes = [vp, C.POINTER(WorldJob), C.c_int32, p_i32, C.POINTER(Crop)]
     L.fxjps_publish_slots.restype = C.c_int
     L.fxjps_publish_slots.argtypes = [vp, C.POINTER(SlotPublish), C.c_int32]
     L.fxjps_debug_read_slot_maps.restype = C.c_int

@@ -189,6 +189,12 @@ struct DevCtx : GridBufs {
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
     DBuf<int32_t> d_slots_res;
+    // fxjps_prepare_slots_cropped / fxjps_refresh_slots_cropped, first phase: the staged input (fx::CropTable | n box records
+    // | the messages), the windows k_crop_window cuts out of them (what the second phase's gather reads as its raws), and
+    // the box records on their way back
+    HBuf<uint8_t> h_crop_in;
+    DBuf<uint8_t> d_crop_in, d_crop_win;
+    HBuf<int32_t> h_crop_box;
     // prior maps (fxjps_set_prior_map): [W][H] bytes the world-frame calls gather from; W == 0: not set
     struct PriorBuf {
         DBuf<uint8_t> occ;
@@ -1952,6 +1958,10 @@ void fxjps_destroy(fxjps_t* h) {
         d.d_slots_in.release();
         d.h_slots_res.release();
         d.d_slots_res.release();
+        d.h_crop_in.release();
+        d.d_crop_in.release();
+        d.d_crop_win.release();
+        d.h_crop_box.release();
         d.h_pub_in.release();
         d.h_pub_out.release();
         d.d_pub_in.release();
@@ -2632,8 +2642,10 @@ constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GR
 // waited for ONCE, whatever n is.  The results are left in d.h_slots_res.  refresh: a job whose slot holds a grid of the
 // prepared extents is compared with it byte by byte while it is gathered, and built only if a byte differed (DESIGN.md
 // section 3.12); the n `changed` words travel in behind the raws and come back behind the results, in the same two copies.
+// staged_raw (a cropped call's second phase, fxjps_prepare_slots_cropped): the raws are on the device already, job j's at
+// that offset of the context's window buffer, and none is copied or staged again.
 int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh,
-                     const WorldCall* world) {
+                     const WorldCall* world, const size_t* staged_raw) {
     HIPCHK(h, hipSetDevice(d.dev));
     if (int e = ensure_slot_tables(h, d)) return e;
     // (no host wait in front: every call of the library that reads a slot has returned; a buffer that grows is freed by
@@ -2665,7 +2677,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
         fx::SlotJobDev& J = T.job[j];
         J.G = G;
         J.occ = g.occ.p;
-        J.raw = d.d_slots_in.p + p.raw_off;
+        J.raw = staged_raw ? d.d_crop_win.p + staged_raw[j] : d.d_slots_in.p + p.raw_off;
         J.W0 = jb.W0;
         J.H0 = jb.H0;
         J.dx = (int32_t)p.dx;
@@ -2689,7 +2701,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
                 S.px = w.px;
                 S.py = w.py;
             }
-            memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)w.rW * (size_t)w.rH);
+            if (!staged_raw) memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)w.rW * (size_t)w.rH);
         } else {
             memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
         }
@@ -2756,7 +2768,8 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
 namespace {
 // fxjps_prepare_slots (out_kept == nullptr, refresh false) and fxjps_refresh_slots: the checks, the call on every context
 // and the outputs are the same code.
-int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const WorldSrc* world_src = nullptr) {
+int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const WorldSrc* world_src = nullptr,
+               const size_t* staged_raw = nullptr) {
     if (!h) return FXJPS_E_ARG;
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
     if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
@@ -2780,7 +2793,7 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
         if (p.ngx < 0 || p.ngy < 0 || p.ngx >= p.W1 || p.ngy >= p.H1)
             return fail(h, FXJPS_E_ARG, "job %d: goal (%lld, %lld) outside the prepared grid %lldx%lld", j, p.ngx, p.ngy, p.W1, p.H1);
         p.raw_off = in_bytes;
-        const size_t raw_bytes = world_src ? (size_t)world_src[j].rW * (size_t)world_src[j].rH : (size_t)jb.W0 * (size_t)jb.H0;
+        const size_t raw_bytes = staged_raw ? 0 : world_src ? (size_t)world_src[j].rW * (size_t)world_src[j].rH : (size_t)jb.W0 * (size_t)jb.H0;
         in_bytes += (raw_bytes + 15) & ~(size_t)15;
     }
     if (n == 0) return FXJPS_OK;
@@ -2788,7 +2801,7 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
     const WorldCall* world = world_src ? &wc : nullptr;
     if (world) in_bytes += ((size_t)n * sizeof(fx::WorldSrcDev) + 15) & ~(size_t)15;
     // every context prepares every job from the caller's raws (host copies, no collective, as fxjps_set_grid_slot)
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world); });
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world, staged_raw); });
     if (rc) {
         drain_all(h);
         for (int j = 0; j < n; j++) {  // (slots of a call that failed on one context are released on all of them)
@@ -2894,7 +2907,7 @@ bool trunc_i32(double q, long long& out) {
 // (global_planner_st.py:210-227 / global_planner_ccst.py:395-412), in float64 with the reference's operations in the
 // reference's order (the library is built with -ffp-contract=off).  Each world job becomes the fxjps_slot_job_t whose raw is
 // the canvas -- which only the gather ever sees, through WorldSrc -- and slots_call does the rest.
-int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what) {
+int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const size_t* staged_raw = nullptr) {
     if (!h) return FXJPS_E_ARG;
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
     if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
@@ -2965,7 +2978,7 @@ int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int
         s.goal_xy[0] = (int32_t)gc[0];
         s.goal_xy[1] = (int32_t)gc[1];
     }
-    int rc = slots_call(h, sj.data(), n, refresh, out_kept, what, src.data());
+    int rc = slots_call(h, sj.data(), n, refresh, out_kept, what, src.data(), staged_raw);
     if (rc) return rc;
     for (int j = 0; j < n; j++) {
         fxjps_world_job_t& wj = jobs[j];
@@ -2992,6 +3005,227 @@ int fxjps_prepare_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n) { 
 
 int fxjps_refresh_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept) {
     return world_call(h, jobs, n, true, out_kept, "fxjps_refresh_slots_world");
+}
+
+// ------------------------------------------------------------------ ... with the ccst node's crop in front
+int fxjps_crop_size(void) { return (int)sizeof(fxjps_crop_t); }
+
+namespace {
+// The staged input of a cropped call's first phase: the job table, n box records, then the messages.
+constexpr size_t CROP_IN_BOX = (sizeof(fx::CropTable) + 15) & ~(size_t)15;
+constexpr size_t CROP_IN_RAWS = CROP_IN_BOX + sizeof(int32_t) * 4 * FXJPS_MAX_GRID_SLOTS;
+static_assert(CROP_IN_RAWS % 16 == 0, "the messages are read with 16-byte loads");
+
+// One context's first phase: ONE copy in, the two crop launches, ONE copy out, ONE wait.  The boxes are left in
+// d.h_crop_box, the windows in d.d_crop_win at the offsets of the messages (a window is never larger than its message).
+int crop_phase_on(fxjps* h, DevCtx& d, const fxjps_world_job_t* jobs, int n, const std::vector<size_t>& off, size_t raw_bytes,
+                  const std::vector<long long>& start0) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    // (no host wait in front: every call that reads the window buffer has returned)
+    HIPCHK(h, d.h_crop_in.ensure(CROP_IN_RAWS + raw_bytes));
+    HIPCHK(h, d.d_crop_in.ensure(CROP_IN_RAWS + raw_bytes));
+    HIPCHK(h, d.d_crop_win.ensure(raw_bytes));
+    HIPCHK(h, d.h_crop_box.ensure((size_t)n * 4));
+    fx::CropTable& T = *reinterpret_cast<fx::CropTable*>(d.h_crop_in.p);
+    int32_t* h_box = reinterpret_cast<int32_t*>(d.h_crop_in.p + CROP_IN_BOX);
+    int32_t* d_box = reinterpret_cast<int32_t*>(d.d_crop_in.p + CROP_IN_BOX);
+    uint32_t at = 0;
+    for (int j = 0; j < n; j++) {
+        const fxjps_world_job_t& wj = jobs[j];
+        const size_t cells = (size_t)wj.W0 * (size_t)wj.H0;
+        fx::CropJobDev& J = T.job[j];
+        J.raw = d.d_crop_in.p + CROP_IN_RAWS + off[(size_t)j];
+        J.win = d.d_crop_win.p + off[(size_t)j];
+        J.W0 = wj.W0;
+        J.H0 = wj.H0;
+        J.layout = wj.layout;
+        J.ifa = wj.ifa;
+        J.s0x = (int32_t)start0[(size_t)j * 2];
+        J.s0y = (int32_t)start0[(size_t)j * 2 + 1];
+        h_box[4 * j + 0] = h_box[4 * j + 1] = INT32_MAX;
+        h_box[4 * j + 2] = h_box[4 * j + 3] = -1;
+        memcpy(d.h_crop_in.p + CROP_IN_RAWS + off[(size_t)j], wj.raw, cells);
+        T.first[j] = at;
+        at += (uint32_t)((cells + fx::CROP_BLOCK_BYTES - 1) / fx::CROP_BLOCK_BYTES);
+    }
+    T.first[n] = at;
+    HIPCHK(h, hipMemcpyAsync(d.d_crop_in.p, d.h_crop_in.p, CROP_IN_RAWS + raw_bytes, hipMemcpyHostToDevice, d.stream));
+    const fx::CropTable* dT = reinterpret_cast<const fx::CropTable*>(d.d_crop_in.p);
+    hipLaunchKernelGGL(fx::k_crop_bounds, dim3(at), dim3(256), 0, d.stream, dT, d_box, n);
+    hipLaunchKernelGGL(fx::k_crop_window, dim3(at), dim3(256), 0, d.stream, dT, (const int32_t*)d_box, n);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_crop_box.p, d_box, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    return FXJPS_OK;
+}
+
+// The slots of the jobs that took no part are left empty on every context (their buffers keep their room): one copy of the
+// descriptor table per context, whatever their number.
+int empty_slots_everywhere(fxjps* h, const std::vector<int32_t>& slots) {
+    return run_side_by_side(h->devs.size(), [&](size_t r) -> int {
+        DevCtx& d = h->devs[r];
+        HIPCHK(h, hipSetDevice(d.dev));
+        if (int e = ensure_slot_tables(h, d)) return e;
+        for (int32_t s : slots) {
+            d.slots[(size_t)s].W = d.slots[(size_t)s].H = 0;
+            d.h_slot_desc[(size_t)s] = GridDev{};
+        }
+        HIPCHK(h, hipMemcpy(d.d_slot_desc.p, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice));
+        return FXJPS_OK;
+    });
+}
+
+// fxjps_prepare_slots_cropped / fxjps_refresh_slots_cropped: remove_zero_rowscols (global_planner_ccst.py:36-63) in front of
+// world_call.  The box of every message is found on the device (first phase); the float64 arithmetic of ccst:47-54 and the
+// per-job outcome are the host's; the jobs that go on are handed to world_call with their windows where the first phase
+// left them.
+int crop_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, fxjps_crop_t* out_crop, const char* what) {
+    if (!h) return FXJPS_E_ARG;
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
+    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    if (n == 0) return FXJPS_OK;
+    // what can be judged without the box, for every job, before anything is queued
+    std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
+    std::vector<size_t> off((size_t)n);
+    std::vector<long long> start0((size_t)n * 2);
+    size_t raw_bytes = 0;
+    const DevCtx& d0 = h->devs[0];
+    for (int j = 0; j < n; j++) {
+        const fxjps_world_job_t& wj = jobs[j];
+        if (wj.slot < 0 || wj.slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "job %d: slot %d is not in 0 .. %d", j, (int)wj.slot, FXJPS_MAX_GRID_SLOTS - 1);
+        if (named[(size_t)wj.slot] >= 0) return fail(h, FXJPS_E_ARG, "job %d: slot %d is already named by job %d", j, (int)wj.slot, named[(size_t)wj.slot]);
+        named[(size_t)wj.slot] = j;
+        if (!wj.raw) return fail(h, FXJPS_E_ARG, "job %d: NULL raw", j);
+        if (wj.W0 < 1 || wj.H0 < 1 || wj.W0 > 8190 || wj.H0 > 8190 || wj.ifa < 0 || wj.ifa > 64 || (wj.variant != 0 && wj.variant != 1) ||
+            (wj.layout != 0 && wj.layout != 1))
+            return fail(h, FXJPS_E_ARG, "job %d: bad arguments (W0 %d, H0 %d, ifa %d, variant %d, layout %d): the message must be 1..8190 cells a side", j,
+                        (int)wj.W0, (int)wj.H0, (int)wj.ifa, (int)wj.variant, (int)wj.layout);
+        if (wj.prior < -1 || wj.prior >= FXJPS_MAX_PRIOR_MAPS)
+            return fail(h, FXJPS_E_ARG, "job %d: prior %d is not in -1 .. %d", j, (int)wj.prior, FXJPS_MAX_PRIOR_MAPS - 1);
+        if (wj.prior >= 0 && ((size_t)wj.prior >= d0.priors.size() || d0.priors[(size_t)wj.prior].W <= 0))
+            return fail(h, FXJPS_E_ARG, "job %d: prior %d is not set", j, (int)wj.prior);
+        const double reso = wj.map_reso;
+        if (!std::isfinite(reso) || !(reso > 0.0)) return fail(h, FXJPS_E_ARG, "job %d: map_reso %g must be finite and > 0", j, reso);
+        for (int k = 0; k < 2; k++) {
+            if (!std::isfinite(wj.map_o[k]) || !std::isfinite(wj.pos_xy[k]) || !std::isfinite(wj.goal_xy[k]) || (wj.prior >= 0 && !std::isfinite(wj.ori_pre[k])))
+                return fail(h, FXJPS_E_ARG, "job %d: a non-finite map_o / pos_xy / goal_xy / ori_pre", j);
+            if (!trunc_i32((wj.pos_xy[k] - wj.map_o[k]) / reso, start0[(size_t)j * 2 + k]))  // ccst:47
+                return fail(h, FXJPS_E_ARG, "job %d: the vehicle's cell in the message is outside int32", j);
+        }
+        off[(size_t)j] = raw_bytes;
+        raw_bytes += ((size_t)wj.W0 * (size_t)wj.H0 + 15) & ~(size_t)15;
+    }
+    // first phase, on every context from the caller's messages (host copies, no collective); no slot is touched
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return crop_phase_on(h, h->devs[r], jobs, n, off, raw_bytes, start0); });
+    if (rc) {
+        drain_all(h);
+        (void)hipGetLastError();
+        return rc;
+    }
+    // ccst:47-54 and the outcome of every job, from context 0's boxes (every context computed the same)
+    const int32_t* box = d0.h_crop_box.p;
+    std::vector<fxjps_crop_t> crop((size_t)n);
+    std::vector<int> outcome((size_t)n);
+    std::vector<fxjps_world_job_t> go;
+    std::vector<size_t> go_off;
+    std::vector<int> go_job;
+    std::vector<int32_t> empty;
+    const auto sat32 = [](long long v) { return (int32_t)std::min<long long>(std::max<long long>(v, INT32_MIN), INT32_MAX); };
+    for (int j = 0; j < n; j++) {
+        const fxjps_world_job_t& wj = jobs[j];
+        fxjps_crop_t& c = crop[(size_t)j];
+        c = fxjps_crop_t{};
+        const bool none = box[4 * j + 2] < 0;
+        long long lo[2] = {0, 0}, win[2] = {0, 0};
+        for (int k = 0; k < 4; k++) c.bbox[k] = box[4 * j + k];
+        for (int k = 0; k < 2; k++) {
+            const long long s0 = start0[(size_t)j * 2 + k];
+            c.start0[k] = (int32_t)s0;
+            if (!none) {
+                lo[k] = std::min<long long>(c.bbox[k], s0);
+                win[k] = (long long)c.bbox[2 + k] - lo[k];
+            }
+            c.lo[k] = (int32_t)lo[k];
+            c.win[k] = sat32(win[k]);
+            c.map_o[k] = (double)lo[k] * wj.map_reso + wj.map_o[k];       // ccst:52
+            c.map_t[k] = c.map_o[k] + (double)win[k] * wj.map_reso;       // ccst:54
+        }
+        int& oc = outcome[(size_t)j];
+        if (none || wj.W0 <= 2 * wj.ifa || win[0] == 0 || win[1] == 0)  // (win >= 0: the product is <= 0 iff one of them is 0)
+            oc = FXJPS_JOB_NOT_PLANNED;
+        else if (lo[0] < 0 || lo[1] < 0)
+            oc = FXJPS_E_ARG;
+        else
+            oc = FXJPS_OK;
+        if (oc != FXJPS_OK) {
+            empty.push_back(wj.slot);
+            continue;
+        }
+        fxjps_world_job_t g = wj;
+        g.W0 = c.win[0];
+        g.H0 = c.win[1];
+        for (int k = 0; k < 2; k++) {
+            g.map_o[k] = c.map_o[k];
+            g.map_t[k] = c.map_t[k];
+        }
+        go.push_back(g);
+        go_off.push_back(off[(size_t)j]);
+        go_job.push_back(j);
+    }
+    // second phase: what needs the box is judged in there, before anything more is queued or any slot is touched
+    std::vector<int32_t> go_kept(go.size() + 1, 0);
+    rc = world_call(h, go.data(), (int32_t)go.size(), refresh, refresh ? go_kept.data() : nullptr, what, go_off.data());
+    if (rc) return rc;
+    if (!empty.empty()) {
+        rc = empty_slots_everywhere(h, empty);
+        for (int32_t s : empty) h->slot_gen[(size_t)s]++;
+        if (rc) {
+            for (int32_t s : empty) release_slot_everywhere(h, s);
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    for (int j = 0; j < n; j++) {
+        if (outcome[(size_t)j] == FXJPS_OK) continue;
+        fxjps_world_job_t& wj = jobs[j];
+        wj.status = outcome[(size_t)j];
+        for (int k = 0; k < 2; k++) {
+            wj.canvas_o[k] = wj.origin[k] = 0.0;
+            wj.start_xy[k] = wj.goal_xy_cell[k] = wj.map_d[k] = 0;
+        }
+        wj.W = wj.H = wj.end_occu = wj.canvas_W = wj.canvas_H = 0;
+        if (out_kept) out_kept[j] = 0;
+    }
+    for (size_t i = 0; i < go.size(); i++) {
+        fxjps_world_job_t& wj = jobs[go_job[i]];
+        const fxjps_world_job_t& g = go[i];
+        wj.status = g.status;
+        for (int k = 0; k < 2; k++) {
+            wj.canvas_o[k] = g.canvas_o[k];
+            wj.origin[k] = g.origin[k];
+            wj.start_xy[k] = g.start_xy[k];
+            wj.goal_xy_cell[k] = g.goal_xy_cell[k];
+            wj.map_d[k] = g.map_d[k];
+        }
+        wj.W = g.W;
+        wj.H = g.H;
+        wj.end_occu = g.end_occu;
+        wj.canvas_W = g.canvas_W;
+        wj.canvas_H = g.canvas_H;
+        if (out_kept) out_kept[go_job[i]] = go_kept[i];
+    }
+    if (out_crop) memcpy(out_crop, crop.data(), sizeof(fxjps_crop_t) * (size_t)n);
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_prepare_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, fxjps_crop_t* out_crop) {
+    return crop_call(h, jobs, n, false, nullptr, out_crop, "fxjps_prepare_slots_cropped");
+}
+
+int fxjps_refresh_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept, fxjps_crop_t* out_crop) {
+    return crop_call(h, jobs, n, true, out_kept, out_crop, "fxjps_refresh_slots_cropped");
 }
 
 // ------------------------------------------------------------------ many slots' maps published, one call

@@ -879,6 +879,117 @@ __global__ __launch_bounds__(L == SL_BUILD_3 ? 1024 : 256) void k_slots_stage(co
         derive_jd_item(G, const_cast<uint16_t*>(G.jd), DiagRange{1, 0, 0, 0, 0}, (long long)b * 256 + threadIdx.x);
 }
 
+// ---- The ccst node's crop in front of the world-frame calls (fxjps_prepare_slots_cropped, DESIGN.md section 3.15):
+// remove_zero_rowscols (global_planner_ccst.py:36-63) cuts every map message down to the box spanned by its non-zero
+// cells and the vehicle's cell.  Two launches over all jobs of the call, queued back to back: k_crop_bounds reduces every
+// message to its box of non-zero cells (a record of min x, min y, max x, max y per job, staged as INT32_MAX, INT32_MAX,
+// -1, -1), k_crop_window copies the window that box and the vehicle's cell span densely into the window buffer, which
+// the gather of the world-frame call then reads as its detected map.  A launch's blocks are dealt to the jobs by a prefix
+// table, as SlotTable::first deals them: a block covers CROP_BLOCK_BYTES cells of its job's message.
+//   Which cells count is the reference's X.nonzero() on the matrix map_callback made (ccst:21-23): a byte != 0 in layout
+// 0; in layout 1 an int8 that is neither 0 nor -1 (100 became 1, -1 became 0; a 50 or a -5 counts for the box, though
+// only values > 0 are occupied for the preparation).
+constexpr int CROP_BLOCK_BYTES = 4096;  // 256 threads, one 16-byte load each
+struct CropJobDev {
+    const uint8_t* raw;  // the message inside the staged input; its room is a multiple of 16 bytes
+    uint8_t* win;        // the job's room in the window buffer (as large as the message's)
+    int32_t W0, H0, layout, ifa;
+    int32_t s0x, s0y;    // the vehicle's cell in the message (ccst:47)
+};
+struct CropTable {
+    uint32_t first[SLOT_JOBS_MAX + 1];
+    CropJobDev job[SLOT_JOBS_MAX];
+};
+
+// A thread loads 16 cells at once and walks their (outer, inner) coordinates from ONE division; cells at and beyond
+// W0 * H0 -- the tail of the room holds whatever an earlier call staged there -- are masked by their index.  The four
+// extremes are reduced across the wavefront's 64 lanes, then across the block's four wavefronts in LDS, and a block that
+// saw a non-zero cell issues four atomics on its job's record; a block that saw none issues none.
+__global__ __launch_bounds__(256) void k_crop_bounds(const CropTable* __restrict__ T, int32_t* __restrict__ box, int n) {
+    const int j = slot_job_of(T->first, n, blockIdx.x);
+    const CropJobDev& J = T->job[j];
+    const int layout = J.layout, ncell = J.W0 * J.H0;  // (at most 8190 x 8190)
+    const int inner = layout ? J.W0 : J.H0;             // extent of the index that runs fastest: y in layout 0, x in layout 1
+    const int i0 = ((int)(blockIdx.x - T->first[j]) * 256 + (int)threadIdx.x) * 16;
+    int mn_o = INT32_MAX, mn_i = INT32_MAX, mx_o = -1, mx_i = -1;
+    if (i0 < ncell) {
+        const uint4 v = *reinterpret_cast<const uint4*>(J.raw + i0);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        int o = i0 / inner, i = i0 - o * inner;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+            if (i0 + k < ncell && b != 0u && !(layout && b == 0xffu)) {
+                mn_o = min(mn_o, o);
+                mx_o = max(mx_o, o);
+                mn_i = min(mn_i, i);
+                mx_i = max(mx_i, i);
+            }
+            if (++i == inner) {
+                i = 0;
+                o++;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        mn_o = min(mn_o, __shfl_xor(mn_o, m, 64));
+        mn_i = min(mn_i, __shfl_xor(mn_i, m, 64));
+        mx_o = max(mx_o, __shfl_xor(mx_o, m, 64));
+        mx_i = max(mx_i, __shfl_xor(mx_i, m, 64));
+    }
+    __shared__ int red[4][4];
+    const int wave = (int)threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+        red[wave][0] = mn_o;
+        red[wave][1] = mn_i;
+        red[wave][2] = mx_o;
+        red[wave][3] = mx_i;
+    }
+    __syncthreads();  // (every thread of the block reaches it: none has returned above)
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; k++) {
+            mn_o = min(mn_o, red[k][0]);
+            mn_i = min(mn_i, red[k][1]);
+            mx_o = max(mx_o, red[k][2]);
+            mx_i = max(mx_i, red[k][3]);
+        }
+        if (mx_o >= 0) {
+            int32_t* B = box + 4 * j;
+            atomicMin(B + 0, layout ? mn_i : mn_o);
+            atomicMin(B + 1, layout ? mn_o : mn_i);
+            atomicMax(B + 2, layout ? mx_i : mx_o);
+            atomicMax(B + 3, layout ? mx_o : mx_i);
+        }
+    }
+}
+
+// The window of every job that goes on: lo = min(box min, vehicle's cell) per axis, win = box max - lo (the last
+// non-zero row and column are EXCLUDED, as the reference's slice excludes them), copied as [win_x][win_y] (layout 0) /
+// [win_y][win_x] (layout 1).  The grid is sized for the whole message; blocks past the window leave, and so do the blocks
+// of a job that will not be planned or is refused -- the host's rule (crop_call), from the same integers.
+__global__ __launch_bounds__(256) void k_crop_window(const CropTable* __restrict__ T, const int32_t* __restrict__ box, int n) {
+    const int j = slot_job_of(T->first, n, blockIdx.x);
+    const CropJobDev& J = T->job[j];
+    const int W0 = J.W0, H0 = J.H0, layout = J.layout;
+    const int32_t* B = box + 4 * j;
+    const int mx_x = B[2], mx_y = B[3];
+    if (mx_x < 0 || W0 <= 2 * J.ifa) return;  // no non-zero cell / ccst:351
+    const int lo_x = min(B[0], J.s0x), lo_y = min(B[1], J.s0y);
+    if (lo_x < 0 || lo_y < 0) return;          // the vehicle lies left of or below the message: refused
+    const int win_x = mx_x - lo_x, win_y = mx_y - lo_y;  // (0 <= lo <= box min <= box max < 8190)
+    if (win_x == 0 || win_y == 0) return;
+    const int ncell = win_x * win_y, base = (int)(blockIdx.x - T->first[j]) * CROP_BLOCK_BYTES;
+    if (base >= ncell) return;
+    const uint8_t* __restrict__ raw = J.raw;
+    uint8_t* __restrict__ win = J.win;
+    const int fast = layout ? win_x : win_y;
+    for (int i = base + (int)threadIdx.x; i < min(base + CROP_BLOCK_BYTES, ncell); i += 256) {
+        const int a = i / fast, b = i - a * fast;  // layout 0: (x, y) of the window; layout 1: (y, x)
+        win[i] = layout ? raw[(size_t)(lo_y + a) * W0 + (lo_x + b)] : raw[(size_t)(lo_x + a) * H0 + (lo_y + b)];
+    }
+}
+
 // Wire / on-disk adapters (SURVEY.md 8f, N3): one tiled byte transpose with a value map.
 //   dst[(fb ? B-1-b : b)][(fa ? A-1-a : a)][0..ch) = map(src[a][b])      src [A][B], dst [B][A][ch]
 // TM_OCC_TO_MSG   grid -> nav_msgs/OccupancyGrid data[] (global_planner_st.py:103,115: 1 -> 100, data.T)

@@ -424,6 +424,42 @@ class Planner(object):
         del keep
         return [o + (bool(k),) + w for o, k, w in zip(self._slot_outs(arr, n, "goal_xy_cell"), kept[:n], self._world_outs(arr, n))]
 
+    def prepare_slots_cropped(self, jobs):
+        """prepare_slots_world with the ccst node's crop in front (fxjps_prepare_slots_cropped): a job's raw, map_o (and
+        extents) are those of the map MESSAGE as map_callback left it, and remove_zero_rowscols (ccst:36-63) -- the cut to
+        the box of the non-zero cells and the vehicle's cell, the moved map_o / map_t -- happens in the call, the box found
+        on the device.  Jobs as prepare_slots_world takes them (map_t is not read).  A matrix raw[x][y] counts as > 0 =
+        occupied, as everywhere; a (data, width, height) message counts for the box as the reference's nonzero() does.
+        -> per job prepare_slots_world's tuple, then status (0; _lib.JOB_NOT_PLANNED: the node does not plan on this
+        tick; _lib.E_ARG: refused, the vehicle lies left of or below the message, or the goal has no free cell) and the
+        crop record (a dict with fxjps_crop_t's fields).  Unless status is 0 the slot is empty and ok is False.
+        worldprep.crop_host is the same crop on the host."""
+        jobs = list(jobs)
+        arr, keep = self._world_jobs(jobs)
+        n = len(jobs)
+        crop = (_lib.Crop * max(n, 1))()
+        self._chk(self._L.fxjps_prepare_slots_cropped(self._h, arr, n, crop))
+        del keep
+        return [o + w + c for o, w, c in zip(self._slot_outs(arr, n, "goal_xy_cell"), self._world_outs(arr, n), self._crop_outs(arr, crop, n))]
+
+    def refresh_slots_cropped(self, jobs):
+        """refresh_slots_world with the crop in front (fxjps_refresh_slots_cropped): -> per job refresh_slots_world's tuple
+        followed by status and the crop record.  A job that is not planned or refused is never kept."""
+        jobs = list(jobs)
+        arr, keep = self._world_jobs(jobs)
+        n = len(jobs)
+        kept = np.zeros(max(n, 1), dtype=np.int32)
+        crop = (_lib.Crop * max(n, 1))()
+        self._chk(self._L.fxjps_refresh_slots_cropped(self._h, arr, n, _lib.ptr(kept, C.c_int32), crop))
+        del keep
+        return [o + (bool(k),) + w + c for o, k, w, c in zip(self._slot_outs(arr, n, "goal_xy_cell"), kept[:n], self._world_outs(arr, n),
+                                                             self._crop_outs(arr, crop, n))]
+
+    @staticmethod
+    def _crop_outs(arr, crop, n):
+        return [(j.status, {"bbox": list(c.bbox), "start0": list(c.start0), "lo": list(c.lo), "win": list(c.win), "map_o": list(c.map_o),
+                            "map_t": list(c.map_t)}) for j, c in zip(arr[:n], crop[:n])]
+
     @staticmethod
     def _world_jobs(jobs):
         """-> the fxjps_world_job_t array of prepare_slots_world's jobs, and the raws it points into."""
@@ -448,14 +484,16 @@ class Planner(object):
         return [([j.origin[0], j.origin[1]], (j.canvas_W, j.canvas_H), [j.canvas_o[0], j.canvas_o[1]]) for j in arr[:n]]
 
     def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
-                         reuse=False):
+                         reuse=False, crop=False):
         """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
         prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
         job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
-        (reuse=True plans through replan_slots)."""
+        (reuse=True plans through replan_slots).  crop=True: the jobs hold the ccst node's map MESSAGES and are prepared
+        through prepare_slots_cropped / refresh_slots_cropped; every record has a further key, not_planned (bool), and a
+        vehicle that is not planned on this tick (ccst:351) or was refused has ok False."""
         jobs = list(jobs)
         return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
-                                image_channels, reuse, world=True)
+                                image_channels, reuse, world=True, crop=crop)
 
     def publish_slots(self, slots, msg=True, image_channels=None):
         """The fleet's publishing quarter of a tick in ONE call (fxjps_publish_slots): for every slot named what publish_map
@@ -508,7 +546,7 @@ class Planner(object):
         return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse)
 
     def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
-                    world=False):
+                    world=False, crop=False):
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -520,7 +558,12 @@ class Planner(object):
         keys = ("status", "cost", "start", "goal", "map_d", "shape", "end_occu", "origin", "wp", "dim", "goal_out", "ang_wp", "n_kept", "point",
                 "path", "dir_path", "dir_back", "msg", "image")
         recs = [dict({"ok": False}, **{k: None for k in keys}) for _ in range(n)]
-        if world:  # (the call's own origin, canvas_shape and canvas_o lie behind the existing tuple)
+        if crop:  # (status and the crop record lie behind the world call's tuple: they are taken off it here)
+            outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
+            for v in range(n):
+                recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
+            outs = [o[:-2] for o in outs]
+        elif world:  # (the call's own origin, canvas_shape and canvas_o lie behind the existing tuple)
             outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
         else:
             outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)

@@ -1,11 +1,13 @@
-"""What each planner node does between the map callback and the grid preparation, per vehicle, in plain numpy: the
-prior-map merge (global_planner_st.py:210-225 / global_planner_ccst.py:395-409) and the world -> cell conversion
-(st:226-227 / ccst:411-412).
+"""What each planner node does between the map callback and the grid preparation, per vehicle, in plain numpy: the ccst
+node's crop of the map message to its occupied box (global_planner_ccst.py:36-63), the prior-map merge
+(global_planner_st.py:210-225 / global_planner_ccst.py:395-409) and the world -> cell conversion (st:226-227 /
+ccst:411-412).
 
 This is the host form of Planner.prepare_slots_world for callers without a device, and what the tests compare the device
 against: the same float64 operations in the same order, truncation toward zero where the reference's .astype(int) /
 int() truncate, and a ValueError where the library refuses.  Pinned by tests/golden/worldprep.json, whose expected
-values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).
+values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).  crop_host is the host form
+of Planner.prepare_slots_cropped in the same way, pinned by tests/golden/cropprep.json (make_golden_cropprep.py).
 """
 import math
 
@@ -50,6 +52,47 @@ def _pair(v, what):
     if not (math.isfinite(a) and math.isfinite(b)):
         raise ValueError("%s is not finite" % what)
     return [a, b]
+
+
+NOT_PLANNED, REFUSED = 1, -1  # crop_host's outcomes besides 0: FXJPS_JOB_NOT_PLANNED, FXJPS_E_ARG
+I32_MAX = 2147483647
+
+
+def crop_host(raw, map_o, map_reso, pos_xy, ifa):
+    """remove_zero_rowscols (ccst:36-63, called at :349) and the node's decision whether to plan at all (ccst:351).  raw:
+    the map MESSAGE as map_callback left it, a matrix [x][y] or (data, width, height) of an OccupancyGrid; map_o: the
+    message's origin.  -> (record, outcome, window).  record: bbox (min x, min y, max x, max y of the non-zero cells;
+    I32_MAX, I32_MAX, -1, -1: none, and lo = win = 0 then), start0 (the vehicle's cell in the message), lo (the window's
+    low corner: min(first non-zero, vehicle's cell) per axis), win (map_c, map_r = bbox max - lo: the last non-zero row
+    and column are EXCLUDED), map_o and map_t (the cropped ones) -- fxjps_crop_t field by field.  outcome: 0, the window
+    X[lo_x:max_x, lo_y:max_y] goes on into merge_host with the record's win, map_o and map_t; NOT_PLANNED (no non-zero
+    cell, width <= 2 * ifa, or win[0] * win[1] <= 0: the node does not plan on this tick); REFUSED (lo < 0 on an axis:
+    the reference's slice counts from the end there, the library refuses the job).  window is None unless outcome is 0."""
+    m = matrix_from_msg(*raw) if isinstance(raw, tuple) else np.asarray(raw)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError("the map message must be 2-D and not empty")
+    reso = float(map_reso)
+    if not (math.isfinite(reso) and reso > 0.0):
+        raise ValueError("map_reso %r must be finite and > 0" % (map_reso,))
+    o = _pair(map_o, "map_o")
+    pos = _pair(pos_xy, "pos_xy")
+    start0 = [_trunc((pos[k] - o[k]) / reso, "the vehicle's cell in the message") for k in range(2)]   # ccst:47
+    nz = m.nonzero()                                                                                   # ccst:42
+    none = len(nz[0]) == 0
+    bbox = [I32_MAX, I32_MAX, -1, -1] if none else [int(nz[0].min()), int(nz[1].min()), int(nz[0].max()), int(nz[1].max())]
+    lo = [0, 0] if none else [min(bbox[k], start0[k]) for k in range(2)]                               # ccst:48-52
+    win = [0, 0] if none else [bbox[2 + k] - lo[k] for k in range(2)]                                  # ccst:49-50
+    o2 = [float(lo[k]) * reso + o[k] for k in range(2)]                                                # ccst:52
+    t2 = [o2[k] + float(win[k]) * reso for k in range(2)]                                              # ccst:54
+    if none or m.shape[0] <= 2 * int(ifa) or win[0] * win[1] <= 0:                                     # ccst:61-63, :351
+        outcome = NOT_PLANNED
+    elif lo[0] < 0 or lo[1] < 0:
+        outcome = REFUSED
+    else:
+        outcome = 0
+    window = m[lo[0]:bbox[2], lo[1]:bbox[3]] if outcome == 0 else None                                 # ccst:56, :60
+    rec = {"bbox": bbox, "start0": start0, "lo": lo, "win": [min(w, I32_MAX) for w in win], "map_o": o2, "map_t": t2}
+    return rec, outcome, window
 
 
 def merge_host(raw, map_o, map_reso, pos_xy, goal_xy, prior=None, ori_pre=(-15, -15), map_t=None):

@@ -92,8 +92,10 @@ typedef struct fxjps fxjps_t;
  *   780  fxjps_prepare_slots_world, fxjps_refresh_slots_world (the two calls from world-frame jobs: the detected map is
  *        merged over a prior map that lives on the device, positions become cells, in the same launches),
  *        fxjps_set_prior_map, fxjps_get_prior_map, fxjps_world_job_size.
+ *   790  fxjps_prepare_slots_cropped, fxjps_refresh_slots_cropped (the world-frame calls with the ccst node's crop of every
+ *        map message to its occupied box in front, the box found on the device), fxjps_crop_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 780
+#define FXJPS_VERSION 790
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -369,6 +371,52 @@ typedef struct fxjps_world_job {
 int fxjps_prepare_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n);
 int fxjps_refresh_slots_world(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept);
 int fxjps_world_job_size(void); /* sizeof(fxjps_world_job_t) as the library was built (cf. fxjps_slot_job_size) */
+/* ---- The world-frame calls with the ccst node's crop in front (version 790): remove_zero_rowscols
+ * (global_planner_ccst.py:36-63, called at :349), the first thing that node does with every map message, moves into the
+ * call.  The job is a fxjps_world_job_t whose raw, W0, H0 and map_o describe the MESSAGE as map_callback left it (W0 is
+ * map_c1); map_t is not read, the crop computes it; reserved_ stays unread.  Per job, with X the message's matrix [x][y]:
+ *     bbox   = min / max x and y over X.nonzero(): layout 0 a byte != 0; layout 1 an int8 that is neither 0 nor -1 (100
+ *              became 1 and -1 became 0 at ccst:22-23: a 50 or a -5 counts here, though only values > 0 are occupied for
+ *              the preparation)                                                                              (ccst:42-44)
+ *     start0 = trunc((pos_xy - map_o) / map_reso)                                                            (ccst:47)
+ *     lo     = min(bbox min, start0) per axis                                                                (ccst:48-52)
+ *     win    = bbox max - lo: map_c, map_r -- the last non-zero row and column are EXCLUDED                  (ccst:49-50)
+ *     map_o' = lo * map_reso + map_o,  map_t' = map_o' + win * map_reso                                      (ccst:52, 54)
+ * in float64 with the reference's operations in the reference's order.  The outcome, decided in this order:
+ *   1. no non-zero cell, or W0 <= 2 * ifa, or win[0] * win[1] <= 0: status = FXJPS_JOB_NOT_PLANNED -- the node takes its
+ *      else branch (ccst:351, :565-584) and does not plan on this tick;
+ *   2. else lo < 0 on an axis (the vehicle lies left of or below the message's origin): status = FXJPS_E_ARG.  The
+ *      reference's slice X[lo:max] counts from the end there, its result is not the window and ccst:435 usually raises (a
+ *      stated deviation, like the clipped rectangles of fxjps_prepare_slots_world);
+ *   3. else the job goes on as the world job whose raw is the window X[lo_x : max_x, lo_y : max_y], W0 / H0 = win,
+ *      map_o / map_t = map_o' / map_t'; the prior merge and everything behind it are those of fxjps_prepare_slots_world.
+ * In cases 1 and 2 the job takes no part in the rest of the call: its slot is left EMPTY and the slot's generation moves,
+ * out_kept[j] = 0, its other outputs are 0, out_crop[j] is filled all the same; the other jobs are not disturbed and the
+ * call returns FXJPS_OK.  (win is computed in 64 bits and stored saturated to int32; it can exceed int32 only in case 2.)
+ *   Whole-call refusals (FXJPS_E_ARG, no slot and no generation changed): those of fxjps_prepare_slots_world, and a start0
+ * quotient outside int32.  What can be judged without the box is judged before anything is queued; what needs it -- the
+ * prepared grid's 8190 limit, a goal outside the prepared grid, a rectangle sticking out of the canvas -- after the box
+ * has come back and before the second phase is queued (only the two crop launches have run by then; fxjps_last_error
+ * then counts the jobs that go on, leaving out those of cases 1 and 2).
+ *   Two phases per context, neither with a number of launches, copies or host waits that depends on n.  The first: one copy
+ * in (the messages, a job table, n box records), one launch that reduces every message to its box with 16-byte loads, one
+ * that copies every window into a window buffer on the device, one copy out (the boxes), one wait.  The second is
+ * fxjps_prepare_slots_world / fxjps_refresh_slots_world on the surviving jobs, whose raws are the windows where they lie:
+ * no raw is copied or staged again.  Rank handles, several contexts, the 2^18 rule, out_kept and the goal with no free
+ * cell are those of the existing calls.  out_crop may be NULL. */
+#define FXJPS_JOB_NOT_PLANNED 1 /* a further value of fxjps_world_job_t::status, from the two calls below only */
+typedef struct fxjps_crop {     /* out, one per job */
+    int32_t bbox[4];   /* min x, min y, max x, max y of the message's non-zero cells; INT32_MAX, INT32_MAX, -1, -1: none
+                          (the reference computes nothing further then: lo and win are 0, map_o / map_t follow from them) */
+    int32_t start0[2]; /* trunc((pos_xy - map_o) / map_reso): the vehicle's cell in the MESSAGE (ccst:47) */
+    int32_t lo[2];     /* min(bbox min, start0) per axis: the window's low corner (ccst:48-52) */
+    int32_t win[2];    /* map_c, map_r = bbox max - lo (ccst:49-50): the window's extents, the last occupied row / column excluded */
+    double map_o[2];   /* lo * map_reso + map_o (ccst:52: int * float, then + the message's origin) */
+    double map_t[2];   /* cropped map_o + win * map_reso (ccst:54) */
+} fxjps_crop_t;
+int fxjps_prepare_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, fxjps_crop_t* out_crop);
+int fxjps_refresh_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept, fxjps_crop_t* out_crop);
+int fxjps_crop_size(void); /* sizeof(fxjps_crop_t) as the library was built */
 /* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
  * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
  * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
