@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 790  # FXJPS_VERSION of include/fxjps.h
+VERSION = 800  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -23,7 +23,8 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch", "fxjps_publish_slots", "fxjps_slot_publish_size",
            "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context", "fxjps_replan_slots",
            "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size",
-           "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size")
+           "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size",
+           "fxjps_refresh_grid", "fxjps_refresh_occupancy_msg", "fxjps_last_refresh_cells", "fxjps_replan_frame_raw")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
@@ -167,6 +168,16 @@ def load():
     L.fxjps_set_queries.argtypes = [vp, p_i32, p_i32, C.c_int64, C.c_int32, C.c_int32]
     L.fxjps_replan_frame.restype = C.c_int
     L.fxjps_replan_frame.argtypes = [vp, p_i32, p_u8, C.c_int64, p_i64, p_i32, C.c_int64, p_i32, p_f64, p_f64]
+    L.fxjps_refresh_grid.restype = C.c_int
+    L.fxjps_refresh_grid.argtypes = [vp, p_u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, p_i32, p_i32, p_i32, p_i32, p_i32, p_i32, p_i64, p_i32]
+    L.fxjps_refresh_occupancy_msg.restype = C.c_int
+    L.fxjps_refresh_occupancy_msg.argtypes = [vp, C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, p_i32, p_i32,
+                                              p_i32, p_i32, p_i32, p_i32, p_i64, p_i32]
+    L.fxjps_last_refresh_cells.restype = C.c_int
+    L.fxjps_last_refresh_cells.argtypes = [vp, p_i32, p_u8, C.c_int64, p_i64]
+    L.fxjps_replan_frame_raw.restype = C.c_int
+    L.fxjps_replan_frame_raw.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, p_i32, p_i32, p_i32, p_i32, p_i32, p_i32,
+                                         p_i64, p_i32, p_i64, p_i32, C.c_int64, p_i32, p_f64, p_f64]
     L.fxjps_plan_batch.restype = C.c_int
     L.fxjps_plan_batch.argtypes = [vp, p_i32, p_i32, C.c_int64, C.c_int32, C.c_int32, p_i32, p_i32, p_f64, p_f64]
     L.fxjps_plan_batch_csr.restype = C.c_int

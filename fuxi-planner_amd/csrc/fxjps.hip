@@ -237,6 +237,10 @@ struct DevCtx : GridBufs {
     int mode = 0;                 // 0 plain batch, 1 search everything and record read sets, 2 the same for h_sel only
     int64_t nrun = 0;             // queries handed to the search kernel
     DBuf<uint8_t> d_raw, d_img;
+    // fxjps_refresh_grid (context 0 only): the diff kernels' buffer (fx::DIFF_HDR header words | the list | the blocks' counts)
+    // and where its header and the head of the list arrive on the host
+    DBuf<uint32_t> d_diff;
+    HBuf<uint32_t> h_diff;
     struct Waypoints {
         // waypoint selection over a batch (fxjps_waypoint_ccst_batch)
         DBuf<double> d_in, d_out;
@@ -324,6 +328,10 @@ struct fxjps {
     // true while the device result buffers and the host read sets of every device describe the stored queries on the
     // resident grid: then a frame only searches the queries whose read set its cell updates touch
     bool q_results_valid = false;
+    // fxjps_refresh_grid / fxjps_replan_frame_raw: the changed cells the last such call found and applied as a cell update
+    // (mode 1; empty after any other mode), for fxjps_last_refresh_cells
+    std::vector<int32_t> refresh_xy;
+    std::vector<uint8_t> refresh_val;
     // fxjps_replan_slots: the previous such call's arguments, the generation of each query's slot then, and its per-query
     // codes; rs_valid while the device buffers of context 0 still hold that batch (whatever drops q_results_valid drops it)
     std::vector<int32_t> rs_ids, rs_starts, rs_goals, rs_len;
@@ -2068,19 +2076,23 @@ SlotPlan prepared_geometry(long long W0, long long H0, long long ifa, int varian
     p.ngy = gy + p.dy - sh;
     return p;
 }
-}  // namespace
 
-static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
-                             int msg_layout, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
-                             int32_t* out_map_d, int32_t* out_end_occu) {
-    if (!h) return FXJPS_E_ARG;
+// prepare_grid's refusals (nothing is touched yet) and the geometry of the prepared grid
+int prepare_check(fxjps_t* h, const char* what, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, const int32_t* start_xy,
+                  const int32_t* goal_xy, SlotPlan* out) {
     if (!raw || !start_xy || !goal_xy || W0 < 1 || H0 < 1 || ifa < 0 || ifa > 64 || (variant != 0 && variant != 1))
         return fail(h, FXJPS_E_ARG, "bad prepare_grid arguments");
-    if (int rr = refuse_on_rank_handle(h, "fxjps_prepare_grid")) return rr;
-    const SlotPlan p = prepared_geometry(W0, H0, ifa, variant, start_xy, goal_xy);
-    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1, nsx = p.nsx, nsy = p.nsy;
-    long long ngx = p.ngx, ngy = p.ngy;
-    if (W1 > 8190 || H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", W1, H1);
+    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    *out = prepared_geometry(W0, H0, ifa, variant, start_xy, goal_xy);
+    if (out->W1 > 8190 || out->H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", out->W1, out->H1);
+    return FXJPS_OK;
+}
+
+// The whole prepared grid written and every derived map built, on every context; returns with all streams idle.
+// d0_staged: the raw map already lies in context 0's d_raw (fxjps_refresh_grid diffed against it).
+int prepare_build(fxjps_t* h, const SlotPlan& p, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout,
+                  bool d0_staged = false) {
+    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1;
     h->have_grid = false;
     h->q_results_valid = h->rs_valid = false;
     for (auto& d : h->devs) {
@@ -2089,7 +2101,7 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
         int rc = alloc_grid(h, d, (int)W1, (int)H1);
         if (rc) return rc;
         // every device pads and dilates the raw grid itself: cheaper than broadcasting the larger result
-        HIPCHK(h, hipMemcpyAsync(d.d_raw.p, raw, (size_t)W0 * H0, hipMemcpyHostToDevice, d.stream));
+        if (!(d0_staged && &d == &h->devs[0])) HIPCHK(h, hipMemcpyAsync(d.d_raw.p, raw, (size_t)W0 * H0, hipMemcpyHostToDevice, d.stream));
         const long long n = W1 * H1;
         hipLaunchKernelGGL(fx::k_prepare_grid, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d.stream, d.d_raw.p, W0, H0,
                            (int)dx, (int)dy, ifa, variant, msg_layout, (int)W1, (int)H1, d.occ.p);
@@ -2103,6 +2115,15 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
     }
     h->have_grid = true;
     h->maps_stale = false;
+    return FXJPS_OK;
+}
+
+// What the callers get back: the shifted start, the goal moved off an obstacle, end_occu, the extents and the padding.
+// Reads the resident grid of context 0, whose stream is idle.
+int prepare_finish(fxjps_t* h, const SlotPlan& p, int32_t ifa, int32_t variant, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W,
+                   int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu) {
+    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1, nsx = p.nsx, nsy = p.nsy;
+    long long ngx = p.ngx, ngy = p.ngy;
     if (ngx < 0 || ngy < 0 || ngx >= W1 || ngy >= H1) return fail(h, FXJPS_E_ARG, "goal outside the prepared grid");
     // :268-272 / :454-458: a goal on an obstacle moves to the nearest free cell of its row, else of its column
     DevCtx& d0 = h->devs[0];
@@ -2156,6 +2177,18 @@ static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t
         out_map_d[1] = (int32_t)dy;
     }
     return FXJPS_OK;
+}
+
+}  // namespace
+
+static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
+                             int msg_layout, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
+                             int32_t* out_map_d, int32_t* out_end_occu) {
+    if (!h) return FXJPS_E_ARG;
+    SlotPlan p{};
+    if (int rc = prepare_check(h, "fxjps_prepare_grid", raw, W0, H0, ifa, variant, start_xy, goal_xy, &p)) return rc;
+    if (int rc = prepare_build(h, p, raw, W0, H0, ifa, variant, msg_layout)) return rc;
+    return prepare_finish(h, p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
 }
 
 int fxjps_prepare_grid(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
@@ -2444,43 +2477,49 @@ int fxjps_set_queries(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals
     return FXJPS_OK;
 }
 
-int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n, int64_t* out_offsets, int32_t* out_cells_xy,
-                       int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
-    const double t0 = now_s();
-    if (!h) return FXJPS_E_ARG;
-    if (!h->q_set) return fail(h, FXJPS_E_ARG, "fxjps_replan_frame before fxjps_set_queries");
-    const int64_t nq = (int64_t)h->q_starts.size() / 2;
-    if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "fxjps_replan_frame before fxjps_set_grid");
-    if (n < 0 || (n > 0 && (!xy || !val))) return fail(h, FXJPS_E_ARG, "bad update arrays");
-    // ---- exact reuse.  Which read-set tiles does this frame's update touch?  Derived data of a cell depends on the
-    // occupancy within Chebyshev distance 1, so every changed cell marks the tiles of its 3 x 3 neighbourhood; a
-    // stored result whose read set (see ReadSet in the kernels) misses all of them is what a from-scratch search
-    // on the new grid would return, bit for bit, and is not searched again.
-    static const bool allow_reuse = !(getenv("FXJPS_REPLAN_REUSE") && atoi(getenv("FXJPS_REPLAN_REUSE")) == 0);
-    DevCtx& d0 = h->devs[0];
+namespace {
+// ---- exact reuse (fxjps_replan_frame, fxjps_replan_frame_raw).  Which read-set tiles does this frame's update touch?
+// Derived data of a cell depends on the occupancy within Chebyshev distance 1, so every changed cell marks the tiles of
+// its 3 x 3 neighbourhood; a stored result whose read set (see ReadSet in the kernels) misses all of them is what a
+// from-scratch search on the new grid would return, bit for bit, and is not searched again.
+struct FrameTiles {
     unsigned long long DX[64], DY[64];  // DX[y tile]: bit per x tile, DY[x tile]: bit per y tile
-    memset(DX, 0, sizeof(DX));
-    memset(DY, 0, sizeof(DY));
-    for (int64_t i = 0; i < n; i++) {
-        const int x = xy[2 * i], y = xy[2 * i + 1];
-        if (x < 0 || y < 0 || x >= d0.W || y >= d0.H) continue;  // (k_update_cells ignores it as well)
-        const int tx0 = std::max(x - 1, 0) >> d0.tsh, tx1 = std::min(x + 1, d0.W - 1) >> d0.tsh;
-        const int ty0 = std::max(y - 1, 0) >> d0.tsh, ty1 = std::min(y + 1, d0.H - 1) >> d0.tsh;
+    FrameTiles() {
+        memset(DX, 0, sizeof(DX));
+        memset(DY, 0, sizeof(DY));
+    }
+    // the cells x0 .. x1, y0 .. y1 (on the grid) and their neighbours
+    void mark_box(const DevCtx& d0, int x0, int x1, int y0, int y1) {
+        const int tx0 = std::max(x0 - 1, 0) >> d0.tsh, tx1 = std::min(x1 + 1, d0.W - 1) >> d0.tsh;
+        const int ty0 = std::max(y0 - 1, 0) >> d0.tsh, ty1 = std::min(y1 + 1, d0.H - 1) >> d0.tsh;
         for (int ty = ty0; ty <= ty1; ty++)
             for (int tx = tx0; tx <= tx1; tx++) {
                 DX[ty] |= 1ull << tx;
                 DY[tx] |= 1ull << ty;
             }
     }
+    void mark_cells(const DevCtx& d0, const int32_t* xy, int64_t n) {
+        for (int64_t i = 0; i < n; i++) {
+            const int x = xy[2 * i], y = xy[2 * i + 1];
+            if (x < 0 || y < 0 || x >= d0.W || y >= d0.H) continue;  // (k_update_cells ignores it as well)
+            mark_box(d0, x, x, y, y);
+        }
+    }
+};
+// -> plan_core's mode for the frame (0 untracked, 1 everything searched and tracked, 2 the queries of DevCtx::h_sel
+// searched); *track: the frame's results carry read sets; *reused: stored results handed back.  search_all: the stored
+// results are void whatever their read sets say (the grid was rebuilt from scratch).
+int frame_reuse_rule(fxjps_t* h, const FrameTiles& T, bool search_all, int64_t* out_reused, bool* out_track) {
+    static const bool allow_reuse = !(getenv("FXJPS_REPLAN_REUSE") && atoi(getenv("FXJPS_REPLAN_REUSE")) == 0);
+    const DevCtx& d0 = h->devs[0];
     int64_t touched = 0, tiles = (int64_t)(((d0.W - 1) >> d0.tsh) + 1) * (((d0.H - 1) >> d0.tsh) + 1);
-    for (int t = 0; t < 64; t++) touched += __builtin_popcountll(DX[t]);
+    for (int t = 0; t < 64; t++) touched += __builtin_popcountll(T.DX[t]);
     // Recording read sets costs a few instructions per ray; it pays only when the next frame can reuse something.
     // A frame that touches most tiles (config 5: 10 % of all cells) leaves nothing to reuse: it runs untracked.
     const bool track = allow_reuse && 2 * touched <= tiles;
     int mode = track ? 1 : 0;
     int64_t reused = 0;
-    if (track && h->q_results_valid) {
+    if (track && h->q_results_valid && !search_all) {
         mode = 2;
         for (auto& d : h->devs) {
             d.h_sel.assign((size_t)d.nq, 1);  // (the shards are those of the previous frame: same query set)
@@ -2490,7 +2529,7 @@ int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
                 const unsigned long long* bx = d.h_qread.data() + (size_t)q * 128;
                 const unsigned long long* by = bx + 64;
                 unsigned long long hit = 0;
-                for (int t = 0; t < 64; t++) hit |= (bx[t] & DX[t]) | (by[t] & DY[t]);
+                for (int t = 0; t < 64; t++) hit |= (bx[t] & T.DX[t]) | (by[t] & T.DY[t]);
                 if (!hit) {
                     d.h_sel[(size_t)q] = 0;
                     reused++;
@@ -2498,6 +2537,26 @@ int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
             }
         }
     }
+    *out_reused = reused;
+    *out_track = track;
+    return mode;
+}
+}  // namespace
+
+int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n, int64_t* out_offsets, int32_t* out_cells_xy,
+                       int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
+    const double t0 = now_s();
+    if (!h) return FXJPS_E_ARG;
+    if (!h->q_set) return fail(h, FXJPS_E_ARG, "fxjps_replan_frame before fxjps_set_queries");
+    const int64_t nq = (int64_t)h->q_starts.size() / 2;
+    if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
+    if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "fxjps_replan_frame before fxjps_set_grid");
+    if (n < 0 || (n > 0 && (!xy || !val))) return fail(h, FXJPS_E_ARG, "bad update arrays");
+    FrameTiles T;
+    T.mark_cells(h->devs[0], xy, n);
+    int64_t reused = 0;
+    bool track = false;
+    const int mode = frame_reuse_rule(h, T, false, &reused, &track);
     // the frame's map update is queued in front of the search on the same streams: the first host wait of the frame
     // is the one for the search results
     h->q_results_valid = h->rs_valid = false;  // (set again below, once the frame is complete)
@@ -2514,6 +2573,182 @@ int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
     h->timing.total_ms = (now_s() - t0) * 1e3;
     if (out_seconds_total) *out_seconds_total = now_s() - t0;
     return rc;
+}
+
+namespace {
+// ---- fxjps_refresh_grid / fxjps_replan_frame_raw: the prepared grid of a raw map against the
+// resident one.  mode 0: no byte differs; 1: `changed` cells differ, their list is in the handle (refresh_xy / refresh_val);
+// 2: the grid is to be rebuilt (no resident grid or other extents: changed == -1, nothing ran; more changed cells than the
+// list holds).  box: the changed cells' bounding box (modes 1 and 2 behind a diff).
+struct RefreshDiff {
+    SlotPlan p;
+    int mode = 2;
+    int64_t changed = -1;
+    bool staged = false;  // the raw map lies in context 0's d_raw
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+};
+int refresh_diff(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout, RefreshDiff* r) {
+    const SlotPlan& p = r->p;
+    DevCtx& d = h->devs[0];
+    h->refresh_xy.clear();
+    h->refresh_val.clear();
+    if (!h->have_grid || p.W1 != d.W || p.H1 != d.H) return FXJPS_OK;
+    const long long ncell = p.W1 * p.H1;
+    const uint32_t nblk = (uint32_t)((ncell + 255) / 256), cap = (uint32_t)std::max<long long>(4096, ncell / 8);
+    constexpr uint32_t HEAD = 4096;  // entries of the list that travel with the header: a longer list takes a second copy
+    HIPCHK(h, hipSetDevice(d.dev));
+    HIPCHK(h, d.d_raw.ensure((size_t)W0 * H0));
+    HIPCHK(h, d.d_diff.ensure((size_t)fx::DIFF_HDR + cap + nblk + 1));
+    HIPCHK(h, d.h_diff.ensure((size_t)fx::DIFF_HDR + HEAD));
+    uint32_t *hdr = d.d_diff.p, *list = hdr + fx::DIFF_HDR, *scan = list + cap;
+    const fx::DiffGeom g{W0, H0, (int)p.dx, (int)p.dy, ifa, variant, msg_layout, (int)p.W1, (int)p.H1};
+    // (on the context's stream: behind cell updates that are still queued there, fxjps_update_cells_deferred)
+    HIPCHK(h, hipMemcpyAsync(d.d_raw.p, raw, (size_t)W0 * H0, hipMemcpyHostToDevice, d.stream));
+    r->staged = true;
+    HIPCHK(h, hipMemsetAsync(hdr, 0, fx::DIFF_HDR * sizeof(uint32_t), d.stream));
+    hipLaunchKernelGGL(fx::k_grid_diff_count, dim3(nblk), dim3(256), 0, d.stream, d.d_raw.p, g, d.occ.p, hdr, scan);
+    hipLaunchKernelGGL(fx::k_grid_diff_scan, dim3(1), dim3(1024), 0, d.stream, scan, nblk, hdr);
+    hipLaunchKernelGGL(fx::k_grid_diff_write, dim3(nblk), dim3(256), 0, d.stream, d.d_raw.p, g, d.occ.p, scan, nblk, cap, list);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_diff.p, hdr, ((size_t)fx::DIFF_HDR + HEAD) * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    const uint32_t n = d.h_diff.p[fx::DIFF_N];
+    r->changed = n;
+    if (n == 0) {
+        r->mode = 0;
+        return FXJPS_OK;
+    }
+    r->x0 = 8191 - (int)d.h_diff.p[fx::DIFF_X0];
+    r->x1 = (int)d.h_diff.p[fx::DIFF_X1] - 1;
+    r->y0 = 8191 - (int)d.h_diff.p[fx::DIFF_Y0];
+    r->y1 = (int)d.h_diff.p[fx::DIFF_Y1] - 1;
+    if (n > cap) return FXJPS_OK;  // (mode 2: the list was not written)
+    h->refresh_xy.resize((size_t)n * 2);
+    h->refresh_val.resize(n);
+    const auto decode = [&](uint32_t k0, uint32_t k1) {  // entries k0 .. k1 - 1 out of the pinned buffer
+        const uint32_t* e = d.h_diff.p + fx::DIFF_HDR;
+        for (uint32_t k = k0; k < k1; k++) {
+            h->refresh_xy[2 * (size_t)k] = (int32_t)(e[k] >> 16);
+            h->refresh_xy[2 * (size_t)k + 1] = (int32_t)((e[k] >> 1) & 0x7FFFu);
+            h->refresh_val[k] = (uint8_t)(e[k] & 1u);
+        }
+    };
+    decode(0, std::min(n, HEAD));
+    if (n > HEAD) {  // the rest of a long list: one more copy, into a buffer sized for the capacity once
+        HIPCHK(h, d.h_diff.ensure((size_t)fx::DIFF_HDR + cap));
+        HIPCHK(h, hipMemcpyAsync(d.h_diff.p + fx::DIFF_HDR + HEAD, list + HEAD, (size_t)(n - HEAD) * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+        decode(HEAD, n);
+    }
+    r->mode = 1;
+    return FXJPS_OK;
+}
+
+// The diff's outcome applied, queued on every context: the list through the cell-update path (which also rebuilds what
+// deferred updates left stale, mode 0 included), or the whole build.
+int refresh_apply(fxjps_t* h, const RefreshDiff& r, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout) {
+    if (r.mode == 2) return prepare_build(h, r.p, raw, W0, H0, ifa, variant, msg_layout, r.staged);
+    int rc = update_cells_async(h, h->refresh_xy.data(), h->refresh_val.data(), r.changed, true);
+    if (rc) drain_all(h);  // the devices in front of the failing one have the update queued
+    return rc;
+}
+
+int refresh_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout, int32_t* start_xy,
+                      int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed,
+                      int32_t* out_mode) {
+    if (!h) return FXJPS_E_ARG;
+    RefreshDiff r;
+    if (int rc = prepare_check(h, "fxjps_refresh_grid", raw, W0, H0, ifa, variant, start_xy, goal_xy, &r.p)) return rc;
+    h->q_results_valid = h->rs_valid = false;  // (as fxjps_update_cells: the grid may change behind the stored results)
+    if (int rc = refresh_diff(h, raw, W0, H0, ifa, variant, msg_layout, &r)) return rc;
+    if (out_changed) *out_changed = r.changed;
+    if (out_mode) *out_mode = r.mode;
+    const bool queued = r.mode == 1 || h->maps_stale;  // (mode 2 waits itself; a mode 0 behind no deferred update queues nothing)
+    if (int rc = refresh_apply(h, r, raw, W0, H0, ifa, variant, msg_layout)) return rc;
+    if (r.mode != 2 && queued)
+        for (auto& d : h->devs) {
+            HIPCHK(h, hipSetDevice(d.dev));
+            HIPCHK(h, hipStreamSynchronize(d.stream));
+        }
+    return prepare_finish(h, r.p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+}
+
+int replan_frame_raw_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout,
+                          int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu,
+                          int64_t* out_changed, int32_t* out_mode, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity,
+                          int32_t* out_len, double* out_cost, double* out_seconds_total) {
+    const double t0 = now_s();
+    if (!h) return FXJPS_E_ARG;
+    RefreshDiff r;
+    if (int rc = prepare_check(h, "fxjps_replan_frame_raw", raw, W0, H0, ifa, variant, start_xy, goal_xy, &r.p)) return rc;
+    const int64_t nq = (int64_t)h->q_starts.size() / 2;
+    if (h->q_set && nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
+    if (!h->q_set || !h->have_grid || r.p.W1 != h->devs[0].W || r.p.H1 != h->devs[0].H)
+        return fail(h, FXJPS_E_ARG, "fxjps_replan_frame_raw needs stored queries and a resident grid of the prepared extents (%lldx%lld): call "
+                    "fxjps_prepare_grid and fxjps_set_queries again", r.p.W1, r.p.H1);
+    if (int rc = refresh_diff(h, raw, W0, H0, ifa, variant, msg_layout, &r)) return rc;
+    if (out_changed) *out_changed = r.changed;
+    if (out_mode) *out_mode = r.mode;
+    // fxjps_replan_frame's rule on the diff's list; a diff too long for its list marks the tiles of its box, and every query is searched
+    FrameTiles T;
+    if (r.mode == 1) T.mark_cells(h->devs[0], h->refresh_xy.data(), r.changed);
+    if (r.mode == 2) T.mark_box(h->devs[0], r.x0, r.x1, r.y0, r.y1);
+    int64_t reused = 0;
+    bool track = false;
+    const int mode = frame_reuse_rule(h, T, r.mode == 2, &reused, &track);
+    h->q_results_valid = h->rs_valid = false;  // (set again below, once the frame is complete)
+    if (int rc = refresh_apply(h, r, raw, W0, H0, ifa, variant, msg_layout)) return rc;
+    int rc = plan_core(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
+    if (rc) return rc;
+    h->q_results_valid = track;
+    h->timing.reused = reused;
+    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
+    if (rc) return rc;
+    for (auto& d : h->devs) {  // (a context without queries of the batch has not waited for its update)
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+    }
+    rc = prepare_finish(h, r.p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+    h->timing.total_ms = (now_s() - t0) * 1e3;
+    if (out_seconds_total) *out_seconds_total = now_s() - t0;
+    return rc;
+}
+}  // namespace
+
+int fxjps_refresh_grid(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int32_t* start_xy,
+                       int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed,
+                       int32_t* out_mode) {
+    return refresh_grid_impl(h, raw, W0, H0, ifa, variant, 0, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu, out_changed, out_mode);
+}
+
+int fxjps_refresh_occupancy_msg(fxjps_t* h, const int8_t* data, int32_t width, int32_t height, int32_t ifa, int32_t variant, int32_t* start_xy,
+                                int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu,
+                                int64_t* out_changed, int32_t* out_mode) {
+    return refresh_grid_impl(h, reinterpret_cast<const uint8_t*>(data), width, height, ifa, variant, 1, start_xy, goal_xy, out_W, out_H,
+                             out_map_d, out_end_occu, out_changed, out_mode);
+}
+
+int fxjps_last_refresh_cells(fxjps_t* h, int32_t* out_xy, uint8_t* out_val, int64_t capacity, int64_t* out_n) {
+    if (!h || !out_n) return FXJPS_E_ARG;
+    const int64_t n = (int64_t)h->refresh_val.size();
+    *out_n = n;
+    if (!out_xy && !out_val) return FXJPS_OK;  // (sizing call)
+    if (!out_xy || !out_val || capacity < n) return fail(h, FXJPS_E_ARG, "the last refresh changed %lld cells, the arrays hold %lld", (long long)n, (long long)capacity);
+    if (n > 0) {
+        memcpy(out_xy, h->refresh_xy.data(), (size_t)n * 2 * sizeof(int32_t));
+        memcpy(out_val, h->refresh_val.data(), (size_t)n);
+    }
+    return FXJPS_OK;
+}
+
+int fxjps_replan_frame_raw(fxjps_t* h, const void* raw, int32_t layout, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int32_t* start_xy,
+                           int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed,
+                           int32_t* out_mode, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len,
+                           double* out_cost, double* out_seconds_total) {
+    if (h && layout != 0 && layout != 1) return fail(h, FXJPS_E_ARG, "layout must be 0 (matrix [x][y]) or 1 (message data[])");
+    return replan_frame_raw_impl(h, static_cast<const uint8_t*>(raw), W0, H0, ifa, variant, layout, start_xy, goal_xy, out_W, out_H, out_map_d,
+                                 out_end_occu, out_changed, out_mode, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost,
+                                 out_seconds_total);
 }
 
 int fxjps_plan_batch_csr(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,

@@ -720,6 +720,87 @@ __global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict_
     out[i] = prepared_byte<false>(raw, nullptr, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
 }
 
+// ---- The prepared grid diffed against the resident one (fxjps_refresh_grid, DESIGN.md section 3.16): which cells of
+// `occ` are not the byte k_prepare_grid would write there, as a list in ascending order of the cell index i = x * H1 + y.
+// Three launches: every block of 256 threads counts the changed cells among its 256 cells (and folds their box into the
+// header); one block turns the counts into exclusive offsets, in place (k_scan_len's form: linear in the number of
+// blocks); every block with a count writes its cells at its offset, in cell order (ballot ranks inside a wavefront, the
+// wavefronts' counts through LDS).  They write nothing but `diff`:
+//   diff[0 .. 8)               header: [0] number of changed cells, [1] max(8191 - x) + ... the box, DIFF_* below; zero: none
+//   diff[8 .. 8 + cap)         the list, one word per cell: x << 16 | y << 1 | v  (v, the prepared byte, is 0 or 1)
+//   diff[8 + cap .. + nblk]    the blocks' counts, after k_grid_diff_scan their offsets, then the total
+// More changed cells than `cap`: the list is not written (the caller rebuilds the grid).
+constexpr int DIFF_HDR = 8, DIFF_N = 0, DIFF_X0 = 1, DIFF_X1 = 2, DIFF_Y0 = 3, DIFF_Y1 = 4;  // X0 / Y0 hold 8191 - min, X1 / Y1 hold max + 1
+struct DiffGeom {
+    int W0, H0, dx, dy, ifa, variant, msg_layout, W1, H1;
+};
+__global__ __launch_bounds__(256) void k_grid_diff_count(const uint8_t* __restrict__ raw, const DiffGeom g, const uint8_t* __restrict__ occ,
+                                                        uint32_t* __restrict__ hdr, uint32_t* __restrict__ scan) {
+    __shared__ int s_box[4];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool chg = false;
+    if (i < (long long)g.W1 * g.H1) chg = occ[i] != prepared_byte<false>(raw, nullptr, g.W0, g.H0, g.dx, g.dy, g.ifa, g.variant, g.msg_layout, g.H1, i);
+    if (threadIdx.x < 4) s_box[threadIdx.x] = 0;
+    const int cnt = __syncthreads_count(chg);
+    if (threadIdx.x == 0) scan[blockIdx.x] = (uint32_t)cnt;
+    if (cnt == 0) return;  // (block-uniform)
+    if (chg) {
+        const int x = (int)(i / g.H1), y = (int)(i % g.H1);
+        atomicMax(&s_box[0], 8191 - x);
+        atomicMax(&s_box[1], x + 1);
+        atomicMax(&s_box[2], 8191 - y);
+        atomicMax(&s_box[3], y + 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) atomicMax(&hdr[DIFF_X0 + threadIdx.x], (uint32_t)s_box[threadIdx.x]);
+}
+__global__ __launch_bounds__(1024) void k_grid_diff_scan(uint32_t* __restrict__ scan, uint32_t nblk, uint32_t* __restrict__ hdr) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (nblk + 1023u) / 1024u;
+    const uint32_t lo = min(tid * per, nblk), hi = min(lo + per, nblk);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += scan[i];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024u; o <<= 1) {
+        const uint32_t v = tid >= o ? s_part[tid - o] : 0u;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = tid ? s_part[tid - 1] : 0u;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t c = scan[i];
+        scan[i] = run;
+        run += c;
+    }
+    if (tid == 1023u) {
+        scan[nblk] = s_part[1023];
+        hdr[DIFF_N] = s_part[1023];
+    }
+}
+__global__ __launch_bounds__(256) void k_grid_diff_write(const uint8_t* __restrict__ raw, const DiffGeom g, const uint8_t* __restrict__ occ,
+                                                        const uint32_t* __restrict__ scan, uint32_t nblk, uint32_t cap, uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t off = scan[blockIdx.x];
+    if (scan[nblk] > cap || scan[blockIdx.x + 1] == off) return;  // (block-uniform)
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    uint8_t v = 0;
+    bool chg = false;
+    if (i < (long long)g.W1 * g.H1) {
+        v = prepared_byte<false>(raw, nullptr, g.W0, g.H0, g.dx, g.dy, g.ifa, g.variant, g.msg_layout, g.H1, i);
+        chg = occ[i] != v;
+    }
+    const uint64_t m = __ballot(chg);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) s_wave[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t pos = off + rank_below(m);
+    for (uint32_t w = 0; w < wave; w++) pos += s_wave[w];
+    if (chg && pos < cap) list[pos] = (uint32_t)(i / g.H1) << 16 | (uint32_t)(i % g.H1) << 1 | (uint32_t)v;
+}
+
 // ---- Many raw maps into grid slots in one call (fxjps_prepare_slots, DESIGN.md section 3.8): the preparation above, the
 // goal relocation and the four-launch build, each ONE launch over all jobs of the call.  A launch's blocks are the blocks
 // the single-grid kernel would run for job 0, then those for job 1, ...: SlotTable::first[launch][j] is the first block

@@ -197,6 +197,79 @@ class Planner(object):
         self.shape = (W.value, H.value)
         return (s[0], s[1]), (g[0], g[1]), (md[0], md[1]), self.shape, eo.value
 
+    # -- streaming replan from whole raw maps
+    @staticmethod
+    def _prep_args(start, goal, variant):
+        v = {"st": 0, "ccst": 1}[variant] if isinstance(variant, str) else int(variant)
+        s = (C.c_int32 * 2)(int(start[0]), int(start[1]))
+        g = (C.c_int32 * 2)(int(goal[0]), int(goal[1]))
+        return v, s, g, C.c_int32(), C.c_int32(), (C.c_int32 * 2)(), C.c_int32(), C.c_int64(), C.c_int32()
+
+    def refresh_grid(self, raw, start, goal, ifa, variant="st"):
+        """prepare_grid for a tick whose raw map mostly did not change: the prepared grid is compared with the resident one on
+        the device and only the cells that differ are applied (a partial rebuild).  -> prepare_grid's tuple + (changed, mode);
+        mode 0: nothing differs, 1: `changed` cells were updated, 2: the whole build ran (changed -1: nothing to compare with)."""
+        raw = np.ascontiguousarray(np.asarray(raw) > 0, dtype=np.uint8)
+        if raw.ndim != 2:
+            raise ValueError("grid must be 2-D")
+        v, s, g, W, H, md, eo, ch, mode = self._prep_args(start, goal, variant)
+        self._resident = None
+        self._chk(self._L.fxjps_refresh_grid(self._h, _lib.ptr(raw, C.c_uint8), raw.shape[0], raw.shape[1], int(ifa), v,
+                                             s, g, C.byref(W), C.byref(H), md, C.byref(eo), C.byref(ch), C.byref(mode)))
+        self.shape = (W.value, H.value)
+        return (s[0], s[1]), (g[0], g[1]), (md[0], md[1]), self.shape, eo.value, ch.value, mode.value
+
+    def refresh_occupancy_msg(self, data, width, height, start, goal, ifa, variant="st"):
+        """refresh_grid straight from a nav_msgs/OccupancyGrid (as prepare_occupancy_msg)."""
+        data = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+        if data.size != width * height:
+            raise ValueError("data has %d cells, expected %d" % (data.size, width * height))
+        v, s, g, W, H, md, eo, ch, mode = self._prep_args(start, goal, variant)
+        self._resident = None
+        self._chk(self._L.fxjps_refresh_occupancy_msg(self._h, _lib.ptr(data, C.c_int8), int(width), int(height), int(ifa), v,
+                                                      s, g, C.byref(W), C.byref(H), md, C.byref(eo), C.byref(ch), C.byref(mode)))
+        self.shape = (W.value, H.value)
+        return (s[0], s[1]), (g[0], g[1]), (md[0], md[1]), self.shape, eo.value, ch.value, mode.value
+
+    def last_refresh_cells(self):
+        """The cells the last refresh_grid / replan_frame_raw applied in mode 1: -> (xy int32[n, 2], val uint8[n]) in ascending
+        order of x * H + y (empty after modes 0 and 2)."""
+        n = C.c_int64()
+        self._resident = None
+        self._chk(self._L.fxjps_last_refresh_cells(self._h, None, None, 0, C.byref(n)))
+        xy, val = np.zeros((n.value, 2), np.int32), np.zeros(n.value, np.uint8)
+        if n.value:
+            self._chk(self._L.fxjps_last_refresh_cells(self._h, _lib.ptr(xy, C.c_int32), _lib.ptr(val, C.c_uint8), n.value, C.byref(n)))
+        return xy, val
+
+    def replan_frame_raw(self, raw, start, goal, ifa, variant="st"):
+        """replan_frame whose frame is a whole raw map (a matrix as for prepare_grid; an int8 array is taken as a message's
+        [height][width] data): diff against the resident grid, reuse what the changed cells cannot reach, plan the stored
+        queries.  Needs set_queries and a resident grid of the prepared extents.
+        -> (offsets, cells, cost, status) + prepare_grid's tuple + (changed, mode)."""
+        raw = np.asarray(raw)
+        if raw.ndim != 2:
+            raise ValueError("grid must be 2-D")
+        if raw.dtype == np.int8:
+            layout, raw, W0, H0 = 1, np.ascontiguousarray(raw), raw.shape[1], raw.shape[0]
+        else:
+            layout, raw, W0, H0 = 0, np.ascontiguousarray(raw > 0, dtype=np.uint8), raw.shape[0], raw.shape[1]
+        v, s, g, W, H, md, eo, ch, mode = self._prep_args(start, goal, variant)
+        n = getattr(self, "_nq", 0)  # (before set_queries: the library refuses the call)
+        self._resident = None
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        status = np.zeros(n, dtype=np.int32)
+        cost = np.zeros(n, dtype=np.float64)
+        secs = C.c_double(0.0)
+        self._chk(self._L.fxjps_replan_frame_raw(self._h, raw.ctypes.data_as(C.c_void_p), layout, W0, H0, int(ifa), v, s, g, C.byref(W),
+                                                 C.byref(H), md, C.byref(eo), C.byref(ch), C.byref(mode), _lib.ptr(offsets, C.c_int64), None, 0,
+                                                 _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double), C.byref(secs)))
+        cells = np.empty((int(offsets[n]), 2), dtype=np.int32)
+        if offsets[n] > 0:
+            self._chk(self._L.fxjps_last_cells(self._h, _lib.ptr(cells, C.c_int32), int(offsets[n])))
+        self.last_seconds = secs.value
+        return offsets, cells, cost, status, (s[0], s[1]), (g[0], g[1]), (md[0], md[1]), (W.value, H.value), eo.value, ch.value, mode.value
+
     def get_grid(self, context=0):
         """The resident uint8 [W][H] occupancy grid (e.g. the prepared map the node publishes); of a multi-device handle:
         the bytes context `context` holds (equal on every device after the broadcast)."""

@@ -94,8 +94,11 @@ typedef struct fxjps fxjps_t;
  *        fxjps_set_prior_map, fxjps_get_prior_map, fxjps_world_job_size.
  *   790  fxjps_prepare_slots_cropped, fxjps_refresh_slots_cropped (the world-frame calls with the ccst node's crop of every
  *        map message to its occupied box in front, the box found on the device), fxjps_crop_size.
+ *   800  fxjps_refresh_grid, fxjps_refresh_occupancy_msg (fxjps_prepare_grid for a tick whose raw map mostly did not change:
+ *        the prepared grid is diffed against the resident one on the device and only the changed cells are applied),
+ *        fxjps_last_refresh_cells, fxjps_replan_frame_raw (fxjps_replan_frame from a whole raw map).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 790
+#define FXJPS_VERSION 800
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -218,6 +221,45 @@ int fxjps_set_queries(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals
 int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n, int64_t* out_offsets,
                        int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len, double* out_cost,
                        double* out_seconds_total);
+
+/* Streaming replan from whole raw maps.  fxjps_refresh_grid / fxjps_refresh_occupancy_msg take
+ * the arguments of fxjps_prepare_grid / fxjps_prepare_occupancy_msg and leave what those leave -- the resident grid, every
+ * derived map, start_xy, goal_xy and the outputs (the goal relocation and end_occu are computed on every call) -- but when
+ * a grid of the prepared extents is resident they compare the prepared bytes with it on the device and apply only the
+ * cells that differ, as fxjps_update_cells would (the component forest may then be coarser than a fresh one, as after any
+ * cell update).  *out_mode says which way was taken:
+ *   0  same extents, no byte differs: nothing is written, no build is queued (*out_changed = 0);
+ *   1  same extents, *out_changed cells differ and fit the list of max(4096, W * H / 8) entries: they went through the
+ *      cell-update path (partial rebuild);
+ *   2  no resident grid, other extents (*out_changed = -1, nothing was compared) or more changed cells than the list
+ *      holds (*out_changed = their number): fxjps_prepare_grid's whole build.
+ * Refusals are fxjps_prepare_grid's.  Cell updates still deferred (fxjps_update_cells_deferred) are ordered in front of
+ * the comparison and covered by the rebuild.  Like fxjps_update_cells the calls drop the stored results of
+ * fxjps_replan_frame / fxjps_replan_slots.
+ * fxjps_last_refresh_cells: the cells the last such call (or fxjps_replan_frame_raw) applied in mode 1, in ascending
+ * order of x * H + y, with the bytes they were set to; *out_n their number (0 after modes 0 and 2).  out_xy == out_val ==
+ * NULL: the number only. */
+int fxjps_refresh_grid(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
+                       int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d,
+                       int32_t* out_end_occu, int64_t* out_changed, int32_t* out_mode);
+int fxjps_refresh_occupancy_msg(fxjps_t* h, const int8_t* data, int32_t width, int32_t height, int32_t ifa,
+                                int32_t variant, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
+                                int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed, int32_t* out_mode);
+int fxjps_last_refresh_cells(fxjps_t* h, int32_t* out_xy, uint8_t* out_val, int64_t capacity, int64_t* out_n);
+
+/* fxjps_replan_frame whose frame is a whole raw map: `raw` is a W0 x H0 matrix (layout 0, as fxjps_prepare_grid) or a
+ * message's data[] (layout 1, as fxjps_prepare_occupancy_msg: W0 = width, H0 = height).  The prepared grid is diffed as
+ * by fxjps_refresh_grid, fxjps_replan_frame's reuse rule runs on the changed cells, they are applied (mode 0 / 1) or the
+ * grid is rebuilt (mode 2: more changed cells than the list holds; every query is searched) and the stored queries are
+ * planned; outputs as fxjps_refresh_grid followed by fxjps_replan_frame's.  Results are bit-identical to
+ * fxjps_prepare_grid + fxjps_plan_batch_csr on a fresh handle.  Needs fxjps_set_queries and a resident grid of the
+ * prepared extents: otherwise FXJPS_E_ARG before anything is touched (call fxjps_prepare_grid and fxjps_set_queries
+ * again; the stored queries are cells of the prepared grid -- out_map_d shows a padding that moved under equal extents). */
+int fxjps_replan_frame_raw(fxjps_t* h, const void* raw, int32_t layout, int32_t W0, int32_t H0, int32_t ifa,
+                           int32_t variant, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
+                           int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed, int32_t* out_mode,
+                           int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len,
+                           double* out_cost, double* out_seconds_total);
 
 /* Plan nq independent (start, goal) queries against the resident grid.
  *   starts_xy, goals_xy : nq (x, y) pairs
