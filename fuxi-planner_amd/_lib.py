@@ -13,13 +13,13 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 800  # FXJPS_VERSION of include/fxjps.h
+VERSION = 810  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
            "fxjps_plan_batch_csr", "fxjps_last_cells", "fxjps_last_timing", "fxjps_last_timing_device", "fxjps_comm_info", "fxjps_set_memory_share", "fxjps_selftest_sqrt", "fxjps_selftest_wavemin", "fxjps_selftest_openlist", "fxjps_debug_read_nbmask", "fxjps_debug_read_maps", "fxjps_debug_counters", "fxjps_debug_qstat",
            "fxjps_waypoint_st", "fxjps_waypoint_ccst", "fxjps_waypoint_ccst_batch", "fxjps_waypoint_st_batch",
-           "fxjps_set_grid_slot", "fxjps_get_grid_slot", "fxjps_plan_batch_slots_csr", "fxjps_debug_read_slot_maps", "fxjps_debug_read_sets",
+           "fxjps_set_grid_slot", "fxjps_get_grid_slot", "fxjps_plan_batch_slots_csr", "fxjps_debug_read_slot_maps", "fxjps_debug_read_sets", "fxjps_debug_live_bytes",
            "fxjps_prepare_slots", "fxjps_slot_job_size", "fxjps_waypoint_slots_batch", "fxjps_publish_slots", "fxjps_slot_publish_size",
            "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context", "fxjps_replan_slots",
            "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size",
@@ -215,6 +215,8 @@ def load():
     L.fxjps_debug_read_slot_maps.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, p_i64]
     L.fxjps_debug_read_slot_context.restype = C.c_int
     L.fxjps_debug_read_slot_context.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, p_i64]
+    L.fxjps_debug_live_bytes.restype = C.c_int
+    L.fxjps_debug_live_bytes.argtypes = [p_i64, p_i64]
     L.fxjps_debug_read_sets.restype = C.c_int
     L.fxjps_debug_read_sets.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, p_i32]
     L.fxjps_last_cells.restype = C.c_int

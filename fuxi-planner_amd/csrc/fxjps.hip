@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -22,6 +23,7 @@
 
 #include "../../include/fxjps.h"
 #include "fxjps_kernels.hip.inc"
+#include "fxjps_owned.h"
 
 namespace {
 
@@ -91,47 +93,60 @@ double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-template <typename T>
-struct DBuf {  // grow-only device buffer
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+// Bytes the library holds right now, over every handle of the process (fxjps_debug_live_bytes): device memory, and pinned
+// host memory.  Counted where memory is allocated or freed, nowhere else.
+std::atomic<int64_t> g_live_device{0}, g_live_pinned{0};
 
+struct DeviceMem {
+    using error = hipError_t;
+    static constexpr hipError_t ok = hipSuccess;
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+    static std::atomic<int64_t>& live() { return g_live_device; }
+};
+struct PinnedMem {
+    using error = hipError_t;
+    static constexpr hipError_t ok = hipSuccess;
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static std::atomic<int64_t>& live() { return g_live_pinned; }
+};
 template <typename T>
-struct HBuf {  // grow-only pinned host buffer
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
+using DBuf = fx::OwnedBuf<T, DeviceMem>;  // grow-only device buffer
+template <typename T>
+using HBuf = fx::OwnedBuf<T, PinnedMem>;  // grow-only pinned host buffer
+
+struct StreamRes {
+    using type = hipStream_t;
+    static hipError_t create(hipStream_t* s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
+    static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+struct EventRes {
+    using type = hipEvent_t;
+    static hipError_t create(hipEvent_t* ev, unsigned flags) { return hipEventCreateWithFlags(ev, flags); }
+    static void destroy(hipEvent_t ev) { (void)hipEventDestroy(ev); }
+};
+struct MappedWordRes {  // one zeroed uint32_t in a 64-byte pinned allocation
+    using type = uint32_t*;
+    static constexpr int64_t BYTES = 64;
+    static hipError_t create(uint32_t** w, unsigned flags) {
+        hipError_t e = hipHostMalloc((void**)w, BYTES, flags);
+        if (e == hipSuccess) {
+            **w = 0u;
+            g_live_pinned += BYTES;
+        } else {
+            *w = nullptr;
+        }
         return e;
     }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
+    static void destroy(uint32_t* w) {
+        (void)hipHostFree(w);
+        g_live_pinned -= BYTES;
     }
 };
+using Stream = fx::Owned<StreamRes>;
+using Event = fx::Owned<EventRes>;
+using MappedWord = fx::Owned<MappedWordRes>;
 
 struct ScratchCfg {
     uint32_t nwaves = 0;
@@ -149,15 +164,7 @@ struct GridBufs {
     DBuf<int> comp;
     DBuf<uint16_t> ci;
     DBuf<uint16_t> jd;  // jump distances [PW][NS][8] (k_derive_jd)
-    void release() {
-        occ.release();
-        comp.release();
-        nb8.release();
-        ci.release();
-        jd.release();
-        bm.release();
-        W = H = 0;
-    }
+    void release() { *this = GridBufs(); }  // an empty slot: extents zero, memory returned at once
 };
 
 struct DevCtx : GridBufs {
@@ -165,17 +172,18 @@ struct DevCtx : GridBufs {
     int n_cu = 256;
     int share = 1;  // contexts of this handle on the same physical device (they split its memory and wavefront slots)
     size_t mem_total = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream_solo = nullptr;  // the launch of the longest queries, one wavefront per CU, beside the batch's launch
-    uint32_t* solo_started = nullptr;   // pinned host word: blocks of such launches that have started (only ever counts up)
+    // (the streams stand in front of every buffer: members go in reverse order, so the buffers are freed while they exist)
+    Stream stream;
+    Stream stream_solo;                 // the launch of the longest queries, one wavefront per CU, beside the batch's launch
+    MappedWord solo_started;            // pinned host word: blocks of such launches that have started (only ever counts up)
     uint32_t solo_target = 0;           // ... and how many have been launched
     int solo_timeouts = 0;              // waits for that counter that ran into their 5 ms bound, since the handle was created
     int solo_timeouts_run = 0;          // ... in a row (3: no more head launches on this device; a cold first launch of a
                                         // kernel -- its code object is loaded then -- is a lone timeout and means nothing)
     size_t cells_bound = 0;             // bytes the batch in progress may still allocate for its packed paths
     bool lds_attr_done[12] = {};        // k_search instantiations whose dynamic-LDS limit has been raised on this device
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_solo0 = nullptr, ev_solo1 = nullptr;
-    hipEvent_t ev_hd0 = nullptr, ev_hd1 = nullptr, ev_bt0 = nullptr, ev_bt1 = nullptr;  // around the head launch / the batch's launch alone
+    Event ev0, ev1, ev_solo0, ev_solo1;
+    Event ev_hd0, ev_hd1, ev_bt0, ev_bt1;  // around the head launch / the batch's launch alone
     bool had_solo = false;              // the last regular-pool launch was two launches
     double head_ms = 0, batch_ms = 0;   // ... and how long each of them ran
     // grid slots (fxjps_set_grid_slot): their maps, and their descriptors on the device (what k_search<.., .., .., true> reads)
@@ -254,16 +262,6 @@ struct DevCtx : GridBufs {
         // the caller's offsets | cells) and output (fx::WpSlotResult per query | the kept cells), pinned and on the device
         HBuf<uint8_t> h_recs_in, h_recs_out;
         DBuf<uint8_t> d_recs_in, d_recs_out;
-        void release() {
-            for (DBuf<double>* b : {&d_in, &d_out, &d_prev, &d_ang, &d_atab}) b->release();
-            for (DBuf<int32_t>* b : {&d_eo, &d_nkept, &d_kept, &d_cells, &d_len, &d_ms, &d_pdim, &d_dim}) b->release();
-            d_off.release();
-            atab_a = atab_b = -1;
-            h_recs_in.release();
-            h_recs_out.release();
-            d_recs_in.release();
-            d_recs_out.release();
-        }
     } wp;
     DBuf<int32_t> d_upd_xy;
     DBuf<uint8_t> d_upd_chg;
@@ -285,11 +283,11 @@ struct DevCtx : GridBufs {
     // pinned staging of a cell-update list: the caller's arrays are copied here before the asynchronous H2D copy, so
     // that they need not outlive the call (ev_upd: the last copy out of the staging buffers has completed)
     HBuf<int32_t> h_upd_xy;
-    hipEvent_t ev_upd = nullptr;
+    Event ev_upd;
     HBuf<uint8_t> h_occ_stage;      // a small grid on its way to the device (fxjps_set_grid returns while it travels)
-    hipEvent_t ev_stage = nullptr;  // ... the copy out of it has completed
+    Event ev_stage;                 // ... the copy out of it has completed
     bool stage_pending = false;
-    hipEvent_t ev_ccl0 = nullptr, ev_ccl1 = nullptr;  // a whole map build: the component labels on the second stream, beside the maps
+    Event ev_ccl0, ev_ccl1;  // a whole map build: the component labels on the second stream, beside the maps
     bool upd_pending = false;
     HBuf<int32_t> h_len, h_cells;
     HBuf<uint32_t> h_path1;       // single calls: the search kernel writes the packed path of its one query here
@@ -304,6 +302,18 @@ struct DevCtx : GridBufs {
     int64_t launches = 0, retried = 0;
     uint32_t waves_used = 0;  // resident wavefronts of the last regular-pool launch
     bool waves_short = false; // a scratch pool was granted fewer wavefronts than the batch asked for (memory budget / out of memory)
+
+    DevCtx() = default;
+    DevCtx(DevCtx&&) = default;  // (std::vector<DevCtx>::resize; nothing moves a context that is in use)
+    DevCtx& operator=(DevCtx&&) = default;
+    // Whatever is queued may still use the buffers: both streams are drained, then every member gives back what it holds,
+    // with the context's device current.
+    ~DevCtx() {
+        if (dev < 0) return;
+        (void)hipSetDevice(dev);
+        if (stream_solo) (void)hipStreamSynchronize(stream_solo);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 }  // namespace
@@ -348,6 +358,14 @@ struct fxjps {
     // one process per GPU without torch (fxjps_create_rank): this handle is rank `rank` of `world`, its one communicator
     // (comms[0]) was made with ncclCommInitRank from the id rank 0 handed out
     int rank = -1, world = 0;
+
+    ~fxjps() {  // the communicators first, then the contexts (their streams may be the ones a broadcast ran on)
+        if (!rccl) return;
+        auto destroy = (int (*)(void*))dlsym(rccl, "ncclCommDestroy");
+        if (destroy)
+            for (void* c : comms)
+                if (c) destroy(c);
+    }
 };
 
 namespace {
@@ -918,7 +936,7 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
             d.solo_target += nsolo / live_solo;
             const auto t0 = std::chrono::steady_clock::now();
             bool late = false;
-            while ((int32_t)(__atomic_load_n(d.solo_started, __ATOMIC_ACQUIRE) - d.solo_target) < 0) {
+            while ((int32_t)(__atomic_load_n(d.solo_started.h, __ATOMIC_ACQUIRE) - d.solo_target) < 0) {
                 if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
                     // (the counter did not arrive in time -- no PCIe atomics, a tool that serialises kernels: after three
                     // such waits in a row this device runs its batches as one launch; fxjps_timing_t::solo_timeouts counts them)
@@ -1745,32 +1763,19 @@ int fxjps_create(int backend, const int* device_ids, int n_dev, fxjps_t** out) {
         hipDeviceProp_t prop;
         hipError_t e = hipSetDevice(d.dev);
         if (e == hipSuccess) e = hipGetDeviceProperties(&prop, d.dev);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = d.stream.create(hipStreamNonBlocking);
         // (FXJPS_ONE_STREAM=1: measurement aid -- no second stream, hence no head launches, on this handle: how the runtime
         // deals its hardware queues out over the streams of many handles)
         const bool one_stream = getenv("FXJPS_ONE_STREAM") && atoi(getenv("FXJPS_ONE_STREAM")) != 0;
-        if (e == hipSuccess && !one_stream) e = hipStreamCreateWithFlags(&d.stream_solo, hipStreamNonBlocking);
-        if (e == hipSuccess && !one_stream) {
-            // (fine-grained, mapped: the kernel counts with a system-scope atomic, the host polls)
-            if (hipHostMalloc((void**)&d.solo_started, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) {
-                *d.solo_started = 0u;
-            } else {
-                (void)hipGetLastError();
-                d.solo_started = nullptr;  // no solo launches on this device
-            }
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_solo0, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_solo1, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev0);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev1);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev_hd0);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev_hd1);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev_bt0);
-        if (e == hipSuccess) e = hipEventCreate(&d.ev_bt1);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_upd, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_stage, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_ccl0, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_ccl1, hipEventDisableTiming);
+        if (e == hipSuccess && !one_stream) e = d.stream_solo.create(hipStreamNonBlocking);
+        // (fine-grained, mapped: the kernel counts with a system-scope atomic, the host polls; without it no solo launches
+        // on this device)
+        if (e == hipSuccess && !one_stream && d.solo_started.create(hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+            (void)hipGetLastError();
+        for (Event* ev : {&d.ev_solo0, &d.ev_solo1, &d.ev_upd, &d.ev_stage, &d.ev_ccl0, &d.ev_ccl1})
+            if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
+        for (Event* ev : {&d.ev0, &d.ev1, &d.ev_hd0, &d.ev_hd1, &d.ev_bt0, &d.ev_bt1})
+            if (e == hipSuccess) e = ev->create(hipEventDefault);
         if (e != hipSuccess) {
             int rc = fail(nullptr, FXJPS_E_HIP, "device %d: %s", d.dev, hipGetErrorString(e));
             fxjps_destroy(h);
@@ -1896,100 +1901,9 @@ int fxjps_set_grid_rank(fxjps_t* h, const uint8_t* occ, int32_t W, int32_t H) {
     return finish_set_grid(h, W, H);  // the broadcast (root = rank 0), then every rank derives its maps itself
 }
 
+// (~fxjps, ~DevCtx and the owners of fxjps_owned.h do the work: there is no list of members to keep here)
 void fxjps_destroy(fxjps_t* h) {
     if (!h) return;
-    if (h->rccl) {
-        auto destroy = (nccl_destroy_t)dlsym(h->rccl, "ncclCommDestroy");
-        if (destroy)
-            for (void* c : h->comms)
-                if (c) destroy(c);
-    }
-    for (auto& d : h->devs) {
-        if (d.dev < 0) continue;
-        (void)hipSetDevice(d.dev);
-        if (d.stream_solo) (void)hipStreamSynchronize(d.stream_solo);
-        if (d.stream) (void)hipStreamSynchronize(d.stream);
-        d.occ.release();
-        d.comp.release();
-        d.nb8.release();
-        d.ci.release();
-        d.jd.release();
-        d.bm.release();
-        for (int p = 0; p < 2; p++) {
-            d.tables[p].release();
-            d.far[p].release();
-            d.wave_gen[p].release();
-        }
-        d.d_starts.release();
-        d.d_goals.release();
-        d.d_len.release();
-        d.d_cells.release();
-        d.d_cost.release();
-        d.d_path.release();
-        d.d_order.release();
-        d.d_redo.release();
-        d.d_offsets.release();
-        d.p_len.release();
-        d.p_cells.release();
-        d.p_cost.release();
-        d.p_offsets.release();
-        d.s_len.release();
-        d.s_cost.release();
-        d.d_rs_src.release();
-        d.h_rs_src.release();
-        d.d_next.release();
-        d.d_counters.release();
-        d.d_qstat.release();
-        d.d_qread.release();
-        d.d_raw.release();
-        d.d_img.release();
-        d.wp.release();
-        d.d_upd_xy.release();
-        d.d_upd_chg.release();
-        d.d_owner.release();
-        d.d_chgmap.release();
-        d.d_chglist.release();
-        d.d_chgcnt.release();
-        d.d_chgovf.release();
-        d.h_len.release();
-        d.h_cells.release();
-        d.h_cost.release();
-        d.h_offsets.release();
-        d.h_counters.release();
-        d.h_upd_xy.release();
-        d.h_path1.release();
-        for (auto& g : d.slots) g.release();
-        for (auto& pr : d.priors) pr.occ.release();
-        d.d_slot_desc.release();
-        d.d_grid_ids.release();
-        d.h_slots_in.release();
-        d.d_slots_in.release();
-        d.h_slots_res.release();
-        d.d_slots_res.release();
-        d.h_crop_in.release();
-        d.d_crop_in.release();
-        d.d_crop_win.release();
-        d.h_crop_box.release();
-        d.h_pub_in.release();
-        d.h_pub_out.release();
-        d.d_pub_in.release();
-        d.d_pub_out.release();
-        if (d.ev_upd) (void)hipEventDestroy(d.ev_upd);
-        if (d.ev_stage) (void)hipEventDestroy(d.ev_stage);
-        d.h_occ_stage.release();
-        if (d.ev_ccl0) (void)hipEventDestroy(d.ev_ccl0);
-        if (d.ev_ccl1) (void)hipEventDestroy(d.ev_ccl1);
-        if (d.solo_started) (void)hipHostFree(d.solo_started);
-        if (d.ev_solo0) (void)hipEventDestroy(d.ev_solo0);
-        if (d.ev_solo1) (void)hipEventDestroy(d.ev_solo1);
-        if (d.stream_solo) (void)hipStreamDestroy(d.stream_solo);
-
-        if (d.ev0) (void)hipEventDestroy(d.ev0);
-        if (d.ev1) (void)hipEventDestroy(d.ev1);
-        for (hipEvent_t ev : {d.ev_hd0, d.ev_hd1, d.ev_bt0, d.ev_bt1})
-            if (ev) (void)hipEventDestroy(ev);
-        if (d.stream) (void)hipStreamDestroy(d.stream);
-    }
     delete h;
 }
 
@@ -4295,6 +4209,13 @@ int fxjps_debug_qstat(fxjps_t* h, unsigned long long* out, int64_t nq) {
     if (!d.d_qstat.p || nq > d.nq) return FXJPS_E_ARG;
     HIPCHK(h, hipSetDevice(d.dev));
     HIPCHK(h, hipMemcpy(out, d.d_qstat.p, (size_t)nq * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return FXJPS_OK;
+}
+
+// what every handle of the process holds right now (tests: a closed handle gives everything back)
+int fxjps_debug_live_bytes(int64_t* out_device, int64_t* out_pinned) {
+    if (out_device) *out_device = g_live_device.load();
+    if (out_pinned) *out_pinned = g_live_pinned.load();
     return FXJPS_OK;
 }
 

@@ -96,6 +96,14 @@ class Planner(object):
         self.shape = (int(W), int(H))
 
     # -- lifetime
+    @staticmethod
+    def live_bytes():
+        """-> (device, pinned): the bytes of device and of pinned host memory that the open handles of this process hold.
+        A closed handle leaves both where they were before it was created."""
+        dev, pin = C.c_int64(), C.c_int64()
+        _lib.load().fxjps_debug_live_bytes(C.byref(dev), C.byref(pin))
+        return dev.value, pin.value
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.fxjps_destroy(self._h)

@@ -97,8 +97,10 @@ typedef struct fxjps fxjps_t;
  *   800  fxjps_refresh_grid, fxjps_refresh_occupancy_msg (fxjps_prepare_grid for a tick whose raw map mostly did not change:
  *        the prepared grid is diffed against the resident one on the device and only the changed cells are applied),
  *        fxjps_last_refresh_cells, fxjps_replan_frame_raw (fxjps_replan_frame from a whole raw map).
+ *   810  fxjps_debug_live_bytes (the bytes of device and of pinned host memory that the process's handles hold; every
+ *        buffer, stream and event of a handle is owned by a member that frees it, so fxjps_destroy has no list to keep).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 800
+#define FXJPS_VERSION 810
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -131,6 +133,8 @@ int fxjps_set_grid_rank(fxjps_t* h, const uint8_t* occ, int32_t W, int32_t H);
 int fxjps_rank_preflight(int device);
 int fxjps_reserve_grid(fxjps_t* h, int32_t W, int32_t H);
 
+/* Everything the handle allocated -- device and pinned host memory, streams, events, communicators -- is returned; its
+ * streams are drained first.  h == NULL: nothing happens. */
 void fxjps_destroy(fxjps_t* h);
 
 /* Last error text for this handle (h == NULL: last create error). */
@@ -631,6 +635,12 @@ int fxjps_debug_read_slot_context(fxjps_t* h, int32_t context, int32_t slot, int
  * nq must be the number of stored queries; *out_tile_shift receives tsh.  FXJPS_E_ARG unless the
  * stored results are tracked (the last call was a fxjps_replan_frame that recorded read sets). */
 int fxjps_debug_read_sets(fxjps_t* h, uint64_t* out, int64_t nq, int32_t* out_tile_shift);
+
+/* The bytes that the handles of this process hold right now: device memory in *out_device, pinned host memory (the
+ * mapped counter word of each context included) in *out_pinned; either may be NULL.  Takes no handle and always returns
+ * FXJPS_OK.  Counted where the library allocates and frees its grow-only buffers, so the figures do not move with what
+ * other processes do on the device; a handle that has been destroyed leaves both where they were before it was created. */
+int fxjps_debug_live_bytes(int64_t* out_device, int64_t* out_pinned);
 
 /* Measurement aids of tools/ (not used by the planner's Python host code).  fxjps_debug_counters: the 64 raw device
  * counters of the last batch on the first context ([0] pops, [1] pushes, [2] far refills, [3] slow pops, [7] table wipes;
