@@ -1964,6 +1964,14 @@ int fxjps_set_grid_device(fxjps_t* h, const void* d_occ, int32_t W, int32_t H) {
 }
 
 namespace {
+// How every call over a job array opens: the handle, the number of jobs, the array, and no rank handle.
+int jobs_call_check(fxjps_t* h, const void* jobs, int32_t n, const char* what) {
+    if (!h) return FXJPS_E_ARG;
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
+    return refuse_on_rank_handle(h, what);
+}
+
 // What the host derives from a raw map's extents, the start and the goal before anything is queued: the padding, the
 // prepared extents and the shifted start and goal.  The callers judge the result (extents over 8190, a goal outside).
 struct SlotPlan {
@@ -1991,131 +1999,125 @@ SlotPlan prepared_geometry(long long W0, long long H0, long long ifa, int varian
     return p;
 }
 
+// What a single-grid prepare call was asked for, filled once by its entry point, and the geometry prepare_check derives.
+struct PrepReq {
+    const uint8_t* raw;
+    int32_t W0, H0, ifa, variant, layout;  // layout 1: `raw` is the int8 data[] of an OccupancyGrid message
+    int32_t *start_xy, *goal_xy;           // in: the raw map's cells; out: the prepared grid's
+    int32_t *out_W, *out_H, *out_map_d, *out_end_occu;  // (each may be NULL)
+    SlotPlan p;
+    fx::PrepGeom geom() const { return fx::PrepGeom{W0, H0, (int32_t)p.dx, (int32_t)p.dy, ifa, variant, layout, (int32_t)p.W1, (int32_t)p.H1}; }
+    bool goal_inside() const { return p.ngx >= 0 && p.ngy >= 0 && p.ngx < p.W1 && p.ngy < p.H1; }
+};
+
 // prepare_grid's refusals (nothing is touched yet) and the geometry of the prepared grid
-int prepare_check(fxjps_t* h, const char* what, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, const int32_t* start_xy,
-                  const int32_t* goal_xy, SlotPlan* out) {
-    if (!raw || !start_xy || !goal_xy || W0 < 1 || H0 < 1 || ifa < 0 || ifa > 64 || (variant != 0 && variant != 1))
+int prepare_check(fxjps_t* h, const char* what, PrepReq* q) {
+    if (!q->raw || !q->start_xy || !q->goal_xy || q->W0 < 1 || q->H0 < 1 || q->ifa < 0 || q->ifa > 64 || (q->variant != 0 && q->variant != 1))
         return fail(h, FXJPS_E_ARG, "bad prepare_grid arguments");
     if (int rr = refuse_on_rank_handle(h, what)) return rr;
-    *out = prepared_geometry(W0, H0, ifa, variant, start_xy, goal_xy);
-    if (out->W1 > 8190 || out->H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", out->W1, out->H1);
+    q->p = prepared_geometry(q->W0, q->H0, q->ifa, q->variant, q->start_xy, q->goal_xy);
+    if (q->p.W1 > 8190 || q->p.H1 > 8190) return fail(h, FXJPS_E_ARG, "prepared grid %lldx%lld exceeds 8190 cells a side", q->p.W1, q->p.H1);
     return FXJPS_OK;
 }
 
-// The whole prepared grid written and every derived map built, on every context; returns with all streams idle.
-// d0_staged: the raw map already lies in context 0's d_raw (fxjps_refresh_grid diffed against it).
-int prepare_build(fxjps_t* h, const SlotPlan& p, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout,
-                  bool d0_staged = false) {
-    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1;
-    h->have_grid = false;
-    h->q_results_valid = h->rs_valid = false;
-    for (auto& d : h->devs) {
-        HIPCHK(h, hipSetDevice(d.dev));
-        HIPCHK(h, d.d_raw.ensure((size_t)W0 * H0));
-        int rc = alloc_grid(h, d, (int)W1, (int)H1);
-        if (rc) return rc;
-        // every device pads and dilates the raw grid itself: cheaper than broadcasting the larger result
-        if (!(d0_staged && &d == &h->devs[0])) HIPCHK(h, hipMemcpyAsync(d.d_raw.p, raw, (size_t)W0 * H0, hipMemcpyHostToDevice, d.stream));
-        const long long n = W1 * H1;
-        hipLaunchKernelGGL(fx::k_prepare_grid, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d.stream, d.d_raw.p, W0, H0,
-                           (int)dx, (int)dy, ifa, variant, msg_layout, (int)W1, (int)H1, d.occ.p);
-        HIPCHK(h, hipGetLastError());
-        rc = derive_maps(h, d);
-        if (rc) return rc;
-    }
+// The goal rule (fx::goal_rule) queued on context 0's stream, behind whatever that stream holds, and its record on the way
+// into h_slots_res (these calls are synchronous, as the slot calls are: the buffers are free).  A goal outside the prepared
+// grid queues nothing: prepare_finish refuses it.
+int goal_queue(fxjps_t* h, const PrepReq& q) {
+    if (!q.goal_inside()) return FXJPS_OK;
+    DevCtx& d0 = h->devs[0];
+    HIPCHK(h, hipSetDevice(d0.dev));
+    HIPCHK(h, d0.h_slots_res.ensure(fx::SLOT_RES));
+    HIPCHK(h, d0.d_slots_res.ensure(fx::SLOT_RES));
+    hipLaunchKernelGGL(fx::k_prepare_goal, dim3(1), dim3(64), 0, d0.stream, d0.occ.p, (int)q.p.W1, (int)q.p.H1, (int)q.p.ngx, (int)q.p.ngy, q.ifa,
+                       q.variant, d0.d_slots_res.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d0.h_slots_res.p, d0.d_slots_res.p, fx::SLOT_RES * sizeof(int32_t), hipMemcpyDeviceToHost, d0.stream));
+    return FXJPS_OK;
+}
+// every context's stream idle
+int wait_all(fxjps_t* h) {
     for (auto& d : h->devs) {
         HIPCHK(h, hipSetDevice(d.dev));
         HIPCHK(h, hipStreamSynchronize(d.stream));
     }
+    return FXJPS_OK;
+}
+
+// The whole prepared grid written and every derived map built, on every context, and the goal rule behind context 0's
+// build; ONE wait, and all streams are idle.  d0_staged: the raw map already lies in context 0's d_raw (fxjps_refresh_grid
+// diffed against it).
+int prepare_build(fxjps_t* h, const PrepReq& q, bool d0_staged = false) {
+    const fx::PrepGeom g = q.geom();
+    const size_t raw_bytes = (size_t)q.W0 * q.H0;
+    h->have_grid = false;
+    h->q_results_valid = h->rs_valid = false;
+    for (auto& d : h->devs) {
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, d.d_raw.ensure(raw_bytes));
+        int rc = alloc_grid(h, d, g.W1, g.H1);
+        if (rc) return rc;
+        // every device pads and dilates the raw grid itself: cheaper than broadcasting the larger result
+        if (!(d0_staged && &d == &h->devs[0])) HIPCHK(h, hipMemcpyAsync(d.d_raw.p, q.raw, raw_bytes, hipMemcpyHostToDevice, d.stream));
+        const long long n = (long long)g.W1 * g.H1;
+        hipLaunchKernelGGL(fx::k_prepare_grid, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d.stream, d.d_raw.p, g, d.occ.p);
+        HIPCHK(h, hipGetLastError());
+        rc = derive_maps(h, d);
+        if (rc) return rc;
+    }
+    if (int rc = goal_queue(h, q)) return rc;
+    if (int rc = wait_all(h)) return rc;
     h->have_grid = true;
     h->maps_stale = false;
     return FXJPS_OK;
 }
 
 // What the callers get back: the shifted start, the goal moved off an obstacle, end_occu, the extents and the padding.
-// Reads the resident grid of context 0, whose stream is idle.
-int prepare_finish(fxjps_t* h, const SlotPlan& p, int32_t ifa, int32_t variant, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W,
-                   int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu) {
-    const long long dx = p.dx, dy = p.dy, W1 = p.W1, H1 = p.H1, nsx = p.nsx, nsy = p.nsy;
-    long long ngx = p.ngx, ngy = p.ngy;
-    if (ngx < 0 || ngy < 0 || ngx >= W1 || ngy >= H1) return fail(h, FXJPS_E_ARG, "goal outside the prepared grid");
-    // :268-272 / :454-458: a goal on an obstacle moves to the nearest free cell of its row, else of its column
-    DevCtx& d0 = h->devs[0];
-    HIPCHK(h, hipSetDevice(d0.dev));
-    std::vector<uint8_t> row((size_t)H1), col((size_t)W1);
-    HIPCHK(h, hipMemcpy(row.data(), d0.occ.p + (size_t)ngx * H1, (size_t)H1, hipMemcpyDeviceToHost));
-    int32_t end_occu = 0;
-    if (row[(size_t)ngy]) {
-        if (variant == 0) end_occu = 1;  // st:273
-        long long best = -1, bd = 0;
-        for (long long y = 0; y < H1; y++)
-            if (!row[(size_t)y] && (best < 0 || std::llabs(y - ngy) < bd)) {  // np.argmin: first of the nearest
-                best = y;
-                bd = std::llabs(y - ngy);
-            }
-        if (best >= 0) {
-            ngy = best;
-        } else {
-            HIPCHK(h, hipMemcpy2D(col.data(), 1, d0.occ.p + (size_t)ngy, (size_t)H1, 1, (size_t)W1, hipMemcpyDeviceToHost));
-            for (long long x = 0; x < W1; x++)
-                if (!col[(size_t)x] && (best < 0 || std::llabs(x - ngx) < bd)) {
-                    best = x;
-                    bd = std::llabs(x - ngx);
-                }
-            if (best < 0) return fail(h, FXJPS_E_ARG, "goal row and column are fully occupied (the reference raises here)");
-            ngx = best;
-        }
+// done: the goal's record is in and every stream is idle (prepare_build ran and waited; a diff that found no change
+// behind no deferred update); else the goal rule is queued here, behind what the caller queued, and every context is waited
+// for once.  Either way the call returns with all streams idle, and a call that fails writes nothing.
+int prepare_finish(fxjps_t* h, const PrepReq& q, bool done) {
+    if (!done) {
+        if (int rc = goal_queue(h, q)) return rc;
+        if (int rc = wait_all(h)) return rc;
     }
-    if (variant == 1 && ifa > 0) {
-        // ccst:461-464: end_occu = (mapu[gx-ifa:gx+ifa, gy-ifa:gy+ifa] == 1).any() around the (moved) goal, with
-        // numpy's slice rules: a negative bound counts from the end, everything is clipped to the array
-        auto bound = [](long long v, long long n) { return v < 0 ? std::max<long long>(v + n, 0) : std::min(v, n); };
-        const long long x0 = bound(ngx - ifa, W1), x1 = bound(ngx + ifa, W1), y0 = bound(ngy - ifa, H1), y1 = bound(ngy + ifa, H1);
-        if (x1 > x0 && y1 > y0) {
-            std::vector<uint8_t> box((size_t)((x1 - x0) * (y1 - y0)));
-            HIPCHK(h, hipMemcpy2D(box.data(), (size_t)(y1 - y0), d0.occ.p + (size_t)x0 * H1 + (size_t)y0, (size_t)H1, (size_t)(y1 - y0),
-                                  (size_t)(x1 - x0), hipMemcpyDeviceToHost));
-            for (uint8_t v : box)
-                if (v) end_occu = 1;
-        }
-    }
-    if (out_end_occu) *out_end_occu = end_occu;
-    start_xy[0] = (int32_t)nsx;
-    start_xy[1] = (int32_t)nsy;
-    goal_xy[0] = (int32_t)ngx;
-    goal_xy[1] = (int32_t)ngy;
-    if (out_W) *out_W = (int32_t)W1;
-    if (out_H) *out_H = (int32_t)H1;
-    if (out_map_d) {
-        out_map_d[0] = (int32_t)dx;
-        out_map_d[1] = (int32_t)dy;
+    if (!q.goal_inside()) return fail(h, FXJPS_E_ARG, "goal outside the prepared grid");
+    const int32_t* res = h->devs[0].h_slots_res.p;
+    if (res[3] != 0) return fail(h, FXJPS_E_ARG, "goal row and column are fully occupied (the reference raises here)");
+    const SlotPlan& p = q.p;
+    if (q.out_end_occu) *q.out_end_occu = res[2];
+    q.start_xy[0] = (int32_t)p.nsx;
+    q.start_xy[1] = (int32_t)p.nsy;
+    q.goal_xy[0] = res[0];
+    q.goal_xy[1] = res[1];
+    if (q.out_W) *q.out_W = (int32_t)p.W1;
+    if (q.out_H) *q.out_H = (int32_t)p.H1;
+    if (q.out_map_d) {
+        q.out_map_d[0] = (int32_t)p.dx;
+        q.out_map_d[1] = (int32_t)p.dy;
     }
     return FXJPS_OK;
 }
 
-}  // namespace
-
-static int prepare_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
-                             int msg_layout, int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H,
-                             int32_t* out_map_d, int32_t* out_end_occu) {
+int prepare_grid_impl(fxjps_t* h, PrepReq q) {
     if (!h) return FXJPS_E_ARG;
-    SlotPlan p{};
-    if (int rc = prepare_check(h, "fxjps_prepare_grid", raw, W0, H0, ifa, variant, start_xy, goal_xy, &p)) return rc;
-    if (int rc = prepare_build(h, p, raw, W0, H0, ifa, variant, msg_layout)) return rc;
-    return prepare_finish(h, p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+    if (int rc = prepare_check(h, "fxjps_prepare_grid", &q)) return rc;
+    if (int rc = prepare_build(h, q)) return rc;
+    return prepare_finish(h, q, true);
 }
+}  // namespace
 
 int fxjps_prepare_grid(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant,
                        int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d,
                        int32_t* out_end_occu) {
-    return prepare_grid_impl(h, raw, W0, H0, ifa, variant, 0, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+    return prepare_grid_impl(h, PrepReq{raw, W0, H0, ifa, variant, 0, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu, {}});
 }
 
 int fxjps_prepare_occupancy_msg(fxjps_t* h, const int8_t* data, int32_t width, int32_t height, int32_t ifa, int32_t variant,
                                 int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d,
                                 int32_t* out_end_occu) {
-    return prepare_grid_impl(h, reinterpret_cast<const uint8_t*>(data), width, height, ifa, variant, 1, start_xy, goal_xy,
-                             out_W, out_H, out_map_d, out_end_occu);
+    return prepare_grid_impl(h, PrepReq{reinterpret_cast<const uint8_t*>(data), width, height, ifa, variant, 1, start_xy, goal_xy, out_W, out_H,
+                                        out_map_d, out_end_occu, {}});
 }
 
 int fxjps_get_grid(fxjps_t* h, uint8_t* out, int32_t* out_W, int32_t* out_H) { return fxjps_get_grid_context(h, 0, out, out_W, out_H); }
@@ -2361,13 +2363,8 @@ static int emit_csr(fxjps_t* h, int64_t nq, int64_t* out_offsets, int32_t* out_c
 int fxjps_update_cells(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n) {
     if (!h) return FXJPS_E_ARG;
     h->q_results_valid = h->rs_valid = false;  // the grid changes behind the stored results
-    int rc = update_cells_async(h, xy, val, n, true);
-    if (rc) return rc;
-    for (auto& d : h->devs) {
-        HIPCHK(h, hipSetDevice(d.dev));
-        HIPCHK(h, hipStreamSynchronize(d.stream));
-    }
-    return FXJPS_OK;
+    if (int rc = update_cells_async(h, xy, val, n, true)) return rc;
+    return wait_all(h);
 }
 
 int fxjps_update_cells_deferred(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n) {
@@ -2495,35 +2492,37 @@ namespace {
 // 2: the grid is to be rebuilt (no resident grid or other extents: changed == -1, nothing ran; more changed cells than the
 // list holds).  box: the changed cells' bounding box (modes 1 and 2 behind a diff).
 struct RefreshDiff {
-    SlotPlan p;
     int mode = 2;
     int64_t changed = -1;
     bool staged = false;  // the raw map lies in context 0's d_raw
     int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
 };
-int refresh_diff(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout, RefreshDiff* r) {
-    const SlotPlan& p = r->p;
+int refresh_diff(fxjps_t* h, const PrepReq& q, RefreshDiff* r) {
+    const fx::PrepGeom g = q.geom();
     DevCtx& d = h->devs[0];
     h->refresh_xy.clear();
     h->refresh_val.clear();
-    if (!h->have_grid || p.W1 != d.W || p.H1 != d.H) return FXJPS_OK;
-    const long long ncell = p.W1 * p.H1;
+    if (!h->have_grid || g.W1 != d.W || g.H1 != d.H) return FXJPS_OK;
+    const long long ncell = (long long)g.W1 * g.H1;
+    const size_t raw_bytes = (size_t)q.W0 * q.H0;
     const uint32_t nblk = (uint32_t)((ncell + 255) / 256), cap = (uint32_t)std::max<long long>(4096, ncell / 8);
     constexpr uint32_t HEAD = 4096;  // entries of the list that travel with the header: a longer list takes a second copy
     HIPCHK(h, hipSetDevice(d.dev));
-    HIPCHK(h, d.d_raw.ensure((size_t)W0 * H0));
+    HIPCHK(h, d.d_raw.ensure(raw_bytes));
     HIPCHK(h, d.d_diff.ensure((size_t)fx::DIFF_HDR + cap + nblk + 1));
     HIPCHK(h, d.h_diff.ensure((size_t)fx::DIFF_HDR + HEAD));
     uint32_t *hdr = d.d_diff.p, *list = hdr + fx::DIFF_HDR, *scan = list + cap;
-    const fx::DiffGeom g{W0, H0, (int)p.dx, (int)p.dy, ifa, variant, msg_layout, (int)p.W1, (int)p.H1};
     // (on the context's stream: behind cell updates that are still queued there, fxjps_update_cells_deferred)
-    HIPCHK(h, hipMemcpyAsync(d.d_raw.p, raw, (size_t)W0 * H0, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.d_raw.p, q.raw, raw_bytes, hipMemcpyHostToDevice, d.stream));
     r->staged = true;
     HIPCHK(h, hipMemsetAsync(hdr, 0, fx::DIFF_HDR * sizeof(uint32_t), d.stream));
     hipLaunchKernelGGL(fx::k_grid_diff_count, dim3(nblk), dim3(256), 0, d.stream, d.d_raw.p, g, d.occ.p, hdr, scan);
     hipLaunchKernelGGL(fx::k_grid_diff_scan, dim3(1), dim3(1024), 0, d.stream, scan, nblk, hdr);
     hipLaunchKernelGGL(fx::k_grid_diff_write, dim3(nblk), dim3(256), 0, d.stream, d.d_raw.p, g, d.occ.p, scan, nblk, cap, list);
     HIPCHK(h, hipGetLastError());
+    // (the goal rule on the resident grid in front of the same wait: a mode 0 has its record when it learns that it is one;
+    // the other modes change the grid and queue the rule again behind that.  Launch behind launch, copy behind copy)
+    if (int rc = goal_queue(h, q)) return rc;
     HIPCHK(h, hipMemcpyAsync(d.h_diff.p, hdr, ((size_t)fx::DIFF_HDR + HEAD) * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     const uint32_t n = d.h_diff.p[fx::DIFF_N];
@@ -2560,47 +2559,42 @@ int refresh_diff(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t
 
 // The diff's outcome applied, queued on every context: the list through the cell-update path (which also rebuilds what
 // deferred updates left stale, mode 0 included), or the whole build.
-int refresh_apply(fxjps_t* h, const RefreshDiff& r, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout) {
-    if (r.mode == 2) return prepare_build(h, r.p, raw, W0, H0, ifa, variant, msg_layout, r.staged);
+int refresh_apply(fxjps_t* h, const PrepReq& q, const RefreshDiff& r) {
+    if (r.mode == 2) return prepare_build(h, q, r.staged);
     int rc = update_cells_async(h, h->refresh_xy.data(), h->refresh_val.data(), r.changed, true);
     if (rc) drain_all(h);  // the devices in front of the failing one have the update queued
     return rc;
 }
 
-int refresh_grid_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout, int32_t* start_xy,
-                      int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed,
-                      int32_t* out_mode) {
+// prepare_finish's `done` behind a diff, judged before the diff's outcome is applied: mode 2 waits in prepare_build; a
+// mode 0 that owes no rebuild to deferred updates queues nothing more, and its goal record came back with the diff's header.
+bool refresh_done(const fxjps_t* h, const RefreshDiff& r) { return r.mode == 2 || (r.mode == 0 && !h->maps_stale); }
+
+int refresh_grid_impl(fxjps_t* h, PrepReq q, int64_t* out_changed, int32_t* out_mode) {
     if (!h) return FXJPS_E_ARG;
     RefreshDiff r;
-    if (int rc = prepare_check(h, "fxjps_refresh_grid", raw, W0, H0, ifa, variant, start_xy, goal_xy, &r.p)) return rc;
+    if (int rc = prepare_check(h, "fxjps_refresh_grid", &q)) return rc;
     h->q_results_valid = h->rs_valid = false;  // (as fxjps_update_cells: the grid may change behind the stored results)
-    if (int rc = refresh_diff(h, raw, W0, H0, ifa, variant, msg_layout, &r)) return rc;
+    if (int rc = refresh_diff(h, q, &r)) return rc;
     if (out_changed) *out_changed = r.changed;
     if (out_mode) *out_mode = r.mode;
-    const bool queued = r.mode == 1 || h->maps_stale;  // (mode 2 waits itself; a mode 0 behind no deferred update queues nothing)
-    if (int rc = refresh_apply(h, r, raw, W0, H0, ifa, variant, msg_layout)) return rc;
-    if (r.mode != 2 && queued)
-        for (auto& d : h->devs) {
-            HIPCHK(h, hipSetDevice(d.dev));
-            HIPCHK(h, hipStreamSynchronize(d.stream));
-        }
-    return prepare_finish(h, r.p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+    const bool done = refresh_done(h, r);
+    if (int rc = refresh_apply(h, q, r)) return rc;
+    return prepare_finish(h, q, done);
 }
 
-int replan_frame_raw_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int msg_layout,
-                          int32_t* start_xy, int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu,
-                          int64_t* out_changed, int32_t* out_mode, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity,
-                          int32_t* out_len, double* out_cost, double* out_seconds_total) {
+int replan_frame_raw_impl(fxjps_t* h, PrepReq q, int64_t* out_changed, int32_t* out_mode, int64_t* out_offsets, int32_t* out_cells_xy,
+                          int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
     const double t0 = now_s();
     if (!h) return FXJPS_E_ARG;
     RefreshDiff r;
-    if (int rc = prepare_check(h, "fxjps_replan_frame_raw", raw, W0, H0, ifa, variant, start_xy, goal_xy, &r.p)) return rc;
+    if (int rc = prepare_check(h, "fxjps_replan_frame_raw", &q)) return rc;
     const int64_t nq = (int64_t)h->q_starts.size() / 2;
     if (h->q_set && nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    if (!h->q_set || !h->have_grid || r.p.W1 != h->devs[0].W || r.p.H1 != h->devs[0].H)
+    if (!h->q_set || !h->have_grid || q.p.W1 != h->devs[0].W || q.p.H1 != h->devs[0].H)
         return fail(h, FXJPS_E_ARG, "fxjps_replan_frame_raw needs stored queries and a resident grid of the prepared extents (%lldx%lld): call "
-                    "fxjps_prepare_grid and fxjps_set_queries again", r.p.W1, r.p.H1);
-    if (int rc = refresh_diff(h, raw, W0, H0, ifa, variant, msg_layout, &r)) return rc;
+                    "fxjps_prepare_grid and fxjps_set_queries again", q.p.W1, q.p.H1);
+    if (int rc = refresh_diff(h, q, &r)) return rc;
     if (out_changed) *out_changed = r.changed;
     if (out_mode) *out_mode = r.mode;
     // fxjps_replan_frame's rule on the diff's list; a diff too long for its list marks the tiles of its box, and every query is searched
@@ -2611,18 +2605,15 @@ int replan_frame_raw_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0
     bool track = false;
     const int mode = frame_reuse_rule(h, T, r.mode == 2, &reused, &track);
     h->q_results_valid = h->rs_valid = false;  // (set again below, once the frame is complete)
-    if (int rc = refresh_apply(h, r, raw, W0, H0, ifa, variant, msg_layout)) return rc;
+    const bool done = refresh_done(h, r);
+    if (int rc = refresh_apply(h, q, r)) return rc;
     int rc = plan_core(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
     if (rc) return rc;
     h->q_results_valid = track;
     h->timing.reused = reused;
     rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
     if (rc) return rc;
-    for (auto& d : h->devs) {  // (a context without queries of the batch has not waited for its update)
-        HIPCHK(h, hipSetDevice(d.dev));
-        HIPCHK(h, hipStreamSynchronize(d.stream));
-    }
-    rc = prepare_finish(h, r.p, ifa, variant, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu);
+    rc = prepare_finish(h, q, done);  // (its wait: a context without queries of the batch has not waited for its update)
     h->timing.total_ms = (now_s() - t0) * 1e3;
     if (out_seconds_total) *out_seconds_total = now_s() - t0;
     return rc;
@@ -2632,14 +2623,14 @@ int replan_frame_raw_impl(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0
 int fxjps_refresh_grid(fxjps_t* h, const uint8_t* raw, int32_t W0, int32_t H0, int32_t ifa, int32_t variant, int32_t* start_xy,
                        int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu, int64_t* out_changed,
                        int32_t* out_mode) {
-    return refresh_grid_impl(h, raw, W0, H0, ifa, variant, 0, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu, out_changed, out_mode);
+    return refresh_grid_impl(h, PrepReq{raw, W0, H0, ifa, variant, 0, start_xy, goal_xy, out_W, out_H, out_map_d, out_end_occu, {}}, out_changed, out_mode);
 }
 
 int fxjps_refresh_occupancy_msg(fxjps_t* h, const int8_t* data, int32_t width, int32_t height, int32_t ifa, int32_t variant, int32_t* start_xy,
                                 int32_t* goal_xy, int32_t* out_W, int32_t* out_H, int32_t* out_map_d, int32_t* out_end_occu,
                                 int64_t* out_changed, int32_t* out_mode) {
-    return refresh_grid_impl(h, reinterpret_cast<const uint8_t*>(data), width, height, ifa, variant, 1, start_xy, goal_xy, out_W, out_H,
-                             out_map_d, out_end_occu, out_changed, out_mode);
+    return refresh_grid_impl(h, PrepReq{reinterpret_cast<const uint8_t*>(data), width, height, ifa, variant, 1, start_xy, goal_xy, out_W, out_H,
+                                        out_map_d, out_end_occu, {}}, out_changed, out_mode);
 }
 
 int fxjps_last_refresh_cells(fxjps_t* h, int32_t* out_xy, uint8_t* out_val, int64_t capacity, int64_t* out_n) {
@@ -2660,9 +2651,9 @@ int fxjps_replan_frame_raw(fxjps_t* h, const void* raw, int32_t layout, int32_t 
                            int32_t* out_mode, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len,
                            double* out_cost, double* out_seconds_total) {
     if (h && layout != 0 && layout != 1) return fail(h, FXJPS_E_ARG, "layout must be 0 (matrix [x][y]) or 1 (message data[])");
-    return replan_frame_raw_impl(h, static_cast<const uint8_t*>(raw), W0, H0, ifa, variant, layout, start_xy, goal_xy, out_W, out_H, out_map_d,
-                                 out_end_occu, out_changed, out_mode, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost,
-                                 out_seconds_total);
+    return replan_frame_raw_impl(h, PrepReq{static_cast<const uint8_t*>(raw), W0, H0, ifa, variant, layout, start_xy, goal_xy, out_W, out_H, out_map_d,
+                                            out_end_occu, {}},
+                                 out_changed, out_mode, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost, out_seconds_total);
 }
 
 int fxjps_plan_batch_csr(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
@@ -2919,10 +2910,7 @@ namespace {
 // and the outputs are the same code.
 int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const WorldSrc* world_src = nullptr,
                const size_t* staged_raw = nullptr) {
-    if (!h) return FXJPS_E_ARG;
-    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
-    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    if (int rc = jobs_call_check(h, jobs, n, what)) return rc;
     // everything the host can judge, for every job, before anything is queued or any slot is touched
     std::vector<SlotPlan> plan((size_t)n);
     std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
@@ -3052,15 +3040,35 @@ bool trunc_i32(double q, long long& out) {
     return true;
 }
 
+// The eleven output fields of a world job: from another job (the slot job's results, a cropped call's second phase) ...
+void copy_world_outputs(fxjps_world_job_t& to, const fxjps_world_job_t& from) {
+    for (int k = 0; k < 2; k++) {
+        to.canvas_o[k] = from.canvas_o[k];
+        to.origin[k] = from.origin[k];
+        to.start_xy[k] = from.start_xy[k];
+        to.goal_xy_cell[k] = from.goal_xy_cell[k];
+        to.map_d[k] = from.map_d[k];
+    }
+    to.W = from.W;
+    to.H = from.H;
+    to.end_occu = from.end_occu;
+    to.status = from.status;
+    to.canvas_W = from.canvas_W;
+    to.canvas_H = from.canvas_H;
+}
+// ... and of a job that took no part: all zero but its status
+void clear_world_outputs(fxjps_world_job_t& wj, int status) {
+    fxjps_world_job_t none{};
+    none.status = status;
+    copy_world_outputs(wj, none);
+}
+
 // The conversion in front of slots_call: the reference's lines between the map callback and the preparation
 // (global_planner_st.py:210-227 / global_planner_ccst.py:395-412), in float64 with the reference's operations in the
 // reference's order (the library is built with -ffp-contract=off).  Each world job becomes the fxjps_slot_job_t whose raw is
 // the canvas -- which only the gather ever sees, through WorldSrc -- and slots_call does the rest.
 int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const size_t* staged_raw = nullptr) {
-    if (!h) return FXJPS_E_ARG;
-    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
-    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    if (int rc = jobs_call_check(h, jobs, n, what)) return rc;
     std::vector<fxjps_slot_job_t> sj((size_t)n);
     std::vector<WorldSrc> src((size_t)n);
     std::vector<double> co((size_t)n * 2);
@@ -3132,19 +3140,21 @@ int world_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int
     for (int j = 0; j < n; j++) {
         fxjps_world_job_t& wj = jobs[j];
         const fxjps_slot_job_t& s = sj[(size_t)j];
+        fxjps_world_job_t o{};
         for (int k = 0; k < 2; k++) {
-            wj.start_xy[k] = s.start_xy[k];
-            wj.goal_xy_cell[k] = s.goal_xy[k];
-            wj.map_d[k] = s.map_d[k];
-            wj.canvas_o[k] = co[(size_t)j * 2 + k];
-            wj.origin[k] = (double)(-(long long)s.map_d[k]) * wj.map_reso + wj.canvas_o[k];  // st:236: map_o2 * map_reso + map_o
+            o.start_xy[k] = s.start_xy[k];
+            o.goal_xy_cell[k] = s.goal_xy[k];
+            o.map_d[k] = s.map_d[k];
+            o.canvas_o[k] = co[(size_t)j * 2 + k];
+            o.origin[k] = (double)(-(long long)s.map_d[k]) * wj.map_reso + o.canvas_o[k];  // st:236: map_o2 * map_reso + map_o
         }
-        wj.W = s.W;
-        wj.H = s.H;
-        wj.end_occu = s.end_occu;
-        wj.status = s.status;
-        wj.canvas_W = s.W0;
-        wj.canvas_H = s.H0;
+        o.W = s.W;
+        o.H = s.H;
+        o.end_occu = s.end_occu;
+        o.status = s.status;
+        o.canvas_W = s.W0;
+        o.canvas_H = s.H0;
+        copy_world_outputs(wj, o);
     }
     return FXJPS_OK;
 }
@@ -3229,10 +3239,7 @@ int empty_slots_everywhere(fxjps* h, const std::vector<int32_t>& slots) {
 // per-job outcome are the host's; the jobs that go on are handed to world_call with their windows where the first phase
 // left them.
 int crop_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, fxjps_crop_t* out_crop, const char* what) {
-    if (!h) return FXJPS_E_ARG;
-    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
-    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    if (int rc = jobs_call_check(h, jobs, n, what)) return rc;
     if (n == 0) return FXJPS_OK;
     // what can be judged without the box, for every job, before anything is queued
     std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
@@ -3337,31 +3344,11 @@ int crop_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int3
     }
     for (int j = 0; j < n; j++) {
         if (outcome[(size_t)j] == FXJPS_OK) continue;
-        fxjps_world_job_t& wj = jobs[j];
-        wj.status = outcome[(size_t)j];
-        for (int k = 0; k < 2; k++) {
-            wj.canvas_o[k] = wj.origin[k] = 0.0;
-            wj.start_xy[k] = wj.goal_xy_cell[k] = wj.map_d[k] = 0;
-        }
-        wj.W = wj.H = wj.end_occu = wj.canvas_W = wj.canvas_H = 0;
+        clear_world_outputs(jobs[j], outcome[(size_t)j]);
         if (out_kept) out_kept[j] = 0;
     }
     for (size_t i = 0; i < go.size(); i++) {
-        fxjps_world_job_t& wj = jobs[go_job[i]];
-        const fxjps_world_job_t& g = go[i];
-        wj.status = g.status;
-        for (int k = 0; k < 2; k++) {
-            wj.canvas_o[k] = g.canvas_o[k];
-            wj.origin[k] = g.origin[k];
-            wj.start_xy[k] = g.start_xy[k];
-            wj.goal_xy_cell[k] = g.goal_xy_cell[k];
-            wj.map_d[k] = g.map_d[k];
-        }
-        wj.W = g.W;
-        wj.H = g.H;
-        wj.end_occu = g.end_occu;
-        wj.canvas_W = g.canvas_W;
-        wj.canvas_H = g.canvas_H;
+        copy_world_outputs(jobs[go_job[i]], go[i]);
         if (out_kept) out_kept[go_job[i]] = go_kept[i];
     }
     if (out_crop) memcpy(out_crop, crop.data(), sizeof(fxjps_crop_t) * (size_t)n);
@@ -3381,10 +3368,7 @@ int fxjps_refresh_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, 
 int fxjps_slot_publish_size(void) { return (int)sizeof(fxjps_slot_publish_t); }
 
 int fxjps_publish_slots(fxjps_t* h, fxjps_slot_publish_t* jobs, int32_t n) {
-    if (!h) return FXJPS_E_ARG;
-    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return fail(h, FXJPS_E_ARG, "NULL jobs");
-    if (int rr = refuse_on_rank_handle(h, "fxjps_publish_slots")) return rr;
+    if (int rc = jobs_call_check(h, jobs, n, "fxjps_publish_slots")) return rc;
     // everything the host can judge, for every job, before anything is queued or written
     constexpr size_t OUT_MAX = (size_t)1 << 30;
     const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };

@@ -685,39 +685,44 @@ struct WorldSrcDev {
     int32_t pW, pH, px, py;  // the prior's extents and where its cell (0, 0) lies in the canvas
     int32_t rW, rH, rx, ry;  // the detected map's (SlotJobDev::raw, SlotJobDev::layout)
 };
+// The geometry of one preparation: the source's extents (a raw map's, a canvas's), the padding, the dilation, the variant
+// (0 st, 1 ccst), the source's layout and the prepared extents.  The host fills it in one place (PrepReq::geom); the slot
+// gather builds it from its job, whose layout the recorded register figures of the k_slots_* family hang on.
+struct PrepGeom {
+    int32_t W0, H0, dx, dy, ifa, variant, layout, W1, H1;
+};
 template <bool WORLD>  // (S is read only when WORLD)
-__device__ __forceinline__ uint8_t prepared_byte(const uint8_t* __restrict__ raw, const WorldSrcDev* __restrict__ S, int W0, int H0, int dx, int dy, int ifa,
-                                                 int variant, int msg_layout, int H1, long long i) {
-    const int x = (int)(i / H1), y = (int)(i % H1);
-    const int step = variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
+__device__ __forceinline__ uint8_t prepared_byte(const uint8_t* __restrict__ raw, const WorldSrcDev* __restrict__ S, const PrepGeom& g, long long i) {
+    const int ifa = g.ifa;
+    const int x = (int)(i / g.H1), y = (int)(i % g.H1);
+    const int step = g.variant == 0 ? (ifa > 0 ? ifa : 1) : 1;
     // (block-uniform: loaded once, into scalar registers.  With the fields read inside the loop the gather had two VGPRs less
     // and the world calls took 1 - 5 % longer: profiles/slot_kernel_family_bench.json)
     const WorldSrcDev W = WORLD ? *S : WorldSrcDev{};
     uint8_t v = 0;
     for (int a = -ifa; a <= ifa; a += step)
         for (int b = -ifa; b <= ifa; b += step) {
-            const int sx = x - dx - a, sy = y - dy - b;
-            if (sx >= 0 && sy >= 0 && sx < W0 && sy < H0) {
+            const int sx = x - g.dx - a, sy = y - g.dy - b;
+            if (sx >= 0 && sy >= 0 && sx < g.W0 && sy < g.H0) {
                 bool o = false;  // canvas cell (sx, sy)
                 if constexpr (WORLD) {
                     const int ux = sx - W.rx, uy = sy - W.ry, qx = sx - W.px, qy = sy - W.py;
                     if (ux >= 0 && uy >= 0 && ux < W.rW && uy < W.rH)
-                        o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)uy * W.rW + ux] > 0) : (raw[(size_t)ux * W.rH + uy] != 0);
+                        o = g.layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)uy * W.rW + ux] > 0) : (raw[(size_t)ux * W.rH + uy] != 0);
                     else if (qx >= 0 && qy >= 0 && qx < W.pW && qy < W.pH)  // (pW == 0 without a prior)
                         o = W.prior[(size_t)qx * W.pH + qy] != 0;
                 } else {
-                    o = msg_layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * W0 + sx] > 0) : (raw[(size_t)sx * H0 + sy] != 0);
+                    o = g.layout ? (reinterpret_cast<const int8_t*>(raw)[(size_t)sy * g.W0 + sx] > 0) : (raw[(size_t)sx * g.H0 + sy] != 0);
                 }
                 if (o) v = 1;
             }
         }
     return v;
 }
-__global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict__ raw, int W0, int H0, int dx, int dy, int ifa,
-                                                     int variant, int msg_layout, int W1, int H1, uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict__ raw, const PrepGeom g, uint8_t* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)W1 * H1) return;
-    out[i] = prepared_byte<false>(raw, nullptr, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
+    if (i >= (long long)g.W1 * g.H1) return;
+    out[i] = prepared_byte<false>(raw, nullptr, g, i);
 }
 
 // ---- The prepared grid diffed against the resident one (fxjps_refresh_grid, DESIGN.md section 3.16): which cells of
@@ -731,15 +736,12 @@ __global__ __launch_bounds__(256) void k_prepare_grid(const uint8_t* __restrict_
 //   diff[8 + cap .. + nblk]    the blocks' counts, after k_grid_diff_scan their offsets, then the total
 // More changed cells than `cap`: the list is not written (the caller rebuilds the grid).
 constexpr int DIFF_HDR = 8, DIFF_N = 0, DIFF_X0 = 1, DIFF_X1 = 2, DIFF_Y0 = 3, DIFF_Y1 = 4;  // X0 / Y0 hold 8191 - min, X1 / Y1 hold max + 1
-struct DiffGeom {
-    int W0, H0, dx, dy, ifa, variant, msg_layout, W1, H1;
-};
-__global__ __launch_bounds__(256) void k_grid_diff_count(const uint8_t* __restrict__ raw, const DiffGeom g, const uint8_t* __restrict__ occ,
+__global__ __launch_bounds__(256) void k_grid_diff_count(const uint8_t* __restrict__ raw, const PrepGeom g, const uint8_t* __restrict__ occ,
                                                         uint32_t* __restrict__ hdr, uint32_t* __restrict__ scan) {
     __shared__ int s_box[4];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     bool chg = false;
-    if (i < (long long)g.W1 * g.H1) chg = occ[i] != prepared_byte<false>(raw, nullptr, g.W0, g.H0, g.dx, g.dy, g.ifa, g.variant, g.msg_layout, g.H1, i);
+    if (i < (long long)g.W1 * g.H1) chg = occ[i] != prepared_byte<false>(raw, nullptr, g, i);
     if (threadIdx.x < 4) s_box[threadIdx.x] = 0;
     const int cnt = __syncthreads_count(chg);
     if (threadIdx.x == 0) scan[blockIdx.x] = (uint32_t)cnt;
@@ -780,7 +782,7 @@ __global__ __launch_bounds__(1024) void k_grid_diff_scan(uint32_t* __restrict__ 
         hdr[DIFF_N] = s_part[1023];
     }
 }
-__global__ __launch_bounds__(256) void k_grid_diff_write(const uint8_t* __restrict__ raw, const DiffGeom g, const uint8_t* __restrict__ occ,
+__global__ __launch_bounds__(256) void k_grid_diff_write(const uint8_t* __restrict__ raw, const PrepGeom g, const uint8_t* __restrict__ occ,
                                                         const uint32_t* __restrict__ scan, uint32_t nblk, uint32_t cap, uint32_t* __restrict__ list) {
     __shared__ uint32_t s_wave[4];
     const uint32_t off = scan[blockIdx.x];
@@ -789,7 +791,7 @@ __global__ __launch_bounds__(256) void k_grid_diff_write(const uint8_t* __restri
     uint8_t v = 0;
     bool chg = false;
     if (i < (long long)g.W1 * g.H1) {
-        v = prepared_byte<false>(raw, nullptr, g.W0, g.H0, g.dx, g.dy, g.ifa, g.variant, g.msg_layout, g.H1, i);
+        v = prepared_byte<false>(raw, nullptr, g, i);
         chg = occ[i] != v;
     }
     const uint64_t m = __ballot(chg);
@@ -856,17 +858,17 @@ __global__ __launch_bounds__(256) void k_slots_gather(const SlotTable* __restric
                                                      uint32_t* __restrict__ changed) {
     const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
     const SlotJobDev& J = T->job[j];
-    const int W0 = J.W0, H0 = J.H0, dx = J.dx, dy = J.dy, ifa = J.ifa, variant = J.variant, msg_layout = J.layout, W1 = J.G.W, H1 = J.G.H;
+    const PrepGeom g{J.W0, J.H0, J.dx, J.dy, J.ifa, J.variant, J.layout, J.G.W, J.G.H};
     const uint8_t* __restrict__ raw = J.raw;
     uint8_t* __restrict__ occ = J.occ;
     const long long i = (long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x;
-    const bool inside = i < (long long)W1 * H1;
+    const bool inside = i < (long long)g.W1 * g.H1;
     const WorldSrcDev* __restrict__ Sj = WORLD ? S + j : nullptr;
     if constexpr (!REFRESH) {
         if (!inside) return;
-        occ[i] = prepared_byte<WORLD>(raw, Sj, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i);
+        occ[i] = prepared_byte<WORLD>(raw, Sj, g, i);
     } else {
-        const uint8_t v = inside ? prepared_byte<WORLD>(raw, Sj, W0, H0, dx, dy, ifa, variant, msg_layout, H1, i) : (uint8_t)0;
+        const uint8_t v = inside ? prepared_byte<WORLD>(raw, Sj, g, i) : (uint8_t)0;
         if (!J.compare) {  // (block-uniform) a job that builds whatever the bytes are: its word is 1 already
             if (inside) occ[i] = v;
             return;
@@ -895,14 +897,13 @@ __device__ __forceinline__ int slot_nearest_free(const uint8_t* __restrict__ lin
     }
     return -1;
 }
-// One wavefront per job: what prepare_grid_impl does on the host with blocking row / column copies -- the goal moved off
-// an obstacle (st:268-272 / ccst:454-458), end_occu (st:273 / ccst:461-464 with numpy's slice rules: a negative bound
-// counts from the end, everything is clipped to the array).
-__device__ __forceinline__ void slots_goal_job(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int j, int lane) {
-    const SlotJobDev& J = T->job[j];
-    const int W1 = J.G.W, H1 = J.G.H, ifa = J.ifa, variant = J.variant;
-    const uint8_t* __restrict__ occ = J.occ;
-    int gx = J.gx, gy = J.gy, end_occu = 0, status = 0;
+// The goal rule, one wavefront, the library's one copy of it: the goal moved off an obstacle (st:268-272 / ccst:454-458),
+// end_occu (st:273 / ccst:461-464 with numpy's slice rules: a negative bound counts from the end, everything is clipped to
+// the array).  (gx, gy) is the shifted goal, inside the W1 x H1 grid `occ`: the host checked.  Lane 0 writes the record
+// res[0 .. SLOT_RES): the (moved) goal, end_occu, status (0, or -1: row and column fully occupied).
+__device__ __forceinline__ void goal_rule(const uint8_t* __restrict__ occ, int W1, int H1, int gx, int gy, int ifa, int variant, int lane,
+                                          int32_t* __restrict__ res) {
+    int end_occu = 0, status = 0;
     if (occ[(size_t)gx * H1 + gy]) {
         if (variant == 0) end_occu = 1;
         int best = slot_nearest_free(occ + (size_t)gx * H1, 1, H1, gy, lane);
@@ -924,11 +925,21 @@ __device__ __forceinline__ void slots_goal_job(const SlotTable* __restrict__ T, 
         end_occu = __ballot(any) != 0ull ? 1 : 0;
     }
     if (lane == 0) {
-        res[j * SLOT_RES + 0] = gx;
-        res[j * SLOT_RES + 1] = gy;
-        res[j * SLOT_RES + 2] = end_occu;
-        res[j * SLOT_RES + 3] = status;
+        res[0] = gx;
+        res[1] = gy;
+        res[2] = end_occu;
+        res[3] = status;
     }
+}
+// ... for the resident grid of a single-grid call (prepare_finish): one block of one wavefront
+__global__ __launch_bounds__(64) void k_prepare_goal(const uint8_t* __restrict__ occ, int W1, int H1, int gx, int gy, int ifa, int variant,
+                                                    int32_t* __restrict__ res) {
+    goal_rule(occ, W1, H1, gx, gy, ifa, variant, (int)threadIdx.x, res);
+}
+// ... and for every job of a slot call, one wavefront per job
+__device__ __forceinline__ void slots_goal_job(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int j, int lane) {
+    const SlotJobDev& J = T->job[j];
+    goal_rule(J.occ, J.G.W, J.G.H, J.gx, J.gy, J.ifa, J.variant, lane, res + j * SLOT_RES);
 }
 template <bool REFRESH>
 __global__ __launch_bounds__(64) void k_slots_goal(const SlotTable* __restrict__ T, int32_t* __restrict__ res, int n, const uint32_t* __restrict__ changed) {

@@ -4,8 +4,9 @@ written to --out, and the table of that section (--design rewrites it between it
 
 Shapes: the reference's 147 x 112 map (st, ifa 1) and a 1024 x 1024 / 20 % synthetic raw (ccst, ifa 1).  Tick kinds: the
 same raw again; 16 raw cells changed inside one 64 x 64 window; 10 % of the raw cells changed (the two raws of a kind
-alternate tick by tick).  Five sides, each on a handle of its own, the same sequence of ticks on each:
+alternate tick by tick).  Six sides, each on a handle of its own, the same sequence of ticks on each:
     refresh   fxjps_refresh_grid of this tree's library
+    parent_refresh   fxjps_refresh_grid of the PARENT commit's library
     prepare   fxjps_prepare_grid of this tree's library, on two handles (prepare, prepare_b)
     parent    fxjps_prepare_grid of the PARENT commit's library (--parent-lib), loaded beside this tree's as a second
               library, on two handles as well (parent, parent_b): two handles that make the same call of the same library
@@ -16,7 +17,10 @@ in one process, a repetition is a window of as many ticks as make a side run >= 
 Before anything is timed the five handles run four ticks of every kind and the resident grid and the derived arrays are
 compared byte for byte across them after each (the component forest of `refresh` only where its whole build ran: a cell
 update unites labels, tests/test_map_updates_gpu.py), and refresh's mode is checked against the kind.
-The one bar fixed in advance: prepare <= 1.05 x parent (its path is untouched).  refresh / parent is reported per kind.
+The bars fixed in advance: prepare <= 1.05 x parent, and refresh <= 1.05 x parent_refresh per tick kind.  refresh / parent
+is reported per kind.
+--goal-on-obstacle: the goal of every tick is a raw cell that is occupied in every raw, so the prepared goal lies on a
+dilated obstacle (its row has free cells: the sides' moved goal is checked) and every call runs the whole goal rule.
 Usage: python tools/refresh_grid_bench.py --parent-lib /tmp/parent/fuxi-planner_amd/libfxjps.so [--reps 5]
        python tools/refresh_grid_bench.py --design profiles/refresh_grid_bench.json [more.json]   (no GPU: the tables only)"""
 import argparse
@@ -100,7 +104,7 @@ class Side(object):
         self.L.fxjps_destroy(self.h)
 
 
-def raws_of(shape, rng):
+def raws_of(shape, rng, goal_on_obstacle=False):
     """-> (raw A uint8 [W0][H0], start, goal, ifa, variant, {kind: raw B})"""
     from fuxi_planner_amd import synth
     if shape == "png_147x112":
@@ -113,6 +117,9 @@ def raws_of(shape, rng):
     s, g = synth.synth_queries(raw, 7, 1)
     start, goal = tuple(int(c) for c in s[0]), tuple(int(c) for c in g[0])
     W0, H0 = raw.shape
+    if goal_on_obstacle:  # the occupied raw cell nearest to the drawn goal
+        occ = np.argwhere(raw != 0)
+        goal = tuple(int(c) for c in occ[np.argmin(np.abs(occ - np.array(goal)).sum(1))])
     other = {"same": raw}
     b = raw.copy()
     x0, y0 = W0 // 2 - min(32, W0 // 2), H0 // 2 - min(32, H0 // 2)
@@ -123,18 +130,20 @@ def raws_of(shape, rng):
     idx = rng.choice(W0 * H0, W0 * H0 // 10, replace=False)
     b.flat[idx] ^= 1
     other["10_percent"] = b
-    for m in other.values():  # start and goal stay free in every raw
-        m[start] = m[goal] = 0
+    for m in other.values():  # the start stays free in every raw, the goal free (or occupied)
+        m[start] = 0
+        m[goal] = 1 if goal_on_obstacle else 0
     return np.ascontiguousarray(raw), start, goal, 1, variant, {k: np.ascontiguousarray(v) for k, v in other.items()}
 
 
 def table(out):
-    rows = ["| raw | tick | refresh mode | changed cells | refresh ms | prepare ms (A, B) | parent ms (A, B) | refresh / parent | prepare / parent | prepare B / parent | parent B / parent |",
-            "|---|---|---|---|---|---|---|---|---|---|---|"]
+    rows = ["| raw | tick | refresh mode | changed cells | refresh ms | prepare ms (A, B) | parent ms (A, B) | refresh / parent | prepare / parent | prepare B / parent | parent B / parent | refresh / parent refresh |",
+            "|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for c in out["cases"]:
-        rows.append("| %s | %s | %d | %d | %.4f | %.4f, %.4f | %.4f, %.4f | %.3f | %.3f | %.3f | %.3f |" % (
+        rows.append("| %s | %s | %d | %d | %.4f | %.4f, %.4f | %.4f, %.4f | %.3f | %.3f | %.3f | %.3f | %s |" % (
             c["shape"], c["kind"].replace("_", " "), c["refresh_mode"], c["changed_cells"], c["refresh_ms"], c["prepare_ms"], c["prepare_b_ms"],
-            c["parent_ms"], c["parent_b_ms"], c["refresh_over_parent"], c["prepare_over_parent"], c["prepare_b_over_parent"], c["parent_b_over_parent"]))
+            c["parent_ms"], c["parent_b_ms"], c["refresh_over_parent"], c["prepare_over_parent"], c["prepare_b_over_parent"], c["parent_b_over_parent"],
+            "%.3f" % c["refresh_over_parent_refresh"] if "refresh_over_parent_refresh" in c else "-"))
     return "\n".join(rows)
 
 
@@ -152,9 +161,10 @@ def main():
     ap.add_argument("--parent-lib", help="libfxjps.so built from the parent commit")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", nargs="+", default=["png_147x112", "synth_1024"])
-    ap.add_argument("--order", nargs="+", default=["refresh", "prepare", "parent", "prepare_b", "parent_b"],
-                    help="the five sides in the order their handles are created and their windows run")
+    ap.add_argument("--order", nargs="+", default=["refresh", "prepare", "parent", "prepare_b", "parent_b", "parent_refresh"],
+                    help="the six sides in the order their handles are created and their windows run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refresh_grid_bench.json"))
+    ap.add_argument("--goal-on-obstacle", action="store_true", help="every tick's goal lies on a dilated obstacle whose row has a free cell")
     ap.add_argument("--design", metavar="JSON", nargs="+", help="rewrite the tables of DESIGN.md section 3.16 from these result files and exit")
     a = ap.parse_args()
     if a.design:
@@ -167,33 +177,36 @@ def main():
     _lib.load()
     # handles are created, and the windows of a repetition run, in the order of --order
     make = {"refresh": (_lib.LIB_PATH, True), "prepare": (_lib.LIB_PATH, False), "prepare_b": (_lib.LIB_PATH, False),
-            "parent": (a.parent_lib, False), "parent_b": (a.parent_lib, False)}
+            "parent": (a.parent_lib, False), "parent_b": (a.parent_lib, False), "parent_refresh": (a.parent_lib, True)}
     assert sorted(a.order) == sorted(make), a.order
     sides = {name: Side(*make[name]) for name in a.order}
     assert sides["parent"].version <= sides["prepare"].version, (sides["parent"].version, sides["prepare"].version)
     state = lambda name: sides[name].state()
 
     out = {"tool": "refresh_grid_bench", "reps": a.reps, "window_s": ftb.WINDOW_S, "ifa": 1, "timed": "the C call", "order": a.order,
-           "parent_version": sides["parent"].version, "version": sides["prepare"].version, "cases": []}
+           "goal_on_obstacle": a.goal_on_obstacle, "parent_version": sides["parent"].version, "version": sides["prepare"].version, "cases": []}
     ms = lambda ts: round(float(np.median(ts)) * 1e3, 4)
     spread = lambda ts: [round(min(ts) * 1e3, 4), round(max(ts) * 1e3, 4)]
     rng = np.random.default_rng(16)
     for shape in a.shapes:
-        raw_a, start, goal, ifa, variant, other = raws_of(shape, rng)
+        raw_a, start, goal, ifa, variant, other = raws_of(shape, rng, a.goal_on_obstacle)
         for kind in KINDS:
             raw_b = other[kind]
-            # the three sides on the same ticks, byte for byte, before anything is timed
+            # the sides on the same ticks, byte for byte, before anything is timed
             modes = []
             for t, raw in enumerate((raw_a, raw_b, raw_a, raw_a)):
                 for s in sides.values():
                     s.call(raw, start, goal, ifa, variant)
                 want, ref = sides["parent"].outputs(), state("parent")
                 modes.append((sides["refresh"].mode.value, sides["refresh"].changed.value))
-                for name in ("prepare", "prepare_b", "parent_b", "refresh"):
+                sh = 1 if variant == 0 else 0
+                if a.goal_on_obstacle:  # (moved: it was occupied, and its row had a free cell)
+                    assert want[1] != (goal[0] + want[2][0] - sh, goal[1] + want[2][1] - sh), (shape, kind, t, want)
+                for name in ("prepare", "prepare_b", "parent_b", "refresh", "parent_refresh"):
                     assert sides[name].outputs() == want, (shape, kind, t, name)
                     got = state(name)
                     for k in ref:
-                        if k == "comp" and name == "refresh" and modes[-1][0] != 2:
+                        if k == "comp" and sides[name].refresh and modes[-1][0] != 2:
                             continue
                         assert got[k] == ref[k], (shape, kind, t, name, k)
             assert modes[0][0] == 2 or kind != "same" or modes[0][0] == 0, (shape, kind, modes)
@@ -218,7 +231,9 @@ def main():
             case["prepare_over_parent"] = round(med["prepare"] / med["parent"], 4)
             case["prepare_b_over_parent"] = round(med["prepare_b"] / med["parent"], 4)
             case["parent_b_over_parent"] = round(med["parent_b"] / med["parent"], 4)
+            case["refresh_over_parent_refresh"] = round(med["refresh"] / med["parent_refresh"], 4)
             case["bar_prepare_1_05_met"] = bool(med["prepare"] <= 1.05 * med["parent"])
+            case["bar_refresh_1_05_met"] = bool(med["refresh"] <= 1.05 * med["parent_refresh"])
             out["cases"].append(case)
     for s in sides.values():
         s.close()
