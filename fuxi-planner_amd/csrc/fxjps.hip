@@ -184,8 +184,6 @@ struct DevCtx : GridBufs {
     bool lds_attr_done[12] = {};        // k_search instantiations whose dynamic-LDS limit has been raised on this device
     Event ev0, ev1, ev_solo0, ev_solo1;
     Event ev_hd0, ev_hd1, ev_bt0, ev_bt1;  // around the head launch / the batch's launch alone
-    bool had_solo = false;              // the last regular-pool launch was two launches
-    double head_ms = 0, batch_ms = 0;   // ... and how long each of them ran
     // grid slots (fxjps_set_grid_slot): their maps, and their descriptors on the device (what k_search<.., .., .., true> reads)
     std::vector<GridBufs> slots;  // [FXJPS_MAX_GRID_SLOTS] once the first slot is set; W == 0: empty
     std::vector<GridDev> h_slot_desc;
@@ -212,20 +210,12 @@ struct DevCtx : GridBufs {
     // fxjps_publish_slots: the call's job table (fx::PubTable) and all its outputs, pinned and on the device
     HBuf<uint8_t> h_pub_in, h_pub_out;
     DBuf<uint8_t> d_pub_in, d_pub_out;
-    // a slots batch in progress: its grid ids (the caller's array) and the largest extents of the slots it names, which
-    // size the scratch, the watchdog and the far band's form in place of the resident grid's
-    const int32_t* mg_ids = nullptr;
-    int mg_W = 0, mg_H = 0;
-    uint64_t mg_cells = 0;
-    int plan_W() const { return mg_ids ? mg_W : W; }
-    int plan_H() const { return mg_ids ? mg_H : H; }
-    uint64_t plan_cells() const { return mg_ids ? mg_cells : (uint64_t)W * H; }
     // search scratch (two pools: the regular one and the large retry one)
     DBuf<TEnt> tables[2];
     DBuf<FarEnt> far[2];
     DBuf<uint32_t> wave_gen[2];
     ScratchCfg cfg[2];
-    int cfg_W = 0, cfg_H = 0;  // the batch extents (plan_W / plan_H) pool 0 was last configured for
+    int cfg_W = 0, cfg_H = 0;  // the batch extents (BatchReq::W / H) pool 0 was last configured for
     bool pool_clean[2] = {false, false};
     // batch buffers
     DBuf<int32_t> d_starts, d_goals, d_len, d_cells;
@@ -241,9 +231,7 @@ struct DevCtx : GridBufs {
     DBuf<long long> p_offsets;
     HBuf<int32_t> h_rs_src;
     std::vector<unsigned long long> h_qread;  // read sets of the resident results (streaming replan)
-    std::vector<uint8_t> h_sel;   // mode 2: which queries of the shard are searched again this frame
-    int mode = 0;                 // 0 plain batch, 1 search everything and record read sets, 2 the same for h_sel only
-    int64_t nrun = 0;             // queries handed to the search kernel
+    std::vector<uint8_t> h_sel;   // BatchReq::mode 2: which queries of the shard are searched again this frame
     DBuf<uint8_t> d_raw, d_img;
     // fxjps_refresh_grid (context 0 only): the diff kernels' buffer (fx::DIFF_HDR header words | the list | the blocks' counts)
     // and where its header and the head of the list arrive on the host
@@ -297,11 +285,17 @@ struct DevCtx : GridBufs {
     std::vector<uint32_t> h_order;
     // shard of the current batch
     int64_t q0 = 0, nq = 0;
-    double kernel_ms = 0;
     int wall_khz = 100000;  // hipDeviceAttributeWallClockRate (wall_clock64 ticks per ms)
-    int64_t launches = 0, retried = 0;
-    uint32_t waves_used = 0;  // resident wavefronts of the last regular-pool launch
-    bool waves_short = false; // a scratch pool was granted fewer wavefronts than the batch asked for (memory budget / out of memory)
+    // ... and what its run left for the handle's timing record (collect_timing)
+    struct RunStats {
+        double kernel_ms = 0;
+        int64_t launches = 0, retried = 0;
+        int64_t nrun = 0;          // queries handed to the search kernel
+        uint32_t waves_used = 0;   // resident wavefronts of the last regular-pool launch
+        bool waves_short = false;  // a scratch pool was granted fewer wavefronts than the batch asked for (memory budget / out of memory)
+        bool had_solo = false;     // the last regular-pool launch was two launches
+        double head_ms = 0, batch_ms = 0;  // ... and how long each of them ran
+    } run;
 
     DevCtx() = default;
     DevCtx(DevCtx&&) = default;  // (std::vector<DevCtx>::resize; nothing moves a context that is in use)
@@ -326,11 +320,13 @@ struct fxjps {
     bool maps_stale = false;  // cell updates were applied without rebuilding the derived maps (fxjps_update_cells_deferred)
     int mem_div = 1;          // handles sharing each device (fxjps_set_memory_share): the scratch budgets are divided by it
     fxjps_timing_t timing{};
-    int64_t last_nq = 0;
-    bool last_on_host = false;  // the last batch was a single call: its CSR is in the pinned host buffers only
-    bool last_slots = false;    // the last batch ran on grid slots: its paths are not the resident grid's ...
-    int last_slots_W = 0, last_slots_H = 0;  // ... they lie within these extents (the largest of the slots it named)
-    std::vector<int32_t> last_slot_ids;      // ... and these are the slots its queries named (fxjps_waypoint_slots_batch)
+    struct LastBatch {  // what the resident forms of the waypoint calls read (nq == 0 while a batch is under way: begin_batch)
+        int64_t nq = 0;
+        bool on_host = false;  // the last batch was a single call: its CSR is in the pinned host buffers only
+        bool slots = false;    // the last batch ran on grid slots: its paths are not the resident grid's ...
+        int slots_W = 0, slots_H = 0;   // ... they lie within these extents (the largest of the slots it named)
+        std::vector<int32_t> slot_ids;  // ... and these are the slots its queries named (fxjps_waypoint_slots_batch)
+    } last;
     // persistent query set of the streaming-replan entry points (fxjps_set_queries / fxjps_replan_frame)
     std::vector<int32_t> q_starts, q_goals;
     int q_hchoice = 0, q_max_len = 0;
@@ -646,6 +642,22 @@ uint32_t ceil_log2(uint64_t v) {
     return l;
 }
 
+// What a planning call asks for, complete and checked before anything is queued (batch_request); every function of the
+// planning path reads it, none changes it -- the shards of a several-context batch share it across their host threads.
+struct BatchReq {
+    const int32_t *starts = nullptr, *goals = nullptr;  // the caller's arrays, borrowed for the call
+    int64_t nq = 0;
+    int hchoice = 0, max_len = 0;
+    int mode = 0;        // 0 plain batch, 1 search everything and record read sets, 2 the same for DevCtx::h_sel only
+    bool slots = false;  // every query runs on the grid slot it names, not on the resident grid
+    const int32_t* grid_ids = nullptr;  // ... these (the caller's array; may be NULL when nq == 0)
+    // the extents the scratch, the watchdog and the far band's form are sized for: the resident grid's, or the largest
+    // among the slots the batch names
+    int W = 0, H = 0;
+    uint64_t cells = 0;
+    bool track() const { return mode != 0; }
+};
+
 // Gives the memory of pool 0 back (a batch buffer did not fit beside it); the next batch sizes it again from what is free.
 void release_pool0(DevCtx& d) {
     if (d.stream_solo) (void)hipStreamSynchronize(d.stream_solo);
@@ -657,11 +669,23 @@ void release_pool0(DevCtx& d) {
     d.pool_clean[0] = false;
 }
 
+// Room for a batch buffer that pool 0 may be in the way of (the scratch of an earlier, smaller batch, or of a search that
+// is over): when it does not fit, the pool's memory is given back and the buffer tried again.
+template <typename T>
+int ensure_beside_pool0(fxjps* h, DevCtx& d, DBuf<T>& buf, size_t n) {
+    if (buf.ensure(n) != hipSuccess) {
+        (void)hipGetLastError();
+        release_pool0(d);
+        HIPCHK(h, buf.ensure(n));
+    }
+    return FXJPS_OK;
+}
+
 // Size the per-wavefront scratch.  pool 0: many wavefronts, tables sized for the
 // typical query; pool 1: few wavefronts, tables that cannot overflow.
-// (A slots batch sizes them from the largest extents among the slots it names: DevCtx::plan_W / plan_H / plan_cells.)
-int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
-    const uint64_t cells = d.plan_cells();
+// (A slots batch sizes them from the largest extents among the slots it names: BatchReq::W / H / cells.)
+int ensure_pool(fxjps* h, DevCtx& d, const BatchReq& req, int pool, uint32_t want_waves) {
+    const uint64_t cells = req.cells;
     ScratchCfg c;
     // Memory budget.  A handle that has the device to itself gives pool 0 up to 80 % of it, less what the batch still
     // has to allocate behind the search (the packed paths: at most nq * max_len cells), the smallest retry pool and a
@@ -713,7 +737,7 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
         // slots: 1024^2, where it is exactly as large as the hashed table was); larger grids keep the hashed table.
         // FXJPS_DIRECT=0: measurement / test aid.
         {
-            const uint32_t lx = std::max(ceil_log2((uint64_t)d.plan_W()), 1u), ly = std::max(ceil_log2((uint64_t)d.plan_H()), 1u);
+            const uint32_t lx = std::max(ceil_log2((uint64_t)req.W), 1u), ly = std::max(ceil_log2((uint64_t)req.H), 1u);
             const uint32_t ld = std::max(lx + ly, 12u);
             const uint64_t full = (uint64_t)d.n_cu * 4u * (uint64_t)fx::OCC / (uint64_t)(d.share * h->mem_div);
             const uint64_t cap = (d.mem_total ? (uint64_t)(d.mem_total * 0.4) : ((uint64_t)32 << 30)) / (uint64_t)(d.share * h->mem_div);
@@ -737,7 +761,7 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
             const uint64_t want = std::max<uint64_t>(wpb_up(want_waves), (uint64_t)fx::WPB);
             const double per_entry = (double)sizeof(TEnt) + (1.0 + 1.0 / 8) * sizeof(FarEnt) / 8.0;
             const ScratchCfg& have = d.cfg[0];
-            if (have.nbuckets != 0u && have.direct_ly == 0u && have.nwaves >= want && d.cfg_W == d.plan_W() && d.cfg_H == d.plan_H()) {
+            if (have.nbuckets != 0u && have.direct_ly == 0u && have.nwaves >= want && d.cfg_W == req.W && d.cfg_H == req.H) {
                 // (the pool in place serves this batch: its size stays -- sizes that follow the free memory of the
                 // moment would have the pool allocated and wiped again and again)
                 entries = (uint64_t)have.nbuckets * (uint64_t)fx::BUCKET;
@@ -766,14 +790,14 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
     const size_t per_wave = ((size_t)fx::BUCKET * c.nbuckets) * sizeof(TEnt) + (size_t)(c.far_cap + c.far_cap / 8) * sizeof(FarEnt);
     uint32_t maxw = (uint32_t)std::min<size_t>(budget / per_wave, 1u << 20);
     maxw = (uint32_t)wpb_down(maxw);
-    if (maxw < (uint32_t)fx::WPB) return fail(h, FXJPS_E_NOMEM, "grid %dx%d needs %zu bytes of scratch per wavefront", d.plan_W(), d.plan_H(), per_wave);
-    if ((uint32_t)wpb_up(c.nwaves) > maxw) d.waves_short = true;
+    if (maxw < (uint32_t)fx::WPB) return fail(h, FXJPS_E_NOMEM, "grid %dx%d needs %zu bytes of scratch per wavefront", req.W, req.H, per_wave);
+    if ((uint32_t)wpb_up(c.nwaves) > maxw) d.run.waves_short = true;
     c.nwaves = std::max((uint32_t)fx::WPB, std::min((uint32_t)wpb_up(c.nwaves), maxw));
     ScratchCfg& cur = d.cfg[pool];
     const bool same = cur.nbuckets == c.nbuckets && cur.usable == c.usable && cur.direct_ly == c.direct_ly && cur.far_cap == c.far_cap && cur.nwaves >= c.nwaves;
     if (pool == 0) {  // (the pool in place, or the one configured below, now serves these extents)
-        d.cfg_W = d.plan_W();
-        d.cfg_H = d.plan_H();
+        d.cfg_W = req.W;
+        d.cfg_H = req.H;
     }
     if (same && d.pool_clean[pool]) return FXJPS_OK;
     if (!same) {
@@ -792,7 +816,7 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
             if (e != hipErrorOutOfMemory || c.nwaves <= (uint32_t)fx::WPB)
                 return fail(h, e == hipErrorOutOfMemory ? FXJPS_E_NOMEM : FXJPS_E_HIP, "scratch pool %d: %s", pool, hipGetErrorString(e));
             c.nwaves = std::max((uint32_t)fx::WPB, (uint32_t)wpb_down(c.nwaves / 2u));
-            d.waves_short = true;
+            d.run.waves_short = true;
             DBG("pool %d: out of memory, retrying with %u wavefronts", pool, c.nwaves);
         }
         cur = c;
@@ -805,30 +829,40 @@ int ensure_pool(fxjps* h, DevCtx& d, int pool, uint32_t want_waves) {
     return FXJPS_OK;
 }
 
-void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* d_order, uint32_t nrun, int max_len, bool track);
-int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const ScratchCfg& c, const uint32_t* d_order, uint32_t nrun, int hchoice, bool track);
-
-int launch_search(fxjps* h, DevCtx& d, int pool, const uint32_t* d_order, uint32_t nrun, int hchoice, int max_len, bool track = false) {
-    const ScratchCfg& c = d.cfg[pool];
-    SearchArgs A;
-    fill_search_args(d, pool, A, d_order, nrun, max_len, track);
-    return launch_search_args(h, d, pool, A, c, d_order, nrun, hchoice, track);
+// The one table of k_search instantiations: heuristic x read-set recording (fxjps_replan_frame) x table indexed by the
+// cell, and heuristic x table indexed by the cell with a grid per query (a slots batch: never with read-set recording,
+// fn == nullptr).  index: the instantiation's place in DevCtx::lds_attr_done.
+using SearchFn = void (*)(SearchArgs);
+struct SearchKernel {
+    SearchFn fn;
+    int index;
+};
+SearchKernel search_kernel(int hchoice, bool track, bool direct, bool grid_per_query) {
+    static const SearchFn table[12] = {fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>,
+                                       fx::k_search<1, true, false, false>,  fx::k_search<1, true, true, false>,
+                                       fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>,
+                                       fx::k_search<2, true, false, false>,  fx::k_search<2, true, true, false>,
+                                       fx::k_search<1, false, false, true>,  fx::k_search<1, false, true, true>,
+                                       fx::k_search<2, false, false, true>,  fx::k_search<2, false, true, true>};
+    if (grid_per_query && track) return SearchKernel{nullptr, -1};
+    const int h2 = hchoice == 1 ? 0 : 1, index = (grid_per_query ? 8 + 2 * h2 : 4 * h2 + (track ? 2 : 0)) + (direct ? 1 : 0);
+    return SearchKernel{table[index], index};
 }
 
-void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* d_order, uint32_t nrun, int max_len, bool track) {
+void fill_search_args(const DevCtx& d, const BatchReq& req, int pool, SearchArgs& A, const uint32_t* d_order, uint32_t nrun) {
     const ScratchCfg& c = d.cfg[pool];
     A.G = grid_of(d);
     A.starts = d.d_starts.p;
     A.goals = d.d_goals.p;
     A.order = d_order;
     A.nrun = nrun;
-    A.max_len = max_len;
+    A.max_len = req.max_len;
     A.out_path = d.d_path.p;
     A.out_len = d.d_len.p;
     A.out_cost = d.d_cost.p;
     A.out_counters = d.d_counters.p;
     A.qstat = d.d_qstat.p;  // nullptr unless FXJPS_QSTAT is set
-    A.qread = track ? d.d_qread.p : nullptr;
+    A.qread = req.track() ? d.d_qread.p : nullptr;
     A.tables = d.tables[pool].p;
     A.far = d.far[pool].p;
     A.nbuckets = c.nbuckets;
@@ -837,7 +871,7 @@ void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* 
     // The far band of the open list in f bands that a refill takes whole (no scan, no compaction): pays where open lists
     // hold thousands of entries (4096^2: + 10 %), costs where they hold hundreds (1024^2: - 10 %, an LDS atomic and a
     // scattered store per push instead of an append at a rank).  FXJPS_BANDED=0/1: measurement / test aid.
-    A.banded = d.plan_cells() >= (1ull << 22) ? 1u : 0u;
+    A.banded = req.cells >= (1ull << 22) ? 1u : 0u;
     if (const char* e = getenv("FXJPS_BANDED")) A.banded = atoi(e) != 0 ? 1u : 0u;
     if (pool != 0) A.banded = 0u;  // the large pool is the last resort: its far tier has no regions that could fill up
     A.far_cap = c.far_cap;
@@ -846,14 +880,18 @@ void fill_search_args(const DevCtx& d, int pool, SearchArgs& A, const uint32_t* 
     if (const char* e = getenv("FXJPS_NEAR_MAX")) A.near_max = (uint32_t)std::max(1, atoi(e));
     A.next = d.d_next.p;
     A.wave_gen = d.wave_gen[pool].p;
-    A.max_pops = 64ull * (unsigned long long)d.plan_cells() + 4096ull;
-    if (d.mg_ids) {  // a slots batch: every query reads the descriptor of its slot
+    A.max_pops = 64ull * (unsigned long long)req.cells + 4096ull;
+    if (req.slots) {  // a slots batch: every query reads the descriptor of its slot
         A.grids = d.d_slot_desc.p;
         A.grid_ids = d.d_grid_ids.p;
     }
 }
 
-int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const ScratchCfg& c, const uint32_t* d_order, uint32_t nrun, int hchoice, bool track) {
+int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint32_t* d_order, uint32_t nrun) {
+    const ScratchCfg& c = d.cfg[pool];
+    const bool track = req.track();
+    SearchArgs A;
+    fill_search_args(d, req, pool, A, d_order, nrun);
     uint32_t waves = std::min<uint32_t>(c.nwaves, (nrun + 0u));
     waves = std::max<uint32_t>((uint32_t)fx::WPB, (uint32_t)wpb_up(waves));
     waves = std::min<uint32_t>(waves, c.nwaves);
@@ -881,31 +919,21 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
     if (nsolo != 0u) waves = std::min<uint32_t>(waves, (uint32_t)wpb_down(c.nwaves - nsolo));
 
     if (pool != 0 || nsolo != 0u || (uint64_t)nrun > (uint64_t)d.n_cu * live_main || d.share * h->mem_div > 1) live_main = 0u;
-    if (pool == 0) d.waves_used = waves;
+    if (pool == 0) d.run.waves_used = waves;
     HIPCHK(h, hipMemsetAsync(d.d_next.p, 0, 4 * sizeof(unsigned int), d.stream));
     const dim3 block(fx::WAVE * fx::WPB);
     DBG("launch k_search pool=%d waves=%u nrun=%u buckets=%u far_cap=%u solo=%u x %u spread=%u", pool, waves, nrun, c.nbuckets, c.far_cap, nsolo,
         live_solo, live_main);
     HIPCHK(h, hipEventRecord(d.ev0, d.stream));
-    // instantiations: heuristic x read-set recording (fxjps_replan_frame) x table indexed by the cell
     {
-        using KFn = void (*)(SearchArgs);
-        static const KFn kfn[2][2][2] = {{{fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>},
-                                          {fx::k_search<1, true, false, false>, fx::k_search<1, true, true, false>}},
-                                         {{fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>},
-                                          {fx::k_search<2, true, false, false>, fx::k_search<2, true, true, false>}}};
-        // ... and a grid per query (a slots batch: never with read-set recording)
-        static const KFn kfn_mg[2][2] = {{fx::k_search<1, false, false, true>, fx::k_search<1, false, true, true>},
-                                         {fx::k_search<2, false, false, true>, fx::k_search<2, false, true, true>}};
-        const bool mg = A.grids != nullptr;
-        if (mg && track) return fail(h, FXJPS_E_ARG, "read-set recording on grid slots");
-        const KFn fn = mg ? kfn_mg[hchoice == 1 ? 0 : 1][c.direct_ly > 0 ? 1 : 0] : kfn[hchoice == 1 ? 0 : 1][track ? 1 : 0][c.direct_ly > 0 ? 1 : 0];
+        const SearchKernel k = search_kernel(req.hchoice, track, c.direct_ly > 0, req.slots);
+        if (!k.fn) return fail(h, FXJPS_E_ARG, "read-set recording on grid slots");
+        const SearchFn fn = k.fn;
         static const size_t pad = 36u << 10;  // 66 .. 74 KB of the block's own + this: no second block fits the CU's 160 KB
         if (nsolo != 0u || live_main != 0u) {
-            const int ki = mg ? 8 + (hchoice == 1 ? 0 : 2) + (c.direct_ly > 0 ? 1 : 0) : (hchoice == 1 ? 0 : 4) + (track ? 2 : 0) + (c.direct_ly > 0 ? 1 : 0);
-            if (!d.lds_attr_done[ki]) {
+            if (!d.lds_attr_done[k.index]) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad) == hipSuccess) {
-                    d.lds_attr_done[ki] = true;
+                    d.lds_attr_done[k.index] = true;
                 } else {  // no such launches on this device then: the batch runs as one launch (speed, not correctness)
                     (void)hipGetLastError();
                     nsolo = 0u;
@@ -959,37 +987,28 @@ int launch_search_args(fxjps* h, DevCtx& d, int pool, SearchArgs& A, const Scrat
             HIPCHK(h, hipEventRecord(d.ev_bt1, d.stream));
             HIPCHK(h, hipStreamWaitEvent(d.stream, d.ev_solo1, 0));
         }
-        if (pool == 0) d.had_solo = nsolo != 0u;
+        if (pool == 0) d.run.had_solo = nsolo != 0u;
     }
     HIPCHK(h, hipEventRecord(d.ev1, d.stream));
-    d.launches += nsolo != 0u ? 2 : 1;  // (the two launches overlap: the events span both)
+    d.run.launches += nsolo != 0u ? 2 : 1;  // (the two launches overlap: the events span both)
     return FXJPS_OK;
 }
 
 // Runs the shard [q0, q0+nq) of the batch on device d up to the point where
 // len/cost/offsets are in pinned host memory and the CSR cells are packed on
 // the device.
-int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, int hchoice, int max_len) {
+int run_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     HIPCHK(h, hipSetDevice(d.dev));
     const int64_t nq = d.nq;
-    d.kernel_ms = 0;
-    d.launches = 0;
-    d.retried = 0;
-    d.nrun = 0;
-    d.waves_used = 0;
-    d.waves_short = false;
-    d.had_solo = false;
+    const int max_len = req.max_len;
+    d.run = DevCtx::RunStats();
     if (nq == 0) return FXJPS_OK;
     HIPCHK(h, d.d_starts.ensure((size_t)nq * 2));
     HIPCHK(h, d.d_goals.ensure((size_t)nq * 2));
     HIPCHK(h, d.d_len.ensure((size_t)nq));
     HIPCHK(h, d.d_cost.ensure((size_t)nq));
     d.cells_bound = (size_t)nq * (size_t)max_len * 2 * sizeof(int32_t);
-    if (d.d_path.ensure((size_t)nq * max_len) != hipSuccess) {  // the scratch pool of an earlier, smaller batch may be in the way
-        (void)hipGetLastError();
-        release_pool0(d);
-        HIPCHK(h, d.d_path.ensure((size_t)nq * max_len));
-    }
+    if (int rc = ensure_beside_pool0(h, d, d.d_path, (size_t)nq * max_len)) return rc;
     HIPCHK(h, d.d_offsets.ensure((size_t)nq + 1));
     HIPCHK(h, d.d_next.ensure(4));
     HIPCHK(h, d.d_counters.ensure(64));
@@ -997,11 +1016,11 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
     HIPCHK(h, d.h_cost.ensure((size_t)nq));
     HIPCHK(h, d.h_offsets.ensure((size_t)nq + 1));
     HIPCHK(h, d.h_counters.ensure(64));
-    HIPCHK(h, hipMemcpyAsync(d.d_starts.p, starts + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-    HIPCHK(h, hipMemcpyAsync(d.d_goals.p, goals + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-    if (d.mg_ids) {
+    HIPCHK(h, hipMemcpyAsync(d.d_starts.p, req.starts + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.d_goals.p, req.goals + 2 * d.q0, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+    if (req.slots) {
         HIPCHK(h, d.d_grid_ids.ensure((size_t)nq));
-        HIPCHK(h, hipMemcpyAsync(d.d_grid_ids.p, d.mg_ids + d.q0, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(h, hipMemcpyAsync(d.d_grid_ids.p, req.grid_ids + d.q0, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
     }
     HIPCHK(h, hipMemsetAsync(d.d_counters.p, 0, 64 * sizeof(unsigned long long), d.stream));
     if (getenv("FXJPS_QSTAT")) {  // diagnostics: per-query start / end time, pops, wavefront (tools/qstat.py)
@@ -1017,8 +1036,8 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
     // 0.94; Manhattan: 0.94 / 0.92) -- the queries that end last are the long DIAGONAL ones, whose open lists are full of
     // equal keys (fewer nodes committed per iteration).  Counting sort, descending.
     {
-        const int32_t* S = starts + 2 * d.q0;
-        const int32_t* G = goals + 2 * d.q0;
+        const int32_t* S = req.starts + 2 * d.q0;
+        const int32_t* G = req.goals + 2 * d.q0;
         constexpr uint32_t KMAX = 3u * 8192u - 1u;
         std::vector<uint32_t> head(KMAX + 3u, 0);
         d.h_order.resize((size_t)nq);
@@ -1026,36 +1045,34 @@ int run_shard(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, 
             const int64_t dx = std::llabs((int64_t)S[2 * i] - G[2 * i]), dy = std::llabs((int64_t)S[2 * i + 1] - G[2 * i + 1]);
             return (uint32_t)std::min<int64_t>(2 * std::max(dx, dy) + std::min(dx, dy), (int64_t)KMAX);
         };
-        const bool subset = d.mode == 2;  // streaming replan: only the queries whose read set was touched
+        const bool subset = req.mode == 2;  // streaming replan: only the queries whose read set was touched
         auto in = [&](int64_t i) -> bool { return !subset || d.h_sel[(size_t)i] != 0; };
         for (int64_t i = 0; i < nq; i++)
             if (in(i)) head[KMAX - key(i) + 1]++;
         for (uint32_t k = 1; k < KMAX + 3u; k++) head[k] += head[k - 1];
-        d.nrun = head[KMAX + 2u];
+        d.run.nrun = head[KMAX + 2u];
         for (int64_t i = 0; i < nq; i++)
             if (in(i)) d.h_order[head[KMAX - key(i)]++] = (uint32_t)i;
         HIPCHK(h, d.d_order.ensure((size_t)nq));
-        if (d.nrun > 0)
-            HIPCHK(h, hipMemcpyAsync(d.d_order.p, d.h_order.data(), (size_t)d.nrun * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+        if (d.run.nrun > 0)
+            HIPCHK(h, hipMemcpyAsync(d.d_order.p, d.h_order.data(), (size_t)d.run.nrun * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     }
-    if (d.mode != 0) {  // read-set bitmaps: 128 x u64 per query, zero for queries that never searched
+    if (req.track()) {  // read-set bitmaps: 128 x u64 per query, zero for queries that never searched
         const size_t had = d.d_qread.cap;
         HIPCHK(h, d.d_qread.ensure((size_t)nq * 128));
         if (d.d_qread.cap != had) HIPCHK(h, hipMemsetAsync(d.d_qread.p, 0, d.d_qread.cap * sizeof(unsigned long long), d.stream));
     }
-    if (d.nrun == 0) return FXJPS_OK;  // every result of the previous frame is still valid
+    if (d.run.nrun == 0) return FXJPS_OK;  // every result of the previous frame is still valid
     DBG("run_shard nq=%lld: inputs queued", (long long)nq);
-    int rc = ensure_pool(h, d, 0, (uint32_t)std::min<int64_t>(full, (d.nrun + 3) & ~3ll));
+    int rc = ensure_pool(h, d, req, 0, (uint32_t)std::min<int64_t>(full, (d.run.nrun + 3) & ~3ll));
     if (rc) return rc;
     DBG("pool ready");
-    rc = launch_search(h, d, 0, d.d_order.p, (uint32_t)d.nrun, hchoice, max_len, d.mode != 0);
-    if (rc) return rc;
-    return FXJPS_OK;
+    return launch_search(h, d, req, 0, d.d_order.p, (uint32_t)d.run.nrun);
 }
 
 // Second half, first part: wait for the search and retry overflowed queries with the large pool.  Leaves the lengths (internal
 // codes included) in d.h_len.
-int finish_search(fxjps* h, DevCtx& d, int hchoice, int max_len) {
+int finish_search(fxjps* h, DevCtx& d, const BatchReq& req) {
     HIPCHK(h, hipSetDevice(d.dev));
     const int64_t nq = d.nq;
     if (nq == 0) return FXJPS_OK;
@@ -1069,52 +1086,57 @@ int finish_search(fxjps* h, DevCtx& d, int hchoice, int max_len) {
     HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     float ms = 0;
-    d.head_ms = d.batch_ms = 0;
-    if (d.launches > 0) {
+    if (d.run.launches > 0) {
         HIPCHK(h, hipEventElapsedTime(&ms, d.ev0, d.ev1));
-        d.kernel_ms += ms;
-        if (d.had_solo) {
+        d.run.kernel_ms += ms;
+        if (d.run.had_solo) {
             float a = 0, b = 0;
             HIPCHK(h, hipEventElapsedTime(&a, d.ev_hd0, d.ev_hd1));
             HIPCHK(h, hipEventElapsedTime(&b, d.ev_bt0, d.ev_bt1));
-            d.head_ms = a;
-            d.batch_ms = b;
+            d.run.head_ms = a;
+            d.run.batch_ms = b;
         }
     }
     std::vector<uint32_t> redo;
     for (int64_t i = 0; i < nq; i++)
         if (d.h_len.p[i] <= fx::QI_TABLE_FULL) redo.push_back((uint32_t)i);
     if (!redo.empty()) {
-        d.retried = (int64_t)redo.size();
-        int rc = ensure_pool(h, d, 1, (uint32_t)std::min<size_t>(256, (redo.size() + 3) & ~(size_t)3));
+        d.run.retried = (int64_t)redo.size();
+        int rc = ensure_pool(h, d, req, 1, (uint32_t)std::min<size_t>(256, (redo.size() + 3) & ~(size_t)3));
         if (rc) return rc;
         HIPCHK(h, d.d_redo.ensure(redo.size()));
         HIPCHK(h, hipMemcpyAsync(d.d_redo.p, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));  // `redo` is pageable host memory
-        rc = launch_search(h, d, 1, d.d_redo.p, (uint32_t)redo.size(), hchoice, max_len, d.mode != 0);
+        rc = launch_search(h, d, req, 1, d.d_redo.p, (uint32_t)redo.size());
         if (rc) return rc;
         HIPCHK(h, hipStreamSynchronize(d.stream));  // (as above: no copy waits in the engine's queue for a search)
         HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));
         HIPCHK(h, hipEventElapsedTime(&ms, d.ev0, d.ev1));
-        d.kernel_ms += ms;
+        d.run.kernel_ms += ms;
     }
-    DBG("kernel %.3f ms, %zu to redo", d.kernel_ms, redo.size());
+    DBG("kernel %.3f ms, %zu to redo", d.run.kernel_ms, redo.size());
     return FXJPS_OK;
+}
+
+// Internal codes must not leak: whatever the large pool could not finish either is FXJPS_Q_CAPACITY to the caller.
+void hide_internal_codes(DevCtx& d) {
+    for (int64_t i = 0; i < d.nq; i++)
+        if (d.h_len.p[i] <= fx::QI_TABLE_FULL) d.h_len.p[i] = FXJPS_Q_CAPACITY;
 }
 
 // Second half: wait for the search, retry overflowed queries with the large
 // pool, pack to CSR, copy len/cost/offsets back.
-int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
+int finish_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     const int64_t nq = d.nq;
     if (nq == 0) return FXJPS_OK;
-    if (int rc = finish_search(h, d, hchoice, max_len)) return rc;
+    if (int rc = finish_search(h, d, req)) return rc;
     hipLaunchKernelGGL(fx::k_scan_len, dim3(1), dim3(1024), 0, d.stream, d.d_len.p, (long long)nq, d.d_offsets.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(d.h_offsets.p, d.d_offsets.p, ((size_t)nq + 1) * sizeof(long long), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipMemcpyAsync(d.h_cost.p, d.d_cost.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipMemcpyAsync(d.h_counters.p, d.d_counters.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
-    if (d.mode != 0 && d.launches > 0) {  // the read sets of what ran (the rest of the buffer is unchanged)
+    if (req.track() && d.run.launches > 0) {  // the read sets of what ran (the rest of the buffer is unchanged)
         d.h_qread.resize((size_t)nq * 128);
         HIPCHK(h, hipMemcpyAsync(d.h_qread.data(), d.d_qread.p, (size_t)nq * 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     }
@@ -1122,22 +1144,16 @@ int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
     const long long total = d.h_offsets.p[nq];
     DBG("scan done, %lld cells", total);
     if (total > 0) {
-        if (d.d_cells.ensure((size_t)total * 2) != hipSuccess) {  // (the search is over: its scratch can go)
-            (void)hipGetLastError();
-            release_pool0(d);
-            HIPCHK(h, d.d_cells.ensure((size_t)total * 2));
-        }
+        if (int rc = ensure_beside_pool0(h, d, d.d_cells, (size_t)total * 2)) return rc;  // (the search is over: its scratch can go)
         HIPCHK(h, d.h_cells.ensure((size_t)total * 2));
         hipLaunchKernelGGL(fx::k_gather_paths, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, d.stream, d.d_path.p,
-                           d.d_len.p, d.d_offsets.p, (long long)nq, max_len, d.d_cells.p, total);
+                           d.d_len.p, d.d_offsets.p, (long long)nq, req.max_len, d.d_cells.p, total);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(d.h_cells.p, d.d_cells.p, (size_t)total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));
     }
     DBG("gather done");
-    // internal codes must not leak
-    for (int64_t i = 0; i < nq; i++)
-        if (d.h_len.p[i] <= fx::QI_TABLE_FULL) d.h_len.p[i] = FXJPS_Q_CAPACITY;
+    hide_internal_codes(d);
     return FXJPS_OK;
 }
 
@@ -1148,19 +1164,13 @@ int finish_shard(fxjps* h, DevCtx& d, int hchoice, int max_len) {
 // path, its length and its cost straight into the handle's pinned host buffers -- one launch, one host wait.  Results
 // land where plan_core's other path leaves them (h_len / h_cost / h_offsets / h_cells), so the callers above see no
 // difference.  Returns 1 when the query has to go through the batch path after all (it outgrew the regular scratch).
-int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals, int hchoice, int max_len) {
+int plan_single(fxjps* h, DevCtx& d, const BatchReq& req) {
     HIPCHK(h, hipSetDevice(d.dev));
+    const int max_len = req.max_len;
     d.q0 = 0;
     d.nq = 1;
-    d.mode = 0;
-    d.kernel_ms = 0;
-    d.launches = 0;
-    d.retried = 0;
-    d.nrun = 1;
-    d.waves_used = 1;
-    d.waves_short = false;
-    d.had_solo = false;
-    d.head_ms = d.batch_ms = 0;
+    d.run = DevCtx::RunStats();
+    d.run.nrun = d.run.waves_used = 1;
     HIPCHK(h, d.h_len.ensure(1));
     HIPCHK(h, d.h_cost.ensure(1));
     HIPCHK(h, d.h_offsets.ensure(2));
@@ -1169,21 +1179,21 @@ int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals
     HIPCHK(h, d.h_path1.ensure((size_t)max_len));
     HIPCHK(h, d.h_cells.ensure((size_t)max_len * 2));
     d.cells_bound = 0;
-    int rc = ensure_pool(h, d, 0, (uint32_t)fx::WPB);
+    int rc = ensure_pool(h, d, req, 0, (uint32_t)fx::WPB);
     if (rc) return rc;
     const ScratchCfg& c = d.cfg[0];
     SearchArgs A;
-    fill_search_args(d, 0, A, nullptr, 1u, max_len, false);
+    fill_search_args(d, req, 0, A, nullptr, 1u);
     A.starts = nullptr;
     A.goals = nullptr;
     A.next = nullptr;
     A.qstat = nullptr;
     A.single = 1u;
     A.solo = 1u;
-    A.imm[0] = starts[0];
-    A.imm[1] = starts[1];
-    A.imm[2] = goals[0];
-    A.imm[3] = goals[1];
+    A.imm[0] = req.starts[0];
+    A.imm[1] = req.starts[1];
+    A.imm[2] = req.goals[0];
+    A.imm[3] = req.goals[1];
     void *dp_path = nullptr, *dp_len = nullptr, *dp_cost = nullptr;
     HIPCHK(h, hipHostGetDevicePointer(&dp_path, d.h_path1.p, 0));
     HIPCHK(h, hipHostGetDevicePointer(&dp_len, d.h_len.p, 0));
@@ -1197,21 +1207,16 @@ int plan_single(fxjps* h, DevCtx& d, const int32_t* starts, const int32_t* goals
     void* dp_cnt = nullptr;
     HIPCHK(h, hipHostGetDevicePointer(&dp_cnt, d.h_counters.p, 0));
     A.host_counters = (unsigned long long*)dp_cnt;
-    {
-        using KFn = void (*)(SearchArgs);
-        static const KFn kfn[2][2] = {{fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>},
-                                      {fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>}};
-        hipLaunchKernelGGL(kfn[hchoice == 1 ? 0 : 1][c.direct_ly > 0 ? 1 : 0], dim3(1), dim3(fx::WAVE * fx::WPB), 0, d.stream, A);
-        HIPCHK(h, hipGetLastError());
-    }
+    hipLaunchKernelGGL(search_kernel(req.hchoice, false, c.direct_ly > 0, false).fn, dim3(1), dim3(fx::WAVE * fx::WPB), 0, d.stream, A);
+    HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(d.stream));
     // (the kernel's time by the device's constant-rate clock, read by the one wavefront at its first and last instruction: two
     // event records and hipEventElapsedTime were three more runtime calls on a 250 us call)
-    d.kernel_ms = (double)(d.h_counters.p[63] - d.h_counters.p[62]) / (double)d.wall_khz;
-    DBG("single call: kernel %.1f us, %llu pops, shader clock %.0f MHz", d.kernel_ms * 1e3, (unsigned long long)d.h_counters.p[0],
-        d.kernel_ms > 0 ? (double)(d.h_counters.p[61] - d.h_counters.p[60]) / (d.kernel_ms * 1e3) : 0.0);
+    d.run.kernel_ms = (double)(d.h_counters.p[63] - d.h_counters.p[62]) / (double)d.wall_khz;
+    DBG("single call: kernel %.1f us, %llu pops, shader clock %.0f MHz", d.run.kernel_ms * 1e3, (unsigned long long)d.h_counters.p[0],
+        d.run.kernel_ms > 0 ? (double)(d.h_counters.p[61] - d.h_counters.p[60]) / (d.run.kernel_ms * 1e3) : 0.0);
     d.h_counters.p[60] = d.h_counters.p[61] = d.h_counters.p[62] = d.h_counters.p[63] = 0ull;
-    d.launches = 1;
+    d.run.launches = 1;
     const int32_t n = d.h_len.p[0];
     if (n <= fx::QI_TABLE_FULL) return 1;  // outgrew the regular scratch (or the watchdog): the batch path has the large pool
     d.h_offsets.p[0] = 0;
@@ -1228,42 +1233,105 @@ int update_cells_async(fxjps* h, const int32_t* xy, const uint8_t* val, int64_t 
 void drain_all(fxjps* h);
 void collect_timing(fxjps* h);
 
-// grid_ids != nullptr: a slots batch (fxjps_plan_batch_slots_csr, which checked the ids and set every context's mg_* fields)
-int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len, int mode = 0,
-              const int32_t* grid_ids = nullptr) {
-    if (!h) return FXJPS_E_ARG;
-    if (!h->have_grid && !grid_ids) return fail(h, FXJPS_E_NOGRID, "fxjps_plan_batch before fxjps_set_grid");
+bool slot_in_use(fxjps* h, int32_t slot) {
+    const DevCtx& d0 = h->devs[0];
+    return slot >= 0 && slot < FXJPS_MAX_GRID_SLOTS && (size_t)slot < d0.slots.size() && d0.slots[(size_t)slot].W > 0;
+}
+
+// What every call that takes queries refuses about them (fxjps_set_queries stores them for later frames).
+int check_queries(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len) {
     if (nq < 0 || (nq > 0 && (!starts || !goals))) return fail(h, FXJPS_E_ARG, "bad query arrays");
     if (hchoice != 1 && hchoice != 2)
         return fail(h, FXJPS_E_ARG, "hchoice must be 1 or 2 (the reference raises TypeError, jps1.py:188)");
     if (max_len < 1 || max_len > (1 << 20)) return fail(h, FXJPS_E_ARG, "max_path_len out of range");
+    return FXJPS_OK;
+}
+
+// A planning call's request, built and checked: every refusal of a batch is made here, and nothing of the handle is
+// touched.  grid_ids == nullptr: a batch on the resident grid (no grid is judged before the arrays); otherwise a slots
+// batch (slots == true; its ids are judged before the arrays, every one of them: the batch is sized by the largest
+// extents among the slots it names).  *req is complete when FXJPS_OK comes back.
+int batch_request(fxjps* h, bool slots, const int32_t* grid_ids, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice,
+                  int max_len, int mode, BatchReq* req) {
+    BatchReq r;
+    r.W = r.H = 1;
+    r.cells = 1;
+    if (slots) {
+        if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
+        std::vector<uint8_t> seen(FXJPS_MAX_GRID_SLOTS, 0);
+        for (int64_t q = 0; q < nq; q++) {
+            const int32_t id = grid_ids[q];
+            if (!slot_in_use(h, id))
+                return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)id,
+                            id < 0 || id >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
+            if (seen[(size_t)id]) continue;
+            seen[(size_t)id] = 1;
+            const GridBufs& g = h->devs[0].slots[(size_t)id];
+            r.W = std::max(r.W, g.W);
+            r.H = std::max(r.H, g.H);
+            r.cells = std::max(r.cells, (uint64_t)g.W * (uint64_t)g.H);
+        }
+    } else {
+        if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "fxjps_plan_batch before fxjps_set_grid");
+        r.W = h->devs[0].W;  // (every context holds the same grid)
+        r.H = h->devs[0].H;
+        r.cells = (uint64_t)r.W * r.H;
+    }
+    if (int rc = check_queries(h, starts, goals, nq, hchoice, max_len)) return rc;
     if (nq > 0x7FFFFFF0ll) return fail(h, FXJPS_E_ARG, "too many queries in one batch");
-    // Until this batch is complete (emit_csr) no earlier batch is "the last batch": the resident-path forms of the
-    // waypoint entry points refuse with FXJPS_E_ARG instead of reading lengths and offsets of different batches.
-    h->last_nq = 0;
-    h->last_slots = grid_ids != nullptr;
-    if (h->maps_stale && !grid_ids) {  // deferred cell updates: the maps are rebuilt once, in front of the search
+    r.starts = starts;
+    r.goals = goals;
+    r.nq = nq;
+    r.hchoice = hchoice;
+    r.max_len = max_len;
+    r.mode = mode;
+    r.slots = slots;
+    r.grid_ids = grid_ids;
+    *req = r;
+    return FXJPS_OK;
+}
+
+// A batch begins.  Until it is complete (emit_csr) no earlier batch is "the last batch": the resident-path forms of the
+// waypoint entry points refuse with FXJPS_E_ARG instead of reading lengths and offsets of different batches; and the
+// results stored for reuse no longer describe the device buffers (fxjps_replan_frame / fxjps_replan_slots say so again
+// once theirs are complete).
+int begin_batch(fxjps* h, const BatchReq& req) {
+    h->last.nq = 0;
+    h->last.slots = req.slots;
+    if (h->maps_stale && !req.slots) {  // deferred cell updates: the maps are rebuilt once, in front of the search
         int rc = update_cells_async(h, nullptr, nullptr, 0, true);
         if (rc) return rc;
     }
+    h->q_results_valid = h->rs_valid = false;
+    h->last.on_host = false;
+    return FXJPS_OK;
+}
+
+// A call's tail: how long it took, into the timing record and to the caller.
+int end_call(fxjps* h, double t0, double* out_seconds_total, int rc) {
+    h->timing.total_ms = (now_s() - t0) * 1e3;
+    if (out_seconds_total) *out_seconds_total = now_s() - t0;
+    return rc;
+}
+
+int plan_core(fxjps* h, const BatchReq& req) {
+    if (int rc = begin_batch(h, req)) return rc;
+    const int64_t nq = req.nq;
     const int nd = (int)h->devs.size();
     for (int r = 0; r < nd; r++) {  // contiguous shards: SURVEY 8(e)
         h->devs[r].q0 = nq * r / nd;
         h->devs[r].nq = nq * (r + 1) / nd - h->devs[r].q0;
-        h->devs[r].mode = mode;
     }
-    h->q_results_valid = h->rs_valid = false;  // (fxjps_replan_frame sets it again once its frame is complete)
     int rc = FXJPS_OK;
-    h->last_on_host = false;
     static const bool single_ok = !(getenv("FXJPS_SINGLE") && atoi(getenv("FXJPS_SINGLE")) == 0) && !getenv("FXJPS_QSTAT");  // (0: test / measurement aid)
     bool done = false;
-    if (nq == 1 && nd == 1 && mode == 0 && single_ok && !grid_ids) {  // (a lone query on a slot takes the batch path)
-        rc = plan_single(h, h->devs[0], starts, goals, hchoice, max_len);
+    if (nq == 1 && nd == 1 && req.mode == 0 && single_ok && !req.slots) {  // (a lone query on a slot takes the batch path)
+        rc = plan_single(h, h->devs[0], req);
         if (rc == 1) {
             rc = FXJPS_OK;  // (rare: on to the batch path)
         } else {
             done = true;
-            h->last_on_host = rc == FXJPS_OK;
+            h->last.on_host = rc == FXJPS_OK;
         }
     }
     if (nd > 1 && !rc && !done) {
@@ -1272,14 +1340,14 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
         // other's host-side tail -- run one after the other, eight tails of ~ 23 ms each behind ~ 570 ms of parallel search
         // capped config 4 at 75 % strong-scaling efficiency by construction.  (The shards share nothing, jps1.py:183-192.)
         rc = run_side_by_side((size_t)nd, [&](size_t r) {
-            int e = run_shard(h, h->devs[r], starts, goals, hchoice, max_len);
-            if (!e) e = finish_shard(h, h->devs[r], hchoice, max_len);
+            int e = run_shard(h, h->devs[r], req);
+            if (!e) e = finish_shard(h, h->devs[r], req);
             return e;
         });
         done = true;
     }
-    for (int r = 0; r < nd && !rc && !done; r++) rc = run_shard(h, h->devs[r], starts, goals, hchoice, max_len);
-    for (int r = 0; r < nd && !rc && !done; r++) rc = finish_shard(h, h->devs[r], hchoice, max_len);
+    for (int r = 0; r < nd && !rc && !done; r++) rc = run_shard(h, h->devs[r], req);
+    for (int r = 0; r < nd && !rc && !done; r++) rc = finish_shard(h, h->devs[r], req);
     if (rc) {
         drain_all(h);  // before the error leaves the library
         for (auto& d : h->devs) d.nq = 0;  // (no shard holds a result)
@@ -1287,6 +1355,13 @@ int plan_core(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq,
     }
     collect_timing(h);
     return FXJPS_OK;
+}
+
+// a batch on the resident grid: its request, then the batch
+int plan_resident(fxjps* h, const int32_t* starts, const int32_t* goals, int64_t nq, int hchoice, int max_len, int mode = 0) {
+    BatchReq req;
+    if (int rc = batch_request(h, false, nullptr, starts, goals, nq, hchoice, max_len, mode, &req)) return rc;
+    return plan_core(h, req);
 }
 
 // the handle's timing record out of what every context's last batch left
@@ -1308,14 +1383,14 @@ void collect_timing(fxjps* h) {
     T.batch_launch_ms = 0;
     T.solo_timeouts = 0;
     for (auto& d : h->devs) {
-        T.head_launch_ms = std::max(T.head_launch_ms, d.head_ms);
-        T.batch_launch_ms = std::max(T.batch_launch_ms, d.batch_ms);
+        T.head_launch_ms = std::max(T.head_launch_ms, d.run.head_ms);
+        T.batch_launch_ms = std::max(T.batch_launch_ms, d.run.batch_ms);
         T.solo_timeouts += d.solo_timeouts;
-        T.waves += d.waves_used;
-        if (d.waves_short) T.waves_short = 1;
-        T.search_kernel_ms = std::max(T.search_kernel_ms, d.kernel_ms);
-        T.search_launches += d.launches;
-        T.retried += d.retried;
+        T.waves += d.run.waves_used;
+        if (d.run.waves_short) T.waves_short = 1;
+        T.search_kernel_ms = std::max(T.search_kernel_ms, d.run.kernel_ms);
+        T.search_launches += d.run.launches;
+        T.retried += d.run.retried;
         if (d.nq > 0) {
             T.pops += (int64_t)d.h_counters.p[0];
             T.pushes += (int64_t)d.h_counters.p[1];
@@ -1473,7 +1548,7 @@ struct WpPaths {
     template <typename F>
     int resolve(fxjps* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, bool name_query, F&& nonneg) {
         static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed over as they are");
-        if (!cells_xy && h->last_on_host) {
+        if (!cells_xy && h->last.on_host) {
             offsets = reinterpret_cast<const int64_t*>(h->devs[0].h_offsets.p);
             cells_xy = h->devs[0].h_cells.p;
         }
@@ -1566,7 +1641,7 @@ bool wp_atab_fits(long long am, long long bm) { return (am + 1) * (2 * bm + 1) <
 // on, a slots batch's within the largest slot it named.
 void wp_st_range(const fxjps* h, const WpPaths& S, int64_t nq, const int32_t* rule, const int32_t* map_start, long long& am, long long& bm) {
     am = bm = 0;
-    const long long W = h->last_slots ? h->last_slots_W : h->devs[0].W, H = h->last_slots ? h->last_slots_H : h->devs[0].H;
+    const long long W = h->last.slots ? h->last.slots_W : h->devs[0].W, H = h->last.slots ? h->last.slots_H : h->devs[0].H;
     for (int64_t q = 0; q < nq; q++) {
         if (rule && rule[q] != 0) continue;
         const long long mx = map_start[2 * q], my = map_start[2 * q + 1];
@@ -2354,7 +2429,7 @@ static int emit_csr(fxjps_t* h, int64_t nq, int64_t* out_offsets, int32_t* out_c
         return 0;
     });
     if (out_offsets) out_offsets[nq] = base;
-    h->last_nq = nq;
+    h->last.nq = nq;
     if (!fits) return fail(h, FXJPS_E_ARG, "out_cells_xy holds %lld pairs, batch needs %lld", (long long)cells_capacity, (long long)base);
     return FXJPS_OK;
 }
@@ -2376,9 +2451,7 @@ int fxjps_update_cells_deferred(fxjps_t* h, const int32_t* xy, const uint8_t* va
 int fxjps_set_queries(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq, int32_t hchoice,
                       int32_t max_path_len) {
     if (!h) return FXJPS_E_ARG;
-    if (nq < 0 || (nq > 0 && (!starts_xy || !goals_xy))) return fail(h, FXJPS_E_ARG, "bad query arrays");
-    if (hchoice != 1 && hchoice != 2) return fail(h, FXJPS_E_ARG, "hchoice must be 1 or 2 (the reference raises TypeError, jps1.py:188)");
-    if (max_path_len < 1 || max_path_len > (1 << 20)) return fail(h, FXJPS_E_ARG, "max_path_len out of range");
+    if (int rc = check_queries(h, starts_xy, goals_xy, nq, hchoice, max_path_len)) return rc;
     h->q_starts.assign(starts_xy, starts_xy + 2 * nq);  // copied: the caller's arrays are not kept
     h->q_goals.assign(goals_xy, goals_xy + 2 * nq);
     h->q_hchoice = hchoice;
@@ -2476,14 +2549,11 @@ int fxjps_replan_frame(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
         drain_all(h);  // the devices in front of the failing one have the update queued
         return rc;
     }
-    rc = plan_core(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
+    rc = plan_resident(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
     if (rc) return rc;
     h->q_results_valid = track;
     h->timing.reused = reused;
-    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return rc;
+    return end_call(h, t0, out_seconds_total, emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost));
 }
 
 namespace {
@@ -2607,16 +2677,13 @@ int replan_frame_raw_impl(fxjps_t* h, PrepReq q, int64_t* out_changed, int32_t* 
     h->q_results_valid = h->rs_valid = false;  // (set again below, once the frame is complete)
     const bool done = refresh_done(h, r);
     if (int rc = refresh_apply(h, q, r)) return rc;
-    int rc = plan_core(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
+    int rc = plan_resident(h, h->q_starts.data(), h->q_goals.data(), nq, h->q_hchoice, h->q_max_len, mode);
     if (rc) return rc;
     h->q_results_valid = track;
     h->timing.reused = reused;
     rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
     if (rc) return rc;
-    rc = prepare_finish(h, q, done);  // (its wait: a context without queries of the batch has not waited for its update)
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return rc;
+    return end_call(h, t0, out_seconds_total, prepare_finish(h, q, done));  // (its wait: a context without queries of the batch has not waited for its update)
 }
 }  // namespace
 
@@ -2662,19 +2729,12 @@ int fxjps_plan_batch_csr(fxjps_t* h, const int32_t* starts_xy, const int32_t* go
     const double t0 = now_s();
     if (!h) return FXJPS_E_ARG;
     if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    int rc = plan_core(h, starts_xy, goals_xy, nq, hchoice, max_path_len);
+    int rc = plan_resident(h, starts_xy, goals_xy, nq, hchoice, max_path_len);
     if (rc) return rc;
-    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return rc;
+    return end_call(h, t0, out_seconds_total, emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost));
 }
 
 namespace {
-bool slot_in_use(fxjps_t* h, int32_t slot) {
-    const DevCtx& d0 = h->devs[0];
-    return slot >= 0 && slot < FXJPS_MAX_GRID_SLOTS && (size_t)slot < d0.slots.size() && d0.slots[(size_t)slot].W > 0;
-}
 // A context's slot tables, created by the first call that sets a slot (the context is current).
 int ensure_slot_tables(fxjps_t* h, DevCtx& d) {
     if (d.slots.empty()) {
@@ -3438,67 +3498,28 @@ int fxjps_publish_slots(fxjps_t* h, fxjps_slot_publish_t* jobs, int32_t n) {
     return FXJPS_OK;
 }
 
-namespace {
-// A slots batch's ids, every one checked before anything is queued; the batch is sized by the largest extents among the
-// slots it names.
-int slots_batch_extents(fxjps_t* h, const int32_t* grid_ids, int64_t nq, int& mw, int& mh, uint64_t& mc) {
-    mw = mh = 1;
-    mc = 1;
-    std::vector<uint8_t> seen(FXJPS_MAX_GRID_SLOTS, 0);
-    for (int64_t q = 0; q < nq; q++) {
-        const int32_t id = grid_ids[q];
-        if (!slot_in_use(h, id))
-            return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)id,
-                        id < 0 || id >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
-        if (seen[(size_t)id]) continue;
-        seen[(size_t)id] = 1;
-        const GridBufs& g = h->devs[0].slots[(size_t)id];
-        mw = std::max(mw, g.W);
-        mh = std::max(mh, g.H);
-        mc = std::max(mc, (uint64_t)g.W * (uint64_t)g.H);
-    }
-    return FXJPS_OK;
-}
-}  // namespace
-
 int fxjps_plan_batch_slots_csr(fxjps_t* h, const int32_t* grid_ids, const int32_t* starts_xy, const int32_t* goals_xy, int64_t nq,
                                int32_t hchoice, int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy,
                                int64_t cells_capacity, int32_t* out_len, double* out_cost, double* out_seconds_total) {
     const double t0 = now_s();
     if (!h) return FXJPS_E_ARG;
     if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
-    int mw = 1, mh = 1;
-    uint64_t mc = 1;
-    if (int rc = slots_batch_extents(h, grid_ids, nq, mw, mh, mc)) return rc;
-    static const int32_t no_ids = 0;  // (an empty batch may pass no array: it is a slots batch all the same)
-    const int32_t* ids = grid_ids ? grid_ids : &no_ids;
-    for (auto& d : h->devs) {
-        d.mg_ids = ids;
-        d.mg_W = mw;
-        d.mg_H = mh;
-        d.mg_cells = mc;
-    }
-    int rc = plan_core(h, starts_xy, goals_xy, nq, hchoice, max_path_len, 0, ids);
-    for (auto& d : h->devs) d.mg_ids = nullptr;  // (the caller's array is only borrowed for the call)
-    if (rc) return rc;
-    h->last_slots_W = mw;
-    h->last_slots_H = mh;
-    h->last_slot_ids.assign(ids, ids + nq);
-    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return rc;
+    BatchReq req;
+    if (int rc = batch_request(h, true, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, 0, &req)) return rc;
+    if (int rc = plan_core(h, req)) return rc;
+    h->last.slots_W = req.W;
+    h->last.slots_H = req.H;
+    h->last.slot_ids.assign(grid_ids, grid_ids + nq);
+    return end_call(h, t0, out_seconds_total, emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost));
 }
 
 namespace {
 // fxjps_replan_slots on a handle with one context.  The arguments are checked; `searched` lists the
 // queries to search, in query order.  Runs them as a sub-batch through run_shard / finish_search, then assembles the full
 // batch on the device: one copy in (the source table), one scan launch, one gather launch, the copies out, one wait.
-int replan_slots_assemble(fxjps* h, DevCtx& d, const int32_t* grid_ids, const int32_t* starts, const int32_t* goals, int64_t nq,
-                          const std::vector<int64_t>& searched, int hchoice, int max_len, int mw, int mh, uint64_t mc) {
+int replan_slots_assemble(fxjps* h, DevCtx& d, const BatchReq& req, const std::vector<int64_t>& searched) {
     HIPCHK(h, hipSetDevice(d.dev));
-    const int64_t nsub = (int64_t)searched.size();
+    const int64_t nq = req.nq, nsub = (int64_t)searched.size();
     // the previous batch's results become the other set: what was `previous` before is written anew
     std::swap(d.d_len, d.p_len);
     std::swap(d.d_cost, d.p_cost);
@@ -3507,37 +3528,29 @@ int replan_slots_assemble(fxjps* h, DevCtx& d, const int32_t* grid_ids, const in
     std::vector<int32_t> sub_len((size_t)nsub);
     d.q0 = 0;
     d.nq = nsub;
-    d.mode = 0;
     if (nsub > 0) {
         std::vector<int32_t> ids((size_t)nsub), st((size_t)nsub * 2), go((size_t)nsub * 2);
         for (int64_t k = 0; k < nsub; k++) {
             const int64_t q = searched[(size_t)k];
-            ids[(size_t)k] = grid_ids[q];
-            st[(size_t)2 * k] = starts[2 * q];
-            st[(size_t)2 * k + 1] = starts[2 * q + 1];
-            go[(size_t)2 * k] = goals[2 * q];
-            go[(size_t)2 * k + 1] = goals[2 * q + 1];
+            ids[(size_t)k] = req.grid_ids[q];
+            st[(size_t)2 * k] = req.starts[2 * q];
+            st[(size_t)2 * k + 1] = req.starts[2 * q + 1];
+            go[(size_t)2 * k] = req.goals[2 * q];
+            go[(size_t)2 * k + 1] = req.goals[2 * q + 1];
         }
-        d.mg_ids = ids.data();  // (the full batch's extents: the scratch is configured as the whole batch would configure it)
-        d.mg_W = mw;
-        d.mg_H = mh;
-        d.mg_cells = mc;
-        int rc = run_shard(h, d, st.data(), go.data(), hchoice, max_len);
-        if (!rc) rc = finish_search(h, d, hchoice, max_len);  // (waits: the pageable arrays above have been read)
-        d.mg_ids = nullptr;
+        BatchReq sub = req;  // (the full batch's extents: the scratch is configured as the whole batch would configure it)
+        sub.grid_ids = ids.data();
+        sub.starts = st.data();
+        sub.goals = go.data();
+        sub.nq = nsub;
+        int rc = run_shard(h, d, sub);
+        if (!rc) rc = finish_search(h, d, sub);  // (waits: the pageable arrays above have been read)
         if (rc) return rc;
         memcpy(sub_len.data(), d.h_len.p, (size_t)nsub * sizeof(int32_t));
         std::swap(d.d_len, d.s_len);  // the sub-batch's lengths and costs step aside for the full batch's
         std::swap(d.d_cost, d.s_cost);
     } else {
-        d.kernel_ms = 0;
-        d.launches = 0;
-        d.retried = 0;
-        d.nrun = 0;
-        d.waves_used = 0;
-        d.waves_short = false;
-        d.had_solo = false;
-        d.head_ms = d.batch_ms = 0;
+        d.run = DevCtx::RunStats();
     }
     if (nq == 0) return FXJPS_OK;
     // every length is known to the host (the stored codes; the sub-batch's, which finish_search brought back): the cells'
@@ -3563,15 +3576,11 @@ int replan_slots_assemble(fxjps* h, DevCtx& d, const int32_t* grid_ids, const in
     HIPCHK(h, d.h_offsets.ensure((size_t)nq + 1));
     HIPCHK(h, d.h_counters.ensure(64));
     if (total > 0) {
-        if (d.d_cells.ensure((size_t)total * 2) != hipSuccess) {  // (the search is over: its scratch can go)
-            (void)hipGetLastError();
-            release_pool0(d);
-            HIPCHK(h, d.d_cells.ensure((size_t)total * 2));
-        }
+        if (int rc = ensure_beside_pool0(h, d, d.d_cells, (size_t)total * 2)) return rc;  // (the search is over: its scratch can go)
         HIPCHK(h, d.h_cells.ensure((size_t)total * 2));
     }
     HIPCHK(h, hipMemcpyAsync(d.d_rs_src.p, d.h_rs_src.p, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
-    const fx::ReplanSrc R{d.d_rs_src.p, d.p_len.p, d.p_cost.p, d.p_offsets.p, d.p_cells.p, d.s_len.p, d.s_cost.p, d.d_path.p, max_len};
+    const fx::ReplanSrc R{d.d_rs_src.p, d.p_len.p, d.p_cost.p, d.p_offsets.p, d.p_cells.p, d.s_len.p, d.s_cost.p, d.d_path.p, req.max_len};
     hipLaunchKernelGGL(fx::k_replan_scan, dim3(1), dim3(1024), 0, d.stream, R, (long long)nq, d.d_len.p, d.d_cost.p, d.d_offsets.p);
     if (total > 0)
         hipLaunchKernelGGL(fx::k_replan_gather, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, d.stream, R, d.d_len.p, d.d_offsets.p, (long long)nq,
@@ -3586,8 +3595,7 @@ int replan_slots_assemble(fxjps* h, DevCtx& d, const int32_t* grid_ids, const in
     if (nsub == 0) memset(d.h_counters.p, 0, 64 * sizeof(unsigned long long));  // (nothing was searched)
     d.nq = nq;
     if (d.h_offsets.p[nq] != total) return fail(h, FXJPS_E_HIP, "the assembled batch has %lld cells, the host counted %lld", (long long)d.h_offsets.p[nq], total);
-    for (int64_t i = 0; i < nq; i++)  // internal codes must not leak
-        if (d.h_len.p[i] <= fx::QI_TABLE_FULL) d.h_len.p[i] = FXJPS_Q_CAPACITY;
+    hide_internal_codes(d);
     return FXJPS_OK;
 }
 }  // namespace
@@ -3603,16 +3611,10 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
         return fxjps_plan_batch_slots_csr(h, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, out_offsets, out_cells_xy, cells_capacity,
                                           out_len, out_cost, out_seconds_total);
     }
-    // the refusals of fxjps_plan_batch_slots_csr and of plan_core, all of them before the stored results are touched
+    // every refusal of fxjps_plan_batch_slots_csr, before the stored results are touched
     if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    if (nq > 0 && !grid_ids) return fail(h, FXJPS_E_ARG, "NULL grid_ids");
-    int mw = 1, mh = 1;
-    uint64_t mc = 1;
-    if (int rc = slots_batch_extents(h, grid_ids, nq, mw, mh, mc)) return rc;
-    if (nq < 0 || (nq > 0 && (!starts_xy || !goals_xy))) return fail(h, FXJPS_E_ARG, "bad query arrays");
-    if (hchoice != 1 && hchoice != 2) return fail(h, FXJPS_E_ARG, "hchoice must be 1 or 2 (the reference raises TypeError, jps1.py:188)");
-    if (max_path_len < 1 || max_path_len > (1 << 20)) return fail(h, FXJPS_E_ARG, "max_path_len out of range");
-    if (nq > 0x7FFFFFF0ll) return fail(h, FXJPS_E_ARG, "too many queries in one batch");
+    BatchReq req;
+    if (int rc = batch_request(h, true, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, 0, &req)) return rc;
     // ---- which queries are searched: plain compares of the arguments against the stored ones, before anything is queued
     static const bool allow_reuse = !(getenv("FXJPS_REPLAN_REUSE") && atoi(getenv("FXJPS_REPLAN_REUSE")) == 0);
     const bool stored = allow_reuse && h->rs_valid && h->rs_nq == nq && h->rs_hchoice == hchoice && h->rs_max_len == max_path_len;
@@ -3626,13 +3628,9 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
                            h->rs_goals[2 * i] == goals_xy[2 * q] && h->rs_goals[2 * i + 1] == goals_xy[2 * q + 1];
         if (!reuse) searched.push_back(q);
     }
-    // (as plan_core: until this batch is complete no earlier batch is "the last batch")
-    h->last_nq = 0;
-    h->last_slots = true;
-    h->last_on_host = false;
-    h->q_results_valid = h->rs_valid = false;
     DevCtx& d = h->devs[0];
-    int rc = replan_slots_assemble(h, d, grid_ids, starts_xy, goals_xy, nq, searched, hchoice, max_path_len, mw, mh, mc);
+    int rc = begin_batch(h, req);  // (a slots batch: nothing is queued, nothing can fail)
+    if (!rc) rc = replan_slots_assemble(h, d, req, searched);
     if (rc) {
         drain_all(h);  // before the error leaves the library
         d.nq = 0;      // (the context holds no result)
@@ -3640,10 +3638,10 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
     }
     collect_timing(h);
     h->timing.reused = nq - (int64_t)searched.size();
-    h->last_slots_W = mw;
-    h->last_slots_H = mh;
-    h->last_slot_ids.assign(grid_ids, grid_ids + nq);
-    h->rs_ids = h->last_slot_ids;
+    h->last.slots_W = req.W;
+    h->last.slots_H = req.H;
+    h->last.slot_ids.assign(grid_ids, grid_ids + nq);
+    h->rs_ids = h->last.slot_ids;
     h->rs_starts.assign(starts_xy, starts_xy + 2 * nq);
     h->rs_goals.assign(goals_xy, goals_xy + 2 * nq);
     h->rs_len.assign(d.h_len.p, d.h_len.p + nq);
@@ -3656,10 +3654,7 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
         for (int64_t q = 0; q < nq; q++) out_reused[q] = 1;
         for (int64_t q : searched) out_reused[q] = 0;
     }
-    rc = emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost);
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return rc;
+    return end_call(h, t0, out_seconds_total, emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost));
 }
 
 int fxjps_last_cells(fxjps_t* h, int32_t* out_cells_xy, int64_t cells_capacity) {
@@ -3697,7 +3692,7 @@ int fxjps_plan_batch(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_
     const double t0 = now_s();
     if (!h) return FXJPS_E_ARG;
     if (nq > 0 && (!out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
-    int rc = plan_core(h, starts_xy, goals_xy, nq, hchoice, max_path_len);
+    int rc = plan_resident(h, starts_xy, goals_xy, nq, hchoice, max_path_len);
     if (rc) return rc;
     for (auto& d : h->devs) {
         if (d.nq == 0) continue;
@@ -3711,9 +3706,7 @@ int fxjps_plan_batch(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_
                            (size_t)n * 2 * sizeof(int32_t));
             }
     }
-    h->timing.total_ms = (now_s() - t0) * 1e3;
-    if (out_seconds_total) *out_seconds_total = now_s() - t0;
-    return FXJPS_OK;
+    return end_call(h, t0, out_seconds_total, FXJPS_OK);
 }
 
 int fxjps_set_memory_share(fxjps_t* h, int32_t handles_per_device) {
@@ -3769,8 +3762,8 @@ int fxjps_last_timing_device(fxjps_t* h, int32_t ctx, int32_t* out_device, int64
     const DevCtx& d = h->devs[(size_t)ctx];
     if (out_device) *out_device = d.dev;
     if (out_nq) *out_nq = d.nq;
-    if (out_kernel_ms) *out_kernel_ms = d.kernel_ms;
-    if (out_waves) *out_waves = d.waves_used;
+    if (out_kernel_ms) *out_kernel_ms = d.run.kernel_ms;
+    if (out_waves) *out_waves = d.run.waves_used;
     return FXJPS_OK;
 }
 
@@ -3782,8 +3775,8 @@ int fxjps_waypoint_ccst_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, co
     if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "fxjps_waypoint_ccst_batch before fxjps_set_grid");
     if (nq < 0 || !origin || (nq > 0 && (!pos || !goal || !out_wp))) return fail(h, FXJPS_E_ARG, "bad waypoint arguments");
     if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
-    if (!cells_xy && nq != h->last_nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
-    if (!cells_xy && h->last_slots)  // (the line tests read the resident grid: those paths were planned on other grids)
+    if (!cells_xy && nq != h->last.nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last.nq, (long long)nq);
+    if (!cells_xy && h->last.slots)  // (the line tests read the resident grid: those paths were planned on other grids)
         return fail(h, FXJPS_E_ARG, "the last batch ran on grid slots: pass its paths explicitly");
     if (h->maps_stale) {  // (the grid is what the line test reads; deferred updates are queued on the same streams anyway)
         int rc = update_cells_async(h, nullptr, nullptr, 0, true);
@@ -3846,7 +3839,7 @@ int fxjps_waypoint_st_batch(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
         return fail(h, FXJPS_E_ARG, "bad waypoint arguments");
     if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
     if ((prev_wp != nullptr) != (prev_dim != nullptr)) return fail(h, FXJPS_E_ARG, "prev_wp and prev_dim go together");
-    if (!cells_xy && nq != h->last_nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
+    if (!cells_xy && nq != h->last.nq) return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last.nq, (long long)nq);
     if (nq == 0) return FXJPS_OK;
     WpPaths S;
     if (int rc = S.resolve(h, nq, offsets, cells_xy, false, [](int64_t) { return false; })) return rc;
@@ -3934,13 +3927,13 @@ static int wp_slots_call(fxjps_t* h, const char* fn, const TickIO* K, int64_t nq
     if ((cells_xy != nullptr) != (offsets != nullptr)) return fail(h, FXJPS_E_ARG, "offsets and cells_xy go together");
     if ((prev_wp != nullptr) != (prev_dim != nullptr)) return fail(h, FXJPS_E_ARG, "prev_wp and prev_dim go together");
     const bool resident = !cells_xy;
-    if (resident && !h->last_slots) return fail(h, FXJPS_E_ARG, "the last batch did not run on grid slots: pass the paths explicitly");
-    if (resident && (nq != h->last_nq || (int64_t)h->last_slot_ids.size() != nq))
-        return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last_nq, (long long)nq);
+    if (resident && !h->last.slots) return fail(h, FXJPS_E_ARG, "the last batch did not run on grid slots: pass the paths explicitly");
+    if (resident && (nq != h->last.nq || (int64_t)h->last.slot_ids.size() != nq))
+        return fail(h, FXJPS_E_ARG, "the last batch had %lld queries, not %lld", (long long)h->last.nq, (long long)nq);
     if (nq == 0) return FXJPS_OK;
     if (K && K->out_point && !K->home_xy) return fail(h, FXJPS_E_ARG, "query 0: out_point needs home_xy");
     // ---- everything the host can judge, for every query, before anything is queued
-    const int32_t* ids = grid_ids ? grid_ids : (resident ? h->last_slot_ids.data() : nullptr);
+    const int32_t* ids = grid_ids ? grid_ids : (resident ? h->last.slot_ids.data() : nullptr);
     int64_t n_st = 0;
     for (int64_t q = 0; q < nq; q++) {
         if (rule[q] != 0 && rule[q] != 1) return fail(h, FXJPS_E_ARG, "query %lld: rule %d is neither 0 (st) nor 1 (ccst)", (long long)q, (int)rule[q]);
