@@ -1231,7 +1231,7 @@ __global__ void k_ccl_update(const uint8_t* __restrict__ occ, int W, int H, cons
 // What the rules below need to know about the grid and the frame of ONE query (wave-uniform): the two batch kernels fill
 // it from their arguments (one grid, one frame for the batch), k_waypoint_slots from its query's record.
 struct WpView {
-    const uint8_t* occ;  // ccst: the grid [W][H] the line tests read, obstacle iff == 1
+    const uint8_t* occ;  // ccst: the grid [W][H] the line tests read, obstacle iff non-zero
     int32_t W, H;
     double reso, ox, oy;
     int32_t msx, msy;    // st: map_start
@@ -1244,7 +1244,7 @@ struct WpSel {
 };
 
 struct WaypointArgs {
-    const uint8_t* occ;      // resident grid [W][H], obstacle iff == 1
+    const uint8_t* occ;      // resident grid [W][H], obstacle iff non-zero
     int32_t W, H;
     const int32_t* cells;    // CSR paths: (x, y) pairs
     const long long* offsets;
@@ -1284,7 +1284,7 @@ __device__ __forceinline__ bool wp_line_is_free(const WpView& V, int ax, int ay,
             // `lb in obstacles of the sub-map` (:279): the sub-map is mapu[x0:x1, y0:y1], clipped to the array
             if (cx >= 0 && cx < x1 - x0 && cy >= 0 && cy < y1 - y0) {
                 const int gx = x0 + cx, gy = y0 + cy;
-                if (gx < V.W && gy < V.H && V.occ[(size_t)gx * V.H + gy] == 1) hit = true;
+                if (gx < V.W && gy < V.H && V.occ[(size_t)gx * V.H + gy] != 0) hit = true;
             }
         }
         RECONV();

@@ -70,7 +70,7 @@ static bool line_is_free(const uint8_t* occ, int32_t W, int32_t H, const int32_t
     bool any = false;
     for (int x = std::max(x0, 0); x < cx1 && !any; x++)
         for (int y = std::max(y0, 0); y < cy1; y++)
-            if (occ[(size_t)x * H + y] == 1) {
+            if (occ[(size_t)x * H + y] != 0) {
                 any = true;
                 break;
             }
@@ -86,7 +86,7 @@ static bool line_is_free(const uint8_t* occ, int32_t W, int32_t H, const int32_t
         const int cx = (int)x, cy = (int)std::nearbyint(slope * x) + (int)p1y;
         if (cx >= 0 && cx < x1 - x0 && cy >= 0 && cy < y1 - y0) {
             const int gx = x0 + cx, gy = y0 + cy;
-            if (gx < W && gy < H && occ[(size_t)gx * H + gy] == 1) return false;  // collide
+            if (gx < W && gy < H && occ[(size_t)gx * H + gy] != 0) return false;  // collide
         }
     }
     return true;

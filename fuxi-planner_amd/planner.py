@@ -150,7 +150,8 @@ class Planner(object):
         self._resident = occ  # (as_occ made a new array: nobody else holds it)
 
     def set_grid_occ(self, occ):
-        """Upload a uint8 [W][H] occupancy array (non-zero = obstacle)."""
+        """Upload a uint8 [W][H] occupancy array (non-zero = obstacle).  The bytes go to the device as they are; every reader
+        tests non-zero, so 1, 100 and 255 are the same obstacle."""
         occ = np.ascontiguousarray(occ, dtype=np.uint8)
         if occ.ndim != 2:
             raise ValueError("grid must be 2-D")
@@ -280,7 +281,8 @@ class Planner(object):
 
     def get_grid(self, context=0):
         """The resident uint8 [W][H] occupancy grid (e.g. the prepared map the node publishes); of a multi-device handle:
-        the bytes context `context` holds (equal on every device after the broadcast)."""
+        the bytes context `context` holds (equal on every device after the broadcast).  Non-zero = obstacle:
+        a grid the library prepared holds 0 / 1, of an uploaded one only the truth of a byte is to be relied on."""
         W, H = C.c_int32(), C.c_int32()
         self._chk(self._L.fxjps_get_grid_context(self._h, int(context), None, C.byref(W), C.byref(H)))
         out = np.empty((W.value, H.value), dtype=np.uint8)
@@ -383,7 +385,7 @@ class Planner(object):
         self._chk(self._L.fxjps_set_grid_slot(self._h, int(slot), None, 0, 0))
 
     def get_grid_slot(self, slot):
-        """The uint8 [W][H] occupancy grid of slot `slot` (1 = obstacle)."""
+        """The uint8 [W][H] occupancy grid of slot `slot` (non-zero = obstacle; 1 when set_grid_slot or a prepare call wrote it)."""
         W, H = C.c_int32(), C.c_int32()
         self._chk(self._L.fxjps_get_grid_slot(self._h, int(slot), None, C.byref(W), C.byref(H)))
         out = np.empty((W.value, H.value), dtype=np.uint8)

@@ -12,7 +12,13 @@
  * Conventions (same as the reference):
  *   - grid is W x H, indexed matrix[x][y], row-major with y contiguous
  *     (occ[x*H + y]); a cell is an obstacle iff its byte is non-zero (the shim
- *     converts with `matrix == 1`, jps1.py:20-29);
+ *     converts with `matrix == 1`, jps1.py:20-29).  Uploaded bytes are kept as
+ *     they are (fxjps_set_grid, fxjps_set_grid_device, fxjps_set_grid_slot,
+ *     fxjps_set_prior_map do not normalise) and every reader, on the device
+ *     and on the host, tests non-zero: 1, 100 and 255 are the same obstacle.
+ *     A cell the library itself writes (a prepare or refresh call) holds 0 or
+ *     1; fxjps_get_grid* hand back the bytes that are resident, so of an
+ *     uploaded grid only their truth (zero / non-zero) is to be relied on;
  *   - cells are (x, y) int32 pairs; a path is the list of JUMP POINTS from
  *     start to goal inclusive, exactly the list jps1.method returns
  *     (jps1.py:200-205), and its cost is the float64 it prints (jps1.py:207);
@@ -662,7 +668,7 @@ int fxjps_debug_qstat(fxjps_t* h, unsigned long long* out, int64_t nq);
  *
  * fxjps_waypoint_ccst: scripts/global_planner_ccst.py:487-544 with map_line_col (:258-283): points closer than
  * 1.5 to the vehicle are dropped, then every point whose neighbours see each other on the grid (occ, uint8 [W][H],
- * obstacle iff == 1: the matrix the search ran on); the waypoint is the 1.4 / 0.6 blend of the second and third
+ * obstacle iff non-zero, as everywhere: the matrix the search ran on); the waypoint is the 1.4 / 0.6 blend of the second and third
  * remaining points, or the goal; with end_occu == 1 (:541-544) the vehicle position becomes both waypoint and goal.
  * out_goal (3 doubles, optional) is global_goal after the block.  kept_cells (2 * n int32, optional) / n_kept
  * receive the remaining cells. */
