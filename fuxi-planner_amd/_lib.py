@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 810  # FXJPS_VERSION of include/fxjps.h
+VERSION = 820  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -24,7 +24,8 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_tick_outputs_slots", "fxjps_refresh_slots", "fxjps_debug_read_slot_context", "fxjps_replan_slots",
            "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size",
            "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size",
-           "fxjps_refresh_grid", "fxjps_refresh_occupancy_msg", "fxjps_last_refresh_cells", "fxjps_replan_frame_raw")
+           "fxjps_refresh_grid", "fxjps_refresh_occupancy_msg", "fxjps_last_refresh_cells", "fxjps_replan_frame_raw",
+           "fxjps_set_grid_slots", "fxjps_refresh_grid_slots", "fxjps_grid_job_size")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
@@ -43,6 +44,11 @@ class SlotJob(C.Structure):
     _fields_ = [("raw", C.c_void_p), ("slot", C.c_int32), ("layout", C.c_int32), ("W0", C.c_int32), ("H0", C.c_int32),
                 ("ifa", C.c_int32), ("variant", C.c_int32), ("start_xy", C.c_int32 * 2), ("goal_xy", C.c_int32 * 2),
                 ("W", C.c_int32), ("H", C.c_int32), ("map_d", C.c_int32 * 2), ("end_occu", C.c_int32), ("status", C.c_int32)]
+
+
+class GridJob(C.Structure):
+    """fxjps_grid_job_t: one prepared grid on its way into a grid slot (fxjps_set_grid_slots)."""
+    _fields_ = [("occ", C.POINTER(C.c_uint8)), ("slot", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("reserved", C.c_int32)]
 
 
 class WorldJob(C.Structure):
@@ -117,6 +123,9 @@ def load():
     L.fxjps_slot_job_size.restype = C.c_int
     if L.fxjps_slot_job_size() != C.sizeof(SlotJob):
         raise FxjpsError(E_ARG, "%s has a %d-byte slot job; this binding's is %d bytes: rebuild it" % (LIB_PATH, L.fxjps_slot_job_size(), C.sizeof(SlotJob)))
+    L.fxjps_grid_job_size.restype = C.c_int
+    if L.fxjps_grid_job_size() != C.sizeof(GridJob):
+        raise FxjpsError(E_ARG, "%s has a %d-byte grid job; this binding's is %d bytes: rebuild it" % (LIB_PATH, L.fxjps_grid_job_size(), C.sizeof(GridJob)))
     L.fxjps_slot_publish_size.restype = C.c_int
     if L.fxjps_slot_publish_size() != C.sizeof(SlotPublish):
         raise FxjpsError(E_ARG, "%s has a %d-byte slot publish job; this binding's is %d bytes: rebuild it"
@@ -197,6 +206,10 @@ def load():
     L.fxjps_prepare_slots.argtypes = [vp, C.POINTER(SlotJob), C.c_int32]
     L.fxjps_refresh_slots.restype = C.c_int
     L.fxjps_refresh_slots.argtypes = [vp, C.POINTER(SlotJob), C.c_int32, p_i32]
+    L.fxjps_set_grid_slots.restype = C.c_int
+    L.fxjps_set_grid_slots.argtypes = [vp, C.POINTER(GridJob), C.c_int32]
+    L.fxjps_refresh_grid_slots.restype = C.c_int
+    L.fxjps_refresh_grid_slots.argtypes = [vp, C.POINTER(GridJob), C.c_int32, p_i32]
     L.fxjps_set_prior_map.restype = C.c_int
     L.fxjps_set_prior_map.argtypes = [vp, C.c_int32, p_u8, C.c_int32, C.c_int32]
     L.fxjps_get_prior_map.restype = C.c_int

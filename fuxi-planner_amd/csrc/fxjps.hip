@@ -191,6 +191,7 @@ struct DevCtx : GridBufs {
     DBuf<int32_t> d_grid_ids;
     // fxjps_prepare_slots / fxjps_refresh_slots: the call's staged input (fx::SlotTable | the 256 slot descriptors | the raw
     // maps | a world-frame call's fx::WorldSrcDev records | a refresh's `changed` words), pinned and on the device, and the per-job results of k_slots_goal
+    // (fxjps_set_grid_slots / fxjps_refresh_grid_slots: the same, prepared grids where the raws are, and only the words come back)
     HBuf<uint8_t> h_slots_in;
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
@@ -2838,6 +2839,28 @@ struct WorldCall {
 constexpr size_t SLOTS_IN_DESC = (sizeof(fx::SlotTable) + 15) & ~(size_t)15;
 constexpr size_t SLOTS_IN_RAWS = (SLOTS_IN_DESC + sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS + 15) & ~(size_t)15;
 
+// Job j's rows of the table: the blocks derive_maps would launch for this grid alone (the fused build: at most 2^18 cells;
+// a larger grid has no blocks in the build launches), behind the blocks of the first launch, each of which covers
+// `first_cells` cells of the grid.  T.job[j].G is set.  -> whether the grid takes the fused build.
+bool slot_job_blocks(fx::SlotTable& T, int j, const GridBufs& g, long long first_cells, uint32_t at[fx::SL_LAUNCHES]) {
+    fx::SlotJobDev& J = T.job[j];
+    const long long ncell = (long long)g.W * g.H, npad = (long long)g.PW * g.PH;
+    const bool fused = ncell <= (1ll << 18);
+    J.nb_rows = (uint32_t)(((long long)g.PW * g.WORDS + 3) / 4);
+    J.nb_cols = (uint32_t)(((long long)g.PH * g.WORDS + 3) / 4);
+    J.nb_ci = (uint32_t)((npad + 255) / 256);
+    J.nb_diag = (uint32_t)((4ll * J.G.DLINES * g.WORDS + 15) / 16);
+    const uint32_t nb_cell = (uint32_t)((ncell + 255) / 256), nb_flat = (uint32_t)((ncell + 1023) / 1024);
+    const uint32_t cnt[fx::SL_LAUNCHES] = {(uint32_t)((ncell + first_cells - 1) / first_cells), fused ? J.nb_rows + J.nb_cols + nb_cell : 0u,
+                                           fused ? J.nb_ci + nb_cell : 0u, fused ? J.nb_diag + nb_flat : 0u,
+                                           fused ? (uint32_t)((npad * 8 + 255) / 256) : 0u};
+    for (int l = 0; l < fx::SL_LAUNCHES; l++) {
+        T.first[l][j] = at[l];
+        at[l] += cnt[l];
+    }
+    return fused;
+}
+
 // One context's part of fxjps_prepare_slots / fxjps_refresh_slots: everything is queued on d.stream behind ONE copy in, and
 // waited for ONCE, whatever n is.  The results are left in d.h_slots_res.  refresh: a job whose slot holds a grid of the
 // prepared extents is compared with it byte by byte while it is gathered, and built only if a byte differed (DESIGN.md
@@ -2905,21 +2928,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
         } else {
             memcpy(d.h_slots_in.p + p.raw_off, jb.raw, (size_t)jb.W0 * (size_t)jb.H0);
         }
-        // the blocks derive_maps would launch for this grid alone (the fused build: at most 2^18 cells)
-        const long long ncell = p.W1 * p.H1, npad = (long long)g.PW * g.PH;
-        const bool fused = ncell <= (1ll << 18);
-        any_large = any_large || !fused;
-        J.nb_rows = (uint32_t)(((long long)g.PW * g.WORDS + 3) / 4);
-        J.nb_cols = (uint32_t)(((long long)g.PH * g.WORDS + 3) / 4);
-        J.nb_ci = (uint32_t)((npad + 255) / 256);
-        J.nb_diag = (uint32_t)((4ll * G.DLINES * g.WORDS + 15) / 16);
-        const uint32_t nb_cell = (uint32_t)((ncell + 255) / 256), nb_flat = (uint32_t)((ncell + 1023) / 1024);
-        const uint32_t cnt[fx::SL_LAUNCHES] = {nb_cell, fused ? J.nb_rows + J.nb_cols + nb_cell : 0u, fused ? J.nb_ci + nb_cell : 0u,
-                                               fused ? J.nb_diag + nb_flat : 0u, fused ? (uint32_t)((npad * 8 + 255) / 256) : 0u};
-        for (int l = 0; l < fx::SL_LAUNCHES; l++) {
-            T.first[l][j] = at[l];
-            at[l] += cnt[l];
-        }
+        any_large = !slot_job_blocks(T, j, g, 256, at) || any_large;
     }
     for (int l = 0; l < fx::SL_LAUNCHES; l++) T.first[l][n] = at[l];
     memcpy(d.h_slots_in.p + SLOTS_IN_DESC, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS);
@@ -3035,6 +3044,121 @@ int fxjps_prepare_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n) { return 
 
 int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept) {
     return slots_call(h, jobs, n, true, out_kept, "fxjps_refresh_slots");
+}
+
+// ------------------------------------------------------------------ many prepared grids into grid slots, one call
+int fxjps_grid_job_size(void) { return (int)sizeof(fxjps_grid_job_t); }
+
+namespace {
+// One context's part of fxjps_set_grid_slots / fxjps_refresh_grid_slots: prepare_slots_on with the
+// copy launch in place of the gather, no goal launch, and the grids where the raws were (off[j], multiples of 16 bytes).
+// refresh: the `changed` words travel in behind the grids and come back into d.h_slots_res, one word per job.
+int grid_slots_on(fxjps* h, DevCtx& d, const fxjps_grid_job_t* jobs, int n, const std::vector<size_t>& off, size_t in_bytes, bool refresh) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    if (int e = ensure_slot_tables(h, d)) return e;
+    const size_t flags_off = in_bytes;
+    if (refresh) in_bytes += (size_t)n * sizeof(uint32_t);
+    HIPCHK(h, d.h_slots_in.ensure(in_bytes));
+    HIPCHK(h, d.d_slots_in.ensure(in_bytes));
+    if (refresh) HIPCHK(h, d.h_slots_res.ensure((size_t)n));
+    fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
+    uint32_t* h_changed = reinterpret_cast<uint32_t*>(d.h_slots_in.p + flags_off);
+    uint32_t* d_changed = reinterpret_cast<uint32_t*>(d.d_slots_in.p + flags_off);
+    uint32_t at[fx::SL_LAUNCHES] = {};
+    bool any_large = false;
+    for (int j = 0; j < n; j++) {
+        const fxjps_grid_job_t& jb = jobs[j];
+        GridBufs& g = d.slots[(size_t)jb.slot];
+        const size_t ncell = (size_t)jb.W * (size_t)jb.H;
+        // (this context's copy of the slot, as fxjps_refresh_slots judges it: a grid beyond the fused build always builds)
+        const bool compare = refresh && g.W == jb.W && g.H == jb.H && ncell <= ((size_t)1 << 18);
+        d.h_slot_desc[(size_t)jb.slot] = GridDev{};
+        int e = alloc_grid_bufs(h, g, jb.W, jb.H);  // (a slot that has room allocates nothing)
+        if (e) return e;
+        fx::SlotJobDev& J = T.job[j];
+        J = fx::SlotJobDev{};
+        J.G = d.h_slot_desc[(size_t)jb.slot] = grid_of(g);
+        J.occ = g.occ.p;
+        J.raw = d.d_slots_in.p + off[(size_t)j];
+        J.W0 = jb.W;
+        J.H0 = jb.H;
+        J.compare = compare ? 1 : 0;
+        if (refresh) h_changed[j] = compare ? 0u : 1u;
+        memcpy(d.h_slots_in.p + off[(size_t)j], jb.occ, ncell);
+        any_large = !slot_job_blocks(T, j, g, fx::SLOT_COPY_BLOCK, at) || any_large;
+    }
+    for (int l = 0; l < fx::SL_LAUNCHES; l++) T.first[l][n] = at[l];
+    memcpy(d.h_slots_in.p + SLOTS_IN_DESC, d.h_slot_desc.data(), sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS);
+    HIPCHK(h, hipMemcpyAsync(d.d_slots_in.p, d.h_slots_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+    const fx::SlotTable* dT = reinterpret_cast<const fx::SlotTable*>(d.d_slots_in.p);
+    using StageFn = void (*)(const fx::SlotTable*, int, const uint32_t*);
+    static const StageFn stage[2][4] = {
+        {fx::k_slots_stage<fx::SL_BUILD_1, false>, fx::k_slots_stage<fx::SL_BUILD_2, false>, fx::k_slots_stage<fx::SL_BUILD_3, false>, fx::k_slots_stage<fx::SL_JD, false>},
+        {fx::k_slots_stage<fx::SL_BUILD_1, true>, fx::k_slots_stage<fx::SL_BUILD_2, true>, fx::k_slots_stage<fx::SL_BUILD_3, true>, fx::k_slots_stage<fx::SL_JD, true>}};
+    uint32_t* dC = refresh ? d_changed : nullptr;
+    hipLaunchKernelGGL(refresh ? fx::k_slots_copy<true> : fx::k_slots_copy<false>, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, dC);
+    if (at[fx::SL_BUILD_1] > 0)
+        for (int l = fx::SL_BUILD_1; l <= fx::SL_JD; l++)
+            hipLaunchKernelGGL(stage[refresh ? 1 : 0][l - fx::SL_BUILD_1], dim3(at[l]), dim3(l == fx::SL_BUILD_3 ? 1024 : 256), 0, d.stream, dT, n,
+                               (const uint32_t*)dC);
+    HIPCHK(h, hipGetLastError());
+    if (any_large)  // (grids beyond the fused build: their maps one by one, as fxjps_set_grid_slot builds them)
+        for (int j = 0; j < n; j++)
+            if ((long long)jobs[j].W * jobs[j].H > (1ll << 18)) {
+                int e = derive_maps(h, d, true, &d.slots[(size_t)jobs[j].slot]);
+                if (e) return e;
+            }
+    HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p, d.h_slots_in.p + SLOTS_IN_DESC, sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice, d.stream));
+    if (refresh) HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d_changed, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    return FXJPS_OK;
+}
+
+// fxjps_set_grid_slots (refresh false) and fxjps_refresh_grid_slots: the checks, the call on every context and the
+// generations are the same code.
+int grid_slots_call(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what) {
+    if (int rc = jobs_call_check(h, jobs, n, what)) return rc;
+    if (refresh && n > 0 && !out_kept) return fail(h, FXJPS_E_ARG, "job 0: NULL out_kept");
+    // everything the host can judge, for every job, before anything is queued or any slot is touched
+    std::vector<size_t> off((size_t)n);
+    std::vector<int> named(FXJPS_MAX_GRID_SLOTS, -1);
+    size_t in_bytes = SLOTS_IN_RAWS;
+    for (int j = 0; j < n; j++) {
+        const fxjps_grid_job_t& jb = jobs[j];
+        if (jb.slot < 0 || jb.slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "job %d: slot %d is not in 0 .. %d", j, (int)jb.slot, FXJPS_MAX_GRID_SLOTS - 1);
+        if (named[(size_t)jb.slot] >= 0) return fail(h, FXJPS_E_ARG, "job %d: slot %d is already named by job %d", j, (int)jb.slot, named[(size_t)jb.slot]);
+        named[(size_t)jb.slot] = j;
+        if (!jb.occ) return fail(h, FXJPS_E_ARG, "job %d: NULL occ (fxjps_set_grid_slot releases a slot)", j);
+        if (jb.W < 1 || jb.H < 1 || jb.W > 8190 || jb.H > 8190) return fail(h, FXJPS_E_ARG, "job %d: grid %dx%d must be 1..8190 cells a side", j, (int)jb.W, (int)jb.H);
+        if (jb.reserved != 0) return fail(h, FXJPS_E_ARG, "job %d: reserved is %d, not 0", j, (int)jb.reserved);
+        off[(size_t)j] = in_bytes;
+        in_bytes += ((size_t)jb.W * (size_t)jb.H + 15) & ~(size_t)15;
+    }
+    if (n == 0) return FXJPS_OK;
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grid_slots_on(h, h->devs[r], jobs, n, off, in_bytes, refresh); });
+    if (rc) {
+        drain_all(h);
+        for (int j = 0; j < n; j++) {  // (slots of a call that failed on one context are released on all of them)
+            release_slot_everywhere(h, jobs[j].slot);
+            h->slot_gen[(size_t)jobs[j].slot]++;
+        }
+        (void)hipGetLastError();
+        return rc;
+    }
+    const int32_t* words = h->devs[0].h_slots_res.p;
+    for (int j = 0; j < n; j++) {
+        const bool kept = refresh && words[j] == 0;  // (no byte of context 0's copy differed: nothing was built)
+        if (out_kept) out_kept[j] = kept ? 1 : 0;
+        if (!kept) h->slot_gen[(size_t)jobs[j].slot]++;
+    }
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_set_grid_slots(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n) { return grid_slots_call(h, jobs, n, false, nullptr, "fxjps_set_grid_slots"); }
+
+int fxjps_refresh_grid_slots(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n, int32_t* out_kept) {
+    return grid_slots_call(h, jobs, n, true, out_kept, "fxjps_refresh_grid_slots");
 }
 
 // ------------------------------------------------------------------ the same two calls from world-frame jobs

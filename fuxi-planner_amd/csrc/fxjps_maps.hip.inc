@@ -971,6 +971,51 @@ __global__ __launch_bounds__(L == SL_BUILD_3 ? 1024 : 256) void k_slots_stage(co
         derive_jd_item(G, const_cast<uint16_t*>(G.jd), DiagRange{1, 0, 0, 0, 0}, (long long)b * 256 + threadIdx.x);
 }
 
+// ---- Many PREPARED grids into grid slots in one call (fxjps_set_grid_slots / fxjps_refresh_grid_slots, DESIGN.md section
+// 3.17): the job's bytes are the slot's bytes, so in place of the gather there is a copy, and there is no goal launch.  The
+// table is the family's: SlotJobDev::raw is the job's grid inside the staged input, G.W x G.H its extents, and the row
+// SlotTable::first[SL_PREPARE] deals SLOT_COPY_BLOCK cells to a block (not the gather's 256).  Both sides are plain streams
+// of bytes -- the staged grids begin at multiples of 16 bytes of one allocation, occ is the start of an allocation of its
+// own -- so a lane moves 16 bytes with one load and one store; the last lane of a job whose cell count is no multiple of 16
+// moves its 1 .. 15 bytes one by one and touches nothing behind the grid.
+//   REFRESH: as in the gather.  A job marked `compare` reads the slot's 16 bytes beside the staged ones and stores only a
+// piece in which a byte differs (bytes, not truthiness); every thread of the block reaches the barrier, one raises the
+// job's word.  A job not marked is stored whole and its word stays at the host's 1.
+constexpr int SLOT_COPY_LANE = 16, SLOT_COPY_BLOCK = 256 * SLOT_COPY_LANE;
+template <bool REFRESH>
+__global__ __launch_bounds__(256) void k_slots_copy(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed) {
+    const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
+    const SlotJobDev& J = T->job[j];
+    const uint8_t* __restrict__ src = J.raw;
+    uint8_t* __restrict__ occ = J.occ;
+    const long long ncell = (long long)J.G.W * J.G.H;
+    const long long i = ((long long)(blockIdx.x - T->first[SL_PREPARE][j]) * blockDim.x + threadIdx.x) * SLOT_COPY_LANE;
+    const bool whole = i + SLOT_COPY_LANE <= ncell;                    // a full piece
+    const int tail = !whole && i < ncell ? (int)(ncell - i) : 0;       // ... or the grid's last 1 .. 15 bytes
+    const bool compare = REFRESH && J.compare != 0;                    // (block-uniform)
+    bool differs = false;
+    if (whole) {
+        const uint4 v = *reinterpret_cast<const uint4*>(src + i);
+        differs = true;
+        if (compare) {
+            const uint4 o = *reinterpret_cast<const uint4*>(occ + i);
+            differs = ((v.x ^ o.x) | (v.y ^ o.y) | (v.z ^ o.z) | (v.w ^ o.w)) != 0u;
+        }
+        if (differs) *reinterpret_cast<uint4*>(occ + i) = v;
+    } else {
+        for (int k = 0; k < tail; k++) {
+            const uint8_t v = src[i + k];
+            const bool d = !compare || occ[i + k] != v;
+            if (d) occ[i + k] = v;
+            differs = differs || d;
+        }
+    }
+    if constexpr (REFRESH) {
+        if (!compare) return;  // (the whole block: its job builds whatever the bytes are)
+        if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+    }
+}
+
 // ---- The ccst node's crop in front of the world-frame calls (fxjps_prepare_slots_cropped, DESIGN.md section 3.15):
 // remove_zero_rowscols (global_planner_ccst.py:36-63) cuts every map message down to the box spanned by its non-zero
 // cells and the vehicle's cell.  Two launches over all jobs of the call, queued back to back: k_crop_bounds reduces every

@@ -418,6 +418,40 @@ class Planner(object):
         del keep
         return [o + (bool(k),) for o, k in zip(self._slot_outs(arr, n), kept[:n])]
 
+    def set_grid_slots(self, jobs):
+        """set_grid_slot for many slots in ONE call (fxjps_set_grid_slots): jobs is a list of (slot, matrix), matrix[x][y]
+        with an obstacle iff == 1, as set_grid_slot takes it.  Afterwards every named slot is what set_grid_slot would have
+        left; the launches and host waits of the call do not depend on len(jobs)."""
+        arr, keep = self._grid_jobs(jobs)  # (keep: the grids, alive until the call has returned)
+        self._chk(self._L.fxjps_set_grid_slots(self._h, arr, len(keep)))
+        del keep
+
+    def refresh_grid_slots(self, jobs):
+        """set_grid_slots for the tick after (fxjps_refresh_grid_slots): the same slots afterwards, but a slot that already
+        holds a grid of the same extents and bytes keeps its maps and its generation, so replan_slots does not search its
+        unchanged queries again.  -> one bool per job, kept; False: the slot was built (it was empty, its extents or a byte
+        differed, or the grid has more than 2^18 cells)."""
+        arr, keep = self._grid_jobs(jobs)
+        n = len(keep)
+        kept = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.fxjps_refresh_grid_slots(self._h, arr, n, _lib.ptr(kept, C.c_int32)))
+        del keep
+        return [bool(k) for k in kept[:n]]
+
+    @staticmethod
+    def _grid_jobs(jobs):
+        """-> the fxjps_grid_job_t array of set_grid_slots' jobs, and the grids it points into."""
+        jobs = list(jobs)
+        arr = (_lib.GridJob * max(len(jobs), 1))()
+        keep = []
+        for j, (slot, matrix) in zip(arr, jobs):
+            occ = as_occ(matrix)
+            if occ.ndim != 2:
+                raise ValueError("grid must be 2-D")
+            keep.append(occ)
+            j.occ, j.slot, j.W, j.H = _lib.ptr(occ, C.c_uint8), int(slot), occ.shape[0], occ.shape[1]
+        return arr, keep
+
     @staticmethod
     def _job_raw(j, slot, raw, ifa, variant):
         """Fill what fxjps_slot_job_t and fxjps_world_job_t share -- raw, layout, W0, H0, slot, ifa, variant -- from a job's

@@ -105,8 +105,11 @@ typedef struct fxjps fxjps_t;
  *        fxjps_last_refresh_cells, fxjps_replan_frame_raw (fxjps_replan_frame from a whole raw map).
  *   810  fxjps_debug_live_bytes (the bytes of device and of pinned host memory that the process's handles hold; every
  *        buffer, stream and event of a handle is owned by a member that frees it, so fxjps_destroy has no list to keep).
+ *   820  fxjps_set_grid_slots, fxjps_refresh_grid_slots (fxjps_set_grid_slot for many slots in one call whose launches and
+ *        host waits do not depend on n; the refresh form keeps the maps and the generation of a slot whose bytes did not
+ *        change), fxjps_grid_job_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 810
+#define FXJPS_VERSION 820
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -368,6 +371,34 @@ int fxjps_slot_job_size(void); /* sizeof(fxjps_slot_job_t) as the library was bu
  * on every context against that context's own copy; out_kept reports context 0's.  out_kept may be NULL; it is not
  * written when the call is refused (nor for n = 0). */
 int fxjps_refresh_slots(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, int32_t* out_kept);
+/* ---- Many PREPARED grids into grid slots in one call (version 820): fxjps_set_grid_slot for a host that holds the
+ * matrices its planner reads -- N vehicles that each end a tick with jps1.method(matrix, ...) -- and nothing to pad or
+ * dilate.  Afterwards every named slot is exactly what fxjps_set_grid_slot(h, slot, occ, W, H) would have left, on every
+ * context: the bytes as handed in (a 7 stays a 7), the six derived arrays, the descriptor, and the slot's generation
+ * moved.  Per context one staged copy carries the job table and all grids in, one launch moves every job's bytes into
+ * its slot, the four build launches of fxjps_prepare_slots build all maps, and the host waits once: none of these counts
+ * depends on n.  Grids of more than 2^18 cells are copied with the others and built one by one behind them.
+ *   Whole-call errors (FXJPS_E_ARG before any slot, generation or stored result is touched, fxjps_last_error names the
+ * job): n outside 0 .. FXJPS_MAX_GRID_SLOTS, a slot out of range or named twice, NULL occ (a slot is released by
+ * fxjps_set_grid_slot), W or H outside 1 .. 8190, reserved != 0, a rank handle (fxjps_create_rank, world > 1).  n == 0
+ * is FXJPS_OK and does nothing.  The resident grid and slots not named are not touched. */
+typedef struct fxjps_grid_job {
+    const uint8_t* occ; /* in: [W][H], y contiguous, non-zero = obstacle; the bytes are kept as they are */
+    int32_t slot;       /* in: 0 .. FXJPS_MAX_GRID_SLOTS - 1 */
+    int32_t W, H;       /* in: 1 .. 8190 */
+    int32_t reserved;   /* in: 0 */
+} fxjps_grid_job_t;
+int fxjps_set_grid_slots(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n);
+/* fxjps_set_grid_slots for the tick after, by the rule of fxjps_refresh_slots: the same checks, the same slots and bytes
+ * afterwards, but a job whose slot already holds a grid of the same extents and the same value in every byte (bytes are
+ * compared, not truthiness) keeps the slot's maps AND its generation -- so fxjps_replan_slots hands back the stored paths
+ * of that slot's unchanged queries -- and reports out_kept[j] = 1.  Every other job is built, its generation moves, and
+ * it reports 0: an empty slot, other extents, any byte that differs, and every grid of more than 2^18 cells.  The
+ * compare happens inside the copy launch; the n answers travel in behind the grids and come back in one copy of their
+ * own.  A handle with several contexts compares on every context against its own copy; out_kept reports context 0's.
+ * NULL out_kept with n > 0 is refused like the errors above; out_kept is not written by a refused call. */
+int fxjps_refresh_grid_slots(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n, int32_t* out_kept);
+int fxjps_grid_job_size(void); /* sizeof(fxjps_grid_job_t) as the library was built (cf. fxjps_slot_job_size) */
 /* ---- The same two calls from world-frame jobs (version 780): what each node does in front of the preparation on every
  * tick (global_planner_st.py:210-227 / global_planner_ccst.py:395-412) moves into the call.
  *   Prior maps: a map known before the flight (st:176-187), uploaded once and held on every context like a slot (host
