@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 820  # FXJPS_VERSION of include/fxjps.h
+VERSION = 830  # FXJPS_VERSION of include/fxjps.h
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -25,7 +25,8 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_set_prior_map", "fxjps_get_prior_map", "fxjps_prepare_slots_world", "fxjps_refresh_slots_world", "fxjps_world_job_size",
            "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size",
            "fxjps_refresh_grid", "fxjps_refresh_occupancy_msg", "fxjps_last_refresh_cells", "fxjps_replan_frame_raw",
-           "fxjps_set_grid_slots", "fxjps_refresh_grid_slots", "fxjps_grid_job_size")
+           "fxjps_set_grid_slots", "fxjps_refresh_grid_slots", "fxjps_grid_job_size",
+           "fxjps_set_slot_reuse", "fxjps_debug_slot_tiles", "fxjps_debug_slot_read_sets")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
@@ -232,6 +233,12 @@ def load():
     L.fxjps_debug_live_bytes.argtypes = [p_i64, p_i64]
     L.fxjps_debug_read_sets.restype = C.c_int
     L.fxjps_debug_read_sets.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, p_i32]
+    L.fxjps_set_slot_reuse.restype = C.c_int
+    L.fxjps_set_slot_reuse.argtypes = [vp, C.c_int32]
+    L.fxjps_debug_slot_tiles.restype = C.c_int
+    L.fxjps_debug_slot_tiles.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), p_i32, p_i32]
+    L.fxjps_debug_slot_read_sets.restype = C.c_int
+    L.fxjps_debug_slot_read_sets.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, p_i32, p_i32]
     L.fxjps_last_cells.restype = C.c_int
     L.fxjps_last_cells.argtypes = [vp, p_i32, C.c_int64]
     L.fxjps_last_timing.restype = C.c_int

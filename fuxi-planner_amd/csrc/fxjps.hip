@@ -181,7 +181,7 @@ struct DevCtx : GridBufs {
     int solo_timeouts_run = 0;          // ... in a row (3: no more head launches on this device; a cold first launch of a
                                         // kernel -- its code object is loaded then -- is a lone timeout and means nothing)
     size_t cells_bound = 0;             // bytes the batch in progress may still allocate for its packed paths
-    bool lds_attr_done[12] = {};        // k_search instantiations whose dynamic-LDS limit has been raised on this device
+    bool lds_attr_done[16] = {};        // k_search instantiations whose dynamic-LDS limit has been raised on this device
     Event ev0, ev1, ev_solo0, ev_solo1;
     Event ev_hd0, ev_hd1, ev_bt0, ev_bt1;  // around the head launch / the batch's launch alone
     // grid slots (fxjps_set_grid_slot): their maps, and their descriptors on the device (what k_search<.., .., .., true> reads)
@@ -195,6 +195,7 @@ struct DevCtx : GridBufs {
     HBuf<uint8_t> h_slots_in;
     DBuf<uint8_t> d_slots_in;
     HBuf<int32_t> h_slots_res;
+    size_t slot_tiles_at = 0;  // the last slots call's tile records begin at this word of h_slots_res (fxjps_set_slot_reuse(1))
     DBuf<int32_t> d_slots_res;
     // fxjps_prepare_slots_cropped / fxjps_refresh_slots_cropped, first phase: the staged input (fx::CropTable | n box records
     // | the messages), the windows k_crop_window cuts out of them (what the second phase's gather reads as its raws), and
@@ -348,6 +349,29 @@ struct fxjps {
     bool rs_valid = false;
     // per-slot generation: bumped by every call that writes a slot's bytes or maps on any context (a release included)
     uint64_t slot_gen[FXJPS_MAX_GRID_SLOTS] = {};
+    // fxjps_set_slot_reuse.  Mode 1: per slot, the read-set tiles that the compared refresh jobs
+    // since generation `base` found changed (FrameTiles' layout); valid while every write of the slot since then was such a
+    // job.  Per query of the stored fxjps_replan_slots results, the read set of the search that produced it (rs_have: it has
+    // one -- a query that ended without a search has none).
+    struct SlotTiles {
+        bool valid = false;
+        uint64_t base = 0;
+        unsigned long long D[128] = {};  // DX[64] (a bit per x tile), then DY[64]
+    };
+    int slot_reuse = 0;
+    std::vector<SlotTiles> slot_tiles = std::vector<SlotTiles>(FXJPS_MAX_GRID_SLOTS);
+    std::vector<unsigned long long> rs_read;
+    std::vector<uint8_t> rs_have;
+    // a slot is written by anything but a compared refresh job: its generation moves and its tile record is void
+    void bump_slot(int32_t slot) {
+        slot_gen[(size_t)slot]++;
+        slot_tiles[(size_t)slot].valid = false;
+    }
+    // ... by a compared refresh job whose changed bytes touch the tiles of `rec`
+    void mark_slot(int32_t slot, const unsigned long long* rec) {
+        slot_gen[(size_t)slot]++;
+        for (int t = 0; t < 128; t++) slot_tiles[(size_t)slot].D[t] |= rec[t];
+    }
     // RCCL (only for n_dev > 1), resolved with dlopen so that a single-GPU
     // deployment does not need librccl at load time
     void* rccl = nullptr;
@@ -831,22 +855,24 @@ int ensure_pool(fxjps* h, DevCtx& d, const BatchReq& req, int pool, uint32_t wan
 }
 
 // The one table of k_search instantiations: heuristic x read-set recording (fxjps_replan_frame) x table indexed by the
-// cell, and heuristic x table indexed by the cell with a grid per query (a slots batch: never with read-set recording,
-// fn == nullptr).  index: the instantiation's place in DevCtx::lds_attr_done.
+// cell, heuristic x table indexed by the cell with a grid per query (a slots batch), and the same with read-set recording
+// (fxjps_replan_slots under fxjps_set_slot_reuse(1)).  index: the instantiation's place in DevCtx::lds_attr_done.
 using SearchFn = void (*)(SearchArgs);
 struct SearchKernel {
     SearchFn fn;
     int index;
 };
 SearchKernel search_kernel(int hchoice, bool track, bool direct, bool grid_per_query) {
-    static const SearchFn table[12] = {fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>,
+    static const SearchFn table[16] = {fx::k_search<1, false, false, false>, fx::k_search<1, false, true, false>,
                                        fx::k_search<1, true, false, false>,  fx::k_search<1, true, true, false>,
                                        fx::k_search<2, false, false, false>, fx::k_search<2, false, true, false>,
                                        fx::k_search<2, true, false, false>,  fx::k_search<2, true, true, false>,
                                        fx::k_search<1, false, false, true>,  fx::k_search<1, false, true, true>,
-                                       fx::k_search<2, false, false, true>,  fx::k_search<2, false, true, true>};
-    if (grid_per_query && track) return SearchKernel{nullptr, -1};
-    const int h2 = hchoice == 1 ? 0 : 1, index = (grid_per_query ? 8 + 2 * h2 : 4 * h2 + (track ? 2 : 0)) + (direct ? 1 : 0);
+                                       fx::k_search<2, false, false, true>,  fx::k_search<2, false, true, true>,
+                                       fx::k_slot_reads_search<1, false>,    fx::k_slot_reads_search<1, true>,
+                                       fx::k_slot_reads_search<2, false>,    fx::k_slot_reads_search<2, true>};
+    const int h2 = hchoice == 1 ? 0 : 1,
+              index = (grid_per_query ? (track ? 12 : 8) + 2 * h2 : 4 * h2 + (track ? 2 : 0)) + (direct ? 1 : 0);
     return SearchKernel{table[index], index};
 }
 
@@ -928,7 +954,6 @@ int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint
     HIPCHK(h, hipEventRecord(d.ev0, d.stream));
     {
         const SearchKernel k = search_kernel(req.hchoice, track, c.direct_ly > 0, req.slots);
-        if (!k.fn) return fail(h, FXJPS_E_ARG, "read-set recording on grid slots");
         const SearchFn fn = k.fn;
         static const size_t pad = 36u << 10;  // 66 .. 74 KB of the block's own + this: no second block fits the CU's 160 KB
         if (nsolo != 0u || live_main != 0u) {
@@ -1061,7 +1086,10 @@ int run_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     if (req.track()) {  // read-set bitmaps: 128 x u64 per query, zero for queries that never searched
         const size_t had = d.d_qread.cap;
         HIPCHK(h, d.d_qread.ensure((size_t)nq * 128));
-        if (d.d_qread.cap != had) HIPCHK(h, hipMemsetAsync(d.d_qread.p, 0, d.d_qread.cap * sizeof(unsigned long long), d.stream));
+        if (d.d_qread.cap != had)
+            HIPCHK(h, hipMemsetAsync(d.d_qread.p, 0, d.d_qread.cap * sizeof(unsigned long long), d.stream));
+        else if (req.slots)  // (a sub-batch of fxjps_replan_slots: row k was another query's the call before)
+            HIPCHK(h, hipMemsetAsync(d.d_qread.p, 0, (size_t)nq * 128 * sizeof(unsigned long long), d.stream));
     }
     if (d.run.nrun == 0) return FXJPS_OK;  // every result of the previous frame is still valid
     DBG("run_shard nq=%lld: inputs queued", (long long)nq);
@@ -2764,7 +2792,7 @@ int fxjps_set_grid_slot(fxjps_t* h, int32_t slot, const uint8_t* occ, int32_t W,
     if (slot < 0 || slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "slot %d is not in 0 .. %d", (int)slot, FXJPS_MAX_GRID_SLOTS - 1);
     if (occ && (W < 1 || H < 1 || W > 8190 || H > 8190)) return fail(h, FXJPS_E_ARG, "grid must be 1..8190 cells a side");
     if (int rr = refuse_on_rank_handle(h, "fxjps_set_grid_slot")) return rr;
-    h->slot_gen[(size_t)slot]++;  // (whatever becomes of the call: the slot's bytes are about to be written or released)
+    h->bump_slot(slot);  // (whatever becomes of the call: the slot's bytes are about to be written or released)
     // Every context gets its own copy from the host (no collective), builds the maps on its own streams, and refreshes its
     // table of slot descriptors.  The resident grid and its update state are not touched.
     int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int {
@@ -2867,18 +2895,32 @@ bool slot_job_blocks(fx::SlotTable& T, int j, const GridBufs& g, long long first
 // section 3.12); the n `changed` words travel in behind the raws and come back behind the results, in the same two copies.
 // staged_raw (a cropped call's second phase, fxjps_prepare_slots_cropped): the raws are on the device already, job j's at
 // that offset of the context's window buffer, and none is copied or staged again.
+// tiles (a refresh under fxjps_set_slot_reuse(1)): the gather is the form that marks the changed
+// tiles.  The n records of 128 words travel in zeroed behind the `changed` words, and the results are written beside them
+// in the staged input's device copy, so that results and records come back in the one copy out: d.h_slots_res holds the
+// results as ever and the records from word d.slot_tiles_at on.
 int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, const std::vector<SlotPlan>& plan, size_t in_bytes, bool refresh,
-                     const WorldCall* world, const size_t* staged_raw) {
+                     const WorldCall* world, const size_t* staged_raw, bool tiles) {
     HIPCHK(h, hipSetDevice(d.dev));
     if (int e = ensure_slot_tables(h, d)) return e;
     // (no host wait in front: every call of the library that reads a slot has returned; a buffer that grows is freed by
     // hipFree, which waits for the device itself)
     const size_t flags_off = in_bytes, n_res = (size_t)n * (fx::SLOT_RES + (refresh ? 1 : 0));
     if (refresh) in_bytes += (size_t)n * sizeof(uint32_t);  // (every raw's room is a multiple of 16 bytes: the words are aligned)
+    const size_t res_bytes = (n_res * sizeof(int32_t) + 7) & ~(size_t)7, rec_bytes = (size_t)n * 128 * sizeof(unsigned long long);
+    size_t res_off = 0;
+    if (tiles) {  // [changed words | results | records], the last two as they come back
+        res_off = in_bytes = (in_bytes + 15) & ~(size_t)15;
+        in_bytes += res_bytes + rec_bytes;
+    }
     HIPCHK(h, d.h_slots_in.ensure(in_bytes));
     HIPCHK(h, d.d_slots_in.ensure(in_bytes));
-    HIPCHK(h, d.h_slots_res.ensure(n_res));
-    HIPCHK(h, d.d_slots_res.ensure(n_res));
+    HIPCHK(h, d.h_slots_res.ensure(tiles ? (res_bytes + rec_bytes) / sizeof(int32_t) : n_res));
+    if (!tiles) HIPCHK(h, d.d_slots_res.ensure(n_res));
+    d.slot_tiles_at = res_bytes / sizeof(int32_t);
+    if (tiles) memset(d.h_slots_in.p + res_off, 0, res_bytes + rec_bytes);
+    int32_t* d_res = tiles ? reinterpret_cast<int32_t*>(d.d_slots_in.p + res_off) : d.d_slots_res.p;
+    unsigned long long* d_rec = tiles ? reinterpret_cast<unsigned long long*>(d.d_slots_in.p + res_off + res_bytes) : nullptr;
     fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
     uint32_t* h_changed = reinterpret_cast<uint32_t*>(d.h_slots_in.p + flags_off);
     uint32_t* d_changed = reinterpret_cast<uint32_t*>(d.d_slots_in.p + flags_off);
@@ -2946,8 +2988,12 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
         {fx::k_slots_stage<fx::SL_BUILD_1, true>, fx::k_slots_stage<fx::SL_BUILD_2, true>, fx::k_slots_stage<fx::SL_BUILD_3, true>, fx::k_slots_stage<fx::SL_JD, true>}};
     const fx::WorldSrcDev* dS = world ? reinterpret_cast<const fx::WorldSrcDev*>(d.d_slots_in.p + world->off) : nullptr;
     uint32_t* dC = refresh ? d_changed : nullptr;
-    hipLaunchKernelGGL(gather[world ? 1 : 0][refresh ? 1 : 0], dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, dS, n, dC);
-    hipLaunchKernelGGL(goal[refresh ? 1 : 0], dim3((unsigned)n), dim3(64), 0, d.stream, dT, d.d_slots_res.p, n, (const uint32_t*)dC);
+    if (tiles)
+        hipLaunchKernelGGL(world ? fx::k_slot_tiles_gather<true> : fx::k_slot_tiles_gather<false>, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, dS,
+                           n, dC, d_rec);
+    else
+        hipLaunchKernelGGL(gather[world ? 1 : 0][refresh ? 1 : 0], dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, dS, n, dC);
+    hipLaunchKernelGGL(goal[refresh ? 1 : 0], dim3((unsigned)n), dim3(64), 0, d.stream, dT, d_res, n, (const uint32_t*)dC);
     if (at[fx::SL_BUILD_1] > 0)
         for (int l = fx::SL_BUILD_1; l <= fx::SL_JD; l++)
             hipLaunchKernelGGL(stage[refresh ? 1 : 0][l - fx::SL_BUILD_1], dim3(at[l]), dim3(l == fx::SL_BUILD_3 ? 1024 : 256), 0, d.stream, dT, n,
@@ -2960,7 +3006,7 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
                 if (e) return e;
             }
     HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p, d.h_slots_in.p + SLOTS_IN_DESC, sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice, d.stream));
-    HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d.d_slots_res.p, n_res * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d_res, tiles ? res_bytes + rec_bytes : n_res * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     // a goal with no free cell in its row or column: that slot stays empty (its buffers keep their room)
     for (int j = 0; j < n; j++)
@@ -2975,6 +3021,10 @@ int prepare_slots_on(fxjps* h, DevCtx& d, const fxjps_slot_job_t* jobs, int n, c
 }  // namespace
 
 namespace {
+// what a context's last slots call staged and brought back: was job j compared; the tile records behind the results
+bool job_compared(const DevCtx& d, int j) { return reinterpret_cast<const fx::SlotTable*>(d.h_slots_in.p)->job[j].compare != 0; }
+const unsigned long long* slot_tile_records(const DevCtx& d) { return reinterpret_cast<const unsigned long long*>(d.h_slots_res.p + d.slot_tiles_at); }
+
 // fxjps_prepare_slots (out_kept == nullptr, refresh false) and fxjps_refresh_slots: the checks, the call on every context
 // and the outputs are the same code.
 int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int32_t* out_kept, const char* what, const WorldSrc* world_src = nullptr,
@@ -3007,12 +3057,14 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
     const WorldCall* world = world_src ? &wc : nullptr;
     if (world) in_bytes += ((size_t)n * sizeof(fx::WorldSrcDev) + 15) & ~(size_t)15;
     // every context prepares every job from the caller's raws (host copies, no collective, as fxjps_set_grid_slot)
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world, staged_raw); });
+    const bool tiles = refresh && h->slot_reuse == 1;
+    int rc = run_side_by_side(h->devs.size(),
+                              [&](size_t r) -> int { return prepare_slots_on(h, h->devs[r], jobs, n, plan, in_bytes, refresh, world, staged_raw, tiles); });
     if (rc) {
         drain_all(h);
         for (int j = 0; j < n; j++) {  // (slots of a call that failed on one context are released on all of them)
             release_slot_everywhere(h, jobs[j].slot);
-            h->slot_gen[(size_t)jobs[j].slot]++;
+            h->bump_slot(jobs[j].slot);
         }
         (void)hipGetLastError();
         return rc;
@@ -3034,7 +3086,13 @@ int slots_call(fxjps_t* h, fxjps_slot_job_t* jobs, int32_t n, bool refresh, int3
         // kept: no byte of context 0's copy differed, so nothing was built (a job that failed has an empty slot: not kept)
         const bool kept = refresh && jb.status == FXJPS_OK && res[(size_t)n * fx::SLOT_RES + (size_t)j] == 0;
         if (out_kept) out_kept[j] = kept ? 1 : 0;
-        if (!kept) h->slot_gen[(size_t)jb.slot]++;  // (built, or left empty; a prepare always builds)
+        if (kept) continue;
+        // built, or left empty; a prepare always builds.  A compared job under the tile rule says where: its marks join the
+        // slot's record (context 0's, as `kept`), whose validity stays what it was; every other write voids the record.
+        if (tiles && jb.status == FXJPS_OK && job_compared(h->devs[0], j))
+            h->mark_slot(jb.slot, slot_tile_records(h->devs[0]) + (size_t)j * 128);
+        else
+            h->bump_slot(jb.slot);
     }
     return FXJPS_OK;
 }
@@ -3053,14 +3111,20 @@ namespace {
 // One context's part of fxjps_set_grid_slots / fxjps_refresh_grid_slots: prepare_slots_on with the
 // copy launch in place of the gather, no goal launch, and the grids where the raws were (off[j], multiples of 16 bytes).
 // refresh: the `changed` words travel in behind the grids and come back into d.h_slots_res, one word per job.
-int grid_slots_on(fxjps* h, DevCtx& d, const fxjps_grid_job_t* jobs, int n, const std::vector<size_t>& off, size_t in_bytes, bool refresh) {
+// tiles: the copy is the form that marks the changed tiles; the records travel in zeroed behind the
+// words and come back behind them in the one copy out, from word d.slot_tiles_at of d.h_slots_res on.
+int grid_slots_on(fxjps* h, DevCtx& d, const fxjps_grid_job_t* jobs, int n, const std::vector<size_t>& off, size_t in_bytes, bool refresh, bool tiles) {
     HIPCHK(h, hipSetDevice(d.dev));
     if (int e = ensure_slot_tables(h, d)) return e;
     const size_t flags_off = in_bytes;
     if (refresh) in_bytes += (size_t)n * sizeof(uint32_t);
+    const size_t words_bytes = ((size_t)n * sizeof(uint32_t) + 7) & ~(size_t)7, rec_bytes = (size_t)n * 128 * sizeof(unsigned long long);
+    if (tiles) in_bytes = flags_off + words_bytes + rec_bytes;
     HIPCHK(h, d.h_slots_in.ensure(in_bytes));
     HIPCHK(h, d.d_slots_in.ensure(in_bytes));
-    if (refresh) HIPCHK(h, d.h_slots_res.ensure((size_t)n));
+    if (refresh) HIPCHK(h, d.h_slots_res.ensure(tiles ? (words_bytes + rec_bytes) / sizeof(int32_t) : (size_t)n));
+    d.slot_tiles_at = words_bytes / sizeof(int32_t);
+    if (tiles) memset(d.h_slots_in.p + flags_off, 0, words_bytes + rec_bytes);
     fx::SlotTable& T = *reinterpret_cast<fx::SlotTable*>(d.h_slots_in.p);
     uint32_t* h_changed = reinterpret_cast<uint32_t*>(d.h_slots_in.p + flags_off);
     uint32_t* d_changed = reinterpret_cast<uint32_t*>(d.d_slots_in.p + flags_off);
@@ -3096,7 +3160,11 @@ int grid_slots_on(fxjps* h, DevCtx& d, const fxjps_grid_job_t* jobs, int n, cons
         {fx::k_slots_stage<fx::SL_BUILD_1, false>, fx::k_slots_stage<fx::SL_BUILD_2, false>, fx::k_slots_stage<fx::SL_BUILD_3, false>, fx::k_slots_stage<fx::SL_JD, false>},
         {fx::k_slots_stage<fx::SL_BUILD_1, true>, fx::k_slots_stage<fx::SL_BUILD_2, true>, fx::k_slots_stage<fx::SL_BUILD_3, true>, fx::k_slots_stage<fx::SL_JD, true>}};
     uint32_t* dC = refresh ? d_changed : nullptr;
-    hipLaunchKernelGGL(refresh ? fx::k_slots_copy<true> : fx::k_slots_copy<false>, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, dC);
+    if (tiles)
+        hipLaunchKernelGGL(fx::k_slot_tiles_copy, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, dC,
+                           reinterpret_cast<unsigned long long*>(d.d_slots_in.p + flags_off + words_bytes));
+    else
+        hipLaunchKernelGGL(refresh ? fx::k_slots_copy<true> : fx::k_slots_copy<false>, dim3(at[fx::SL_PREPARE]), dim3(256), 0, d.stream, dT, n, dC);
     if (at[fx::SL_BUILD_1] > 0)
         for (int l = fx::SL_BUILD_1; l <= fx::SL_JD; l++)
             hipLaunchKernelGGL(stage[refresh ? 1 : 0][l - fx::SL_BUILD_1], dim3(at[l]), dim3(l == fx::SL_BUILD_3 ? 1024 : 256), 0, d.stream, dT, n,
@@ -3109,7 +3177,8 @@ int grid_slots_on(fxjps* h, DevCtx& d, const fxjps_grid_job_t* jobs, int n, cons
                 if (e) return e;
             }
     HIPCHK(h, hipMemcpyAsync(d.d_slot_desc.p, d.h_slots_in.p + SLOTS_IN_DESC, sizeof(GridDev) * FXJPS_MAX_GRID_SLOTS, hipMemcpyHostToDevice, d.stream));
-    if (refresh) HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d_changed, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    if (refresh)
+        HIPCHK(h, hipMemcpyAsync(d.h_slots_res.p, d_changed, tiles ? words_bytes + rec_bytes : (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     return FXJPS_OK;
 }
@@ -3135,12 +3204,13 @@ int grid_slots_call(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n, bool re
         in_bytes += ((size_t)jb.W * (size_t)jb.H + 15) & ~(size_t)15;
     }
     if (n == 0) return FXJPS_OK;
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grid_slots_on(h, h->devs[r], jobs, n, off, in_bytes, refresh); });
+    const bool tiles = refresh && h->slot_reuse == 1;
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grid_slots_on(h, h->devs[r], jobs, n, off, in_bytes, refresh, tiles); });
     if (rc) {
         drain_all(h);
         for (int j = 0; j < n; j++) {  // (slots of a call that failed on one context are released on all of them)
             release_slot_everywhere(h, jobs[j].slot);
-            h->slot_gen[(size_t)jobs[j].slot]++;
+            h->bump_slot(jobs[j].slot);
         }
         (void)hipGetLastError();
         return rc;
@@ -3149,7 +3219,11 @@ int grid_slots_call(fxjps_t* h, const fxjps_grid_job_t* jobs, int32_t n, bool re
     for (int j = 0; j < n; j++) {
         const bool kept = refresh && words[j] == 0;  // (no byte of context 0's copy differed: nothing was built)
         if (out_kept) out_kept[j] = kept ? 1 : 0;
-        if (!kept) h->slot_gen[(size_t)jobs[j].slot]++;
+        if (kept) continue;
+        if (tiles && job_compared(h->devs[0], j))  // (as fxjps_refresh_slots: a compared job's marks join the slot's record)
+            h->mark_slot(jobs[j].slot, slot_tile_records(h->devs[0]) + (size_t)j * 128);
+        else
+            h->bump_slot(jobs[j].slot);
     }
     return FXJPS_OK;
 }
@@ -3519,7 +3593,7 @@ int crop_call(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, bool refresh, int3
     if (rc) return rc;
     if (!empty.empty()) {
         rc = empty_slots_everywhere(h, empty);
-        for (int32_t s : empty) h->slot_gen[(size_t)s]++;
+        for (int32_t s : empty) h->bump_slot(s);
         if (rc) {
             for (int32_t s : empty) release_slot_everywhere(h, s);
             (void)hipGetLastError();
@@ -3641,6 +3715,8 @@ namespace {
 // fxjps_replan_slots on a handle with one context.  The arguments are checked; `searched` lists the
 // queries to search, in query order.  Runs them as a sub-batch through run_shard / finish_search, then assembles the full
 // batch on the device: one copy in (the source table), one scan launch, one gather launch, the copies out, one wait.
+// req.track() (fxjps_set_slot_reuse(1)): the sub-batch runs the tracking instantiation, and its read sets come back among
+// the copies out -- one copy, row k the k-th searched query's -- into d.h_qread.
 int replan_slots_assemble(fxjps* h, DevCtx& d, const BatchReq& req, const std::vector<int64_t>& searched) {
     HIPCHK(h, hipSetDevice(d.dev));
     const int64_t nq = req.nq, nsub = (int64_t)searched.size();
@@ -3715,6 +3791,10 @@ int replan_slots_assemble(fxjps* h, DevCtx& d, const BatchReq& req, const std::v
     HIPCHK(h, hipMemcpyAsync(d.h_cost.p, d.d_cost.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, d.stream));
     if (nsub > 0) HIPCHK(h, hipMemcpyAsync(d.h_counters.p, d.d_counters.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     if (total > 0) HIPCHK(h, hipMemcpyAsync(d.h_cells.p, d.d_cells.p, (size_t)total * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    if (req.track() && nsub > 0) {
+        d.h_qread.resize((size_t)nsub * 128);
+        HIPCHK(h, hipMemcpyAsync(d.h_qread.data(), d.d_qread.p, (size_t)nsub * 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    }
     HIPCHK(h, hipStreamSynchronize(d.stream));
     if (nsub == 0) memset(d.h_counters.p, 0, 64 * sizeof(unsigned long long));  // (nothing was searched)
     d.nq = nq;
@@ -3737,20 +3817,37 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
     }
     // every refusal of fxjps_plan_batch_slots_csr, before the stored results are touched
     if (nq > 0 && (!out_offsets || !out_len || !out_cost)) return fail(h, FXJPS_E_ARG, "NULL output array");
+    // (the tile rule, DESIGN.md section 3.18: every search of the call records its read set)
+    const bool tiles = h->slot_reuse == 1;
     BatchReq req;
-    if (int rc = batch_request(h, true, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, 0, &req)) return rc;
+    if (int rc = batch_request(h, true, grid_ids, starts_xy, goals_xy, nq, hchoice, max_path_len, tiles ? 1 : 0, &req)) return rc;
     // ---- which queries are searched: plain compares of the arguments against the stored ones, before anything is queued
     static const bool allow_reuse = !(getenv("FXJPS_REPLAN_REUSE") && atoi(getenv("FXJPS_REPLAN_REUSE")) == 0);
     const bool stored = allow_reuse && h->rs_valid && h->rs_nq == nq && h->rs_hchoice == hchoice && h->rs_max_len == max_path_len;
     std::vector<int64_t> searched;
     std::vector<uint64_t> gen((size_t)nq);
+    std::vector<int32_t> flag((size_t)nq, 0);  // out_reused: 0 searched, 1 the slot did not change, 2 it changed elsewhere
     for (int64_t q = 0; q < nq; q++) {
         const size_t i = (size_t)q;
         gen[i] = h->slot_gen[(size_t)grid_ids[q]];
-        const bool reuse = stored && h->rs_ids[i] == grid_ids[q] && h->rs_gen[i] == gen[i] && h->rs_len[i] != FXJPS_Q_CAPACITY &&
-                           h->rs_starts[2 * i] == starts_xy[2 * q] && h->rs_starts[2 * i + 1] == starts_xy[2 * q + 1] &&
-                           h->rs_goals[2 * i] == goals_xy[2 * q] && h->rs_goals[2 * i + 1] == goals_xy[2 * q + 1];
-        if (!reuse) searched.push_back(q);
+        const bool same = stored && h->rs_ids[i] == grid_ids[q] && h->rs_len[i] != FXJPS_Q_CAPACITY &&
+                          h->rs_starts[2 * i] == starts_xy[2 * q] && h->rs_starts[2 * i + 1] == starts_xy[2 * q + 1] &&
+                          h->rs_goals[2 * i] == goals_xy[2 * q] && h->rs_goals[2 * i + 1] == goals_xy[2 * q + 1];
+        if (same && h->rs_gen[i] == gen[i]) {
+            flag[i] = 1;
+        } else if (same && tiles) {
+            // the slot's bytes changed, and every change since the stored search went through a compared refresh job: the
+            // stored path stands iff no changed cell's box meets a tile the search read (a length <= 0 depends on more
+            // than a read set, as in frame_reuse_rule)
+            const fxjps::SlotTiles& R = h->slot_tiles[(size_t)grid_ids[q]];
+            if (R.valid && R.base == h->rs_gen[i] && h->rs_len[i] > 0 && h->rs_have[i]) {
+                const unsigned long long* b = h->rs_read.data() + i * 128;
+                unsigned long long hit = 0;
+                for (int t = 0; t < 128; t++) hit |= b[t] & R.D[t];
+                if (!hit) flag[i] = 2;
+            }
+        }
+        if (flag[i] == 0) searched.push_back(q);
     }
     DevCtx& d = h->devs[0];
     int rc = begin_batch(h, req);  // (a slots batch: nothing is queued, nothing can fail)
@@ -3774,11 +3871,66 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
     h->rs_hchoice = hchoice;
     h->rs_max_len = max_path_len;
     h->rs_valid = true;
-    if (out_reused) {
-        for (int64_t q = 0; q < nq; q++) out_reused[q] = 1;
-        for (int64_t q : searched) out_reused[q] = 0;
+    if (tiles) {
+        // the read set of the search that produced each stored result: a searched query's is new (none, all zero, when it
+        // ended without a search: a search marks its start and its goal at the least); a reused query keeps its own -- a
+        // fresh search would read the same bits.  Every slot's record begins again at the generation just recorded.
+        h->rs_read.resize((size_t)nq * 128);
+        h->rs_have.resize((size_t)nq);
+        for (size_t k = 0; k < searched.size(); k++) {
+            const unsigned long long* src = d.h_qread.data() + k * 128;
+            unsigned long long any = 0;
+            for (int t = 0; t < 128; t++) any |= src[t];
+            memcpy(h->rs_read.data() + (size_t)searched[k] * 128, src, 128 * sizeof(unsigned long long));
+            h->rs_have[(size_t)searched[k]] = any != 0;
+        }
+        for (int s2 = 0; s2 < FXJPS_MAX_GRID_SLOTS; s2++) {
+            fxjps::SlotTiles& R = h->slot_tiles[(size_t)s2];
+            R.valid = true;
+            R.base = h->slot_gen[(size_t)s2];
+            memset(R.D, 0, sizeof(R.D));
+        }
     }
+    if (out_reused) memcpy(out_reused, flag.data(), (size_t)nq * sizeof(int32_t));
     return end_call(h, t0, out_seconds_total, emit_csr(h, nq, out_offsets, out_cells_xy, cells_capacity, out_len, out_cost));
+}
+
+// ------------------------------------------------------------------ fxjps_replan_slots under the tile rule
+int fxjps_set_slot_reuse(fxjps_t* h, int32_t mode) {
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_set_slot_reuse")) return rr;
+    if (mode != 0 && mode != 1) return fail(h, FXJPS_E_ARG, "slot reuse mode %d: 0 (the generation rule) or 1 (the tile rule)", (int)mode);
+    if (mode == h->slot_reuse) return FXJPS_OK;
+    h->slot_reuse = mode;
+    h->rs_valid = false;  // (the stored results carry the other mode's bookkeeping)
+    h->rs_read.clear();
+    h->rs_have.clear();
+    for (auto& R : h->slot_tiles) R = fxjps::SlotTiles();
+    return FXJPS_OK;
+}
+
+int fxjps_debug_slot_tiles(fxjps_t* h, int32_t slot, uint64_t out[128], int32_t* tsh, int32_t* valid) {
+    if (!h || !out || !tsh || !valid) return FXJPS_E_ARG;
+    if (slot < 0 || slot >= FXJPS_MAX_GRID_SLOTS) return fail(h, FXJPS_E_ARG, "slot %d is not in 0 .. %d", (int)slot, FXJPS_MAX_GRID_SLOTS - 1);
+    const fxjps::SlotTiles& R = h->slot_tiles[(size_t)slot];
+    static_assert(sizeof(R.D) == 128 * sizeof(uint64_t), "the record is the caller's 128 words");
+    memcpy(out, R.D, sizeof(R.D));
+    *tsh = slot_in_use(h, slot) ? h->devs[0].slots[(size_t)slot].tsh : 0;
+    *valid = R.valid ? 1 : 0;
+    return FXJPS_OK;
+}
+
+int fxjps_debug_slot_read_sets(fxjps_t* h, uint64_t* out, int64_t nq, int32_t* out_tsh, int32_t* out_have) {
+    if (!h || (nq > 0 && (!out || !out_tsh || !out_have))) return FXJPS_E_ARG;
+    if (h->slot_reuse != 1 || !h->rs_valid) return fail(h, FXJPS_E_ARG, "no stored read sets: the last batch call was not a fxjps_replan_slots under the tile rule");
+    if (nq != h->rs_nq) return fail(h, FXJPS_E_ARG, "the stored results hold %lld queries, not %lld", (long long)h->rs_nq, (long long)nq);
+    if (nq > 0) memcpy(out, h->rs_read.data(), (size_t)nq * 128 * sizeof(uint64_t));
+    for (int64_t q = 0; q < nq; q++) {
+        const int32_t id = h->rs_ids[(size_t)q];
+        out_tsh[q] = slot_in_use(h, id) ? h->devs[0].slots[(size_t)id].tsh : 0;
+        out_have[q] = h->rs_have[(size_t)q] ? 1 : 0;
+    }
+    return FXJPS_OK;
 }
 
 int fxjps_last_cells(fxjps_t* h, int32_t* out_cells_xy, int64_t cells_capacity) {

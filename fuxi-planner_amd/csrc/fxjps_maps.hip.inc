@@ -852,10 +852,43 @@ __device__ __forceinline__ int slot_job_of(const uint32_t* __restrict__ first, i
     return lo;
 }
 
+// TILES, a further parameter of the bodies below (fxjps_set_slot_reuse(1), DESIGN.md section 3.18; the kernels of that form
+// are k_slot_tiles_gather<WORLD> and k_slot_tiles_copy, the REFRESH forms' bodies under kernel names of their own): a
+// compared job also says WHERE its bytes differ, in read-set tiles.  Every cell whose byte differs marks the tiles of its box
+// [max(x-1,0) .. min(x+1,W-1)] x [max(y-1,0) .. min(y+1,H-1)] shifted by G.tsh -- FrameTiles::mark_box for one cell -- in the
+// job's record of 128 words: tiles[j * 128 + ty] has a bit per x tile, tiles[j * 128 + 64 + tx] a bit per y tile.  A block in
+// which no byte differs does nothing more than the REFRESH form; a block in which one does gathers its marks in 1 KB of LDS
+// and flushes the non-zero words with one atomic each (a 256-cell block lies in one or two columns of the grid: a handful of
+// words), so a tick that changed every byte does not queue up on 128 words per job.
+struct SlotTileMarks {
+    unsigned long long w[128];
+};
+// (every thread of the block calls both, `any` being block-uniform and true)
+__device__ __forceinline__ void slot_tiles_clear(SlotTileMarks& M) {
+    if (threadIdx.x < 128) M.w[threadIdx.x] = 0ull;
+    __syncthreads();
+}
+__device__ __forceinline__ void slot_tiles_mark(SlotTileMarks& M, const GridDev& G, long long cell) {
+    const int x = (int)(cell / G.H), y = (int)(cell - (long long)x * G.H);  // occ is [W][H]
+    const int tx0 = max(x - 1, 0) >> G.tsh, tx1 = min(x + 1, G.W - 1) >> G.tsh;
+    const int ty0 = max(y - 1, 0) >> G.tsh, ty1 = min(y + 1, G.H - 1) >> G.tsh;  // (at most 63: the host chose tsh so)
+    const unsigned long long mx = (~0ull >> (63 - tx1)) & (~0ull << tx0), my = (~0ull >> (63 - ty1)) & (~0ull << ty0);
+    for (int ty = ty0; ty <= ty1; ty++) atomicOr(&M.w[ty], mx);  // (at most three words each)
+    for (int tx = tx0; tx <= tx1; tx++) atomicOr(&M.w[64 + tx], my);
+}
+__device__ __forceinline__ void slot_tiles_flush(SlotTileMarks& M, unsigned long long* __restrict__ rec) {
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const unsigned long long v = M.w[threadIdx.x];
+        if (v != 0ull) atomicOr(rec + threadIdx.x, v);
+    }
+}
+
 // k_prepare_grid's gather, for every output cell of every job.
-template <bool WORLD, bool REFRESH>
-__global__ __launch_bounds__(256) void k_slots_gather(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
-                                                     uint32_t* __restrict__ changed) {
+template <bool WORLD, bool REFRESH, bool TILES>
+__device__ __forceinline__ void slots_gather_body(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
+                                                  uint32_t* __restrict__ changed, unsigned long long* __restrict__ tiles) {
+    static_assert(REFRESH || !TILES, "only a refresh compares");
     const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
     const SlotJobDev& J = T->job[j];
     const PrepGeom g{J.W0, J.H0, J.dx, J.dy, J.ifa, J.variant, J.layout, J.G.W, J.G.H};
@@ -876,8 +909,26 @@ __global__ __launch_bounds__(256) void k_slots_gather(const SlotTable* __restric
         const bool differs = inside && occ[i] != v;  // bytes, not truthiness: a slot set to 7 where this is 1 is rewritten
         if (differs) occ[i] = v;
         // (every thread of the block reaches the barrier: none has returned above)
-        if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+        const bool any = __syncthreads_or(differs) != 0;
+        if (any && threadIdx.x == 0) changed[j] = 1u;
+        if constexpr (TILES) {
+            if (!any) return;  // (block-uniform)
+            __shared__ SlotTileMarks s_marks;
+            slot_tiles_clear(s_marks);
+            if (differs) slot_tiles_mark(s_marks, J.G, i);
+            slot_tiles_flush(s_marks, tiles + (size_t)j * 128);
+        }
     }
+}
+template <bool WORLD, bool REFRESH>
+__global__ __launch_bounds__(256) void k_slots_gather(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
+                                                     uint32_t* __restrict__ changed) {
+    slots_gather_body<WORLD, REFRESH, false>(T, S, n, changed, nullptr);
+}
+template <bool WORLD>
+__global__ __launch_bounds__(256) void k_slot_tiles_gather(const SlotTable* __restrict__ T, const WorldSrcDev* __restrict__ S, int n,
+                                                          uint32_t* __restrict__ changed, unsigned long long* __restrict__ tiles) {
+    slots_gather_body<WORLD, true, true>(T, S, n, changed, tiles);
 }
 
 // The free cell of line[0], line[stride], .. (n cells) nearest to index c, the lower index of two equally near ones
@@ -982,8 +1033,11 @@ __global__ __launch_bounds__(L == SL_BUILD_3 ? 1024 : 256) void k_slots_stage(co
 // piece in which a byte differs (bytes, not truthiness); every thread of the block reaches the barrier, one raises the
 // job's word.  A job not marked is stored whole and its word stays at the host's 1.
 constexpr int SLOT_COPY_LANE = 16, SLOT_COPY_BLOCK = 256 * SLOT_COPY_LANE;
-template <bool REFRESH>
-__global__ __launch_bounds__(256) void k_slots_copy(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed) {
+//   TILES: as in the gather, exact per byte: a piece that is stored marks only the bytes of it that differ.
+template <bool REFRESH, bool TILES>
+__device__ __forceinline__ void slots_copy_body(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed,
+                                                unsigned long long* __restrict__ tiles) {
+    static_assert(REFRESH || !TILES, "only a refresh compares");
     const int j = slot_job_of(T->first[SL_PREPARE], n, blockIdx.x);
     const SlotJobDev& J = T->job[j];
     const uint8_t* __restrict__ src = J.raw;
@@ -994,12 +1048,18 @@ __global__ __launch_bounds__(256) void k_slots_copy(const SlotTable* __restrict_
     const int tail = !whole && i < ncell ? (int)(ncell - i) : 0;       // ... or the grid's last 1 .. 15 bytes
     const bool compare = REFRESH && J.compare != 0;                    // (block-uniform)
     bool differs = false;
+    uint32_t dbytes = 0u;  // TILES: bit k set, byte i + k of a compared job differs
     if (whole) {
         const uint4 v = *reinterpret_cast<const uint4*>(src + i);
         differs = true;
         if (compare) {
             const uint4 o = *reinterpret_cast<const uint4*>(occ + i);
             differs = ((v.x ^ o.x) | (v.y ^ o.y) | (v.z ^ o.z) | (v.w ^ o.w)) != 0u;
+            if constexpr (TILES) {
+                const uint32_t xw[4] = {v.x ^ o.x, v.y ^ o.y, v.z ^ o.z, v.w ^ o.w};
+#pragma unroll
+                for (int k = 0; k < 16; k++) dbytes |= ((xw[k >> 2] >> (8 * (k & 3))) & 0xFFu) != 0u ? 1u << k : 0u;
+            }
         }
         if (differs) *reinterpret_cast<uint4*>(occ + i) = v;
     } else {
@@ -1008,12 +1068,29 @@ __global__ __launch_bounds__(256) void k_slots_copy(const SlotTable* __restrict_
             const bool d = !compare || occ[i + k] != v;
             if (d) occ[i + k] = v;
             differs = differs || d;
+            if constexpr (TILES) dbytes |= compare && d ? 1u << k : 0u;
         }
     }
     if constexpr (REFRESH) {
         if (!compare) return;  // (the whole block: its job builds whatever the bytes are)
-        if (__syncthreads_or(differs) && threadIdx.x == 0) changed[j] = 1u;
+        const bool any = __syncthreads_or(differs) != 0;
+        if (any && threadIdx.x == 0) changed[j] = 1u;
+        if constexpr (TILES) {
+            if (!any) return;  // (block-uniform)
+            __shared__ SlotTileMarks s_marks;
+            slot_tiles_clear(s_marks);
+            for (uint32_t m = dbytes; m != 0u; m &= m - 1u) slot_tiles_mark(s_marks, J.G, i + __builtin_ctz(m));
+            slot_tiles_flush(s_marks, tiles + (size_t)j * 128);
+        }
     }
+}
+template <bool REFRESH>
+__global__ __launch_bounds__(256) void k_slots_copy(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed) {
+    slots_copy_body<REFRESH, false>(T, n, changed, nullptr);
+}
+__global__ __launch_bounds__(256) void k_slot_tiles_copy(const SlotTable* __restrict__ T, int n, uint32_t* __restrict__ changed,
+                                                        unsigned long long* __restrict__ tiles) {
+    slots_copy_body<true, true>(T, n, changed, tiles);
 }
 
 // ---- The ccst node's crop in front of the world-frame calls (fxjps_prepare_slots_cropped, DESIGN.md section 3.15):

@@ -21,6 +21,8 @@ def as_occ(matrix):
 
 class Planner(object):
     """A resident occupancy grid plus batched (start, goal) planning on the GPU."""
+    _slot_reuse = 0  # set_slot_reuse: the handle's mode
+    _slot_nq = 0     # the last replan_slots call's number of queries
 
     def __init__(self, devices=None):
         L = _lib.load()
@@ -659,7 +661,9 @@ class Planner(object):
         what its slot already holds keeps the slot's maps.  The same arguments, the same records, and in every live
         vehicle's record a further key, kept (bool).  reuse=True: the batch is planned through replan_slots, so a vehicle
         whose slot was kept and whose start and goal cells did not move is not searched again; its record says so in a
-        further key, reused (bool).  Every other value is what reuse=False gives."""
+        further key, reused (bool).  Every other value is what reuse=False gives.  After set_slot_reuse("tiles") a vehicle
+        whose slot changed only where its path's search did not read is not searched either: reused is True and a further
+        key, reused_tiles (bool), says that this was why."""
         return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse)
 
     def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
@@ -710,6 +714,8 @@ class Planner(object):
                 recs[v]["kept"] = o[6]
             if reuse:
                 recs[v]["reused"] = bool(reused[i])
+                if self._slot_reuse == 1:
+                    recs[v]["reused_tiles"] = int(reused[i]) == 2
         return recs
 
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
@@ -720,9 +726,40 @@ class Planner(object):
     def replan_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):
         """plan_batch_slots for the tick after (fxjps_replan_slots): a query whose slot, start and goal are those of the
         previous replan_slots call, on a slot nothing has written since, hands back its stored path without a search.
-        -> (offsets, cells, cost, status, reused); reused: one bool per query.  The results are byte for byte those of
+        -> (offsets, cells, cost, status, reused); reused: the call's flag per query (int32): 0 searched, 1 handed back
+        because nothing wrote its slot, 2 (only after set_slot_reuse("tiles")) handed back although its slot changed,
+        because no changed cell touches a tile its search read.  The results are byte for byte those of
         plan_batch_slots.  A max_path_len that grows makes that retry a full search."""
         return self._plan_slots(True, grid_ids, starts, goals, hchoice, max_path_len)
+
+    SLOT_REUSE_MODES = {"generation": 0, "tiles": 1}
+
+    def set_slot_reuse(self, mode):
+        """Which stored paths replan_slots hands back (fxjps_set_slot_reuse): "generation" (the default: those of slots
+        nothing has written) or "tiles" (also those of slots whose refresh changed bytes only in read-set tiles the stored
+        search did not read).  A change of mode drops the stored results."""
+        if mode not in self.SLOT_REUSE_MODES:
+            raise ValueError("mode must be 'generation' or 'tiles'")
+        self._chk(self._L.fxjps_set_slot_reuse(self._h, self.SLOT_REUSE_MODES[mode]))
+        self._slot_reuse = self.SLOT_REUSE_MODES[mode]
+
+    def debug_slot_tiles(self, slot):
+        """The changed-tile record of a slot (fxjps_debug_slot_tiles): -> (uint64[128], tsh, valid).  Tile (tx, ty) is
+        marked iff bit tx of [ty] and bit ty of [64 + tx] are set."""
+        out = np.zeros(128, dtype=np.uint64)
+        tsh, valid = C.c_int32(-1), C.c_int32(-1)
+        self._chk(self._L.fxjps_debug_slot_tiles(self._h, int(slot), _lib.ptr(out, C.c_uint64), C.byref(tsh), C.byref(valid)))
+        return out, tsh.value, bool(valid.value)
+
+    def debug_slot_read_sets(self):
+        """The read sets kept with the stored results of the last replan_slots under the tile rule
+        (fxjps_debug_slot_read_sets): -> (uint64[nq, 128], tsh int32[nq], have bool[nq]), laid out as debug_read_sets'."""
+        n = self._slot_nq  # (of the last replan_slots)
+        out = np.zeros((n, 128), dtype=np.uint64)
+        tsh = np.zeros(n, dtype=np.int32)
+        have = np.zeros(n, dtype=np.int32)
+        self._chk(self._L.fxjps_debug_slot_read_sets(self._h, _lib.ptr(out, C.c_uint64), n, _lib.ptr(tsh, C.c_int32), _lib.ptr(have, C.c_int32)))
+        return out, tsh, have.astype(bool)
 
     def _plan_slots(self, replan, grid_ids, starts, goals, hchoice, max_path_len):
         ids = np.ascontiguousarray(grid_ids, dtype=np.int32).reshape(-1)
@@ -751,6 +788,7 @@ class Planner(object):
             secs = C.c_double(0.0)
             reused = np.zeros(n, dtype=np.int32)
             if replan:
+                self._slot_nq = n
                 self._chk(self._L.fxjps_replan_slots(self._h, _lib.ptr(ids, C.c_int32), _lib.ptr(starts, C.c_int32),
                                                      _lib.ptr(goals, C.c_int32), n, int(hchoice), mpl, _lib.ptr(offsets, C.c_int64),
                                                      None, 0, _lib.ptr(status, C.c_int32), _lib.ptr(cost, C.c_double),
@@ -767,7 +805,7 @@ class Planner(object):
                 continue
             break
         self.last_seconds = secs.value
-        return offsets, cells, cost, status, reused.astype(bool)
+        return offsets, cells, cost, status, reused
 
     # -- streaming replan (persistent goals, one call per frame)
     def set_queries(self, starts, goals, hchoice=2, max_path_len=None):

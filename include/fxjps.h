@@ -108,8 +108,11 @@ typedef struct fxjps fxjps_t;
  *   820  fxjps_set_grid_slots, fxjps_refresh_grid_slots (fxjps_set_grid_slot for many slots in one call whose launches and
  *        host waits do not depend on n; the refresh form keeps the maps and the generation of a slot whose bytes did not
  *        change), fxjps_grid_job_size.
+ *   830  fxjps_set_slot_reuse (fxjps_replan_slots under the tile rule: a refresh that changed a slot's bytes records which
+ *        read-set tiles the changed cells touch, and a stored path whose read set misses them all is handed back without
+ *        a search, out_reused 2), fxjps_debug_slot_tiles, fxjps_debug_slot_read_sets.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 820
+#define FXJPS_VERSION 830
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -527,6 +530,35 @@ int fxjps_replan_slots(fxjps_t* h, const int32_t* grid_ids, const int32_t* start
                        int32_t hchoice, int32_t max_path_len, int64_t* out_offsets, int32_t* out_cells_xy,
                        int64_t cells_capacity, int32_t* out_len, double* out_cost, int32_t* out_reused,
                        double* out_seconds_total);
+
+/* ---- fxjps_replan_slots under the tile rule (version 830): the fleet tick's counterpart of fxjps_replan_frame's exact
+ * reuse.  mode 0 (the default) is the generation rule above and changes nothing about any call.  mode 1:
+ *   - the refresh calls (fxjps_refresh_slots, its _world and _cropped forms, fxjps_refresh_grid_slots) say, for every job
+ *     they compare byte by byte (the slot holds a grid of the same extents, at most 2^18 cells), which read-set tiles the
+ *     cells whose byte differs touch: the tiles ((1 << tsh) cells a side, tsh the least shift that leaves at most 64 x 64)
+ *     of the box [max(x-1,0) .. min(x+1,W-1)] x [max(y-1,0) .. min(y+1,H-1)] of every such cell (x, y), found in the
+ *     launches that write the bytes.  The library ORs them into a record per slot; the slot's generation moves as before.
+ *     Every other write of a slot (a prepare or set call, a job that was not compared or failed, the cropped calls' jobs
+ *     that leave a slot empty) voids the slot's record.
+ *   - every search of fxjps_replan_slots records its read set (the tiles whose derived data it read, as
+ *     fxjps_replan_frame's searches do) and the call keeps it with the stored result.
+ *   - query q is not searched iff the first two conditions of fxjps_replan_slots hold, its stored code is not
+ *     FXJPS_Q_CAPACITY, and EITHER the slot's generation is the recorded one (out_reused[q] = 1) OR the slot's record is
+ *     valid and began at the recorded generation, the stored length is > 0, q has a stored read set, and no tile is set in
+ *     both (out_reused[q] = 2): a fresh search on the slot as it is now would read the same bits, take the same decisions
+ *     and return the same path.  Bytes are compared, not truthiness: a 1 that becomes a 7 marks its tiles.
+ *   - at the end of every fxjps_replan_slots each slot's record is cleared and begins again at the slot's generation.
+ * Every output of every call is byte for byte what mode 0 gives.  Any change of mode drops the stored results of
+ * fxjps_replan_slots and voids every record.  A handle with several contexts accepts mode 1 and fxjps_replan_slots stays
+ * the plain batch it is; a rank handle (world > 1) and any other mode value are refused with FXJPS_E_ARG. */
+int fxjps_set_slot_reuse(fxjps_t* h, int32_t mode);
+/* (tests) The record of `slot` (0 .. FXJPS_MAX_GRID_SLOTS - 1): out[ty] has a bit per x tile, out[64 + tx] a bit per y tile;
+ * *tsh the slot's tile shift (0 for an empty slot), *valid whether the record is valid. */
+int fxjps_debug_slot_tiles(fxjps_t* h, int32_t slot, uint64_t out[128], int32_t* tsh, int32_t* valid);
+/* (tests) The read sets kept with the stored results of the last fxjps_replan_slots (nq must be that call's): out[q][128]
+ * as fxjps_debug_read_sets lays them out, out_tsh[q] the tile shift of q's slot, out_have[q] whether q has one (a query that
+ * ended without a search has none).  FXJPS_E_ARG when there are no stored results or the mode is 0. */
+int fxjps_debug_slot_read_sets(fxjps_t* h, uint64_t* out, int64_t nq, int32_t* out_tsh, int32_t* out_have);
 
 /* ---- Many slots' maps published in one call (the last quarter of a fleet tick: every vehicle's prepared map leaves the
  * device as the message and / or the snapshot image a node publishes).  Job by job the results are those of
