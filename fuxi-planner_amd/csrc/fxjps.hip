@@ -325,6 +325,7 @@ struct fxjps {
     struct LastBatch {  // what the resident forms of the waypoint calls read (nq == 0 while a batch is under way: begin_batch)
         int64_t nq = 0;
         bool on_host = false;  // the last batch was a single call: its CSR is in the pinned host buffers only
+        int W = 0, H = 0;      // the extents of the resident grid when a batch on it began: its paths lie on THAT grid, whatever is resident now
         bool slots = false;    // the last batch ran on grid slots: its paths are not the resident grid's ...
         int slots_W = 0, slots_H = 0;   // ... they lie within these extents (the largest of the slots it named)
         std::vector<int32_t> slot_ids;  // ... and these are the slots its queries named (fxjps_waypoint_slots_batch)
@@ -1327,6 +1328,10 @@ int batch_request(fxjps* h, bool slots, const int32_t* grid_ids, const int32_t* 
 int begin_batch(fxjps* h, const BatchReq& req) {
     h->last.nq = 0;
     h->last.slots = req.slots;
+    if (!req.slots) {
+        h->last.W = req.W;
+        h->last.H = req.H;
+    }
     if (h->maps_stale && !req.slots) {  // deferred cell updates: the maps are rebuilt once, in front of the search
         int rc = update_cells_async(h, nullptr, nullptr, 0, true);
         if (rc) return rc;
@@ -1670,7 +1675,7 @@ bool wp_atab_fits(long long am, long long bm) { return (am + 1) * (2 * bm + 1) <
 // on, a slots batch's within the largest slot it named.
 void wp_st_range(const fxjps* h, const WpPaths& S, int64_t nq, const int32_t* rule, const int32_t* map_start, long long& am, long long& bm) {
     am = bm = 0;
-    const long long W = h->last.slots ? h->last.slots_W : h->devs[0].W, H = h->last.slots ? h->last.slots_H : h->devs[0].H;
+    const long long W = h->last.slots ? h->last.slots_W : h->last.W, H = h->last.slots ? h->last.slots_H : h->last.H;
     for (int64_t q = 0; q < nq; q++) {
         if (rule && rule[q] != 0) continue;
         const long long mx = map_start[2 * q], my = map_start[2 * q + 1];

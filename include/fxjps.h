@@ -210,7 +210,7 @@ int fxjps_snapshot_image(fxjps_t* h, uint8_t* out, int32_t channels, int32_t* ou
 /* Streaming replan: set n cells (xy pairs) to val[i] (0 free / non-zero obstacle) on the resident grid and rebuild the
  * derived maps -- only what the changed cells can reach (their box for the scan words, the rows and columns through it
  * for the cell infos; small lists are united into the component labels).  Cells outside the grid are ignored; a cell
- * named more than once takes the value of its last entry. */
+ * named more than once takes the value of its last entry.  The byte written is 0 or 1, whatever non-zero value was given. */
 int fxjps_update_cells(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_t n);
 
 /* fxjps_update_cells without the rebuild of the derived maps: the updates are applied to the resident grid (calls are
@@ -511,7 +511,7 @@ int fxjps_crop_size(void); /* sizeof(fxjps_crop_t) as the library was built */
  *   - the handle's previous batch call was a fxjps_replan_slots with the same nq, hchoice and max_path_len (calls that
  *     touch neither the resident paths nor the stored results may lie in between: fxjps_prepare_slots, fxjps_refresh_slots,
  *     fxjps_publish_slots, the waypoint and tick-output calls, fxjps_set_grid_slot; every other batch call and every change
- *     of the resident grid drops the stored results, as it drops those of fxjps_replan_frame),
+ *     of the resident grid drops the stored results, as it drops those of fxjps_replan_frame; so does fxjps_set_queries),
  *   - grid_ids[q], the start and the goal equal that call's values for q,
  *   - the slot's generation is the one recorded then (a counter per slot, kept by the library: fxjps_set_grid_slot and
  *     fxjps_prepare_slots bump it for every slot they name, fxjps_refresh_slots for every job it did not report kept), and
@@ -744,7 +744,8 @@ int fxjps_waypoint_ccst(const int32_t* cells, int32_t n, const uint8_t* occ, int
 
 /* ---- The same for every path of a batch.  offsets / cells_xy: the paths as fxjps_plan_batch_csr returns them (nq + 1
  * offsets, (x, y) pairs); both NULL: the paths of the handle's most recent batch, which are still resident on the
- * device(s) -- nq must be that batch's (after a grid-slots batch: fxjps_waypoint_st_batch takes its paths, which lie
+ * device(s) -- nq must be that batch's; they are cells of the grid that was resident when that batch ran, whatever has been
+ * made resident since (after a grid-slots batch: fxjps_waypoint_st_batch takes its paths, which lie
  * within the largest slot it named; fxjps_waypoint_ccst_batch refuses with FXJPS_E_ARG, its line tests read the
  * resident grid: fxjps_waypoint_slots_batch below is the call for such a batch).  A query without a path gets the goal as its waypoint (`wp = global_goal`,
  * scripts/global_planner_st.py:287-290, scripts/global_planner_ccst.py:481-485).  pos, goal, out_wp, out_goal are nq x 3
