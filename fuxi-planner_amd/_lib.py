@@ -13,7 +13,8 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 830  # FXJPS_VERSION of include/fxjps.h
+VERSION = 840  # FXJPS_VERSION of include/fxjps.h
+PATH_VALID, PATH_EMPTY, PATH_BLOCKED, PATH_OUTSIDE, PATH_MALFORMED = 1, 0, 2, 3, -1  # FXJPS_PATH_*: fxjps_check_path's verdicts
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
            "fxjps_set_grid", "fxjps_set_grid_device", "fxjps_prepare_grid", "fxjps_prepare_occupancy_msg", "fxjps_get_grid", "fxjps_get_grid_context", "fxjps_publish_map", "fxjps_set_grid_image", "fxjps_snapshot_image", "fxjps_update_cells", "fxjps_update_cells_deferred", "fxjps_set_queries", "fxjps_replan_frame", "fxjps_plan_batch",
@@ -26,7 +27,8 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_prepare_slots_cropped", "fxjps_refresh_slots_cropped", "fxjps_crop_size",
            "fxjps_refresh_grid", "fxjps_refresh_occupancy_msg", "fxjps_last_refresh_cells", "fxjps_replan_frame_raw",
            "fxjps_set_grid_slots", "fxjps_refresh_grid_slots", "fxjps_grid_job_size",
-           "fxjps_set_slot_reuse", "fxjps_debug_slot_tiles", "fxjps_debug_slot_read_sets")
+           "fxjps_set_slot_reuse", "fxjps_debug_slot_tiles", "fxjps_debug_slot_read_sets",
+           "fxjps_check_path", "fxjps_check_paths_slots")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
@@ -98,6 +100,8 @@ def bind_host(L):
     L.fxjps_waypoint_ccst.restype = C.c_int
     L.fxjps_waypoint_ccst.argtypes = [p_i32, C.c_int32, p_u8, C.c_int32, C.c_int32, C.c_double, p_f64, p_f64, p_f64, C.c_int32, p_f64, p_f64,
                                       p_i32, p_i32]
+    L.fxjps_check_path.restype = C.c_int
+    L.fxjps_check_path.argtypes = [p_i32, C.c_int32, p_u8, C.c_int32, C.c_int32, p_i32, p_i32, p_i32, p_i32]
     return L
 
 
@@ -282,6 +286,8 @@ def load():
     L.fxjps_tick_outputs_slots.argtypes = [vp, C.c_int64, p_i64, p_i32, p_i32, p_i32, p_i32, p_f64, p_f64, p_f64, p_f64, p_i32, C.c_double,
                                            C.c_double, p_f64, p_i32, p_f64, p_f64, p_i32, p_f64, p_f64, p_i32, p_i32, C.c_int64, p_f64, p_f64,
                                            C.c_int64, p_f64, p_i32, p_i32, C.c_int64, C.c_int32]
+    L.fxjps_check_paths_slots.restype = C.c_int
+    L.fxjps_check_paths_slots.argtypes = [vp, C.c_int64, p_i64, p_i32, p_i32, p_i32, p_i32, p_i32, p_i32]
     bind_host(L)
     _lib = L
     return L

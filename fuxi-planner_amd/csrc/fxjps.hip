@@ -4420,6 +4420,75 @@ int fxjps_tick_outputs_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, con
                          nthreads);
 }
 
+// ------------------------------------------------------------------ kept paths against their slots
+// wp_slots_call's pattern on context 0: everything the host can judge first, then ONE copy in (the queries' records with
+// their slots' occupancy pointers and extents, the offsets and the cells behind them), ONE launch, ONE copy back and one
+// wait, whatever nq is and however many slots are named.  The staging buffers are the waypoint calls' own; nothing a slot,
+// a stored result or a resident path lives in is written.
+int fxjps_check_paths_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                            const int32_t* shift_xy, int32_t* out_verdict, int32_t* out_seg, int32_t* out_cell_xy) {
+    static_assert(fx::CHECK_VALID == FXJPS_PATH_VALID && fx::CHECK_EMPTY == FXJPS_PATH_EMPTY && fx::CHECK_BLOCKED == FXJPS_PATH_BLOCKED &&
+                      fx::CHECK_OUTSIDE == FXJPS_PATH_OUTSIDE && fx::CHECK_MALFORMED == FXJPS_PATH_MALFORMED,
+                  "the kernel's verdicts are the header's");
+    static_assert(sizeof(fx::CheckQuery) % 8 == 0, "the offsets and cells behind the records stay aligned");
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_check_paths_slots")) return rr;
+    if (nq < 0) return fail(h, FXJPS_E_ARG, "query 0: nq = %lld", (long long)nq);
+    if (nq == 0) return FXJPS_OK;
+    if (!offsets && !cells_xy) return fail(h, FXJPS_E_ARG, "query 0: resident paths are not checked: pass the paths explicitly");
+    if (!offsets || !cells_xy || !grid_ids || !out_verdict || !out_seg || !out_cell_xy)
+        return fail(h, FXJPS_E_ARG, "query 0: offsets, cells_xy, grid_ids and the three outputs are required");
+    if (offsets[0] != 0) return fail(h, FXJPS_E_ARG, "query 0: offsets[0] must be 0");
+    for (int64_t q = 0; q < nq; q++) {
+        if (!slot_in_use(h, grid_ids[q]))
+            return fail(h, FXJPS_E_ARG, "query %lld names grid slot %d, which is %s", (long long)q, (int)grid_ids[q],
+                        grid_ids[q] < 0 || grid_ids[q] >= FXJPS_MAX_GRID_SLOTS ? "out of range" : "empty");
+        if (offsets[q + 1] < offsets[q]) return fail(h, FXJPS_E_ARG, "query %lld: offsets must ascend", (long long)q);
+    }
+    DevCtx& d = h->devs[0];
+    const size_t n = (size_t)nq, tot = (size_t)offsets[nq];
+    const size_t in_off = n * sizeof(fx::CheckQuery), in_cells = in_off + (n + 1) * sizeof(long long);
+    const size_t in_bytes = in_cells + tot * 2 * sizeof(int32_t), out_bytes = n * sizeof(fx::CheckResult);
+    const auto run = [&]() -> int {
+        HIPCHK(h, hipSetDevice(d.dev));
+        HIPCHK(h, d.wp.h_recs_in.ensure(in_bytes));
+        HIPCHK(h, d.wp.d_recs_in.ensure(in_bytes));
+        HIPCHK(h, d.wp.h_recs_out.ensure(out_bytes));
+        HIPCHK(h, d.wp.d_recs_out.ensure(out_bytes));
+        fx::CheckQuery* rec = reinterpret_cast<fx::CheckQuery*>(d.wp.h_recs_in.p);
+        for (size_t q = 0; q < n; q++) {
+            const GridBufs& g = d.slots[(size_t)grid_ids[q]];
+            rec[q] = fx::CheckQuery{g.occ.p, g.W, g.H, shift_xy ? shift_xy[2 * q] : 0, shift_xy ? shift_xy[2 * q + 1] : 0};
+        }
+        memcpy(d.wp.h_recs_in.p + in_off, offsets, (n + 1) * sizeof(long long));
+        if (tot > 0) memcpy(d.wp.h_recs_in.p + in_cells, cells_xy, tot * 2 * sizeof(int32_t));
+        HIPCHK(h, hipMemcpyAsync(d.wp.d_recs_in.p, d.wp.h_recs_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+        fx::CheckPathsArgs A;
+        A.in = reinterpret_cast<const fx::CheckQuery*>(d.wp.d_recs_in.p);
+        A.out = reinterpret_cast<fx::CheckResult*>(d.wp.d_recs_out.p);
+        A.cells = reinterpret_cast<const int32_t*>(d.wp.d_recs_in.p + in_cells);
+        A.offsets = reinterpret_cast<const long long*>(d.wp.d_recs_in.p + in_off);
+        A.nq = (long long)nq;
+        hipLaunchKernelGGL(fx::k_check_paths_slots, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, d.stream, A);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(d.wp.h_recs_out.p, d.wp.d_recs_out.p, out_bytes, hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+        return FXJPS_OK;
+    };
+    if (int rc = run()) {
+        drain_all(h);
+        return rc;
+    }
+    const fx::CheckResult* res = reinterpret_cast<const fx::CheckResult*>(d.wp.h_recs_out.p);
+    for (size_t q = 0; q < n; q++) {
+        out_verdict[q] = res[q].verdict;
+        out_seg[q] = res[q].seg;
+        out_cell_xy[2 * q] = res[q].cx;
+        out_cell_xy[2 * q + 1] = res[q].cy;
+    }
+    return FXJPS_OK;
+}
+
 int fxjps_last_timing(fxjps_t* h, fxjps_timing_t* out) {
     if (!h || !out) return FXJPS_E_ARG;
     *out = h->timing;

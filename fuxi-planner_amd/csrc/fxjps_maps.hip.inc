@@ -1849,3 +1849,138 @@ __global__ __launch_bounds__(256) void k_tick_outputs_slots(TickOutputsArgs A) {
         R.dir_back = dir_back;
     }
 }
+
+// ---------------------------------------------------------------- kept paths against their slots (DESIGN.md section 3.19)
+// fxjps_check_paths_slots: does the grid of its slot, as it is now, still allow path q?  One wavefront per path.  The
+// segments are taken 64 at a time, one per lane: its direction, its length (0 from the first malformed segment of the chunk
+// on) and, by a shuffle scan over the lanes, the number of unit steps up to its end.  The chunk's unit steps are then taken
+// in path order, 64 at a time, one per lane: the lane finds its segment in the scanned lengths (a binary search through
+// lane reads), reads the one to three occupancy bytes blocked() of scripts/jps1.py:14-31 reads for that step, and the
+// lowest failing lane of the first group of steps that has one is the answer.  A malformed segment is reported when the
+// steps before it have passed.  The slot's grid comes with the query's record, resolved by the host from the context's slot
+// records when the call is staged, as for k_waypoint_slots.  The verdicts are FXJPS_PATH_* of include/fxjps.h.
+struct CheckQuery {
+    const uint8_t* occ;  // the slot's grid [W][H], obstacle iff non-zero
+    int32_t W, H;
+    int32_t sx, sy;      // every cell of the path is moved by this first
+};
+struct CheckResult {
+    int32_t verdict, seg, cx, cy;
+};
+struct CheckPathsArgs {
+    const CheckQuery* in;      // [nq]
+    CheckResult* out;          // [nq]
+    const int32_t* cells;      // CSR paths: (x, y) pairs
+    const long long* offsets;  // [nq + 1]
+    long long nq;
+};
+constexpr int CHECK_VALID = 1, CHECK_EMPTY = 0, CHECK_BLOCKED = 2, CHECK_OUTSIDE = 3, CHECK_MALFORMED = -1;
+
+__global__ __launch_bounds__(256) void k_check_paths_slots(CheckPathsArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= A.nq) return;
+    const CheckQuery& Q = A.in[q];
+    const uint8_t* occ = reinterpret_cast<const uint8_t*>(rfl64((uint64_t)Q.occ));
+    const long long W = rfli(Q.W), H = rfli(Q.H), sx = rfli(Q.sx), sy = rfli(Q.sy);
+    const long long off = (long long)rfl64((uint64_t)A.offsets[q]);
+    const long long n = (long long)rfl64((uint64_t)A.offsets[q + 1]) - off;
+    const int2* c = reinterpret_cast<const int2*>(A.cells) + off;
+    const auto outside = [&](long long x, long long y) { return x < 0 || x >= W || y < 0 || y >= H; };
+    // the first cell: lane 0 judges it like a step's target and the answer comes back through the same ballot and lane
+    // reads as a step's
+    int verdict = n > 0 ? CHECK_VALID : CHECK_EMPTY;
+    long long seg = -1, fx = -1, fy = -1;
+    {
+        long long x0 = 0, y0 = 0;
+        bool out0 = false;
+        if (n > 0 && lane == 0) {
+            const int2 p0 = c[0];
+            x0 = (long long)p0.x + sx;
+            y0 = (long long)p0.y + sy;
+            out0 = outside(x0, y0);
+        }
+        RECONV();
+        if (__ballot(out0) != 0ull) {
+            verdict = CHECK_OUTSIDE;
+            seg = 0;
+            fx = (long long)rfl64((uint64_t)__shfl(x0, 0, WAVE));
+            fy = (long long)rfl64((uint64_t)__shfl(y0, 0, WAVE));
+        }
+    }
+    const long long nseg = n - 1;
+    for (long long s0 = 0; verdict == CHECK_VALID && s0 < nseg; s0 += WAVE) {
+        // ---- this lane's segment
+        const long long s = s0 + lane;
+        long long ax = 0, ay = 0, len = 0;
+        int ux = 0, uy = 0;
+        bool bad = false;
+        if (s < nseg) {
+            const int2 a = c[s], b = c[s + 1];
+            const long long dx = (long long)b.x - a.x, dy = (long long)b.y - a.y;
+            const long long mx = dx < 0 ? -dx : dx, my = dy < 0 ? -dy : dy;
+            bad = (dx == 0 && dy == 0) || (dx != 0 && dy != 0 && mx != my);
+            len = mx > my ? mx : my;
+            ux = (dx > 0) - (dx < 0);
+            uy = (dy > 0) - (dy < 0);
+            ax = (long long)a.x + sx;
+            ay = (long long)a.y + sy;
+        }
+        RECONV();
+        const uint64_t bm = __ballot(bad);
+        const int mlane = bm != 0ull ? (int)__builtin_ctzll(bm) : WAVE;  // the walk ends in front of the first malformed segment
+        if (lane >= mlane) len = 0;
+        long long incl = len;  // unit steps up to the end of this lane's segment
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const long long t = __shfl_up(incl, o, WAVE);
+            if (lane >= o) incl += t;
+        }
+        const long long T = (long long)rfl64((uint64_t)__shfl(incl, WAVE - 1, WAVE));
+        // ---- the chunk's unit steps, 64 at a time
+        for (long long t0 = 0; t0 < T; t0 += WAVE) {
+            const long long t = t0 + lane;
+            int j = 0;  // the step's segment: the first whose scanned length exceeds t
+            for (int w = WAVE / 2; w > 0; w >>= 1) {
+                const long long v = __shfl(incl, j + w - 1, WAVE);
+                if (v <= t) j += w;
+            }
+            const long long k = t - (__shfl(incl, j, WAVE) - __shfl(len, j, WAVE));  // steps of that segment already taken
+            const long long bx = __shfl(ax, j, WAVE), by = __shfl(ay, j, WAVE);
+            const int vx = __shfl(ux, j, WAVE), vy = __shfl(uy, j, WAVE);
+            const long long cx = bx + vx * k, cy = by + vy * k, tx = cx + vx, ty = cy + vy;
+            int f = 0;
+            if (t < T) {
+                if (outside(cx, cy) || outside(tx, ty)) {  // (a step from outside: the step that left the grid is an earlier one)
+                    f = CHECK_OUTSIDE;
+                } else {
+                    bool o = occ[(size_t)tx * (size_t)H + (size_t)ty] != 0;
+                    if (!o && vx != 0 && vy != 0) o = occ[(size_t)tx * (size_t)H + (size_t)cy] != 0 && occ[(size_t)cx * (size_t)H + (size_t)ty] != 0;
+                    if (o) f = CHECK_BLOCKED;
+                }
+            }
+            RECONV();
+            const uint64_t fm = __ballot(f != 0);
+            if (fm != 0ull) {
+                const int fl = (int)__builtin_ctzll(fm);
+                verdict = rfli(__shfl(f, fl, WAVE));
+                seg = s0 + rfli(__shfl(j, fl, WAVE));
+                fx = (long long)rfl64((uint64_t)__shfl(tx, fl, WAVE));
+                fy = (long long)rfl64((uint64_t)__shfl(ty, fl, WAVE));
+                break;
+            }
+        }
+        if (verdict == CHECK_VALID && bm != 0ull) {
+            verdict = CHECK_MALFORMED;
+            seg = s0 + mlane;
+            fx = (long long)rfl64((uint64_t)__shfl(ax, mlane, WAVE));
+            fy = (long long)rfl64((uint64_t)__shfl(ay, mlane, WAVE));
+        }
+    }
+    if (lane == 0) {
+        CheckResult& R = A.out[q];
+        R.verdict = verdict;
+        R.seg = (int32_t)seg;
+        R.cx = (int32_t)fx;
+        R.cy = (int32_t)fy;
+    }
+}

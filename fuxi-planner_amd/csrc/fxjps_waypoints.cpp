@@ -154,4 +154,39 @@ int fxjps_waypoint_ccst(const int32_t* cells, int32_t n, const uint8_t* occ, int
     return FXJPS_OK;
 }
 
+// ------------------------------------------------------------------ is a kept path still allowed by a grid
+// The jump points of a path, moved by `shift`, walked unit step by unit step with blocked() of scripts/jps1.py:14-31 on occ
+// (obstacle iff non-zero).  The first failing step in path order decides; the start cell's own occupancy is not read.
+int fxjps_check_path(const int32_t* cells_xy, int32_t n, const uint8_t* occ, int32_t W, int32_t H, const int32_t* shift_xy,
+                     int32_t* out_verdict, int32_t* out_seg, int32_t* out_cell_xy) {
+    if (n < 0 || (n > 0 && !cells_xy) || !occ || W < 1 || H < 1 || !out_verdict || !out_seg || !out_cell_xy) return FXJPS_E_ARG;
+    const int64_t sx = shift_xy ? shift_xy[0] : 0, sy = shift_xy ? shift_xy[1] : 0;
+    const auto done = [&](int verdict, int64_t seg, int64_t x, int64_t y) {
+        *out_verdict = verdict;
+        *out_seg = (int32_t)seg;
+        out_cell_xy[0] = (int32_t)x;
+        out_cell_xy[1] = (int32_t)y;
+        return FXJPS_OK;
+    };
+    const auto outside = [&](int64_t x, int64_t y) { return x < 0 || x >= W || y < 0 || y >= H; };
+    const auto at = [&](int64_t x, int64_t y) { return occ[(size_t)x * (size_t)H + (size_t)y] != 0; };
+    if (n == 0) return done(FXJPS_PATH_EMPTY, -1, -1, -1);
+    int64_t cx = (int64_t)cells_xy[0] + sx, cy = (int64_t)cells_xy[1] + sy;
+    if (outside(cx, cy)) return done(FXJPS_PATH_OUTSIDE, 0, cx, cy);
+    for (int32_t i = 0; i + 1 < n; i++) {
+        const int64_t dx = (int64_t)cells_xy[2 * i + 2] - cells_xy[2 * i], dy = (int64_t)cells_xy[2 * i + 3] - cells_xy[2 * i + 1];
+        const int64_t ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+        if ((dx == 0 && dy == 0) || (dx != 0 && dy != 0 && ax != ay)) return done(FXJPS_PATH_MALFORMED, i, cx, cy);
+        const int64_t ux = (dx > 0) - (dx < 0), uy = (dy > 0) - (dy < 0);
+        for (int64_t k = std::max(ax, ay); k > 0; k--) {
+            const int64_t tx = cx + ux, ty = cy + uy;
+            if (outside(tx, ty)) return done(FXJPS_PATH_OUTSIDE, i, tx, ty);
+            if (at(tx, ty) || (ux != 0 && uy != 0 && at(tx, cy) && at(cx, ty))) return done(FXJPS_PATH_BLOCKED, i, tx, ty);
+            cx = tx;
+            cy = ty;
+        }
+    }
+    return done(FXJPS_PATH_VALID, -1, -1, -1);
+}
+
 }  // extern "C"

@@ -603,16 +603,83 @@ class Planner(object):
         return [([j.origin[0], j.origin[1]], (j.canvas_W, j.canvas_H), [j.canvas_o[0], j.canvas_o[1]]) for j in arr[:n]]
 
     def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
-                         reuse=False, crop=False):
+                         reuse=False, crop=False, throttle=None, check_kept=True):
         """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
         prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
         job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
         (reuse=True plans through replan_slots).  crop=True: the jobs hold the ccst node's map MESSAGES and are prepared
         through prepare_slots_cropped / refresh_slots_cropped; every record has a further key, not_planned (bool), and a
-        vehicle that is not planned on this tick (ccst:351) or was refused has ok False."""
+        vehicle that is not planned on this tick (ccst:351) or was refused has ok False.  throttle / check_kept: the ccst
+        node's replan throttle, as fleet_tick_throttled describes it."""
         jobs = list(jobs)
         return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
-                                image_channels, reuse, world=True, crop=crop)
+                                image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept)
+
+    def check_paths_slots(self, grid_ids, offsets, cells, shift=None):
+        """Which kept paths do their slots' grids, as they are now, still allow (fxjps_check_paths_slots: one launch for
+        the fleet, one wavefront per path): path q -- cells[offsets[q]:offsets[q + 1]], jump points as the plan calls return
+        them -- is moved by the integer shift[q] (one pair, n x 2, or None) and walked unit step by unit step on the grid of
+        slot grid_ids[q] with blocked() of scripts/jps1.py:14-31.  -> (verdict int32[n], seg int32[n], cell int32[n, 2]) as
+        waypoints.check_path gives them path by path on get_grid_slot(grid_ids[q]).  Nothing of the handle changes."""
+        ids = np.ascontiguousarray(grid_ids, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n = len(ids)
+        if len(off) != n + 1:
+            raise ValueError("%d offsets for %d paths" % (len(off), n))
+        c = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        if n and int(off.max()) > c.shape[0]:
+            raise ValueError("the offsets name %d cells, there are %d" % (int(off.max()), c.shape[0]))
+        if c.shape[0] == 0:
+            c = np.zeros((1, 2), dtype=np.int32)  # (empty paths only: the pointer is still required)
+        s = None if shift is None else np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.int32), (n, 2)))
+        verdict, seg, cell = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+        self._chk(self._L.fxjps_check_paths_slots(self._h, n, _lib.ptr(off, C.c_int64), _lib.ptr(c, C.c_int32), _lib.ptr(ids, C.c_int32),
+                                                  None if s is None else _lib.ptr(s, C.c_int32), _lib.ptr(verdict, C.c_int32),
+                                                  _lib.ptr(seg, C.c_int32), _lib.ptr(cell, C.c_int32)))
+        return verdict, seg, cell
+
+    def fleet_tick_throttled(self, jobs, pos, global_goals, home, map_reso, map_o, throttle, prev_wp=None, prev_dim=None, publish=True,
+                             image_channels=None, check_kept=True):
+        """fleet_tick under the ccst node's replan throttle (global_planner_ccst.py:476): a vehicle is searched again only
+        when it has moved more than 0.3 m since its last search, 0.3 s have passed, or nothing has been searched yet; on
+        every other tick it republishes the outputs of its last search with a new pointw.z and its new map.  (A sibling
+        method: fleet_tick's parameter list is pinned; fleet_tick_refresh and fleet_tick_world take throttle= / check_kept=
+        themselves.)
+
+        throttle: a replan.FleetThrottle(len(jobs)); it also keeps every vehicle's previous record, the caller keeps no
+        state.  The maps of ALL vehicles are prepared and published as in fleet_tick.  due = throttle.due(pos); a vehicle
+        without a previous record, or whose previous record has ok False, is due.  check_kept (the node does not do this:
+        it republishes a kept path whatever the new map says): the live, not-due vehicles whose previous record holds a
+        path are checked in ONE check_paths_slots call against this tick's slots, each path moved by shift = (previous
+        origin - this tick's origin) / reso -- the previous origin being that of the tick the path was searched on, which
+        the throttle keeps while the path is kept; a vehicle whose resolution changed, whose shift is farther than 1e-6 from a
+        whole number of cells on either axis, or whose verdict is not PATH_VALID is forced due.  The due vehicles are
+        planned and post-processed as fleet_tick does it, over the due subset (with reuse=True through replan_slots, which
+        compares by query index: a subset that changes from tick to tick reuses less, never wrongly), then
+        throttle.mark(due, pos[due]).
+
+        -> fleet_tick's records with four further keys: cells (the path's int32 cells, so that it can be checked later),
+        due (bool), forced (bool: due only because of the check) and path_check (the verdict, None if not checked).  A
+        not-due vehicle's record takes status, cost, wp, dim, goal_out, ang_wp, n_kept, path, dir_path, dir_back and cells
+        from its previous record and start, goal, map_d, shape, end_occu, origin, msg, image (and kept) from this tick;
+        point is (wp[0], wp[1], z) with z by st:335 / ccst:559-562 from this tick's pos and end_occu; reused, where the
+        records have it, is False."""
+        return self._fleet_tick(False, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
+                                throttle=throttle, check_kept=check_kept)
+
+    @staticmethod
+    def _point_z(variant, wp, goal_out, home, pos, end_occu):
+        """pointw.z of st:335 / ccst:559-562 in the arithmetic of the tick-outputs call's host form (IEEE multiply, add,
+        divide and sqrt; min is Python's: 1 iff 1 < r)."""
+        f = np.float64
+        with np.errstate(all="ignore"):
+            def norm2(x, y):
+                return np.sqrt(f(x) * f(x) + f(y) * f(y))
+            if variant == 1 and (norm2(f(goal_out[0]) - f(pos[0]), f(goal_out[1]) - f(pos[1])) < 0.5 or end_occu != 0):
+                return f(0.0)
+            r = norm2(f(wp[0]) - f(home[0]), f(wp[1]) - f(home[1])) / norm2(f(goal_out[0]) - f(home[0]), f(goal_out[1]) - f(home[1]))
+            r1 = f(1.0) if 1.0 < r else r
+            return f(1.0) + r1 * (f(goal_out[2]) - f(1.0))
 
     def publish_slots(self, slots, msg=True, image_channels=None):
         """The fleet's publishing quarter of a tick in ONE call (fxjps_publish_slots): for every slot named what publish_map
@@ -656,18 +723,24 @@ class Planner(object):
         return self._fleet_tick(False, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels)
 
     def fleet_tick_refresh(self, jobs, pos, global_goals, home, map_reso, map_o, prev_wp=None, prev_dim=None, publish=True, image_channels=None,
-                           reuse=False):
+                           reuse=False, throttle=None, check_kept=True):
         """fleet_tick for the tick after: the maps are prepared through refresh_slots, so a vehicle whose prepared map is
         what its slot already holds keeps the slot's maps.  The same arguments, the same records, and in every live
         vehicle's record a further key, kept (bool).  reuse=True: the batch is planned through replan_slots, so a vehicle
         whose slot was kept and whose start and goal cells did not move is not searched again; its record says so in a
         further key, reused (bool).  Every other value is what reuse=False gives.  After set_slot_reuse("tiles") a vehicle
         whose slot changed only where its path's search did not read is not searched either: reused is True and a further
-        key, reused_tiles (bool), says that this was why."""
-        return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse)
+        key, reused_tiles (bool), says that this was why.  throttle (a replan.FleetThrottle) / check_kept: the ccst
+        node's replan throttle, as fleet_tick_throttled describes it; with throttle=None nothing of that runs and the
+        records are what they were."""
+        return self._fleet_tick(True, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse,
+                                throttle=throttle, check_kept=check_kept)
 
     def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
-                    world=False, crop=False):
+                    world=False, crop=False, throttle=None, check_kept=True):
+        if throttle is not None:
+            return self._fleet_tick_throttled(refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
+                                              reuse, world, crop, throttle, check_kept)
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -716,6 +789,109 @@ class Planner(object):
                 recs[v]["reused"] = bool(reused[i])
                 if self._slot_reuse == 1:
                     recs[v]["reused_tiles"] = int(reused[i]) == 2
+        return recs
+
+    def _fleet_tick_throttled(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
+                              reuse, world, crop, throttle, check_kept):
+        """_fleet_tick under a replan.FleetThrottle (fleet_tick_throttled's docstring): the same calls in the same order, the
+        plan and the tick outputs over the due vehicles only, one check_paths_slots call in front of them."""
+        from . import waypoints
+        jobs = list(jobs)
+        n = len(jobs)
+        if throttle.n != n:
+            raise ValueError("the throttle is for %d vehicles, the tick has %d" % (throttle.n, n))
+        pos = np.asarray(pos, dtype=np.float64).reshape(n, 3)
+        goals = np.asarray(global_goals, dtype=np.float64).reshape(n, 3)
+        home = np.broadcast_to(np.asarray(home, dtype=np.float64), (n, 2))
+        reso = np.broadcast_to(np.asarray(map_reso, dtype=np.float64), (n,))
+        orig = None if world else np.broadcast_to(np.asarray(map_o, dtype=np.float64), (n, 2))
+        keys = ("status", "cost", "start", "goal", "map_d", "shape", "end_occu", "origin", "wp", "dim", "goal_out", "ang_wp", "n_kept", "point",
+                "path", "dir_path", "dir_back", "msg", "image", "cells", "path_check")
+        recs = [dict({"ok": False, "due": True, "forced": False}, **{k: None for k in keys}) for _ in range(n)]
+        # ---- every vehicle's map, as without a throttle
+        if crop:
+            outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
+            for v in range(n):
+                recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
+            outs = [o[:-2] for o in outs]
+        elif world:
+            outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
+        else:
+            outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
+        variant_at = 7 if world else 5
+        variant = [{"st": 0, "ccst": 1}[j[variant_at]] if isinstance(j[variant_at], str) else int(j[variant_at]) for j in jobs]
+        live = [v for v in range(n) if outs[v][5]]
+        origin = {v: outs[v][-3] if world else Planner.shifted_origin(orig[v], outs[v][2], reso[v]) for v in live}
+        # ---- who is due: the node's condition, then the kept paths against this tick's slots
+        prev = throttle.records
+        due = throttle.due(pos)
+        for v in range(n):
+            if prev[v] is None or not prev[v]["ok"]:
+                due[v] = True
+        if check_kept:
+            ask, shifts = [], []
+            for v in live:
+                if due[v] or prev[v]["status"] <= 0:
+                    continue
+                # (the kept cells are cells of the grid the vehicle was last SEARCHED on: the previous record's origin when that
+                # was a search tick, and the throttle's copy of it on every later one)
+                s = (throttle.search_origin[v] - np.asarray(origin[v], dtype=np.float64)) / reso[v]
+                if throttle.search_reso[v] != reso[v] or not np.all(np.abs(s - np.rint(s)) <= 1e-6):
+                    due[v] = recs[v]["forced"] = True
+                    continue
+                ask.append(v)
+                shifts.append(np.rint(s).astype(np.int32))
+            if ask:
+                off = np.concatenate([[0], np.cumsum([len(prev[v]["cells"]) for v in ask])]).astype(np.int64)
+                verdict, _, _ = self.check_paths_slots([int(jobs[v][0]) for v in ask], off, np.concatenate([prev[v]["cells"] for v in ask]),
+                                                       np.array(shifts, dtype=np.int32))
+                for i, v in enumerate(ask):
+                    recs[v]["path_check"] = int(verdict[i])
+                    if verdict[i] != _lib.PATH_VALID:
+                        due[v] = recs[v]["forced"] = True
+        # ---- the due vehicles: planned and post-processed as without a throttle
+        go = [v for v in live if due[v]]
+        if go:
+            offsets, cells, cost, status, reused = self._plan_slots(reuse, [int(jobs[v][0]) for v in go], [outs[v][0] for v in go],
+                                                                    [outs[v][1] for v in go], 2, None)
+            pw = pd = None
+            if prev_wp is not None:
+                pw = np.asarray(prev_wp, dtype=np.float64).reshape(n, 3)[go]
+                pd = np.asarray(prev_dim, dtype=np.int32).reshape(n)[go]
+            wp, dim, gout, ang, nk, point, paths, dirs, back = waypoints.tick_outputs_slots(
+                self, [variant[v] for v in go], [outs[v][0] for v in go], reso[go], [origin[v] for v in go], pos[go], goals[go], home[go],
+                [outs[v][4] for v in go], pw, pd, offsets=offsets)
+            for i, v in enumerate(go):
+                recs[v].update(status=int(status[i]), cost=float(cost[i]), wp=wp[i, :dim[i]], dim=int(dim[i]), goal_out=gout[i], ang_wp=float(ang[i]),
+                               n_kept=int(nk[i]), point=point[i], path=paths[i], dir_path=dirs[i], dir_back=int(back[i]),
+                               cells=cells[int(offsets[i]):int(offsets[i + 1])].copy())
+                if reuse:
+                    recs[v]["reused"] = bool(reused[i])
+                    if self._slot_reuse == 1:
+                        recs[v]["reused_tiles"] = int(reused[i]) == 2
+            throttle.mark(go, pos[go])
+            throttle.search_origin[go] = [origin[v] for v in go]
+            throttle.search_reso[go] = reso[go]
+        pub = None
+        if live and (publish or image_channels is not None):
+            pub = self.publish_slots([int(jobs[v][0]) for v in live], msg=publish, image_channels=image_channels)
+        for i, v in enumerate(live):
+            o, r = outs[v], recs[v]
+            r.update(ok=True, due=bool(due[v]), start=o[0], goal=o[1], map_d=o[2], shape=o[3], end_occu=o[4], origin=origin[v])
+            if pub is not None:
+                r.update(msg=pub[i][0], image=pub[i][2])
+            if refresh:
+                r["kept"] = o[6]
+            if not due[v]:  # the outputs of the vehicle's last search, pointw.z anew (ccst:559-562 / st:335)
+                p = prev[v]
+                for k in ("status", "cost", "wp", "dim", "goal_out", "ang_wp", "n_kept", "path", "dir_path", "dir_back", "cells"):
+                    r[k] = p[k]
+                r["point"] = np.array([p["wp"][0], p["wp"][1], Planner._point_z(variant[v], p["wp"], p["goal_out"], home[v], pos[v], o[4])])
+                if reuse:
+                    r["reused"] = False
+                    if self._slot_reuse == 1:
+                        r["reused_tiles"] = False
+        throttle.records = list(recs)
         return recs
 
     def plan_batch_slots(self, grid_ids, starts, goals, hchoice=2, max_path_len=None):

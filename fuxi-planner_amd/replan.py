@@ -76,6 +76,44 @@ class ReplanThrottle(object):
         self.last_time = self.clock()
 
 
+class FleetThrottle(object):
+    """ReplanThrottle for n vehicles: element by element its state and its condition (the `last_pos[0] == 0` quirk
+    included; the norm is taken vehicle by vehicle, as the node takes it).  The throttled fleet ticks
+    (Planner.fleet_tick_throttled, fleet_tick_refresh / fleet_tick_world with throttle=) also keep every vehicle's previous
+    record here, in `records`, so a host needs no state of its own.
+
+        throttle = FleetThrottle(len(jobs))
+        while flying:
+            recs = planner.fleet_tick_refresh(jobs, pos, goals, home, reso, map_o, throttle=throttle)
+    """
+
+    def __init__(self, n, min_move=0.3, min_interval=0.3, clock=time.time):
+        self.n = int(n)
+        self.min_move = min_move
+        self.min_interval = min_interval
+        self.clock = clock
+        self.last_pos = np.zeros((self.n, 3))  # ccst:311
+        self.last_time = np.zeros(self.n)      # ccst:312
+        self.records = [None] * self.n         # each vehicle's record of the tick before
+        self.search_origin = np.full((self.n, 2), np.nan)  # origin and resolution of the grid each vehicle was last searched
+        self.search_reso = np.full(self.n, np.nan)         # on: the frame of the kept record's cells
+
+    def due(self, pos):
+        """ccst:476 per vehicle.  pos: n x 3.  -> bool[n]"""
+        p = np.asarray(pos, dtype=np.float64).reshape(self.n, 3)
+        now = self.clock()
+        return np.array([bool(self.last_pos[v, 0] == 0 or np.linalg.norm(self.last_pos[v] - p[v]) > self.min_move or
+                              now - self.last_time[v] > self.min_interval) for v in range(self.n)], dtype=bool)
+
+    def mark(self, idx, pos):
+        """ccst:479-480 for the vehicles idx; pos: their positions (len(idx) x 3)."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if len(idx) == 0:
+            return
+        self.last_pos[idx] = np.asarray(pos, dtype=np.float64).reshape(len(idx), 3)
+        self.last_time[idx] = self.clock()
+
+
 class FramePipeline(object):
     """Streaming replan with several frames in flight (BASELINE config 5: a 60 Hz *rate*).
 

@@ -82,6 +82,31 @@ def select_ccst(path, mapu, map_reso, map_o, pos, global_goal, end_occu=0, retur
     return wp, kept[:nk.value].copy()
 
 
+def check_path(path, occ, shift=None):
+    """Does the grid still allow a kept path (fxjps_check_path, host code): every unit step of the jump-point path, moved by
+    the integer `shift` (sx, sy) first, judged by blocked() of scripts/jps1.py:14-31 on occ -- the uint8 [W][H] bytes a slot
+    holds (get_grid_slot), obstacle iff non-zero; an array of another type counts as != 0.  The path may be empty.
+    -> (verdict, seg, (x, y)): _lib.PATH_VALID / PATH_EMPTY (seg -1, cell (-1, -1)), or PATH_BLOCKED / PATH_OUTSIDE /
+    PATH_MALFORMED with the segment of the first failing step and that step's target cell in shifted coordinates
+    (malformed: the segment's first cell)."""
+    L = _L()
+    c = np.ascontiguousarray(np.asarray(path, dtype=np.int32).reshape(-1, 2))
+    g = np.asarray(occ)
+    g = np.ascontiguousarray(g if g.dtype == np.uint8 else (g != 0).view(np.uint8))
+    if g.ndim != 2:
+        raise ValueError("grid must be 2-D")
+    s = None if shift is None else np.ascontiguousarray(np.asarray(shift, dtype=np.int32).ravel())
+    if s is not None and s.shape[0] != 2:
+        raise ValueError("expected 2 components")
+    verdict, seg = C.c_int32(0), C.c_int32(0)
+    cell = np.zeros(2, dtype=np.int32)
+    rc = L.fxjps_check_path(_lib.ptr(c, C.c_int32), c.shape[0], _lib.ptr(g, C.c_uint8), g.shape[0], g.shape[1],
+                            None if s is None else _lib.ptr(s, C.c_int32), C.byref(verdict), C.byref(seg), _lib.ptr(cell, C.c_int32))
+    if rc != 0:
+        raise _lib.FxjpsError(rc, "fxjps_check_path: bad argument")
+    return verdict.value, seg.value, (int(cell[0]), int(cell[1]))
+
+
 def _batch_vec(v, n):
     a = np.asarray(v, dtype=np.float64)
     if a.ndim == 1:

@@ -111,8 +111,10 @@ typedef struct fxjps fxjps_t;
  *   830  fxjps_set_slot_reuse (fxjps_replan_slots under the tile rule: a refresh that changed a slot's bytes records which
  *        read-set tiles the changed cells touch, and a stored path whose read set misses them all is handed back without
  *        a search, out_reused 2), fxjps_debug_slot_tiles, fxjps_debug_slot_read_sets.
+ *   840  fxjps_check_path, fxjps_check_paths_slots (does a grid still allow a kept path: every unit step of the path judged
+ *        by the reference's blocked(); the slots form checks a fleet's kept paths against their slots in one launch).
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 830
+#define FXJPS_VERSION 840
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -847,6 +849,42 @@ int fxjps_tick_outputs_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, con
                              double* out_ang_wp, int32_t* out_n_kept, int32_t* out_kept_cells, int64_t kept_capacity, double* out_point,
                              double* out_path_xyz, int64_t path_capacity, double* out_dir_xyz, int32_t* out_dir_n, int32_t* out_dir_back,
                              int64_t dir_capacity, int32_t nthreads);
+
+/* ---- Does a grid still allow a kept path (version 840).  The ccst node republishes the path of its last search for up to
+ * 0.3 s whatever the new map says (global_planner_ccst.py:476); a host that keeps paths asks here which of them the new
+ * grid still allows.
+ *
+ * A path is n jump points p_0 .. p_{n-1} ((x, y) pairs, as the plan calls return them) on occ[W][H], obstacle iff non-zero.
+ * Every cell is first moved by shift (sx, sy) (NULL: 0, 0): a path kept from a grid whose origin lay elsewhere.  Segments
+ * are walked in order; for segment i, d = p_{i+1} - p_i:
+ *   d == (0, 0), or |dx| != |dy| with both non-zero: FXJPS_PATH_MALFORMED at segment i (cell: p_i + shift);
+ *   else max(|dx|, |dy|) unit steps c -> c + u, u = (sgn dx, sgn dy):
+ *     target outside the grid: FXJPS_PATH_OUTSIDE (also p_0 + shift outside: segment 0, cell p_0 + shift);
+ *     blocked(c, ux, uy) of scripts/jps1.py:14-31 -- straight: the target is occupied; diagonal: the target is occupied, or
+ *     both orthogonal neighbours are: FXJPS_PATH_BLOCKED.
+ * The first failing step in path order decides verdict, segment and cell (the step's target c + u, shifted coordinates).
+ * The occupancy of p_0 itself is not read (the reference searches from an occupied start).  n == 0: FXJPS_PATH_EMPTY;
+ * n == 1 inside the grid: FXJPS_PATH_VALID.  out_seg is -1 and out_cell_xy (-1, -1) for VALID and EMPTY.
+ *
+ * fxjps_check_path: host function, no handle, no device.  FXJPS_E_ARG: n < 0, W or H < 1, a NULL pointer but shift_xy.
+ *
+ * fxjps_check_paths_slots: nq paths as explicit CSR (offsets nq + 1, cells_xy; resident paths, NULL / NULL, are refused),
+ * path q against the grid of slot grid_ids[q] AS IT IS WHEN THE CALL RUNS, moved by shift_xy[2 q .. 2 q + 1] (NULL: no
+ * shifts).  One wavefront per path on context 0: one staged copy in, one launch, one copy back and one wait, whatever nq is
+ * and however many slots are named.  Query by query the three outputs (nq, nq, nq x 2) equal fxjps_check_path on the bytes
+ * fxjps_get_grid_slot(grid_ids[q]) returns.  nq == 0 returns FXJPS_OK.  Refused with FXJPS_E_ARG, nothing queued,
+ * fxjps_last_error naming the first offending query: a slot out of range or empty, offsets that do not begin at 0 or do not
+ * ascend, a NULL pointer but shift_xy, a handle of fxjps_create_rank with world > 1.  The call changes no slot, generation,
+ * resident grid, stored result or resident path. */
+#define FXJPS_PATH_VALID 1
+#define FXJPS_PATH_EMPTY 0
+#define FXJPS_PATH_BLOCKED 2
+#define FXJPS_PATH_OUTSIDE 3
+#define FXJPS_PATH_MALFORMED (-1)
+int fxjps_check_path(const int32_t* cells_xy, int32_t n, const uint8_t* occ, int32_t W, int32_t H, const int32_t* shift_xy,
+                     int32_t* out_verdict, int32_t* out_seg, int32_t* out_cell_xy);
+int fxjps_check_paths_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, const int32_t* cells_xy, const int32_t* grid_ids,
+                            const int32_t* shift_xy, int32_t* out_verdict, int32_t* out_seg, int32_t* out_cell_xy);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
