@@ -813,6 +813,7 @@ int ensure_pool(fxjps* h, DevCtx& d, const BatchReq& req, int pool, uint32_t wan
         c.nwaves = want_waves;
     }
     c.far_cap = (c.far_cap + 7u) & ~7u;  // the u16 cell-info array behind the entries stays 16-byte granular
+    // (one size for both open-list layouts: the slotless instantiations keep the cell info inside the entry and leave that array alone)
     const size_t per_wave = ((size_t)fx::BUCKET * c.nbuckets) * sizeof(TEnt) + (size_t)(c.far_cap + c.far_cap / 8) * sizeof(FarEnt);
     uint32_t maxw = (uint32_t)std::min<size_t>(budget / per_wave, 1u << 20);
     maxw = (uint32_t)wpb_down(maxw);
@@ -957,6 +958,7 @@ int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint
         const SearchKernel k = search_kernel(req.hchoice, track, c.direct_ly > 0, req.slots);
         const SearchFn fn = k.fn;
         static const size_t pad = 36u << 10;  // 66 .. 74 KB of the block's own + this: no second block fits the CU's 160 KB
+                                              // (74 KB + 36 KB = 110 KB fit, 184 KB with a second block do not: tests/test_slotless_open_list_host.py)
         if (nsolo != 0u || live_main != 0u) {
             if (!d.lds_attr_done[k.index]) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad) == hipSuccess) {

@@ -64,7 +64,7 @@ struct __attribute__((aligned(16))) TEnt {  // visited-table entry: gscore / cam
 struct __attribute__((aligned(16))) FarEnt {  // open-list entry spilled to global memory
     uint64_t fbits;  // f as raw bits (f >= +0, so unsigned order == numeric order)
     uint32_t xyd;    // x:13 | y:13 | pd:4   (compare as u32 == (x, y) tuple order)
-    uint32_t slot;
+    uint32_t slot;   // table slot of the node; in the slotless layout (see WaveLdsT) the node's cell info instead
 };
 
 struct __attribute__((aligned(16))) BmWord {  // 64 cells of one scan line
@@ -540,13 +540,32 @@ constexpr int MSLOT = MCAP / WAVE; // M entries a lane looks at when the whole t
 #ifndef FXJPS_HZ_LOG2
 #define FXJPS_HZ_LOG2 9
 #endif
-constexpr int HZ_LOG2 = FXJPS_HZ_LOG2, HZ_SIZE = 1 << HZ_LOG2;
+#ifndef FXJPS_HZ_LOG2_DIRECT
+#define FXJPS_HZ_LOG2_DIRECT 10
+#endif
+// Cells of the slot-collision detector (WaveLds::hz), a property of the instantiation: the untracked searches on
+// cell-indexed tables carry no slot payload in LDS (see SLOTLESS below) and spend what that frees on a detector of twice
+// the size; everywhere else -- the tracking instantiations hold 8 KB of read-set rows per block, the hashed ones keep s[] --
+// it is FXJPS_HZ_LOG2.
+constexpr int HZ_LOG2 = FXJPS_HZ_LOG2, HZ_LOG2_DIRECT = FXJPS_HZ_LOG2_DIRECT;
+static_assert(HZ_LOG2 >= 7 && HZ_LOG2 <= 12 && HZ_LOG2_DIRECT >= 7 && HZ_LOG2_DIRECT <= 12, "detector sizes the hashes and the LDS budget were written for");
 
 // Pointers into LDS carry their address space: through a generic pointer every access becomes a flat_load /
 // flat_store (texture-path latency, and a wait on every outstanding global store) instead of ds_read / ds_write.
 #define LDS_PTR(T) __attribute__((address_space(3))) T*
 
-struct WaveLds {  // LDS of one wavefront.  One base pointer: every array below is an immediate offset of the ds_* instruction
+// The layout of the open list is a property of the instantiation.  On a table indexed by the cell a node's slot is a
+// function of its cell (slot = x << direct_ly | y), so an open-list entry need not carry it: the SLOTLESS layout has no
+// slot in R (RTier::s is never touched and takes no register), none in M, and the fourth dword of a far entry holds the
+// entry's cell info instead (nothing is kept in the u16 array behind the entries).  The slot is derived where it is first
+// needed, at the lane deal.  The carrying layout is the one of the hashed tables, of the tracking searches and of
+// k_selftest_openlist (whose payloads are arbitrary numbers).
+template <bool NOSLOT, int HZL>
+struct WaveLdsT;
+template <int HZL>
+struct WaveLdsT<false, HZL> {  // LDS of one wavefront.  One base pointer: every array below is an immediate offset of the ds_* instruction
+    static constexpr bool SLOTLESS = false;
+    static constexpr int HZ_LOG2 = HZL, HZ_SIZE = 1 << HZL;
     unsigned long long f[MCAP];  // M tier: keys (f as raw bits)
     uint32_t x[MCAP];            //         packed (x, y, direction)
     uint32_t s[MCAP];            //         table slot
@@ -555,8 +574,26 @@ struct WaveLds {  // LDS of one wavefront.  One base pointer: every array below 
     uint32_t hz[HZ_SIZE];        // HZ_SIZE cells (all ones at rest): slot-collision detector of the vectorised commit
     uint32_t bcnt[NBANDS];       // entries in each region of the far band's ring (k_search<2, ..>)
 };
-struct Mid {
-    LDS_PTR(WaveLds) w;
+template <int HZL>
+struct WaveLdsT<true, HZL> {  // the same without the slots
+    static constexpr bool SLOTLESS = true;
+    static constexpr int HZ_LOG2 = HZL, HZ_SIZE = 1 << HZL;
+    unsigned long long f[MCAP];
+    uint32_t x[MCAP];
+    uint16_t c[MCAP];
+    uint16_t idx[WAVE];
+    uint32_t hz[HZ_SIZE];
+    uint32_t bcnt[NBANDS];
+};
+using WaveLds = WaveLdsT<false, HZ_LOG2>;  // the carrying layout
+// what k_search<HC, TRK, DIRECT, MG> runs on
+template <bool TRK, bool DIRECT>
+using SearchLds = WaveLdsT<DIRECT && !TRK, (DIRECT && !TRK) ? HZ_LOG2_DIRECT : HZ_LOG2>;
+template <class WL>
+struct MidT {
+    static constexpr bool SLOTLESS = WL::SLOTLESS;
+    static constexpr int HZ_LOG2 = WL::HZ_LOG2, HZ_SIZE = WL::HZ_SIZE;
+    LDS_PTR(WL) w;
     LDS_PTR(const uint32_t) dirlut;  // block-wide LDS copy of c_dirlut
     LDS_PTR(unsigned long long) bx;  // read set (k_search<HC, true> only), see ReadSet: [64] rows = y tiles, bits = x tiles;
                                      // followed by by[64]: rows = x tiles, bits = y tiles
@@ -564,6 +601,7 @@ struct Mid {
     unsigned long long* dbg;      // diagnostic build: out_counters
 #endif
 };
+using Mid = MidT<WaveLds>;
 #if defined(FXJPS_PROF) && !defined(FXJPS_PROF_LIGHT)  // (FXJPS_PROF_LIGHT: the cycle counters per phase alone, without the event counters' atomics inside the phases)
 #define DBG_COUNT(M, k, v)                                                     \
     do {                                                                       \
@@ -592,12 +630,14 @@ __device__ __forceinline__ void rs_or(LDS_PTR(unsigned long long) row, unsigned 
     __hip_atomic_fetch_or(row, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 // cells a .. b (padded positions, either order) of scan line `line`; alongY: the line is a padded x, positions are y
-__device__ __forceinline__ void rs_mark_scan(const Mid& S, int tsh, bool alongY, int line, int a, int b) {
+template <class MID>
+__device__ __forceinline__ void rs_mark_scan(const MID& S, int tsh, bool alongY, int line, int a, int b) {
     const int tl = rs_tile(line, tsh), ta = rs_tile(min(a, b), tsh), tb = rs_tile(max(a, b), tsh);
     rs_or(alongY ? S.bx + 64 + tl : S.bx + tl, rs_span(ta, tb));
 }
 // a cell whose cell info `m` was read: its own tile, and the tiles its straight sub-jumps reach
-__device__ __forceinline__ void rs_mark_cell(const Mid& S, int tsh, int px, int py, uint32_t m) {
+template <class MID>
+__device__ __forceinline__ void rs_mark_cell(const MID& S, int tsh, int px, int py, uint32_t m) {
     const int tx = rs_tile(px, tsh), ty = rs_tile(py, tsh);
     const int cx = (int)((m >> 12) & 3u), cy = (int)((m >> 14) & 3u);
     rs_or(S.bx + ty, cx == 3 ? ~0ull : rs_span(max(tx - cx, 0), min(tx + cx, 63)));
@@ -640,6 +680,8 @@ __device__ __forceinline__ void key_midpoint(uint64_t lo, uint64_t hi, uint32_t 
 
 // Append the entries held by the lanes of `out` (key (kf, kx), payload ks, kc) to the far tier: to the near band when
 // below the band threshold, else to the far band.  The bands are the two halves of the wavefront's far array.
+// NOSLOT (the slotless layout): the entry is {f, xyd, cell info}, one 16-byte store; ks and fci are not used.
+template <bool NOSLOT>
 __device__ __forceinline__ bool far_append(OpenList& Q, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, uint32_t half, bool check,
                                            bool out, uint64_t kf, uint32_t kx, uint32_t ks, uint32_t kc) {
     const uint64_t om = __ballot(out);
@@ -651,11 +693,11 @@ __device__ __forceinline__ bool far_append(OpenList& Q, FarEnt* __restrict__ far
         FarEnt e;
         e.fbits = kf;
         e.xyd = kx;
-        e.slot = ks;
+        e.slot = NOSLOT ? kc : ks;
         const bool toB = (uint32_t)(kf >> 32) >= Q.T2hi;
         const uint32_t j = (toB ? half + Q.farb_n : Q.far_n) + rank_below(toB ? bm : am);
         far[j] = e;
-        fci[j] = (uint16_t)kc;
+        if (!NOSLOT) fci[j] = (uint16_t)kc;
     }
     RECONV();
     Q.far_n += na;
@@ -677,7 +719,8 @@ __device__ __forceinline__ uint32_t band_shift(uint32_t lo, uint32_t hi, double 
 }
 // The entry held by the lanes of `on` goes to the region of its band (its key is at or above the start of the ring).
 // Returns the lanes whose region is full.
-__device__ __forceinline__ uint64_t ring_put(const OpenList& Q, const Mid& M, FarEnt* __restrict__ far, uint32_t far_cap, bool on,
+template <class MID>
+__device__ __forceinline__ uint64_t ring_put(const OpenList& Q, const MID& M, FarEnt* __restrict__ far, uint32_t far_cap, bool on,
                                              uint64_t kf, uint32_t kx, uint32_t ks) {
     const uint32_t half = far_cap >> 1;
     const uint32_t phys = min(Q.cur0 + (((uint32_t)(kf >> 32) - Q.T2hi) >> Q.hshift), (uint32_t)NBANDS - 1u);
@@ -698,13 +741,14 @@ __device__ __forceinline__ uint64_t ring_put(const OpenList& Q, const Mid& M, Fa
 }
 // Pushes that go to the far tier: below the start of the ring to the near band (appended at their rank, as ever), the
 // others to the ring.
-template <bool BANDED>
-__device__ __forceinline__ bool far_push(OpenList& Q, const Mid& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, uint32_t far_cap,
+template <bool BANDED, class MID>  // (the ring carries slots: it serves the hashed tables only)
+__device__ __forceinline__ bool far_push(OpenList& Q, const MID& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, uint32_t far_cap,
                                          bool out, uint64_t kf, uint32_t kx, uint32_t ks, uint32_t kc) {
-    if (!BANDED || !Q.banded) return far_append(Q, far, fci, far_cap >> 1, true, out, kf, kx, ks, kc);
+    static_assert(!(BANDED && MID::SLOTLESS), "the ring of bands keeps the carrying layout");
+    if (!BANDED || !Q.banded) return far_append<MID::SLOTLESS>(Q, far, fci, far_cap >> 1, true, out, kf, kx, ks, kc);
     const bool toB = out && (uint32_t)(kf >> 32) >= Q.T2hi;
     const uint64_t bm = __ballot(toB);
-    if (__ballot(out && !toB) != 0ull && !far_append(Q, far, fci, far_cap >> 1, true, out && !toB, kf, kx, ks, kc)) return false;
+    if (__ballot(out && !toB) != 0ull && !far_append<MID::SLOTLESS>(Q, far, fci, far_cap >> 1, true, out && !toB, kf, kx, ks, kc)) return false;
     if (bm != 0ull) {
         if (ring_put(Q, M, far, far_cap, toB, kf, kx, ks) != 0ull) return false;
         Q.farb_n += (uint32_t)__popcll(bm);
@@ -713,7 +757,8 @@ __device__ __forceinline__ bool far_push(OpenList& Q, const Mid& M, FarEnt* __re
 }
 
 // Move the M entries with key >= P to the far tier, close the gaps, and make P the M / far threshold.
-__device__ __forceinline__ bool m_evict(OpenList& Q, const Mid& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, int lane,
+template <class MID>
+__device__ __forceinline__ bool m_evict(OpenList& Q, const MID& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, int lane,
                                         uint64_t Pf, uint32_t Px, uint32_t far_cap, bool check = true) {
     open_uniform(Q);
     Pf = rfl64(Pf);
@@ -749,16 +794,16 @@ __device__ __forceinline__ bool m_evict(OpenList& Q, const Mid& M, FarEnt* __res
         const uint64_t km = __ballot(keep);
         uint32_t es = 0, ec = 0;
         if (valid) {
-            es = M.w->s[i];
+            if constexpr (!MID::SLOTLESS) es = M.w->s[i];
             ec = M.w->c[i];
         }
         RECONV();
-        (void)far_append(Q, far, fci, bhalf, false, out, f[k], x[k], es, ec);
+        (void)far_append<MID::SLOTLESS>(Q, far, fci, bhalf, false, out, f[k], x[k], es, ec);
         if (keep) {  // compaction moves entries down only, onto slots every lane has already read
             const uint32_t j = mw + rank_below(km);
             M.w->f[j] = f[k];
             M.w->x[j] = x[k];
-            M.w->s[j] = es;
+            if constexpr (!MID::SLOTLESS) M.w->s[j] = es;
             M.w->c[j] = (uint16_t)ec;
         }
         RECONV();
@@ -771,7 +816,8 @@ __device__ __forceinline__ bool m_evict(OpenList& Q, const Mid& M, FarEnt* __res
 }
 
 // M is full: release its upper half (by key range) to the far tier.
-__device__ __forceinline__ bool m_split(OpenList& Q, const Mid& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, int lane,
+template <class MID>
+__device__ __forceinline__ bool m_split(OpenList& Q, const MID& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci, int lane,
                                         uint32_t far_cap) {
     open_uniform(Q);
     const uint32_t n = Q.m_n;
@@ -805,7 +851,8 @@ __device__ __forceinline__ bool m_split(OpenList& Q, const Mid& M, FarEnt* __res
 
 // R is full: its upper half (it is sorted: the lanes from r_n / 2 on) moves to M; the first key that leaves becomes
 // the R / M threshold.
-__device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci,
+template <class MID>
+__device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const MID& M, FarEnt* __restrict__ far, uint16_t* __restrict__ fci,
                                         int lane, uint32_t far_cap) {
     open_uniform(Q);
     const int keep = Q.r_n / 2;
@@ -819,7 +866,7 @@ __device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, Far
         const uint32_t j = Q.m_n + (uint32_t)(lane - keep);
         M.w->f[j] = R.f;
         M.w->x[j] = R.x;
-        M.w->s[j] = R.s;
+        if constexpr (!MID::SLOTLESS) M.w->s[j] = R.s;
         M.w->c[j] = (uint16_t)R.c;
         R.f = ~0ull;
         R.x = ~0u;
@@ -899,55 +946,115 @@ __device__ __forceinline__ bool r_split(OpenList& Q, RTier& R, const Mid& M, Far
 #define FX_U3 "0xff00ff00", "0xff00ff00"
 #define FX_U4 "0xffff0000", "0xffff0000"
 #define FX_U5 "0", "-1"
-__device__ __forceinline__ void r_sort(RTier& R, int lane, int n) {
-    uint32_t flo = (uint32_t)R.f, fhi = (uint32_t)(R.f >> 32), kx = R.x, ks = R.s, kc = R.c, scr;
-    asm volatile("s_nop 1" : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(ks), "+v"(kc));  // (DPP reads want two wait states behind the VALU writes)
-    // blocks of 2
-    FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
-    // blocks of 4: mirror, then 1
-    FX_BITONIC_DPP("quad_perm:[3,2,1,0]", FX_U1);
-    FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
-    // blocks of 8: mirror, 2, 1
-    FX_BITONIC_DPP("row_half_mirror", FX_U2);
-    FX_BITONIC_DPP("quad_perm:[2,3,0,1]", FX_U1);
-    FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
-    // blocks of 16: mirror, 4, 2, 1
-    FX_BITONIC_DPP("row_mirror", FX_U3);
-    FX_BITONIC_SWZ(4, FX_U2);
-    FX_BITONIC_DPP("quad_perm:[2,3,0,1]", FX_U1);
-    FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
-    if (n > 16) {
-        // blocks of 32: mirror (lane ^ 31), 8, 4, 2, 1
-        FX_BITONIC_SWZ(31, FX_U4);
-        FX_BITONIC_DPP("row_ror:8", FX_U3);
-        FX_BITONIC_SWZ(4, FX_U2);
-        FX_BITONIC_DPP("quad_perm:[2,3,0,1]", FX_U1);
-        FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
+// The same three without the slot (the slotless layout): a stage is 7 vector instructions, and one crossbar transfer less
+// where the partner comes over LDS.
+#define FX_BITONIC3_DPP_(DPPSTR, ULO, UHI)                                                              \
+    asm volatile("s_mov_b32 vcc_lo, " ULO "\n\ts_mov_b32 vcc_hi, " UHI "\n\t"                             \
+                 "v_subb_co_u32_dpp %4, vcc, %2, %2, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"      \
+                 "v_subb_co_u32_dpp %4, vcc, %0, %0, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"      \
+                 "v_subb_co_u32_dpp %4, vcc, %1, %1, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"      \
+                 "s_xnor_b32 vcc_lo, vcc_lo, " ULO "\n\ts_xnor_b32 vcc_hi, vcc_hi, " UHI "\n\t"           \
+                 "v_cndmask_b32_dpp %2, %2, %2, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"           \
+                 "v_cndmask_b32_dpp %0, %0, %0, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"           \
+                 "v_cndmask_b32_dpp %1, %1, %1, vcc " DPPSTR " row_mask:0xf bank_mask:0xf\n\t"           \
+                 "v_cndmask_b32_dpp %3, %3, %3, vcc " DPPSTR " row_mask:0xf bank_mask:0xf"                \
+                 : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(kc), "=&v"(scr)                                   \
+                 :                                                                                        \
+                 : "vcc", "scc")
+#define FX_BITONIC3_XCH_(ULO, UHI)                                                                      \
+    asm volatile("s_mov_b32 vcc_lo, " ULO "\n\ts_mov_b32 vcc_hi, " UHI "\n\t"                             \
+                 "v_subb_co_u32 %4, vcc, %7, %2, vcc\n\t"                                                \
+                 "v_subb_co_u32 %4, vcc, %5, %0, vcc\n\t"                                                \
+                 "v_subb_co_u32 %4, vcc, %6, %1, vcc\n\t"                                                \
+                 "s_xnor_b32 vcc_lo, vcc_lo, " ULO "\n\ts_xnor_b32 vcc_hi, vcc_hi, " UHI "\n\t"           \
+                 "v_cndmask_b32 %2, %7, %2, vcc\n\t"                                                    \
+                 "v_cndmask_b32 %0, %5, %0, vcc\n\t"                                                    \
+                 "v_cndmask_b32 %1, %6, %1, vcc\n\t"                                                    \
+                 "v_cndmask_b32 %3, %8, %3, vcc"                                                         \
+                 : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(kc), "=&v"(scr)                                   \
+                 : "v"(pflo), "v"(pfhi), "v"(px), "v"(pc)                                                 \
+                 : "vcc", "scc")
+#define FX_BITONIC3_SWZ_(M, ULO, UHI)                                                                   \
+    do {                                                                                                \
+        const uint32_t pflo = (uint32_t)__builtin_amdgcn_ds_swizzle((int)flo, 0x1F | ((M) << 10));      \
+        const uint32_t pfhi = (uint32_t)__builtin_amdgcn_ds_swizzle((int)fhi, 0x1F | ((M) << 10));      \
+        const uint32_t px = (uint32_t)__builtin_amdgcn_ds_swizzle((int)kx, 0x1F | ((M) << 10));         \
+        const uint32_t pc = (uint32_t)__builtin_amdgcn_ds_swizzle((int)kc, 0x1F | ((M) << 10));         \
+        FX_BITONIC3_XCH_(ULO, UHI);                                                                     \
+    } while (0)
+#define FX_BITONIC3_DPP(D, U) FX_BITONIC3_DPP_(D, U)
+#define FX_BITONIC3_XCH(U) FX_BITONIC3_XCH_(U)
+#define FX_BITONIC3_SWZ(M, U) FX_BITONIC3_SWZ_(M, U)
+// The network, written once for both layouts: DPP / SWZ / M63 name the stage macros.
+#define FX_BITONIC_NETWORK(DPP, SWZ, M63)                                          \
+    /* blocks of 2 */                                                             \
+    DPP("quad_perm:[1,0,3,2]", FX_U0);                                            \
+    /* blocks of 4: mirror, then 1 */                                             \
+    DPP("quad_perm:[3,2,1,0]", FX_U1);                                            \
+    DPP("quad_perm:[1,0,3,2]", FX_U0);                                            \
+    /* blocks of 8: mirror, 2, 1 */                                               \
+    DPP("row_half_mirror", FX_U2);                                                \
+    DPP("quad_perm:[2,3,0,1]", FX_U1);                                            \
+    DPP("quad_perm:[1,0,3,2]", FX_U0);                                            \
+    /* blocks of 16: mirror, 4, 2, 1 */                                           \
+    DPP("row_mirror", FX_U3);                                                     \
+    SWZ(4, FX_U2);                                                                \
+    DPP("quad_perm:[2,3,0,1]", FX_U1);                                            \
+    DPP("quad_perm:[1,0,3,2]", FX_U0);                                            \
+    if (n > 16) {                                                                 \
+        /* blocks of 32: mirror (lane ^ 31), 8, 4, 2, 1 */                        \
+        SWZ(31, FX_U4);                                                           \
+        DPP("row_ror:8", FX_U3);                                                  \
+        SWZ(4, FX_U2);                                                            \
+        DPP("quad_perm:[2,3,0,1]", FX_U1);                                        \
+        DPP("quad_perm:[1,0,3,2]", FX_U0);                                        \
+    }                                                                             \
+    if (n > 32) {                                                                 \
+        /* the wavefront: mirror (lane ^ 63), 16, 8, 4, 2, 1 */                   \
+        M63();                                                                    \
+        SWZ(16, FX_U4);                                                           \
+        DPP("row_ror:8", FX_U3);                                                  \
+        SWZ(4, FX_U2);                                                            \
+        DPP("quad_perm:[2,3,0,1]", FX_U1);                                        \
+        DPP("quad_perm:[1,0,3,2]", FX_U0);                                        \
     }
-    if (n > 32) {
-        // the wavefront: mirror (lane ^ 63), 16, 8, 4, 2, 1
-        {
-            const int a = (lane ^ 63) << 2;
-            const uint32_t pflo = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)flo), pfhi = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)fhi),
-                           px = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kx), ps = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)ks),
-                           pc = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kc);
-            FX_BITONIC_XCH(FX_U5);
-        }
-        FX_BITONIC_SWZ(16, FX_U4);
-        FX_BITONIC_DPP("row_ror:8", FX_U3);
-        FX_BITONIC_SWZ(4, FX_U2);
-        FX_BITONIC_DPP("quad_perm:[2,3,0,1]", FX_U1);
-        FX_BITONIC_DPP("quad_perm:[1,0,3,2]", FX_U0);
+// the stage whose partner is lane ^ 63 (ds_bpermute)
+#define FX_BITONIC_M63()                                                                                                     \
+    do {                                                                                                                     \
+        const int a = (lane ^ 63) << 2;                                                                                      \
+        const uint32_t pflo = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)flo), pfhi = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)fhi), \
+                       px = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kx), ps = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)ks),       \
+                       pc = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kc);                                              \
+        FX_BITONIC_XCH(FX_U5);                                                                                               \
+    } while (0)
+#define FX_BITONIC3_M63()                                                                                                    \
+    do {                                                                                                                     \
+        const int a = (lane ^ 63) << 2;                                                                                      \
+        const uint32_t pflo = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)flo), pfhi = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)fhi), \
+                       px = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kx), pc = (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)kc);       \
+        FX_BITONIC3_XCH(FX_U5);                                                                                              \
+    } while (0)
+template <bool NOSLOT>
+__device__ __forceinline__ void r_sort(RTier& R, int lane, int n) {
+    uint32_t flo = (uint32_t)R.f, fhi = (uint32_t)(R.f >> 32), kx = R.x, kc = R.c, scr;
+    if constexpr (NOSLOT) {
+        asm volatile("s_nop 1" : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(kc));  // (DPP reads want two wait states behind the VALU writes)
+        FX_BITONIC_NETWORK(FX_BITONIC3_DPP, FX_BITONIC3_SWZ, FX_BITONIC3_M63)
+    } else {
+        uint32_t ks = R.s;
+        asm volatile("s_nop 1" : "+v"(flo), "+v"(fhi), "+v"(kx), "+v"(ks), "+v"(kc));  // (DPP reads want two wait states behind the VALU writes)
+        FX_BITONIC_NETWORK(FX_BITONIC_DPP, FX_BITONIC_SWZ, FX_BITONIC_M63)
+        R.s = ks;
     }
     R.f = ((uint64_t)fhi << 32) | (uint64_t)flo;
     R.x = kx;
-    R.s = ks;
     R.c = kc;
 }
 
 // R runs low: hand it the smallest M entries, as many as it has room for, sorted behind the entries it still holds
 // (every M key is at or above the R / M threshold, every R key below it), and close the gaps in M.
-__device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, int lane) {
+template <class MID>
+__device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const MID& M, int lane) {
     open_uniform(Q);
 #ifdef FXJPS_PROF
     unsigned long long rt_ = __builtin_readcyclecounter();
@@ -1072,14 +1179,14 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
         const uint32_t j = M.w->idx[(uint32_t)lane - r0];
         R.f = M.w->f[j];
         R.x = M.w->x[j];
-        R.s = M.w->s[j];
+        if constexpr (!MID::SLOTLESS) R.s = M.w->s[j];
         R.c = M.w->c[j];
     }
     RECONV();
     DBG_COUNT(M, 20, 1);
     DBG_COUNT(M, 23, take_n);
     RT_MARK(41);  // select + gather
-    r_sort(R, lane, (int)(r0 + take_n));
+    r_sort<MID::SLOTLESS>(R, lane, (int)(r0 + take_n));
     RT_MARK(42);  // sort
     // ---- close the gaps (entries move down only, onto slots already read)
     uint32_t mw = 0;
@@ -1090,7 +1197,7 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
         const uint64_t km = __ballot(keep);
         uint32_t es = 0, ec = 0;
         if (keep) {
-            es = M.w->s[i];
+            if constexpr (!MID::SLOTLESS) es = M.w->s[i];
             ec = M.w->c[i];
         }
         RECONV();
@@ -1098,7 +1205,7 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
             const uint32_t j = mw + rank_below(km);
             M.w->f[j] = f[k];
             M.w->x[j] = x[k];
-            M.w->s[j] = es;
+            if constexpr (!MID::SLOTLESS) M.w->s[j] = es;
             M.w->c[j] = (uint16_t)ec;
         }
         RECONV();
@@ -1117,7 +1224,8 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const Mid& M, in
 
 // R after a batch: its first `drop` lanes (the committed nodes) leave and the entries held by the lanes of `rm`
 // (key (kf, kx), payload ks, kc) merge in, keeping R sorted.  Each lane of the new R pulls its entry: a new one from
-// the lane that pushed it, an old one from the lane it sat in.
+// the lane that pushed it, an old one from the lane it sat in.  NOSLOT (the slotless layout): no slot is pulled, ks is not used.
+template <bool NOSLOT>
 __device__ __forceinline__ void r_merge(OpenList& Q, RTier& R, int lane, int drop, bool toR, uint64_t rm, uint64_t kf, uint32_t kx,
                                         uint32_t ks, uint32_t kc) {
     const int old_n = Q.r_n;
@@ -1142,18 +1250,18 @@ __device__ __forceinline__ void r_merge(OpenList& Q, RTier& R, int lane, int dro
     const uint32_t srcl = (isnew ? nsrc : (uint32_t)(lane + drop) - rank_below(newmask)) & 63u;
     const bool live = lane < new_n;
     const uint32_t oflo = lane_pull((uint32_t)R.f, srcl), ofhi = lane_pull((uint32_t)(R.f >> 32), srcl);
-    const uint32_t ox = lane_pull(R.x, srcl), os = lane_pull(R.s, srcl), oc = lane_pull(R.c, srcl);
+    const uint32_t ox = lane_pull(R.x, srcl), os = NOSLOT ? 0u : lane_pull(R.s, srcl), oc = lane_pull(R.c, srcl);
     if (rm != 0ull) {
         const uint32_t nflo = lane_pull((uint32_t)kf, srcl), nfhi = lane_pull((uint32_t)(kf >> 32), srcl);
-        const uint32_t nx = lane_pull(kx, srcl), ns = lane_pull(ks, srcl), nc = lane_pull(kc, srcl);
+        const uint32_t nx = lane_pull(kx, srcl), ns = NOSLOT ? 0u : lane_pull(ks, srcl), nc = lane_pull(kc, srcl);
         R.f = !live ? ~0ull : (isnew ? (((uint64_t)nfhi << 32) | (uint64_t)nflo) : (((uint64_t)ofhi << 32) | (uint64_t)oflo));
         R.x = !live ? ~0u : (isnew ? nx : ox);
-        R.s = isnew ? ns : os;
+        if (!NOSLOT) R.s = isnew ? ns : os;
         R.c = isnew ? nc : oc;
     } else {
         R.f = !live ? ~0ull : (((uint64_t)ofhi << 32) | (uint64_t)oflo);
         R.x = !live ? ~0u : ox;
-        R.s = os;
+        if (!NOSLOT) R.s = os;
         R.c = oc;
     }
     Q.r_n = new_n;
@@ -1162,8 +1270,8 @@ __device__ __forceinline__ void r_merge(OpenList& Q, RTier& R, int lane, int dro
 // The open list after a batch: the first `drop` entries of R (the committed nodes) leave, and the entries held by the
 // lanes with `w` (key (kf, kx), payload ks, kc) go into R when below the R / M threshold, into M when below the
 // M / far threshold, else into the far tier.  jps1.py:227-228 for a whole batch.
-template <bool BANDED>
-__device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
+template <bool BANDED, class MID>
+__device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RTier& R, const MID& M, FarEnt* __restrict__ far,
                                             int lane, int lane_c, int drop, bool w, uint64_t kf, uint32_t kx, uint32_t ks,
                                             uint32_t kc PF_PARAMS) {  // lane_c: the lane number again, for the rarely taken paths
     PF(2);
@@ -1177,7 +1285,7 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
         rm = __ballot(toR);
         if (FX_USUAL(Q.r_n - drop + __popcll(rm) <= WAVE)) break;
         if (drop > 0) {  // (rare: take the committed nodes out first, then halve what is left)
-            r_merge(Q, R, lane_c, drop, false, 0ull, 0ull, 0u, 0u, 0u);
+            r_merge<MID::SLOTLESS>(Q, R, lane_c, drop, false, 0ull, 0ull, 0u, 0u, 0u);
             drop = 0;
         }
         if (!r_split(Q, R, M, far, fci, lane_c, A.far_cap)) return false;
@@ -1198,14 +1306,14 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
     DBG_COUNT(M, 32, __popcll(rm));   // pushes merged into R
     DBG_COUNT(M, 58, __popcll(mm));   // ... appended to M (the rest of the pushes goes to the far tier)
     DBG_COUNT(M, 50, (rm != 0ull || drop > 0) ? 1 : 0);
-    if (rm != 0ull || drop > 0) r_merge(Q, R, lane, drop, toR, rm, kf, kx, ks, kc);
+    if (rm != 0ull || drop > 0) r_merge<MID::SLOTLESS>(Q, R, lane, drop, toR, rm, kf, kx, ks, kc);
     PF(13);
     if (mm != 0ull) {
         if (toM) {
             const uint32_t j = Q.m_n + rank_below(mm);
             M.w->f[j] = kf;
             M.w->x[j] = kx;
-            M.w->s[j] = ks;
+            if constexpr (!MID::SLOTLESS) M.w->s[j] = ks;
             M.w->c[j] = (uint16_t)kc;
         }
         RECONV();
@@ -1224,9 +1332,10 @@ __device__ __forceinline__ bool open_insert(const SearchArgs& A, OpenList& Q, RT
 #define COLD_SYNC() __builtin_amdgcn_s_waitcnt(0x0F70)
 // Make sure the minimum of the open list is in R (the heappop of jps1.py:198 then reads lane 0).  Returns false when
 // the open list is empty.
-template <bool BANDED, bool NOCI = false>  // NOCI: nobody reads the entries' cell info (rays on the jump-distance records)
-__device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G, OpenList& Q, RTier& R, const Mid& M, FarEnt* __restrict__ far,
+template <bool BANDED, bool NOCI = false, class MID>  // NOCI: nobody reads the entries' cell info (rays on the jump-distance records)
+__device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G, OpenList& Q, RTier& R, const MID& M, FarEnt* __restrict__ far,
                                           int lane) {
+    constexpr bool NOSLOT = MID::SLOTLESS;  // far entries are {f, xyd, cell info}: the u16 array behind them is not used
     uint16_t* fci = far_ci(far, A.far_cap);
     bool topped = false;
     for (;;) {
@@ -1378,7 +1487,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                             const uint32_t ec = cell_info(e.xyd);
                             M.w->f[mn + i] = e.fbits;
                             M.w->x[mn + i] = e.xyd;
-                            M.w->s[mn + i] = e.slot;
+                            if constexpr (!MID::SLOTLESS) M.w->s[mn + i] = e.slot;  // (the ring serves the carrying layout only)
                             M.w->c[mn + i] = (uint16_t)ec;
                         }
                         RECONV();
@@ -1489,7 +1598,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                         uint32_t ec = 0;
                         if (valid) {
                             e = far[half + i];
-                            ec = fci[half + i];
+                            ec = NOSLOT ? e.slot : (uint32_t)fci[half + i];
                         }
                         RECONV();
                         const bool down = valid && (uint32_t)(e.fbits >> 32) < t2;
@@ -1498,13 +1607,13 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                         if (down) {  // (the near band is empty and at most as long as what has been read: no overlap)
                             const uint32_t j = wa + rank_below(dm);
                             far[j] = e;
-                            fci[j] = (uint16_t)ec;
+                            if (!NOSLOT) fci[j] = (uint16_t)ec;
                         }
                         RECONV();
                         if (stay) {  // compaction moves entries down only, onto slots already read
                             const uint32_t j = half + wb + rank_below(sm);
                             far[j] = e;
-                            fci[j] = (uint16_t)ec;
+                            if (!NOSLOT) fci[j] = (uint16_t)ec;
                             fmin = e.fbits < fmin ? e.fbits : fmin;
                         }
                         RECONV();
@@ -1535,7 +1644,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                     uint32_t ec = 0;
                     if (valid) {
                         e = far[i];
-                        ec = fci[i];
+                        ec = NOSLOT ? e.slot : (uint32_t)fci[i];
                     }
                     RECONV();
                     const bool up = valid && (uint32_t)(e.fbits >> 32) >= t2;
@@ -1544,13 +1653,13 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                     if (up) {
                         const uint32_t j = half + wb + rank_below(um);
                         far[j] = e;
-                        fci[j] = (uint16_t)ec;
+                        if (!NOSLOT) fci[j] = (uint16_t)ec;
                     }
                     RECONV();
                     if (stay) {
                         const uint32_t j = wa + rank_below(sm);
                         far[j] = e;
-                        fci[j] = (uint16_t)ec;
+                        if (!NOSLOT) fci[j] = (uint16_t)ec;
                     }
                     RECONV();
                     wa += (uint32_t)__popcll(sm);
@@ -1612,7 +1721,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                 const uint32_t i0 = (uint32_t)(k * WAVE) + (uint32_t)lane;
                 if (i0 < fn) {
                     eq[k] = far[i0];
-                    cq[k] = fci[i0];
+                    if (!NOSLOT) cq[k] = fci[i0];
                 }
                 RECONV();
             }
@@ -1624,12 +1733,12 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                 if (base >= fn) break;
                 const uint32_t i = base + lane;
                 const FarEnt e = eq[k];
-                const uint32_t ec = cq[k];
+                const uint32_t ec = NOSLOT ? e.slot : cq[k];  // (the slotless layout: the cell info is the entry's fourth dword)
                 const bool valid = i < fn;
                 eq[k].fbits = ~0ull;
                 if (i + FPD * WAVE < fn) {
                     eq[k] = far[i + FPD * WAVE];
-                    cq[k] = fci[i + FPD * WAVE];
+                    if (!NOSLOT) cq[k] = fci[i + FPD * WAVE];
                 }
                 RECONV();
                 const bool want = valid && key_lt(e.fbits, e.xyd, Tnb, Tnx);
@@ -1653,7 +1762,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                     const uint32_t j = mn + rank;
                     M.w->f[j] = e.fbits;
                     M.w->x[j] = e.xyd;
-                    M.w->s[j] = e.slot;
+                    if constexpr (!NOSLOT) M.w->s[j] = e.slot;
                     M.w->c[j] = (uint16_t)ec;
                 }
                 RECONV();
@@ -1670,7 +1779,7 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
                 if (keep) {
                     const uint32_t j = wr + rank_below(km);
                     far[j] = e;
-                    fci[j] = (uint16_t)ec;
+                    if (!NOSLOT) fci[j] = (uint16_t)ec;
                 }
                 RECONV();
                 wr += (uint32_t)__popcll(km);
@@ -1792,21 +1901,21 @@ __device__ __forceinline__ bool open_fill(const SearchArgs& A, const GridDev& G,
         const uint64_t own = __ballot(ci >= 0 && cf == gf && cx == gx);
         const uint32_t fi = rfl((uint32_t)__shfl(ci, (int)__builtin_ctzll(own), WAVE));
         {  // it becomes the only entry of R
-            const uint32_t gs = rfl(far[fi].slot), gc = rfl((uint32_t)fci[fi]);
+            const uint32_t gs = rfl(far[fi].slot), gc = NOSLOT ? gs : rfl((uint32_t)fci[fi]);
             const bool l0 = lane == 0;
             R.f = l0 ? gf : ~0ull;
             R.x = l0 ? gx : ~0u;
-            R.s = gs;
+            if (!NOSLOT) R.s = gs;
             R.c = gc;
             Q.r_n = 1;
         }
         const uint32_t last = Q.far_n - 1;
         if (fi != last) {
             const FarEnt le = far[last];
-            const uint16_t lc = fci[last];
+            const uint16_t lc = NOSLOT ? (uint16_t)0 : fci[last];
             if (lane == 0) {
                 far[fi] = le;
-                fci[fi] = lc;
+                if (!NOSLOT) fci[fi] = lc;
             }
             RECONV();
         }
@@ -2006,7 +2115,8 @@ __device__ __forceinline__ void expand_jd(const GridDev& G, uint32_t r0, uint32_
 // cell's info (the tiles its two straight sub-jumps scanned).  The record itself depends on nothing else up to there;
 // what lies behind the ending cell (a goal or a sub-jump onto the goal ended the ray early) does not change the answer.
 // The cell infos are independent loads, four per round: no chain of round trips as in the stepping form.
-__device__ __forceinline__ void rs_mark_ray(const GridDev& G, const Mid& S, int cpx, int cpy, const uint32_t code, int kres) {
+template <class MID>
+__device__ __forceinline__ void rs_mark_ray(const GridDev& G, const MID& S, int cpx, int cpy, const uint32_t code, int kres) {
     const bool act = code != DIR_NONE && kres >= 1;
     const int dx = (int)(code >> 2) - 1, dy = (int)(code & 3u) - 1;
     const bool diag = act && dx != 0 && dy != 0;
@@ -2047,9 +2157,9 @@ __device__ __forceinline__ void expand_batch(const GridDev& G, uint32_t r0, uint
 
 // The whole of jps1.method (jps1.py:183-230) for one query on one wavefront.
 // Returns the result code; *res_cost is gscore[goal].
-template <int HC, bool TRK, bool DIRECT, bool MG>
+template <int HC, bool TRK, bool DIRECT, bool MG, class MID>
 __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev& Gq, const uint32_t q, const int sx, const int sy, const int gx,
-                              const int gy, const Mid& S, TEnt* __restrict__ tab, FarEnt* __restrict__ far,
+                              const int gy, const MID& S, TEnt* __restrict__ tab, FarEnt* __restrict__ far,
                               const uint32_t gen, double* res_cost, unsigned long long* cnt4) {
     // The map pointers, the table pointer and the scan-line stride are used in per-lane address arithmetic only, a
     // dozen times per iteration.  Held in SGPRs they were spilled (the kernel runs at the scalar-register limit) and
@@ -2074,6 +2184,9 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev
     // tables of config 2 the read in front of the table lookup is a dependent wait the lone queries feel (62.1 -> 63.6 ms,
     // c2 145 k -> 141 k), so there the successor's cell info keeps riding along with its probe.
     constexpr bool JD2 = !DIRECT && !TRK;
+    constexpr bool NOSLOT = MID::SLOTLESS;
+    static_assert(!NOSLOT || DIRECT, "a node's slot follows from its cell on cell-indexed tables only");
+    constexpr int HZ_LOG2 = MID::HZ_LOG2, HZ_SIZE = MID::HZ_SIZE;  // (this instantiation's detector)
     const uint32_t nbk = A.nbuckets;
     constexpr bool R2_ON = DIRECT;  // the second round (section 3.1b): on the cell-indexed tables, tracked searches included
     constexpr int KCAP_MIN2 = R2_ON ? 16 : 8;  // smallest batch of the Euclidean-key rule below
@@ -2239,7 +2352,8 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev
         pf_popped += (unsigned long long)nb;
 #endif
         // the lanes of node i take its packed cell, table slot, cell info and directions from lane i ("my node")
-        const uint32_t n_xyd = lane_pull(R.x, (uint32_t)mynode), n_slot = lane_pull(R.s, (uint32_t)mynode),
+        // (the slotless layout hands over three values: the slot is the cell's, derived here)
+        const uint32_t n_xyd = lane_pull(R.x, (uint32_t)mynode), n_slot = NOSLOT ? probe_at(n_xyd >> 4) : lane_pull(R.s, (uint32_t)mynode),
                        n_pk = lane_pull(pk_j, (uint32_t)mynode), n_codes = lane_pull(my_codes, (uint32_t)mynode);
         uint32_t nr0 = 0u, nr1 = 0u, nr2 = 0u, nr3 = 0u;  // my node's jump-distance record
         if (JD2) {
@@ -2998,8 +3112,8 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev
     return (int32_t)rfl(res_len);
 }
 
-template <int HC, bool TRK, bool DIRECT, bool MG>
-__device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q, const Mid& S, TEnt* __restrict__ tab,
+template <int HC, bool TRK, bool DIRECT, bool MG, class MID>
+__device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q, const MID& S, TEnt* __restrict__ tab,
                           FarEnt* __restrict__ far, uint32_t& gen) {
     // The grid: the handle's resident one, or (MG) the slot this query names -- its descriptor read once, with scalar loads
     // (the id is wave-uniform; read through the constant address space, the descriptor's 80 bytes are scalar loads).
@@ -3153,7 +3267,7 @@ __global__ __launch_bounds__(WAVE) void k_selftest_openlist(SearchArgs A, const 
                                                            uint32_t* __restrict__ out_info, uint32_t out_cap) {
     __shared__ WaveLds s_w[1];
     const int lane = threadIdx.x & 63;
-    for (int i = lane; i < HZ_SIZE; i += WAVE) s_w[0].hz[i] = ~0u;
+    for (int i = lane; i < WaveLds::HZ_SIZE; i += WAVE) s_w[0].hz[i] = ~0u;
     if (lane < NBANDS) s_w[0].bcnt[lane] = 0u;
     __syncthreads();
     Mid S;

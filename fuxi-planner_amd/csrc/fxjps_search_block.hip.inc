@@ -1,13 +1,14 @@
 // The body of the search kernel, included by the kernels that are it under another name (fxjps_kernels.hip.inc: k_search, and
 // k_slot_reads_search with TRK = MG = true): the text is compiled where it stands, so each kernel is exactly the code it would
 // be had it been written out there.  In scope: HC, TRK, DIRECT, MG and the kernel's argument, SearchArgs A.
-    __shared__ WaveLds s_w[WPB];             // per wavefront: the M tier, transfer indices, collision detector
+    using WL = SearchLds<TRK, DIRECT>;       // the open-list layout and the detector size of this instantiation
+    __shared__ WL s_w[WPB];                  // per wavefront: the M tier, transfer indices, collision detector
     __shared__ uint32_t s_dirlut[11 * 256];  // nodeNeighbours table: LDS latency instead of an L2 round trip per batch
     __shared__ unsigned long long s_rs[TRK ? WPB : 1][TRK ? 128 : 1];  // read-set bitmaps (tracking instantiation only)
     if (TRK)
         for (int i = threadIdx.x; i < WPB * 128; i += WAVE * WPB) (&s_rs[0][0])[i] = 0ull;
     for (int i = threadIdx.x; i < 11 * 256; i += WAVE * WPB) s_dirlut[i] = c_dirlut[i];
-    for (int i = threadIdx.x; i < WPB * HZ_SIZE; i += WAVE * WPB) s_w[i / HZ_SIZE].hz[i % HZ_SIZE] = ~0u;
+    for (int i = threadIdx.x; i < WPB * WL::HZ_SIZE; i += WAVE * WPB) s_w[i / WL::HZ_SIZE].hz[i % WL::HZ_SIZE] = ~0u;
     __syncthreads();  // the only block-wide barrier: every wavefront is still here
     const int lane = threadIdx.x & 63;
     const int wib = rfli((int)(threadIdx.x >> 6));
@@ -18,8 +19,8 @@
     const size_t wave = A.solo != 0u ? (size_t)A.wave_base + (size_t)blockIdx.x * A.solo + wib : (size_t)blockIdx.x * WPB + wib;
     TEnt* tab = A.tables + wave * ((size_t)BUCKET * A.nbuckets);
     FarEnt* far = A.far + wave * (size_t)(A.far_cap + A.far_cap / 8);  // entries + their u16 cell info
-    Mid S;
-    S.w = (LDS_PTR(WaveLds))&s_w[wib];
+    MidT<WL> S;
+    S.w = (LDS_PTR(WL))&s_w[wib];
     S.dirlut = (LDS_PTR(const uint32_t))s_dirlut;
     S.bx = (LDS_PTR(unsigned long long))s_rs[TRK ? wib : 0];
 #ifdef FXJPS_PROF
