@@ -15,6 +15,7 @@ Files written:
     maps_png.npz/.json   every reference maps/*.png (+ the 256x256 canvas case)
     synth1024.json       128 queries of the config-2 workload (1024^2, 20 %)
     synth4096.json       (--big) 4 queries of the config-3 workload
+    families.json        (make_golden_families.py) structured map families, both hchoice
 """
 import argparse
 import contextlib

@@ -240,6 +240,18 @@ def test_random_small_goldens(planner):
         check_rec(planner, rec)
 
 
+def test_family_goldens(planner):
+    """The planner against the real jps1.py directly on the families the oracle-based tests lean on (families.json):
+    cells and float64 cost, status 0 where the reference returned (0, t)."""
+    n = 0
+    for f in load_golden("families.json")["families"]:
+        planner.set_grid_occ(grid_from_bits(f["grid_bits"], f["shape"]))
+        for rec in f["records"]:
+            check_rec(planner, rec)
+            n += 1
+    assert n == 268
+
+
 def test_reference_maps_goldens(planner, map_grids):
     cur = None
     for rec in load_golden("maps_png.json"):

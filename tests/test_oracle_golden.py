@@ -50,6 +50,29 @@ def test_random_small(oracle):
         check(oracle, grid, rec, literal=False)
 
 
+FAMILIES = ("empty 60x45", "empty 150x110", "sparse 120x90", "rooms 65x65", "serpentine 34x34", "line 1x200", "line 200x1", "strip 2x90",
+            "checkerboard 30x30", "diagonal wall 50x50", "thick diagonal wall 50x50")
+
+
+def test_families(oracle):
+    """The map families the GPU suite leans on (tests/golden/make_golden_families.py): wide-open and 1 % maps, rooms with a
+    sealed pocket, the notched serpentine, one- and two-cell-wide grids, a checkerboard, diagonal walls -- path, cost and,
+    in literal mode, the reference's cells / pushes / pops on every record."""
+    fams = load_golden("families.json")["families"]
+    assert tuple(f["family"] for f in fams) == FAMILIES
+    n = nopath = 0
+    for f in fams:
+        grid = grid_from_bits(f["grid_bits"], f["shape"])
+        assert len(f["records"]) >= 24 and {r["hchoice"] for r in f["records"]} == {1, 2}, f["family"]
+        for rec in f["records"]:
+            assert "cells" in rec
+            check(oracle, grid, rec)
+            check(oracle, grid, rec, literal=False)
+            n += 1
+            nopath += rec["path"] is None
+    assert n == 268 and nopath >= 20, (n, nopath)
+
+
 def test_reference_maps(oracle, map_grids):
     recs = load_golden("maps_png.json")
     assert len({r["map"] for r in recs}) == 35
