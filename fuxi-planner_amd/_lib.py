@@ -273,6 +273,8 @@ def load():
     L.fxjps_debug_read_nbmask.argtypes = [vp, p_u8]
     L.fxjps_debug_qstat.restype = C.c_int
     L.fxjps_debug_qstat.argtypes = [vp, p_u64, C.c_int64]
+    L.fxjps_debug_counters.restype = C.c_int
+    L.fxjps_debug_counters.argtypes = [vp, p_u64]
     L.fxjps_waypoint_ccst_batch.restype = C.c_int
     L.fxjps_waypoint_ccst_batch.argtypes = [vp, C.c_int64, p_i64, p_i32, C.c_double, p_f64, p_f64, p_f64, p_i32, p_f64, p_f64, p_i32, p_i32,
                                             C.c_int64]

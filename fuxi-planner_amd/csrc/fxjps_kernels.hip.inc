@@ -603,9 +603,11 @@ struct MidT {
 };
 using Mid = MidT<WaveLds>;
 #if defined(FXJPS_PROF) && !defined(FXJPS_PROF_LIGHT)  // (FXJPS_PROF_LIGHT: the cycle counters per phase alone, without the event counters' atomics inside the phases)
+// (v is evaluated by the whole wavefront, in front of the branch that leaves lane 0 alone: a __ballot in it would see lane 0 only)
 #define DBG_COUNT(M, k, v)                                                     \
     do {                                                                       \
-        if ((M).dbg && (threadIdx.x & 63) == 0) atomicAdd(&(M).dbg[k], (unsigned long long)(v)); \
+        const unsigned long long dbg_v_ = (unsigned long long)(v);             \
+        if ((M).dbg && (threadIdx.x & 63) == 0) atomicAdd(&(M).dbg[k], dbg_v_); \
     } while (0)
 #else
 #define DBG_COUNT(M, k, v) \
@@ -1071,7 +1073,11 @@ __device__ __forceinline__ void r_refill(OpenList& Q, RTier& R, const MID& M, in
     do {           \
     } while (0)
 #endif
+    // (the entry of r_refill: a mark of the FXJPS_MARK build.  The diagnostic build starts its clock above and counts
+    // nothing here -- counter 39 is the detector's, the iterations with a hold)
+#if !defined(FXJPS_PROF)
     RT_MARK(39);
+#endif
     const uint32_t n = Q.m_n;
     const uint32_t room = min((uint32_t)(WAVE - Q.r_n), (uint32_t)WAVE);  // (r_n >= 0: the clamp is a no-op, kept for the instruction schedule it was measured with)
     uint64_t f[MSLOT];

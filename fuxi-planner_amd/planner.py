@@ -1179,6 +1179,14 @@ class Planner(object):
         self._chk(self._L.fxjps_debug_qstat(self._h, _lib.ptr(out, C.c_uint64), int(nq)))
         return out
 
+    def debug_counters(self):
+        """The raw device counters of the last batch on the first context (fxjps_debug_counters): -> uint64[64].  [0] pops,
+        [1] pushes, [2] far-tier refills, [3] slow pops in every build; the rest is filled by the diagnostic build
+        (-DFXJPS_PROF) only and is zero otherwise: DBG_COUNT(k) of csrc/fxjps_kernels.hip.inc is [k]."""
+        out = np.zeros(64, dtype=np.uint64)
+        self._chk(self._L.fxjps_debug_counters(self._h, _lib.ptr(out, C.c_uint64)))
+        return out
+
     def debug_nbmask(self):
         W, H = self.shape
         buf = np.empty((W + 2, H + 2), dtype=np.uint8)

@@ -15,6 +15,8 @@ KNOBS = [
     ["-DFXJPS_KN=32"], ["-DFXJPS_KN=8"], ["-DFXJPS_PROF"], ["-DFXJPS_PROF", "-DFXJPS_PROF_LIGHT"],
     ["-DFXJPS_PHASE_S=7", "-DFXJPS_PHASE_E=2"], ["-DFXJPS_MARK"], ["-DFXJPS_HWID"],
     ["-DFXJPS_OCC=5", "-DFXJPS_WPB=5", "-DFXJPS_HZ_LOG2=7"],
+    # the stress builds of tests/test_search_stress_builds_gpu.py
+    ["-DFXJPS_HZ_LOG2=7", "-DFXJPS_HZ_LOG2_DIRECT=7"], ["-DFXJPS_KN=32", "-DFXJPS_HZ_LOG2=7", "-DFXJPS_HZ_LOG2_DIRECT=7"],
 ]
 
 

@@ -351,16 +351,22 @@ def run_scenario(fx, oracle, sc, h):
     return line, bad
 
 
-def child_main():
+def child_main(select=None):
     """Every scenario, one after the other, in THIS process (FXJPS_QSTAT=1 is in its environment from the start); one line
-    per scenario.  A scenario whose counts differ is reported and the next one runs; an error of the library ends the run."""
+    per scenario.  A scenario whose counts differ is reported and the next one runs; an error of the library ends the run.
+    `select`: the names (SCENARIOS[i][0]) of the scenarios to run, in the table's order; all of them without it."""
     assert os.environ.get("FXJPS_QSTAT") == "1"
     import fuxi_planner_amd as fx
     from oracle import oracle
     oracle.build()
     knobs = sorted({k for sc in SCENARIOS for k in sc[3]})
     failed = 0
+    if select is not None:
+        unknown = set(select) - {sc[0] for sc in SCENARIOS}
+        assert not unknown, unknown
     for sc in SCENARIOS:
+        if select is not None and sc[0] not in select:
+            continue
         for k in knobs:
             os.environ.pop(k, None)
         os.environ.update(sc[3])
