@@ -298,6 +298,11 @@ struct DevCtx : GridBufs {
         bool had_solo = false;     // the last regular-pool launch was two launches
         double head_ms = 0, batch_ms = 0;  // ... and how long each of them ran
     } run;
+    // fxjps_absorb_prior: the call's staged input (fx::AbsorbTable | the rows of each raw that hold its rectangle), pinned
+    // and on the device, and the table's counters on their way back
+    HBuf<uint8_t> h_absorb_in;
+    DBuf<uint8_t> d_absorb_in;
+    HBuf<unsigned long long> h_absorb_out;
 
     DevCtx() = default;
     DevCtx(DevCtx&&) = default;  // (std::vector<DevCtx>::resize; nothing moves a context that is in use)
@@ -4488,6 +4493,196 @@ int fxjps_check_paths_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
         out_cell_xy[2 * q] = res[q].cx;
         out_cell_xy[2 * q + 1] = res[q].cy;
     }
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ detected maps into the prior maps
+int fxjps_absorb_job_size(void) { return (int)sizeof(fxjps_absorb_job_t); }
+
+namespace {
+static_assert(fx::ABSORB_JOBS_MAX == FXJPS_MAX_GRID_SLOTS && fx::ABSORB_PRIORS_MAX == FXJPS_MAX_PRIOR_MAPS, "the kernel's table holds every job and a box per prior");
+static_assert(fx::ABSORB_OVERWRITE == FXJPS_ABSORB_OVERWRITE && fx::ABSORB_OCCUPIED == FXJPS_ABSORB_OCCUPIED && fx::ABSORB_KNOWN == FXJPS_ABSORB_KNOWN,
+              "the kernel's modes are the header's");
+constexpr size_t ABSORB_IN_RAWS = (sizeof(fx::AbsorbTable) + 15) & ~(size_t)15;
+
+// What the host derives from one job before anything is queued: where the rectangle lies in its prior and which rows of
+// raw are staged -- the rows (layout 0: x, layout 1: y) that hold the rectangle, one contiguous piece of raw.
+struct AbsorbPlan {
+    long long d[2];         // the prior cell that rectangle cell (0, 0) lands on
+    long long c0[2], c1[2]; // the rectangle clipped to the prior, in prior cells: [c0, c1)
+    long long inside;
+    size_t raw_off, raw_bytes, in_off;  // the piece of raw, and where it lies in the staged input (a job that misses its prior stages nothing)
+};
+
+int absorb_refuse(char* msg, size_t len, const char* fmt, ...) {
+    if (msg && len > 0) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(msg, len, fmt, ap);
+        va_end(ap);
+    }
+    return FXJPS_E_ARG;
+}
+
+// Everything fxjps_absorb_prior refuses except a rank handle, from the arguments and the priors' extents alone; the
+// placement is world_call's: float64, the reference's operations in the reference's order (st:212-214).  Writes nothing
+// unless every job passes; then plan (n records, may be nullptr), in_bytes and every job's inside / outside.
+int absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, AbsorbPlan* plan, size_t* in_bytes, char* msg, size_t len) {
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return absorb_refuse(msg, len, "job 0: n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
+    if (!prior_wh) return absorb_refuse(msg, len, "job 0: NULL prior extents");
+    if (mode < 0 || mode > 2) return absorb_refuse(msg, len, "job 0: mode %d is not FXJPS_ABSORB_OVERWRITE, _OCCUPIED or _KNOWN", (int)mode);
+    std::vector<AbsorbPlan> own;
+    if (!plan) {
+        own.resize((size_t)n);
+        plan = own.data();
+    }
+    size_t total = ABSORB_IN_RAWS;
+    for (int j = 0; j < n; j++) {
+        const fxjps_absorb_job_t& a = jobs[j];
+        if (!a.raw) return absorb_refuse(msg, len, "job %d: NULL raw", j);
+        if (a.layout != 0 && a.layout != 1) return absorb_refuse(msg, len, "job %d: layout %d is not 0 or 1", j, (int)a.layout);
+        if (a.W0 < 1 || a.H0 < 1 || a.W0 > 8190 || a.H0 > 8190)
+            return absorb_refuse(msg, len, "job %d: bad extents (W0 %d, H0 %d): raw must be 1..8190 cells a side", j, (int)a.W0, (int)a.H0);
+        const long long ext[2] = {a.W0, a.H0};
+        for (int k = 0; k < 2; k++)
+            if (a.win[k] < 1 || a.lo[k] < 0 || (long long)a.lo[k] + a.win[k] > ext[k])
+                return absorb_refuse(msg, len, "job %d: axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %lld cells", j, k, (int)a.lo[k],
+                                     (int)a.win[k], ext[k]);
+        if (a.prior < 0 || a.prior >= FXJPS_MAX_PRIOR_MAPS) return absorb_refuse(msg, len, "job %d: prior %d is not in 0 .. %d", j, (int)a.prior, FXJPS_MAX_PRIOR_MAPS - 1);
+        const long long l[2] = {prior_wh[2 * a.prior], prior_wh[2 * a.prior + 1]};
+        if (l[0] < 1 || l[1] < 1) return absorb_refuse(msg, len, "job %d: prior %d is not set", j, (int)a.prior);
+        const double reso = a.map_reso;
+        if (!std::isfinite(reso) || !(reso > 0.0)) return absorb_refuse(msg, len, "job %d: map_reso %g must be finite and > 0", j, reso);
+        AbsorbPlan& p = plan[j];
+        p = AbsorbPlan{};
+        p.inside = 1;
+        for (int k = 0; k < 2; k++) {
+            if (!std::isfinite(a.map_o[k]) || !std::isfinite(a.ori_pre[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_o / ori_pre", j);
+            const double o1 = std::min(a.map_o[k], a.ori_pre[k]);  // st:212
+            long long at_raw, at_pre;
+            if (!trunc_i32((a.map_o[k] - o1) / reso, at_raw) || !trunc_i32((a.ori_pre[k] - o1) / reso, at_pre))  // st:213-214
+                return absorb_refuse(msg, len, "job %d: a placement index is outside int32", j);
+            p.d[k] = at_raw - at_pre;
+            p.c0[k] = std::max(p.d[k], 0ll);
+            p.c1[k] = std::min(p.d[k] + (long long)a.win[k], l[k]);
+            p.inside *= std::max(p.c1[k] - p.c0[k], 0ll);
+        }
+        if (p.inside > 0) {
+            const size_t row = (size_t)(a.layout ? a.W0 : a.H0), k = a.layout ? 1 : 0;
+            p.raw_off = (size_t)a.lo[k] * row;
+            p.raw_bytes = (size_t)a.win[k] * row;
+            p.in_off = total;
+            total += (p.raw_bytes + 15) & ~(size_t)15;
+            if (total > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
+        }
+    }
+    for (int j = 0; j < n; j++) {
+        jobs[j].inside = plan[j].inside;
+        jobs[j].outside = (long long)jobs[j].win[0] * jobs[j].win[1] - plan[j].inside;
+    }
+    if (in_bytes) *in_bytes = total;
+    return FXJPS_OK;
+}
+
+// One context's part of fxjps_absorb_prior: ONE copy in, ONE launch, one copy back and one wait, whatever n is.  The
+// counters are left in d.h_absorb_out.
+int absorb_on(fxjps* h, DevCtx& d, const fxjps_absorb_job_t* jobs, int n, int mode, const std::vector<AbsorbPlan>& plan, size_t in_bytes) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    HIPCHK(h, d.h_absorb_in.ensure(in_bytes));
+    HIPCHK(h, d.d_absorb_in.ensure(in_bytes));
+    HIPCHK(h, d.h_absorb_out.ensure(FXJPS_MAX_PRIOR_MAPS));
+    fx::AbsorbTable& T = *reinterpret_cast<fx::AbsorbTable*>(d.h_absorb_in.p);
+    memset(&T, 0, sizeof(T));
+    T.mode = mode;
+    int nb = 0, nj = 0;
+    uint32_t at = 0;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
+        fx::AbsorbBoxDev B{};
+        long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};
+        B.job0 = nj;
+        for (int j = 0; j < n; j++) {
+            const fxjps_absorb_job_t& a = jobs[j];
+            const AbsorbPlan& q = plan[(size_t)j];
+            if (a.prior != p || q.inside <= 0) continue;
+            fx::AbsorbJobDev& J = T.job[nj++];
+            J.at = d.d_absorb_in.p + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]);
+            J.stride = a.layout ? a.W0 : a.H0;
+            J.layout = a.layout;
+            J.x0 = (int32_t)q.d[0];
+            J.y0 = (int32_t)q.d[1];
+            J.w = a.win[0];
+            J.h = a.win[1];
+            memcpy(d.h_absorb_in.p + q.in_off, static_cast<const uint8_t*>(a.raw) + q.raw_off, q.raw_bytes);
+            for (int k = 0; k < 2; k++) {
+                lo[k] = std::min(lo[k], q.c0[k]);
+                hi[k] = std::max(hi[k], q.c1[k]);
+            }
+        }
+        B.njobs = nj - B.job0;
+        if (B.njobs == 0) continue;
+        const DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+        B.occ = pr.occ.p;
+        B.pH = pr.H;
+        B.x0 = (int32_t)lo[0];
+        B.y0 = (int32_t)lo[1];
+        B.w = (int32_t)(hi[0] - lo[0]);
+        B.h = (int32_t)(hi[1] - lo[1]);
+        B.prior = p;
+        T.first[nb] = at;
+        T.box[nb++] = B;
+        at += (uint32_t)(((long long)B.w * B.h + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+    }
+    T.first[nb] = at;
+    T.nbox = nb;
+    if (nb == 0) {  // (no rectangle meets its prior: nothing to queue)
+        memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
+        return FXJPS_OK;
+    }
+    HIPCHK(h, hipMemcpyAsync(d.d_absorb_in.p, d.h_absorb_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
+    hipLaunchKernelGGL(fx::k_prior_absorb, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::AbsorbTable*>(d.d_absorb_in.p));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_absorb_out.p, d.d_absorb_in.p, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, char* msg, int32_t msg_len) {
+    if (msg && msg_len > 0) msg[0] = 0;
+    return absorb_check(jobs, n, mode, prior_wh, nullptr, nullptr, msg, msg_len > 0 ? (size_t)msg_len : 0);
+}
+
+int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, int64_t out_changed[FXJPS_MAX_PRIOR_MAPS]) {
+    static_assert(offsetof(fx::AbsorbTable, changed) == 0, "the counters come back from the head of the staged input");
+    if (!h) return FXJPS_E_ARG;
+    if (!out_changed) return fail(h, FXJPS_E_ARG, "job 0: NULL out_changed");
+    if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior")) return rr;
+    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
+    const DevCtx& d0 = h->devs[0];
+    for (size_t p = 0; p < d0.priors.size(); p++) {
+        prior_wh[2 * p] = d0.priors[p].W;
+        prior_wh[2 * p + 1] = d0.priors[p].H;
+    }
+    std::vector<AbsorbPlan> plan((size_t)std::max(n, 0));
+    size_t in_bytes = 0;
+    char why[400] = "";
+    if (absorb_check(jobs, n, mode, prior_wh, plan.data(), &in_bytes, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
+    // every context pastes into its own copy of the priors from the caller's raws (host copies, no collective)
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return absorb_on(h, h->devs[r], jobs, n, mode, plan, in_bytes); });
+    if (rc) {
+        drain_all(h);
+        for (int j = 0; j < n; j++)  // (a prior whose paste failed on one context is released on all of them, as fxjps_set_prior_map does)
+            for (auto& d : h->devs)
+                if ((size_t)jobs[j].prior < d.priors.size()) {
+                    DevCtx::PriorBuf& pr = d.priors[(size_t)jobs[j].prior];
+                    if (hipSetDevice(d.dev) == hipSuccess) pr.occ.release();
+                    pr.W = pr.H = 0;
+                }
+        (void)hipGetLastError();
+        return rc;
+    }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out_changed[p] = (int64_t)h->devs[0].h_absorb_out.p[p];
     return FXJPS_OK;
 }
 

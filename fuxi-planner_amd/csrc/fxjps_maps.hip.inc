@@ -1984,3 +1984,84 @@ __global__ __launch_bounds__(256) void k_check_paths_slots(CheckPathsArgs A) {
         R.cy = (int32_t)fy;
     }
 }
+
+// ---------------------------------------------------------------- detected maps into the prior maps (DESIGN.md section 3.20)
+// fxjps_absorb_prior: the rectangles of up to 256 jobs pasted into the prior maps they name, as n sequential slice
+// assignments on the host would paste them (global_planner_st.py:219-220).  ONE launch over the prior cells of the union
+// boxes, one box per named prior: the host clips every rectangle to its prior, drops the jobs that miss it and deals the
+// launch's blocks to the boxes by a prefix table (AbsorbTable::first, as SlotTable::first deals them).  A thread owns one
+// prior cell, adjacent lanes adjacent y -- the contiguous axis of the prior and of a layout-0 raw.  It walks the jobs of
+// ITS prior from the last to the first, out of the block's copy of them in LDS (every lane reads the same record: a
+// broadcast), and stops at the first job that decides the cell under the mode's rule; it then stores the byte if it
+// differs.  No thread reads a byte that another writes (the raws are the staged input, the prior byte is the thread's
+// own), no atomic touches a map byte, and the result does not depend on the order in which threads run.  A layout-1 raw
+// is [y][x]: its reads are strided across the lanes, taken as they come like those of prepared_byte and k_crop_window
+// (a raw is read once per covering cell and stays in L2 for the lanes that share its lines).  The flips -- cells whose
+// non-zero test changed -- are counted by one ballot per wavefront and one atomic add per wavefront that saw any, into
+// the box's counter at the head of the table, which the staged copy zeroed and the one copy back returns.
+constexpr int ABSORB_JOBS_MAX = 256, ABSORB_PRIORS_MAX = 16;  // FXJPS_MAX_GRID_SLOTS jobs, FXJPS_MAX_PRIOR_MAPS boxes
+constexpr int ABSORB_OVERWRITE = 0, ABSORB_OCCUPIED = 1, ABSORB_KNOWN = 2;  // FXJPS_ABSORB_*
+struct AbsorbJobDev {
+    const uint8_t* at;  // the byte of rectangle cell (0, 0) inside the staged input
+    int32_t stride;     // layout 0: cell (i, j) is at[i * stride + j] (stride = H0); layout 1: at[j * stride + i] (W0)
+    int32_t layout;
+    int32_t x0, y0;     // the prior cell that rectangle cell (0, 0) lands on (may lie outside the prior)
+    int32_t w, h;       // the rectangle's extents
+};
+struct AbsorbBoxDev {
+    uint8_t* occ;           // the prior [pW][pH] on this context
+    int32_t pH;
+    int32_t x0, y0, w, h;   // the union of the prior's clipped rectangles: every cell of it lies inside the prior
+    int32_t job0, njobs;    // its jobs, AbsorbTable::job[job0 .. job0 + njobs), in job order
+    int32_t prior;          // ... and its counter
+};
+struct AbsorbTable {
+    unsigned long long changed[ABSORB_PRIORS_MAX];  // staged as 0; what comes back
+    uint32_t first[ABSORB_PRIORS_MAX + 1];          // first[b]: the first block of box b; first[nbox]: the grid size
+    int32_t nbox, mode;
+    AbsorbBoxDev box[ABSORB_PRIORS_MAX];
+    AbsorbJobDev job[ABSORB_JOBS_MAX];
+};
+static_assert(sizeof(AbsorbJobDev) % 4 == 0, "the job records are copied to LDS word by word");
+
+__global__ __launch_bounds__(256) void k_prior_absorb(AbsorbTable* __restrict__ T) {
+    __shared__ AbsorbJobDev s_job[ABSORB_JOBS_MAX];
+    const int nbox = T->nbox, mode = T->mode;
+    int b = 0;  // (block-uniform)
+    while (b + 1 < nbox && T->first[b + 1] <= blockIdx.x) b++;
+    const AbsorbBoxDev B = T->box[b];
+    {
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(T->job + B.job0);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(s_job);
+        const int nw = B.njobs * (int)(sizeof(AbsorbJobDev) / 4);
+        for (int i = (int)threadIdx.x; i < nw; i += 256) dst[i] = src[i];
+    }
+    __syncthreads();  // (every thread of the block reaches it: none has returned above)
+    const long long c = (long long)(blockIdx.x - T->first[b]) * 256 + threadIdx.x;
+    bool flip = false;
+    if (c < (long long)B.w * B.h) {
+        const int cx = (int)(c / B.h), x = B.x0 + cx, y = B.y0 + (int)(c - (long long)cx * B.h);
+        int val = -1;  // undecided
+        for (int k = B.njobs - 1; k >= 0; k--) {
+            const AbsorbJobDev& J = s_job[k];
+            const int i = x - J.x0, j = y - J.y0;
+            if ((unsigned)i >= (unsigned)J.w || (unsigned)j >= (unsigned)J.h) continue;
+            const uint8_t v = J.layout ? J.at[(size_t)j * (size_t)J.stride + (size_t)i] : J.at[(size_t)i * (size_t)J.stride + (size_t)j];
+            const bool occupied = J.layout ? (int8_t)v > 0 : v != 0;  // prepared_byte's predicate
+            const bool unknown = J.layout && v == 0xffu;              // -1 of an OccupancyGrid
+            if (mode == ABSORB_OVERWRITE || (mode == ABSORB_OCCUPIED && occupied) || (mode == ABSORB_KNOWN && !unknown)) {
+                val = occupied ? 1 : 0;
+                break;
+            }
+        }
+        if (val >= 0) {
+            uint8_t* p = B.occ + (size_t)x * (size_t)B.pH + (size_t)y;
+            const uint8_t old = *p;
+            if (old != (uint8_t)val) *p = (uint8_t)val;
+            flip = (old != 0) != (val != 0);
+        }
+    }
+    RECONV();
+    const uint64_t m = __ballot(flip);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&T->changed[B.prior], (unsigned long long)__popcll(m));
+}

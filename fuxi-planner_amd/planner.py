@@ -602,18 +602,81 @@ class Planner(object):
     def _world_outs(arr, n):
         return [([j.origin[0], j.origin[1]], (j.canvas_W, j.canvas_H), [j.canvas_o[0], j.canvas_o[1]]) for j in arr[:n]]
 
+    def absorb_prior(self, jobs, mode="overwrite", crops=None):
+        """Fold the vehicles' detected maps into the prior maps they name, on the device (fxjps_absorb_prior: one launch
+        whatever len(jobs) is): every job's rectangle is pasted into its prior where the world-frame calls' canvas puts it,
+        cells outside the prior are dropped, and the next world-frame call of ANY vehicle sees the result under its own
+        detected map.  jobs: world jobs as prepare_slots_world takes them (the slot, pos_xy, goal_xy, ifa, variant and
+        map_t are not read; prior None is a ValueError), at most 256, applied in order.  crops[j]: None, or the crop record
+        prepare_slots_cropped returned for job j -- then the job's raw is the map MESSAGE and the rectangle is the record's
+        window (lo, win) at the record's map_o.  mode "overwrite" (the reference's slice assignment: a free detected cell
+        clears the prior's), "occupied" (only ever adds obstacles) or "known" (cells that are -1 in a message leave the
+        prior as it is).  -> ([(inside, outside) per job], {prior: cells whose occupancy flipped}).  No slot, no stored
+        result and not the resident grid is touched.  worldprep.absorb_host is the same paste on the host."""
+        jobs = list(jobs)
+        n = len(jobs)
+        if mode not in _lib.ABSORB_MODES:
+            raise ValueError("mode %r is not one of %r" % (mode, tuple(_lib.ABSORB_MODES)))
+        if crops is not None and len(crops) != n:
+            raise ValueError("%d crop records for %d jobs" % (len(crops), n))
+        arr = (_lib.AbsorbJob * max(n, 1))()
+        keep = []  # (the raws, alive until the call has returned)
+        for v, (a, job) in enumerate(zip(arr, jobs)):
+            raw, map_o, map_reso = job[1], job[2], job[3]
+            prior, ori_pre = (tuple(job[8:10]) + (None, (-15, -15))[len(job[8:10]):])[:2]
+            if prior is None:
+                raise ValueError("job %d names no prior map" % v)
+            w = _lib.WorldJob()  # (raw, layout and extents as the world-frame calls take them)
+            keep.append(Planner._job_raw(w, 0, raw, 0, 0))
+            a.raw, a.layout, a.W0, a.H0 = w.raw, w.layout, w.W0, w.H0
+            rec = None if crops is None else crops[v]
+            lo, win = ((0, 0), (a.W0, a.H0)) if rec is None else (rec["lo"], rec["win"])
+            if rec is not None:
+                map_o = rec["map_o"]
+            a.prior, a.map_reso = int(prior), float(map_reso)
+            for k in range(2):
+                a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k])
+        changed = np.zeros(_lib.MAX_PRIOR_MAPS, dtype=np.int64)
+        self._chk(self._L.fxjps_absorb_prior(self._h, arr, n, _lib.ABSORB_MODES[mode], _lib.ptr(changed, C.c_int64)))
+        del keep
+        named = sorted({int(a.prior) for a in arr[:n]})
+        return [(int(a.inside), int(a.outside)) for a in arr[:n]], {p: int(changed[p]) for p in named}
+
+    def _tick_absorb(self, absorb, jobs, outs, crop, recs):
+        """fleet_tick_world's absorb=: after the tick's prepare / refresh call, every job that names a prior is absorbed --
+        a cropped job through its window, unless it has none (not planned, refused).  recs[v]["absorbed"] is set."""
+        if absorb is None:
+            return
+        take, crops = [], []
+        for v, job in enumerate(jobs):
+            recs[v]["absorbed"] = None
+            if len(job) <= 8 or job[8] is None:
+                continue
+            if crop and outs[v][-2] in (_lib.JOB_NOT_PLANNED, _lib.E_ARG):
+                continue
+            take.append(v)
+            crops.append(outs[v][-1] if crop else None)
+        if take:
+            counts, _ = self.absorb_prior([jobs[v] for v in take], absorb, crops if crop else None)
+            for v, c in zip(take, counts):
+                recs[v]["absorbed"] = c
+
     def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
-                         reuse=False, crop=False, throttle=None, check_kept=True):
+                         reuse=False, crop=False, throttle=None, check_kept=True, absorb=None):
         """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
         prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
         job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
         (reuse=True plans through replan_slots).  crop=True: the jobs hold the ccst node's map MESSAGES and are prepared
         through prepare_slots_cropped / refresh_slots_cropped; every record has a further key, not_planned (bool), and a
         vehicle that is not planned on this tick (ccst:351) or was refused has ok False.  throttle / check_kept: the ccst
-        node's replan throttle, as fleet_tick_throttled describes it."""
+        node's replan throttle, as fleet_tick_throttled describes it.  absorb: None, or "overwrite" / "occupied" / "known": after the
+        tick's prepare / refresh call every job that names a prior is folded into it through absorb_prior (a cropped job
+        through its window; not one that is not planned or refused), so THIS tick's records are what absorb=None gives and
+        the next tick of every vehicle sees the merged prior; every record then has a further key, absorbed: (inside,
+        outside), or None for a job that was not absorbed."""
         jobs = list(jobs)
         return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
-                                image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept)
+                                image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept, absorb=absorb)
 
     def check_paths_slots(self, grid_ids, offsets, cells, shift=None):
         """Which kept paths do their slots' grids, as they are now, still allow (fxjps_check_paths_slots: one launch for
@@ -737,10 +800,10 @@ class Planner(object):
                                 throttle=throttle, check_kept=check_kept)
 
     def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
-                    world=False, crop=False, throttle=None, check_kept=True):
+                    world=False, crop=False, throttle=None, check_kept=True, absorb=None):
         if throttle is not None:
             return self._fleet_tick_throttled(refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
-                                              reuse, world, crop, throttle, check_kept)
+                                              reuse, world, crop, throttle, check_kept, absorb)
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -756,9 +819,11 @@ class Planner(object):
             outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
             for v in range(n):
                 recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
+            self._tick_absorb(absorb, jobs, outs, True, recs)
             outs = [o[:-2] for o in outs]
         elif world:  # (the call's own origin, canvas_shape and canvas_o lie behind the existing tuple)
             outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
+            self._tick_absorb(absorb, jobs, outs, False, recs)
         else:
             outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
         variant_at = 7 if world else 5
@@ -792,7 +857,7 @@ class Planner(object):
         return recs
 
     def _fleet_tick_throttled(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
-                              reuse, world, crop, throttle, check_kept):
+                              reuse, world, crop, throttle, check_kept, absorb=None):
         """_fleet_tick under a replan.FleetThrottle (fleet_tick_throttled's docstring): the same calls in the same order, the
         plan and the tick outputs over the due vehicles only, one check_paths_slots call in front of them."""
         from . import waypoints
@@ -813,9 +878,11 @@ class Planner(object):
             outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
             for v in range(n):
                 recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
+            self._tick_absorb(absorb, jobs, outs, True, recs)
             outs = [o[:-2] for o in outs]
         elif world:
             outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
+            self._tick_absorb(absorb, jobs, outs, False, recs)
         else:
             outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
         variant_at = 7 if world else 5

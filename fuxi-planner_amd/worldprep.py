@@ -7,7 +7,9 @@ This is the host form of Planner.prepare_slots_world for callers without a devic
 against: the same float64 operations in the same order, truncation toward zero where the reference's .astype(int) /
 int() truncate, and a ValueError where the library refuses.  Pinned by tests/golden/worldprep.json, whose expected
 values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).  crop_host is the host form
-of Planner.prepare_slots_cropped in the same way, pinned by tests/golden/cropprep.json (make_golden_cropprep.py).
+of Planner.prepare_slots_cropped in the same way, pinned by tests/golden/cropprep.json (make_golden_cropprep.py), and
+absorb_host that of Planner.absorb_prior: the same slice assignment kept in the prior map, pinned by the canvases of
+worldprep.json.
 """
 import math
 
@@ -93,6 +95,78 @@ def crop_host(raw, map_o, map_reso, pos_xy, ifa):
     window = m[lo[0]:bbox[2], lo[1]:bbox[3]] if outcome == 0 else None                                 # ccst:56, :60
     rec = {"bbox": bbox, "start0": start0, "lo": lo, "win": [min(w, I32_MAX) for w in win], "map_o": o2, "map_t": t2}
     return rec, outcome, window
+
+
+ABSORB_MODES = ("overwrite", "occupied", "known")  # FXJPS_ABSORB_OVERWRITE, _OCCUPIED, _KNOWN
+
+
+def absorb_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, win=None):
+    """One job of Planner.absorb_prior on the host: the rectangle lo .. lo + win - 1 of raw (None: the whole map) pasted
+    into the prior map, the slice assignment of st:219-220 kept.  prior: the prior's bytes [x][y] at world origin ori_pre;
+    raw: a matrix [x][y] (> 0 = occupied; it has no unknown cells) or (data, width, height) of an OccupancyGrid (> 0 =
+    occupied, -1 = unknown); map_o: the world origin of the RECTANGLE (a cropped job: the crop record's map_o).  The
+    rectangle's cell (0, 0) lands on prior cell d = trunc((map_o - o1) / map_reso) - trunc((ori_pre - o1) / map_reso), o1 =
+    min(map_o, ori_pre), per axis -- where merge_host's canvas puts the two (st:212-214); cells that fall outside the prior
+    are dropped.  mode "overwrite": every covered cell becomes the rectangle's occupancy, 1 or 0 (unknown counts as free);
+    "occupied": 1 where the rectangle is occupied, else the byte stays; "known": the occupancy where the rectangle is not
+    unknown, else the byte stays.  A byte that is not decided stays as it is (a 255 stays 255).
+    -> (new prior uint8, inside, outside, changed): the cells of the rectangle inside / outside the prior, and the cells
+    whose occupancy (non-zero) flipped.  Several jobs: call it job by job on the result.  ValueError where the library
+    refuses."""
+    if mode not in ABSORB_MODES:
+        raise ValueError("mode %r is not one of %r" % (mode, ABSORB_MODES))
+    pre = np.asarray(prior)
+    if pre.ndim != 2 or pre.shape[0] < 1 or pre.shape[1] < 1:
+        raise ValueError("the prior map must be 2-D and not empty")
+    if isinstance(raw, tuple):
+        data, width, height = raw
+        a = np.asarray(data, dtype=np.int8).reshape(-1)
+        if a.size != width * height:
+            raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+        m = a.reshape(height, width).T
+        unknown = m == -1
+    else:
+        m = np.asarray(raw)
+        unknown = None
+    if m.ndim != 2 or not (1 <= m.shape[0] <= 8190 and 1 <= m.shape[1] <= 8190):
+        raise ValueError("raw must be 2-D and 1..8190 cells a side")
+    occupied = m > 0
+    lo = [0, 0] if lo is None else [int(lo[0]), int(lo[1])]
+    win = [m.shape[k] - lo[k] for k in range(2)] if win is None else [int(win[0]), int(win[1])]
+    for k in range(2):
+        if win[k] < 1 or lo[k] < 0 or lo[k] + win[k] > m.shape[k]:
+            raise ValueError("axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %d cells" % (k, lo[k], win[k], m.shape[k]))
+    reso = float(map_reso)
+    if not (math.isfinite(reso) and reso > 0.0):
+        raise ValueError("map_reso %r must be finite and > 0" % (map_reso,))
+    o = _pair(map_o, "map_o")
+    op = _pair(ori_pre, "ori_pre")
+    new = np.array(pre, dtype=np.uint8)
+    a0, a1 = [0, 0], [0, 0]  # the rectangle clipped to the prior, in prior cells
+    d = [0, 0]
+    for k in range(2):
+        o1 = min(o[k], op[k])                                                       # st:212
+        d[k] = _trunc((o[k] - o1) / reso, "the detected map's index") - _trunc((op[k] - o1) / reso, "the prior's index")  # st:213-214
+        a0[k] = max(d[k], 0)
+        a1[k] = min(d[k] + win[k], int(pre.shape[k]))
+    inside = max(a1[0] - a0[0], 0) * max(a1[1] - a0[1], 0)
+    changed = 0
+    if inside > 0:
+        cut = tuple(slice(lo[k] + a0[k] - d[k], lo[k] + a1[k] - d[k]) for k in range(2))
+        occ = occupied[cut]
+        target = new[a0[0]:a1[0], a0[1]:a1[1]]
+        before = target != 0
+        if mode == "overwrite":
+            target[...] = occ
+        elif mode == "occupied":
+            target[occ] = 1
+        elif unknown is None:
+            target[...] = occ
+        else:
+            known = ~unknown[cut]
+            target[known] = occ[known]
+        changed = int(np.count_nonzero((target != 0) != before))
+    return new, inside, win[0] * win[1] - inside, changed
 
 
 def merge_host(raw, map_o, map_reso, pos_xy, goal_xy, prior=None, ori_pre=(-15, -15), map_t=None):

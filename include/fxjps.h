@@ -113,8 +113,11 @@ typedef struct fxjps fxjps_t;
  *        a search, out_reused 2), fxjps_debug_slot_tiles, fxjps_debug_slot_read_sets.
  *   840  fxjps_check_path, fxjps_check_paths_slots (does a grid still allow a kept path: every unit step of the path judged
  *        by the reference's blocked(); the slots form checks a fleet's kept paths against their slots in one launch).
+ *   850  fxjps_absorb_prior (the detected rectangles of up to 256 jobs pasted into the prior maps they name, on the device,
+ *        in one launch whatever n is: what one vehicle has seen, every vehicle's next world-frame tick sees),
+ *        fxjps_absorb_check (its argument check and placement without a handle), fxjps_absorb_job_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 840
+#define FXJPS_VERSION 850
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -505,6 +508,57 @@ typedef struct fxjps_crop {     /* out, one per job */
 int fxjps_prepare_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, fxjps_crop_t* out_crop);
 int fxjps_refresh_slots_cropped(fxjps_t* h, fxjps_world_job_t* jobs, int32_t n, int32_t* out_kept, fxjps_crop_t* out_crop);
 int fxjps_crop_size(void); /* sizeof(fxjps_crop_t) as the library was built */
+/* ---- The detected maps folded into the prior maps (version 850): the slice assignment the nodes perform on their canvas
+ * every tick (mapu0[map_o[0]:map_o[0]+map_c, map_o[1]:map_o[1]+map_r] = mapu, st:219-220 / ccst:404-405), kept: the
+ * rectangles of up to 256 jobs are pasted into the prior maps they name, on the device, so that what one vehicle has seen
+ * every vehicle's next world-frame tick sees under its own detected map.
+ *   Placement, per axis k, in float64 with the reference's operations in the reference's order (st:212-214), as the
+ * world-frame calls place the two rectangles on the canvas:
+ *     o1 = min(map_o, ori_pre);  at_raw = trunc((map_o - o1) / map_reso);  at_pre = trunc((ori_pre - o1) / map_reso)
+ *     d  = at_raw - at_pre
+ * Rectangle cell (i, j) is raw's cell (lo[0] + i, lo[1] + j) and lands on prior cell (d[0] + i, d[1] + j) if that cell lies
+ * inside the prior; otherwise it is dropped and counted in `outside`: the prior does not grow.  A rectangle wholly outside
+ * its prior is no error (inside = 0).
+ *   The value read is the world-frame calls': layout 0 occupied when the byte is non-zero; layout 1 occupied when the int8
+ * is > 0, and UNKNOWN when it is -1 (layout 0 has no unknown).  Jobs are applied in job order -- the result is that of n
+ * sequential pastes on the host (worldprep.absorb_host):
+ *     FXJPS_ABSORB_OVERWRITE  the last covering job's occupancy is written, 1 or 0; unknown counts as free (as after
+ *                             map_callback): the reference's slice assignment
+ *     FXJPS_ABSORB_OCCUPIED   1 where any covering job has the cell occupied; otherwise the byte stays
+ *     FXJPS_ABSORB_KNOWN      the occupancy of the last covering job whose cell is not unknown; if there is none the byte stays
+ * A byte that no job decides is left as it is (a 255 stays 255).  out_changed[p]: the cells of prior p whose occupancy
+ * (the non-zero test) flipped, 0 for a prior that no job names; context 0's figure.
+ *   Whole-call refusals (FXJPS_E_ARG with the job's number in fxjps_last_error, before anything is queued or written): NULL
+ * jobs or out_changed, n outside 0 .. 256, a mode outside 0 .. 2; per job NULL raw, a layout outside 0 .. 1, extents
+ * outside 1 .. 8190, a rectangle that is empty or does not lie inside raw, a prior out of range or not set, a non-finite
+ * map_o / ori_pre, map_reso not finite or <= 0, a truncated quotient outside int32; more than 2^30 staged bytes; a rank
+ * handle.  fxjps_absorb_check is that check without a handle (prior_wh: the extents of the 16 priors, [p][2], 0 0 = not
+ * set; msg may be NULL): it fills inside / outside of every job and changes nothing else.
+ *   The call touches no slot, no slot generation, no stored result, not the resident grid and no prior it does not name.
+ * It is queued on the handle's stream: earlier world-frame calls have read the old prior, later ones read the new one, and
+ * fxjps_get_prior_map returns the new bytes.  Per context: one staged copy in (a job table and the rows of each raw that
+ * hold its rectangle), ONE launch whatever n is, one copy back (16 counters) and one host wait; a handle with several
+ * contexts applies the call to every context's copy, as fxjps_set_prior_map uploads to each. */
+#define FXJPS_ABSORB_OVERWRITE 0
+#define FXJPS_ABSORB_OCCUPIED  1
+#define FXJPS_ABSORB_KNOWN     2
+typedef struct fxjps_absorb_job {
+    const void* raw;      /* in: the detected map or the map message, as fxjps_world_job_t::raw */
+    int32_t layout;       /* in: 0 bytes [x][y], 1 int8 OccupancyGrid data[] [y][x] */
+    int32_t W0, H0;       /* in: extents of raw */
+    int32_t lo[2], win[2];/* in: the rectangle of raw that is absorbed: cells lo .. lo + win - 1 (whole map: 0, 0, W0, H0;
+                             a cropped job: fxjps_crop_t::lo / ::win) */
+    int32_t prior;        /* in: 0 .. FXJPS_MAX_PRIOR_MAPS - 1 */
+    int32_t reserved_;    /* in: 0 */
+    double map_o[2];      /* in: world origin of the RECTANGLE (the node's map_o; a cropped job: fxjps_crop_t::map_o) */
+    double map_reso;      /* in */
+    double ori_pre[2];    /* in: the prior's world origin */
+    int64_t inside;       /* out: cells of the rectangle that lie inside the prior */
+    int64_t outside;      /* out: win[0] * win[1] - inside (dropped: the prior does not grow) */
+} fxjps_absorb_job_t;
+int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, int64_t out_changed[FXJPS_MAX_PRIOR_MAPS]);
+int fxjps_absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, char* msg, int32_t msg_len);
+int fxjps_absorb_job_size(void); /* sizeof(fxjps_absorb_job_t) as the library was built */
 /* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
  * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
  * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
