@@ -24,6 +24,7 @@
 #include "../../include/fxjps.h"
 #include "fxjps_kernels.hip.inc"
 #include "fxjps_owned.h"
+#include "fxjps_results.h"
 
 namespace {
 
@@ -284,6 +285,24 @@ struct DevCtx : GridBufs {
     HBuf<double> h_cost;
     HBuf<long long> h_offsets;
     HBuf<unsigned long long> h_counters;
+    // A plain batch streams its results: the search kernel leaves every finished path in h_arena
+    // (packed cells, x << 16 | y, wherever d_cursor stood) and its place in h_base, its length in h_len, its cost in h_cost.
+    // h_cells and the device CSR (d_offsets / d_cells) are then built by whoever asks first: host_cells / device_csr.
+    HBuf<uint32_t> h_arena;
+    HBuf<long long> h_base;
+    DBuf<unsigned long long> d_cursor;
+    long long arena_peak = 0;  // the largest total of cells a batch of this context has produced
+    struct Streaming {         // the batch in progress streams: what fill_search_args hands the kernel (device pointers)
+        bool on = false;
+        uint32_t* cells = nullptr;
+        unsigned long long cap = 0;
+        long long* base = nullptr;
+        int32_t* len = nullptr;
+        double* cost = nullptr;
+        unsigned long long* counters = nullptr;
+    } st;
+    bool cells_on_host = true, csr_on_device = true;  // h_cells / d_offsets and d_cells hold the last batch (false: only the arena does)
+    int last_max_len = 0;                             // ... whose path slots in d_path are this long
     std::vector<uint32_t> h_order;
     // shard of the current batch
     int64_t q0 = 0, nq = 0;
@@ -687,6 +706,7 @@ struct BatchReq {
     int W = 0, H = 0;
     uint64_t cells = 0;
     bool track() const { return mode != 0; }
+    bool stream = false;  // plan_core: a plain batch, its results go to the host as the queries end (DevCtx::st)
 };
 
 // Gives the memory of pool 0 back (a batch buffer did not fit beside it); the next batch sizes it again from what is free.
@@ -919,6 +939,14 @@ void fill_search_args(const DevCtx& d, const BatchReq& req, int pool, SearchArgs
         A.grids = d.d_slot_desc.p;
         A.grid_ids = d.d_grid_ids.p;
     }
+    if (d.st.on) {  // a plain batch that streams: each query's results go to the host as it ends
+        A.host_cells = d.st.cells;
+        A.host_cap = d.st.cap;
+        A.host_cursor = d.d_cursor.p;
+        A.host_base = d.st.base;
+        A.host_len = d.st.len;
+        A.host_cost = d.st.cost;
+    }
 }
 
 int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint32_t* d_order, uint32_t nrun) {
@@ -1024,13 +1052,47 @@ int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint
         if (pool == 0) d.run.had_solo = nsolo != 0u;
     }
     HIPCHK(h, hipEventRecord(d.ev1, d.stream));
+    if (d.st.on) {  // (behind both launches: the stream waits for the head launch above)
+        hipLaunchKernelGGL(fx::k_counters_out, dim3(1), dim3(64), 0, d.stream, d.d_counters.p, d.st.counters);
+        HIPCHK(h, hipGetLastError());
+    }
     d.run.launches += nsolo != 0u ? 2 : 1;  // (the two launches overlap: the events span both)
     return FXJPS_OK;
 }
 
-// Runs the shard [q0, q0+nq) of the batch on device d up to the point where
-// len/cost/offsets are in pinned host memory and the CSR cells are packed on
-// the device.
+// A plain batch is about to be queued: the room its results stream into.  The arena starts at nq * min(max_len, 512)
+// cells and follows 1.25 x the largest total this context has produced; ARENA_BYTES per handle, divided among its
+// contexts, bound it, and a batch that is expected to need more does not stream (d.st.on stays false: today's tail).
+// FXJPS_ARENA_CELLS=n: the arena holds n cells for this call (test aid: n below a batch's total makes it overflow).
+constexpr size_t ARENA_BYTES = (size_t)1 << 30;
+int begin_streaming(fxjps* h, DevCtx& d, const BatchReq& req) {
+    const int64_t nq = d.nq;
+    const unsigned long long limit = ARENA_BYTES / sizeof(uint32_t) / h->devs.size();
+    unsigned long long want = (unsigned long long)nq * (unsigned long long)std::min(req.max_len, 512);
+    want = std::max(want, (unsigned long long)d.arena_peak + (unsigned long long)d.arena_peak / 4);
+    if (const char* e = getenv("FXJPS_ARENA_CELLS")) want = (unsigned long long)std::max(0ll, atoll(e));
+    if (want > limit) return FXJPS_OK;
+    HIPCHK(h, d.h_arena.ensure((size_t)std::max(want, 1ull)));
+    HIPCHK(h, d.h_base.ensure((size_t)nq));
+    HIPCHK(h, d.d_cursor.ensure(1));
+    void *dp_cells = nullptr, *dp_base = nullptr, *dp_len = nullptr, *dp_cost = nullptr, *dp_cnt = nullptr;
+    HIPCHK(h, hipHostGetDevicePointer(&dp_cells, d.h_arena.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_base, d.h_base.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_len, d.h_len.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_cost, d.h_cost.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_cnt, d.h_counters.p, 0));
+    HIPCHK(h, hipMemsetAsync(d.d_cursor.p, 0, sizeof(unsigned long long), d.stream));
+    d.st.on = true;
+    d.st.cells = (uint32_t*)dp_cells;
+    d.st.cap = want;
+    d.st.base = (long long*)dp_base;
+    d.st.len = (int32_t*)dp_len;
+    d.st.cost = (double*)dp_cost;
+    d.st.counters = (unsigned long long*)dp_cnt;
+    return FXJPS_OK;
+}
+
+// Runs the shard [q0, q0+nq) of the batch on device d up to the point where the search is queued.
 int run_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     HIPCHK(h, hipSetDevice(d.dev));
     const int64_t nq = d.nq;
@@ -1057,6 +1119,7 @@ int run_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
         HIPCHK(h, hipMemcpyAsync(d.d_grid_ids.p, req.grid_ids + d.q0, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, d.stream));
     }
     HIPCHK(h, hipMemsetAsync(d.d_counters.p, 0, 64 * sizeof(unsigned long long), d.stream));
+    d.st = DevCtx::Streaming();
     if (getenv("FXJPS_QSTAT")) {  // diagnostics: per-query start / end time, pops, wavefront (tools/qstat.py)
         HIPCHK(h, d.d_qstat.ensure((size_t)nq * 4));
         HIPCHK(h, hipMemsetAsync(d.d_qstat.p, 0, (size_t)nq * 4 * sizeof(unsigned long long), d.stream));
@@ -1104,6 +1167,9 @@ int run_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     int rc = ensure_pool(h, d, req, 0, (uint32_t)std::min<int64_t>(full, (d.run.nrun + 3) & ~3ll));
     if (rc) return rc;
     DBG("pool ready");
+    // (the search kernels with cell-indexed tables are the ones that stream: profiles/result_streaming_resource_usage.json)
+    if (req.stream && d.cfg[0].direct_ly > 0)
+        if ((rc = begin_streaming(h, d, req)) != FXJPS_OK) return rc;
     return launch_search(h, d, req, 0, d.d_order.p, (uint32_t)d.run.nrun);
 }
 
@@ -1120,8 +1186,10 @@ int finish_search(fxjps* h, DevCtx& d, const BatchReq& req) {
     DBG("waiting for the search kernel");
     HIPCHK(h, hipStreamSynchronize(d.stream));
     DBG("search kernel done");
-    HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(h, hipStreamSynchronize(d.stream));
+    if (!d.st.on) {  // (a streamed batch: the kernel left the lengths in h_len)
+        HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(h, hipStreamSynchronize(d.stream));
+    }
     float ms = 0;
     if (d.run.launches > 0) {
         HIPCHK(h, hipEventElapsedTime(&ms, d.ev0, d.ev1));
@@ -1144,11 +1212,15 @@ int finish_search(fxjps* h, DevCtx& d, const BatchReq& req) {
         HIPCHK(h, d.d_redo.ensure(redo.size()));
         HIPCHK(h, hipMemcpyAsync(d.d_redo.p, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));  // `redo` is pageable host memory
+        if (d.cfg[1].direct_ly == 0) d.st = DevCtx::Streaming();  // (the large pool's tables are hashed: its kernel leaves the retried
+                                                                  // queries' results on the device only, and the batch is packed there)
         rc = launch_search(h, d, req, 1, d.d_redo.p, (uint32_t)redo.size());
         if (rc) return rc;
         HIPCHK(h, hipStreamSynchronize(d.stream));  // (as above: no copy waits in the engine's queue for a search)
-        HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
-        HIPCHK(h, hipStreamSynchronize(d.stream));
+        if (!d.st.on) {
+            HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(h, hipStreamSynchronize(d.stream));
+        }
         HIPCHK(h, hipEventElapsedTime(&ms, d.ev0, d.ev1));
         d.run.kernel_ms += ms;
     }
@@ -1162,12 +1234,9 @@ void hide_internal_codes(DevCtx& d) {
         if (d.h_len.p[i] <= fx::QI_TABLE_FULL) d.h_len.p[i] = FXJPS_Q_CAPACITY;
 }
 
-// Second half: wait for the search, retry overflowed queries with the large
-// pool, pack to CSR, copy len/cost/offsets back.
-int finish_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
+// The search is over and its lengths are on the host: pack to CSR on the device, copy offsets / costs / counters / cells back.
+int pack_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
     const int64_t nq = d.nq;
-    if (nq == 0) return FXJPS_OK;
-    if (int rc = finish_search(h, d, req)) return rc;
     hipLaunchKernelGGL(fx::k_scan_len, dim3(1), dim3(1024), 0, d.stream, d.d_len.p, (long long)nq, d.d_offsets.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(d.h_offsets.p, d.d_offsets.p, ((size_t)nq + 1) * sizeof(long long), hipMemcpyDeviceToHost, d.stream));
@@ -1190,7 +1259,75 @@ int finish_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
         HIPCHK(h, hipStreamSynchronize(d.stream));
     }
     DBG("gather done");
+    d.cells_on_host = d.csr_on_device = true;
+    return FXJPS_OK;
+}
+
+// Second half: wait for the search, retry overflowed queries with the large pool, and leave lengths, costs, offsets and
+// counters in pinned host memory.  A batch that streamed has them there already, with its cells in the arena: the offsets
+// are a host prefix sum, and h_cells and the device CSR wait for a reader (host_cells / device_csr).  Any other batch, and
+// a streamed one whose arena overflowed, packs on the device and copies back (pack_shard).
+int finish_shard(fxjps* h, DevCtx& d, const BatchReq& req) {
+    const int64_t nq = d.nq;
+    if (nq == 0) return FXJPS_OK;
+    if (int rc = finish_search(h, d, req)) return rc;
+    d.last_max_len = req.max_len;
+    bool packed = !d.st.on;
+    if (d.st.on) {
+        const fx::StreamedResults R{d.h_len.p, d.h_base.p, d.h_arena.p, nq};
+        const long long total = fx::result_offsets(d.h_len.p, nq, d.h_offsets.p);
+        d.arena_peak = std::max(d.arena_peak, total);
+        packed = fx::result_overflows(R, 0, nq) != 0;  // (the next batch's arena is sized from the total just recorded)
+        d.cells_on_host = d.csr_on_device = false;
+        DBG("streamed %lld cells into an arena of %llu%s", total, d.st.cap, packed ? ": overflow" : "");
+    }
+    if (packed)
+        if (int rc = pack_shard(h, d, req)) return rc;
     hide_internal_codes(d);
+    return FXJPS_OK;
+}
+
+// A streamed batch's cells out of the arena into dst (int32 pairs, query order), by query ranges over host threads.
+void expand_arena(const DevCtx& d, int32_t* dst) {
+    const fx::StreamedResults R{d.h_len.p, d.h_base.p, d.h_arena.p, d.nq};
+    fx::result_expand_split(R, d.h_offsets.p, dst, fx::result_threads(d.h_offsets.p[d.nq]), [](size_t n, auto&& job) {
+        (void)run_side_by_side(n, [&](size_t i) {
+            job(i);
+            return 0;
+        });
+    });
+}
+
+// The last batch's cells in h_cells (int32 pairs, query order): a streamed batch's are expanded out of the arena the first
+// time a reader asks.
+int host_cells(fxjps* h, DevCtx& d) {
+    if (d.cells_on_host || d.nq == 0) return FXJPS_OK;
+    const long long total = d.h_offsets.p[d.nq];
+    HIPCHK(h, hipSetDevice(d.dev));
+    HIPCHK(h, d.h_cells.ensure((size_t)std::max(total, 1ll) * 2));
+    expand_arena(d, d.h_cells.p);
+    d.cells_on_host = true;
+    return FXJPS_OK;
+}
+
+// ... and on the device (d_offsets / d_cells, for the resident forms of the waypoint calls): packed out of the path slots,
+// which hold the batch until the next one begins, the first time a reader asks.  (Lazy, not queued behind the search: a
+// batch whose paths nobody reads on the device pays nothing for them.)
+int device_csr(fxjps* h, DevCtx& d) {
+    if (d.csr_on_device || d.nq == 0) return FXJPS_OK;
+    const int64_t nq = d.nq;
+    const long long total = d.h_offsets.p[nq];
+    HIPCHK(h, hipSetDevice(d.dev));
+    hipLaunchKernelGGL(fx::k_scan_len, dim3(1), dim3(1024), 0, d.stream, d.d_len.p, (long long)nq, d.d_offsets.p);
+    HIPCHK(h, hipGetLastError());
+    if (total > 0) {
+        if (int rc = ensure_beside_pool0(h, d, d.d_cells, (size_t)total * 2)) return rc;
+        hipLaunchKernelGGL(fx::k_gather_paths, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, d.stream, d.d_path.p,
+                           d.d_len.p, d.d_offsets.p, (long long)nq, d.last_max_len, d.d_cells.p, total);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    d.csr_on_device = true;
     return FXJPS_OK;
 }
 
@@ -1208,6 +1345,8 @@ int plan_single(fxjps* h, DevCtx& d, const BatchReq& req) {
     d.nq = 1;
     d.run = DevCtx::RunStats();
     d.run.nrun = d.run.waves_used = 1;
+    d.st = DevCtx::Streaming();
+    d.cells_on_host = d.csr_on_device = true;  // (a single call's CSR is on the host only: LastBatch::on_host)
     HIPCHK(h, d.h_len.ensure(1));
     HIPCHK(h, d.h_cost.ensure(1));
     HIPCHK(h, d.h_offsets.ensure(2));
@@ -1355,7 +1494,13 @@ int end_call(fxjps* h, double t0, double* out_seconds_total, int rc) {
     return rc;
 }
 
-int plan_core(fxjps* h, const BatchReq& req) {
+int plan_core(fxjps* h, const BatchReq& request) {
+    BatchReq req = request;
+    // FXJPS_STREAM_RESULTS=1, read per call: a plain batch streams its results to the host (begin_streaming).  Off by
+    // default (and with =0): the results are packed on the device and copied back when the search is over.  Measured
+    // (profiles/result_streaming.txt): the stores to host memory slow the search down by what the
+    // shorter tail saves on config 2 (+ 0.8 ms of kernel time for - 0.85 ms behind it) and by more on 125 000 queries.
+    req.stream = req.mode == 0 && getenv("FXJPS_STREAM_RESULTS") && atoi(getenv("FXJPS_STREAM_RESULTS")) != 0;
     if (int rc = begin_batch(h, req)) return rc;
     const int64_t nq = req.nq;
     const int nd = (int)h->devs.size();
@@ -1597,6 +1742,8 @@ struct WpPaths {
         if (resident) {
             for (auto& d : h->devs) {
                 if (d.nq == 0) continue;
+                if (int rc = host_cells(h, d)) return rc;  // (a streamed batch builds both forms here, the first time)
+                if (int rc = device_csr(h, d)) return rc;
                 const long long t = d.h_offsets.p[d.nq];
                 parts.push_back(Part{&d, d.q0, d.nq, t, total, d.h_offsets.p, d.h_cells.p, d.d_offsets.p, d.d_cells.p, d.d_len.p});
                 total += t;
@@ -2439,6 +2586,18 @@ static void host_copy(void* dst, const void* src, size_t bytes) {
     });
 }
 
+// The last batch's cells of one context -> the caller's array: a copy of h_cells where they are there, otherwise (a
+// streamed batch nobody has read on the host yet) expanded straight out of the arena, by query ranges over host threads --
+// the caller's pages are touched once.
+static void put_cells(const DevCtx& d, int32_t* dst) {
+    const long long total = d.h_offsets.p[d.nq];
+    if (d.cells_on_host) {
+        host_copy(dst, d.h_cells.p, (size_t)total * 2 * sizeof(int32_t));
+        return;
+    }
+    expand_arena(d, dst);
+}
+
 // plan_core's results -> the caller's CSR arrays
 static int emit_csr(fxjps_t* h, int64_t nq, int64_t* out_offsets, int32_t* out_cells_xy, int64_t cells_capacity, int32_t* out_len,
              double* out_cost) {
@@ -2466,7 +2625,7 @@ static int emit_csr(fxjps_t* h, int64_t nq, int64_t* out_offsets, int32_t* out_c
         memcpy(out_len + dp->q0, dp->h_len.p, (size_t)dp->nq * sizeof(int32_t));
         memcpy(out_cost + dp->q0, dp->h_cost.p, (size_t)dp->nq * sizeof(double));
         for (int64_t k = 0; k < dp->nq; k++) out_offsets[dp->q0 + k] = u.base + dp->h_offsets.p[k];
-        if (u.cells) host_copy(out_cells_xy + 2 * u.base, dp->h_cells.p, (size_t)u.total * 2 * sizeof(int32_t));
+        if (u.cells) put_cells(*dp, out_cells_xy + 2 * u.base);
         return 0;
     });
     if (out_offsets) out_offsets[nq] = base;
@@ -3810,6 +3969,7 @@ int replan_slots_assemble(fxjps* h, DevCtx& d, const BatchReq& req, const std::v
     HIPCHK(h, hipStreamSynchronize(d.stream));
     if (nsub == 0) memset(d.h_counters.p, 0, 64 * sizeof(unsigned long long));  // (nothing was searched)
     d.nq = nq;
+    d.cells_on_host = d.csr_on_device = true;
     if (d.h_offsets.p[nq] != total) return fail(h, FXJPS_E_HIP, "the assembled batch has %lld cells, the host counted %lld", (long long)d.h_offsets.p[nq], total);
     hide_internal_codes(d);
     return FXJPS_OK;
@@ -3957,18 +4117,17 @@ int fxjps_last_cells(fxjps_t* h, int32_t* out_cells_xy, int64_t cells_capacity) 
     base = 0;
     struct Put {
         int32_t* dst;
-        const int32_t* src;
-        int64_t total;
+        const DevCtx* d;
     };
     std::vector<Put> puts;  // (several contexts: their slices are copied side by side, as in emit_csr)
     for (auto& d : h->devs) {
         if (d.nq == 0 || !d.h_offsets.p) continue;
         const int64_t total = d.h_offsets.p[d.nq];
-        if (total > 0) puts.push_back(Put{out_cells_xy + 2 * base, d.h_cells.p, total});
+        if (total > 0) puts.push_back(Put{out_cells_xy + 2 * base, &d});
         base += total;
     }
     (void)run_side_by_side(puts.size(), [&](size_t i) {
-        host_copy(puts[i].dst, puts[i].src, (size_t)puts[i].total * 2 * sizeof(int32_t));
+        put_cells(*puts[i].d, puts[i].dst);
         return 0;
     });
     return FXJPS_OK;
@@ -3986,13 +4145,13 @@ int fxjps_plan_batch(fxjps_t* h, const int32_t* starts_xy, const int32_t* goals_
         if (d.nq == 0) continue;
         memcpy(out_len + d.q0, d.h_len.p, (size_t)d.nq * sizeof(int32_t));
         memcpy(out_cost + d.q0, d.h_cost.p, (size_t)d.nq * sizeof(double));
-        if (out_cells_xy)
-            for (int64_t i = 0; i < d.nq; i++) {
-                const int32_t n = d.h_len.p[i];
-                if (n > 0)
-                    memcpy(out_cells_xy + (size_t)(d.q0 + i) * max_path_len * 2, d.h_cells.p + 2 * d.h_offsets.p[i],
-                           (size_t)n * 2 * sizeof(int32_t));
-            }
+        if (!out_cells_xy) continue;
+        if ((rc = host_cells(h, d)) != FXJPS_OK) return rc;
+        for (int64_t i = 0; i < d.nq; i++) {
+            const int32_t n = d.h_len.p[i];
+            if (n > 0)
+                memcpy(out_cells_xy + (size_t)(d.q0 + i) * max_path_len * 2, d.h_cells.p + 2 * d.h_offsets.p[i], (size_t)n * 2 * sizeof(int32_t));
+        }
     }
     return end_call(h, t0, out_seconds_total, FXJPS_OK);
 }

@@ -128,6 +128,15 @@ struct SearchArgs {
     // k_search<.., .., .., true> (grid slots): query q runs on grids[grid_ids[q]] instead of G (the host checked every id)
     const GridDev* grids = nullptr;     // [FXJPS_MAX_GRID_SLOTS] descriptors of the context's slots
     const int32_t* grid_ids = nullptr;  // [nq]
+    // a plain batch's results straight to the host as each query ends (DESIGN.md section 7; all null / zero: off).  Device
+    // pointers of pinned host memory: the arena of packed cells and how many it holds, per query where its cells begin in
+    // it (-1: they did not fit), its length and its cost; and the arena's cursor, in device memory.
+    uint32_t* host_cells = nullptr;
+    unsigned long long host_cap = 0ull;
+    unsigned long long* host_cursor = nullptr;
+    long long* host_base = nullptr;
+    int32_t* host_len = nullptr;
+    double* host_cost = nullptr;
 };
 
 // nodeNeighbours (jps1.py:49-93) as a table: entry [pd*256 + nbm] holds, for each of a node's 8 rays,
@@ -467,6 +476,13 @@ struct OpenList {  // per-wavefront open-list state, all wave-uniform
 // the jump past the join into whatever follows (a loop back-edge, a return), and its divergence analysis then
 // treats every wave-uniform value merged there as lane-dependent (VGPRs and exec-mask loops instead of SGPRs).
 #define RECONV() __builtin_amdgcn_wave_barrier()
+
+// Which lane touches which cell of a query's path slot: cell k belongs to lane k % WAVE.  search_one stores the slot by this
+// rule and store_result reads it back by it with no fence between the two -- a lane only ever reads what it stored itself.
+template <typename F>
+__device__ __forceinline__ void for_path_cells(int lane, uint32_t n, F&& f) {
+    for (uint32_t k = (uint32_t)lane; k < n; k += WAVE) f(k);
+}
 
 // The open-list state is wave-uniform by construction.  Saying so (readfirstlane folds away for values already
 // in SGPRs) stops the compiler's divergence analysis from dragging it through joins of lane-dependent branches.
@@ -2948,7 +2964,7 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev
                 } else {
                     res_len = n;
                     uint32_t* dst = A.out_path + (size_t)q * A.max_len;
-                    for (uint32_t k = lane; k < n; k += WAVE) dst[k] = scratch[n - 1 - k];
+                    for_path_cells(lane, n, [&](uint32_t k) { dst[k] = scratch[n - 1 - k]; });  // (store_result reads the slot back by the same rule)
                     RECONV();
                 }
                 GEN_NEXT;
@@ -3118,6 +3134,41 @@ __device__ __forceinline__ int32_t search_one(const SearchArgs& A, const GridDev
     return (int32_t)rfl(res_len);
 }
 
+// A plain batch: a finished path goes to the host now, not when the slowest query of the batch has ended (DESIGN.md
+// section 7).  The wavefront takes res_len cells of the arena (every lane takes part in the add, as in the work counter's
+// fetch: lane 0 adds, the others add 0) and copies its path slot there.  search_one's lanes stored the slot by the same
+// rule (for_path_cells), so each lane reads back what it stored itself and program order is all the copy needs -- a
+// release fence in front of it writes the L2 back once per query (profiles/result_streaming.txt section 1: + 6 % kernel
+// time on 125 000 queries).  (The large retry pool's kernels are hashed ones and do not come here: a batch that retried is
+// packed on the device, finish_search.)
+// A function of its own, handed the kernel-argument segment (the kernel's one argument is SearchArgs, at offset 0):
+// inlined into run_query, its six pointers are loaded in front of the loop over the queries and stay live across every
+// search -- more scalar spills in every instantiation, a vector spill in the hashed ones.
+__device__ __noinline__ __attribute__((cold)) void store_result(const __attribute__((address_space(4))) SearchArgs* A, uint32_t q, int32_t res_len, double res_cost,
+                                                                uint32_t start_cell) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+        if (start_cell != ~0u) A->out_path[(size_t)q * A->max_len] = start_cell;  // (start == goal: the path is the start)
+        A->out_len[q] = res_len;
+        A->out_cost[q] = (res_len == 0 || res_len <= QI_TABLE_FULL) ? 0.0 : res_cost;
+    }
+    if (A->host_len == nullptr) return;
+    if (res_len > 0) {
+        const unsigned long long base = rfl64(atomicAdd(A->host_cursor, lane == 0 ? (unsigned long long)res_len : 0ull));
+        const bool fits = base + (unsigned long long)res_len <= A->host_cap;
+        if (fits) {
+            const uint32_t* src = A->out_path + (size_t)q * A->max_len;
+            uint32_t* dst = A->host_cells + base;
+            for_path_cells(lane, (uint32_t)res_len, [&](uint32_t k) { dst[k] = src[k]; });
+        }
+        if (lane == 0) A->host_base[q] = fits ? (long long)base : -1ll;
+    }
+    if (lane == 0) {
+        A->host_len[q] = res_len;
+        A->host_cost[q] = (res_len == 0 || res_len <= QI_TABLE_FULL) ? 0.0 : res_cost;
+    }
+}
+
 template <int HC, bool TRK, bool DIRECT, bool MG, class MID>
 __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q, const MID& S, TEnt* __restrict__ tab,
                           FarEnt* __restrict__ far, uint32_t& gen) {
@@ -3213,14 +3264,21 @@ __device__ __forceinline__ void run_query(const SearchArgs& A, const uint32_t q,
             RECONV();
         }
     }
-    if (lane == 0) {
-        if (start_only) A.out_path[(size_t)q * A.max_len] = ((uint32_t)sx << 16) | (uint32_t)sy;
-        A.out_len[q] = res_len;
-        A.out_cost[q] = (res_len == 0 || res_len <= QI_TABLE_FULL) ? 0.0 : res_cost;
+    if (TRK || !DIRECT) {
+        if (lane == 0) {
+            if (start_only) A.out_path[(size_t)q * A.max_len] = ((uint32_t)sx << 16) | (uint32_t)sy;
+            A.out_len[q] = res_len;
+            A.out_cost[q] = (res_len == 0 || res_len <= QI_TABLE_FULL) ? 0.0 : res_cost;
+        }
+        RECONV();
+    } else {  // (cell-indexed tables, no read sets: the same three stores, and a plain batch's results to the host)
+        store_result((const __attribute__((address_space(4))) SearchArgs*)__builtin_amdgcn_kernarg_segment_ptr(), q, res_len, res_cost,
+                     start_only ? ((uint32_t)sx << 16) | (uint32_t)sy : ~0u);
+        RECONV();
     }
-    RECONV();
 }
 
+// (SearchArgs is the kernel's ONE argument, so it lies at offset 0 of the kernel-argument segment: store_result reads it there)
 template <int HC, bool TRK, bool DIRECT, bool MG>
 __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
 #include "fxjps_search_block.hip.inc"
@@ -3231,6 +3289,7 @@ __global__ __launch_bounds__(WAVE* WPB, OCC) void k_search(SearchArgs A) {
 // queries of different slots, and a read set lands at A.qread + q * 128, q being the index in the (sub-)batch.
 // (A kernel name of its own, not k_search<HC, true, DIRECT, true>: the slots batch's k_search instantiations stay the four
 // untracked ones, and so does every kernel the tile rule does not use.)
+// (one argument, as k_search: run_query's exit may read SearchArgs at offset 0 of the kernel-argument segment)
 template <int HC, bool DIRECT>
 __global__ __launch_bounds__(WAVE* WPB, OCC) void k_slot_reads_search(SearchArgs A) {
     constexpr bool TRK = true, MG = true;
@@ -3352,6 +3411,12 @@ __global__ __launch_bounds__(WAVE) void k_selftest_openlist(SearchArgs A, const 
         out_info[6] = Q.far_n;
         out_info[7] = Q.farb_n;
     }
+}
+
+// A streamed batch's 64 counters into the handle's pinned buffer, queued behind each of its searches: a kernel and not a
+// copy, because a copy that waits in the copy engine's queue for a search holds up every copy queued after it (finish_search).
+__global__ __launch_bounds__(64) void k_counters_out(const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host) {
+    host[threadIdx.x] = counters[threadIdx.x];
 }
 
 // ---------------------------------------------------------------- CSR packing
