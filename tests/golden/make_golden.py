@@ -16,6 +16,7 @@ Files written:
     synth1024.json       128 queries of the config-2 workload (1024^2, 20 %)
     synth4096.json       (--big) 4 queries of the config-3 workload
     families.json        (make_golden_families.py) structured map families, both hchoice
+    exhaustive.npz       (make_golden_exhaustive.py) digests of every query on every grid of <= 12 cells and of 4 x 4
 """
 import argparse
 import contextlib
