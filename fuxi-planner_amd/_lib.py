@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 850  # FXJPS_VERSION of include/fxjps.h
+VERSION = 860  # FXJPS_VERSION of include/fxjps.h
 PATH_VALID, PATH_EMPTY, PATH_BLOCKED, PATH_OUTSIDE, PATH_MALFORMED = 1, 0, 2, 3, -1  # FXJPS_PATH_*: fxjps_check_path's verdicts
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
@@ -29,7 +29,8 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_set_grid_slots", "fxjps_refresh_grid_slots", "fxjps_grid_job_size",
            "fxjps_set_slot_reuse", "fxjps_debug_slot_tiles", "fxjps_debug_slot_read_sets",
            "fxjps_check_path", "fxjps_check_paths_slots",
-           "fxjps_absorb_prior", "fxjps_absorb_check", "fxjps_absorb_job_size")
+           "fxjps_absorb_prior", "fxjps_absorb_check", "fxjps_absorb_job_size",
+           "fxjps_absorb_prior_grow", "fxjps_grow_check", "fxjps_grow_job_size", "fxjps_prior_grown_size")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 ABSORB_OVERWRITE, ABSORB_OCCUPIED, ABSORB_KNOWN = 0, 1, 2  # FXJPS_ABSORB_*: fxjps_absorb_prior's modes
@@ -81,6 +82,18 @@ class AbsorbJob(C.Structure):
     _fields_ = [("raw", C.c_void_p), ("layout", C.c_int32), ("W0", C.c_int32), ("H0", C.c_int32), ("lo", C.c_int32 * 2),
                 ("win", C.c_int32 * 2), ("prior", C.c_int32), ("reserved_", C.c_int32), ("map_o", C.c_double * 2),
                 ("map_reso", C.c_double), ("ori_pre", C.c_double * 2), ("inside", C.c_int64), ("outside", C.c_int64)]
+
+
+class GrowJob(C.Structure):
+    """fxjps_grow_job_t: fxjps_absorb_job_t's fields, then the rectangle's top and where it landed in the grown prior
+    (fxjps_absorb_prior_grow)."""
+    _fields_ = AbsorbJob._fields_ + [("map_t", C.c_double * 2), ("at", C.c_int32 * 2)]
+
+
+class PriorGrown(C.Structure):
+    """fxjps_prior_grown_t: what fxjps_absorb_prior_grow made of one prior map."""
+    _fields_ = [("named", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("shift", C.c_int32 * 2), ("reserved_", C.c_int32),
+                ("origin", C.c_double * 2), ("changed", C.c_int64)]
 
 
 class SlotPublish(C.Structure):
@@ -156,6 +169,11 @@ def load():
     if L.fxjps_absorb_job_size() != C.sizeof(AbsorbJob):
         raise FxjpsError(E_ARG, "%s has a %d-byte absorb job; this binding's is %d bytes: rebuild it"
                          % (LIB_PATH, L.fxjps_absorb_job_size(), C.sizeof(AbsorbJob)))
+    L.fxjps_grow_job_size.restype = C.c_int
+    L.fxjps_prior_grown_size.restype = C.c_int
+    if L.fxjps_grow_job_size() != C.sizeof(GrowJob) or L.fxjps_prior_grown_size() != C.sizeof(PriorGrown):
+        raise FxjpsError(E_ARG, "%s has a %d-byte grow job and a %d-byte grown-prior record; this binding's are %d and %d bytes: rebuild it"
+                         % (LIB_PATH, L.fxjps_grow_job_size(), L.fxjps_prior_grown_size(), C.sizeof(GrowJob), C.sizeof(PriorGrown)))
     L.fxjps_last_timing_sized.restype = C.c_int
     L.fxjps_last_timing_sized.argtypes = [vp, vp, C.c_int64]
     L.fxjps_rank_preflight.restype = C.c_int
@@ -308,6 +326,10 @@ def load():
     L.fxjps_absorb_prior.argtypes = [vp, C.POINTER(AbsorbJob), C.c_int32, C.c_int32, p_i64]
     L.fxjps_absorb_check.restype = C.c_int  # (no handle, no device: the call's argument check and placement)
     L.fxjps_absorb_check.argtypes = [C.POINTER(AbsorbJob), C.c_int32, C.c_int32, p_i32, C.c_char_p, C.c_int32]
+    L.fxjps_absorb_prior_grow.restype = C.c_int
+    L.fxjps_absorb_prior_grow.argtypes = [vp, C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, C.POINTER(PriorGrown)]
+    L.fxjps_grow_check.restype = C.c_int  # (no handle, no device: the call's geometry and refusals)
+    L.fxjps_grow_check.argtypes = [C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, p_i32, C.POINTER(PriorGrown), C.c_char_p, C.c_int32]
     bind_host(L)
     _lib = L
     return L

@@ -208,6 +208,8 @@ struct DevCtx : GridBufs {
     struct PriorBuf {
         DBuf<uint8_t> occ;
         int W = 0, H = 0;
+        DBuf<uint8_t> next;  // fxjps_absorb_prior_grow: the grown prior on its way in; swapped with occ once every context has
+                             // succeeded, and afterwards the spare the next grow writes into
     };
     std::vector<PriorBuf> priors;  // [FXJPS_MAX_PRIOR_MAPS] once the first prior is set
     // fxjps_publish_slots: the call's job table (fx::PubTable) and all its outputs, pinned and on the device
@@ -318,7 +320,7 @@ struct DevCtx : GridBufs {
         double head_ms = 0, batch_ms = 0;  // ... and how long each of them ran
     } run;
     // fxjps_absorb_prior: the call's staged input (fx::AbsorbTable | the rows of each raw that hold its rectangle), pinned
-    // and on the device, and the table's counters on their way back
+    // and on the device, and the table's counters on their way back (fxjps_absorb_prior_grow: the same with a fx::GrowTable)
     HBuf<uint8_t> h_absorb_in;
     DBuf<uint8_t> d_absorb_in;
     HBuf<unsigned long long> h_absorb_out;
@@ -3422,6 +3424,7 @@ int fxjps_set_prior_map(fxjps_t* h, int32_t prior, const uint8_t* occ, int32_t W
         DevCtx::PriorBuf& pr = d.priors[(size_t)prior];
         HIPCHK(h, hipStreamSynchronize(d.stream));  // (whatever is queued may still read the prior's bytes)
         pr.W = pr.H = 0;
+        pr.next.release();  // (a grown prior's spare buffer goes with it)
         if (!occ) {
             pr.occ.release();
             return FXJPS_OK;
@@ -4842,6 +4845,250 @@ int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t 
         return rc;
     }
     for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out_changed[p] = (int64_t)h->devs[0].h_absorb_out.p[p];
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ ... into prior maps that grow
+int fxjps_grow_job_size(void) { return (int)sizeof(fxjps_grow_job_t); }
+int fxjps_prior_grown_size(void) { return (int)sizeof(fxjps_prior_grown_t); }
+
+namespace {
+constexpr size_t GROW_IN_RAWS = (sizeof(fx::GrowTable) + 15) & ~(size_t)15;
+
+// What the host folds from the jobs before anything is queued.  Per job: where the rectangle lies in the prior as the
+// call leaves it, and which rows of raw are staged (as AbsorbPlan).  Per prior: the grown extents, where the old prior's
+// cell (0, 0) lies in them, the new origin and the union box of its rectangles.
+struct GrowPlan {
+    struct Job {
+        long long at[2];
+        size_t raw_off, raw_bytes, in_off;
+    };
+    struct Prior {
+        bool named = false;
+        int first = -1;                  // the first job that names it: every later one has its ori_pre and map_reso
+        long long ext[2] = {0, 0};       // the extents, job after job
+        long long shift[2] = {0, 0};     // the sum of every job's at_pre
+        double op[2] = {0.0, 0.0};       // the origin, job after job
+        long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};  // the union box, in the final frame
+    };
+    std::vector<Job> job;
+    Prior prior[FXJPS_MAX_PRIOR_MAPS];
+    size_t in_bytes = GROW_IN_RAWS;
+};
+
+// Everything fxjps_absorb_prior_grow refuses except a rank handle, and the whole geometry, from the arguments and the
+// priors' extents alone: float64, the reference's operations in the reference's order (st:187, :212-216), job after job
+// on the extents and origin the job before left.  Writes nothing unless every job passes; then plan, every job's inside /
+// outside / at and every field of out but `changed`.  (The per-job argument checks are absorb_check's, word for word.)
+int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, fxjps_prior_grown_t* out, GrowPlan& plan,
+               char* msg, size_t len) {
+    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return absorb_refuse(msg, len, "job 0: n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
+    if (n > 0 && !jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
+    if (!prior_wh) return absorb_refuse(msg, len, "job 0: NULL prior extents");
+    if (!out) return absorb_refuse(msg, len, "job 0: NULL out");
+    if (mode < 0 || mode > 2) return absorb_refuse(msg, len, "job 0: mode %d is not FXJPS_ABSORB_OVERWRITE, _OCCUPIED or _KNOWN", (int)mode);
+    long long limit[2] = {8190, 8190};
+    if (limit_wh)
+        for (int k = 0; k < 2; k++) {
+            limit[k] = limit_wh[k];
+            if (limit[k] < 1 || limit[k] > 8190) return absorb_refuse(msg, len, "job 0: axis %d: the limit %lld is not in 1 .. 8190", k, limit[k]);
+        }
+    plan = GrowPlan{};
+    plan.job.resize((size_t)n);
+    for (int j = 0; j < n; j++) {
+        const fxjps_grow_job_t& a = jobs[j];
+        if (!a.raw) return absorb_refuse(msg, len, "job %d: NULL raw", j);
+        if (a.layout != 0 && a.layout != 1) return absorb_refuse(msg, len, "job %d: layout %d is not 0 or 1", j, (int)a.layout);
+        if (a.W0 < 1 || a.H0 < 1 || a.W0 > 8190 || a.H0 > 8190)
+            return absorb_refuse(msg, len, "job %d: bad extents (W0 %d, H0 %d): raw must be 1..8190 cells a side", j, (int)a.W0, (int)a.H0);
+        const long long ext[2] = {a.W0, a.H0};
+        for (int k = 0; k < 2; k++)
+            if (a.win[k] < 1 || a.lo[k] < 0 || (long long)a.lo[k] + a.win[k] > ext[k])
+                return absorb_refuse(msg, len, "job %d: axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %lld cells", j, k, (int)a.lo[k],
+                                     (int)a.win[k], ext[k]);
+        if (a.prior < 0 || a.prior >= FXJPS_MAX_PRIOR_MAPS) return absorb_refuse(msg, len, "job %d: prior %d is not in 0 .. %d", j, (int)a.prior, FXJPS_MAX_PRIOR_MAPS - 1);
+        GrowPlan::Prior& P = plan.prior[a.prior];
+        if (!P.named) {
+            P.ext[0] = prior_wh[2 * a.prior];
+            P.ext[1] = prior_wh[2 * a.prior + 1];
+        }
+        if (P.ext[0] < 1 || P.ext[1] < 1) return absorb_refuse(msg, len, "job %d: prior %d is not set", j, (int)a.prior);
+        const double reso = a.map_reso;
+        if (!std::isfinite(reso) || !(reso > 0.0)) return absorb_refuse(msg, len, "job %d: map_reso %g must be finite and > 0", j, reso);
+        for (int k = 0; k < 2; k++) {
+            if (!std::isfinite(a.map_o[k]) || !std::isfinite(a.ori_pre[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_o / ori_pre", j);
+            if (!std::isfinite(a.map_t[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_t", j);
+        }
+        if (!P.named) {
+            P.named = true;
+            P.first = j;
+            P.op[0] = a.ori_pre[0];
+            P.op[1] = a.ori_pre[1];
+        } else {
+            const fxjps_grow_job_t& f = jobs[P.first];
+            if (memcmp(f.ori_pre, a.ori_pre, sizeof(a.ori_pre)) != 0 || memcmp(&f.map_reso, &a.map_reso, sizeof(double)) != 0)
+                return absorb_refuse(msg, len, "job %d: ori_pre / map_reso are not bit-equal to those of job %d, which names prior %d as well", j, P.first,
+                                     (int)a.prior);
+        }
+        GrowPlan::Job& q = plan.job[(size_t)j];
+        long long at_pre[2];
+        for (int k = 0; k < 2; k++) {
+            const double o = a.map_o[k], op = P.op[k];
+            const double o1 = std::min(o, op);                       // st:212
+            const double t_pre = op + reso * (double)P.ext[k];       // st:187, with the current extents
+            long long at_raw, ref;
+            if (!trunc_i32((o - o1) / reso, at_raw) || !trunc_i32((op - o1) / reso, at_pre[k]) ||  // st:213-214
+                !trunc_i32((std::max(t_pre, a.map_t[k]) - o1) / reso, ref))                        // st:215-216
+                return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
+            const long long size = std::max(ref, std::max(at_pre[k] + P.ext[k], at_raw + (long long)a.win[k]));
+            if (size > limit[k])
+                return absorb_refuse(msg, len, "job %d: axis %d: prior %d would grow to %lld cells, above the limit of %lld", j, k, (int)a.prior, size, limit[k]);
+            q.at[k] = at_raw;
+            P.ext[k] = size;
+            P.op[k] = o1;
+            P.shift[k] += at_pre[k];
+        }
+        for (int i = 0; i < j; i++)  // (the earlier rectangles on this prior move with the old prior)
+            if (jobs[i].prior == a.prior)
+                for (int k = 0; k < 2; k++) plan.job[(size_t)i].at[k] += at_pre[k];
+        const size_t row = (size_t)(a.layout ? a.W0 : a.H0), k = a.layout ? 1 : 0;
+        q.raw_off = (size_t)a.lo[k] * row;
+        q.raw_bytes = (size_t)a.win[k] * row;
+        q.in_off = plan.in_bytes;
+        plan.in_bytes += (q.raw_bytes + 15) & ~(size_t)15;
+        if (plan.in_bytes > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
+    }
+    for (int j = 0; j < n; j++) {
+        GrowPlan::Prior& P = plan.prior[jobs[j].prior];
+        const GrowPlan::Job& q = plan.job[(size_t)j];
+        for (int k = 0; k < 2; k++) {
+            P.lo[k] = std::min(P.lo[k], q.at[k]);
+            P.hi[k] = std::max(P.hi[k], q.at[k] + (long long)jobs[j].win[k]);
+            jobs[j].at[k] = (int32_t)q.at[k];
+        }
+        jobs[j].inside = (long long)jobs[j].win[0] * jobs[j].win[1];
+        jobs[j].outside = 0;
+    }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        const GrowPlan::Prior& P = plan.prior[p];
+        fxjps_prior_grown_t& g = out[p];
+        g.named = P.named ? 1 : 0;
+        g.W = P.named ? (int32_t)P.ext[0] : prior_wh[2 * p];
+        g.H = P.named ? (int32_t)P.ext[1] : prior_wh[2 * p + 1];
+        g.reserved_ = 0;
+        for (int k = 0; k < 2; k++) {
+            g.shift[k] = (int32_t)P.shift[k];
+            g.origin[k] = P.op[k];
+        }
+    }
+    return FXJPS_OK;
+}
+
+// One context's part of fxjps_absorb_prior_grow: the grown priors into the spare buffers (PriorBuf::next) with ONE copy
+// in, ONE launch, one copy back and one wait, whatever n is.  Nothing the world-frame calls read is touched; the
+// counters are left in d.h_absorb_out.
+int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, const GrowPlan& plan) {
+    HIPCHK(h, hipSetDevice(d.dev));
+    HIPCHK(h, d.h_absorb_in.ensure(plan.in_bytes));
+    HIPCHK(h, d.d_absorb_in.ensure(plan.in_bytes));
+    HIPCHK(h, d.h_absorb_out.ensure(FXJPS_MAX_PRIOR_MAPS));
+    fx::GrowTable& T = *reinterpret_cast<fx::GrowTable*>(d.h_absorb_in.p);
+    memset(&T, 0, sizeof(T));
+    T.mode = mode;
+    int nb = 0, nj = 0;
+    uint32_t at = 0;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
+        const GrowPlan::Prior& P = plan.prior[p];
+        if (!P.named) continue;
+        DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+        HIPCHK(h, pr.next.ensure((size_t)(P.ext[0] * P.ext[1])));
+        fx::GrowBoxDev B{};
+        B.job0 = nj;
+        for (int j = 0; j < n; j++) {
+            const fxjps_grow_job_t& a = jobs[j];
+            const GrowPlan::Job& q = plan.job[(size_t)j];
+            if (a.prior != p) continue;
+            fx::AbsorbJobDev& J = T.job[nj++];
+            J.at = d.d_absorb_in.p + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]);
+            J.stride = a.layout ? a.W0 : a.H0;
+            J.layout = a.layout;
+            J.x0 = (int32_t)q.at[0];
+            J.y0 = (int32_t)q.at[1];
+            J.w = a.win[0];
+            J.h = a.win[1];
+            memcpy(d.h_absorb_in.p + q.in_off, static_cast<const uint8_t*>(a.raw) + q.raw_off, q.raw_bytes);
+        }
+        B.njobs = nj - B.job0;
+        B.old = pr.occ.p;
+        B.out = pr.next.p;
+        B.oW = pr.W;
+        B.oH = pr.H;
+        B.sx = (int32_t)P.shift[0];
+        B.sy = (int32_t)P.shift[1];
+        B.nW = (int32_t)P.ext[0];
+        B.nH = (int32_t)P.ext[1];
+        B.x0 = (int32_t)P.lo[0];
+        B.y0 = (int32_t)P.lo[1];
+        B.w = (int32_t)(P.hi[0] - P.lo[0]);
+        B.h = (int32_t)(P.hi[1] - P.lo[1]);
+        B.prior = p;
+        T.first[nb] = at;
+        T.box[nb++] = B;
+        at += (uint32_t)((P.ext[0] * P.ext[1] + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+    }
+    T.first[nb] = at;
+    T.nbox = nb;
+    memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
+    if (nb == 0) return FXJPS_OK;  // (n == 0: nothing to queue)
+    HIPCHK(h, hipMemcpyAsync(d.d_absorb_in.p, d.h_absorb_in.p, plan.in_bytes, hipMemcpyHostToDevice, d.stream));
+    hipLaunchKernelGGL(fx::k_prior_grow, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d.h_absorb_out.p, d.d_absorb_in.p, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(h, hipStreamSynchronize(d.stream));
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
+                     fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len) {
+    if (msg && msg_len > 0) msg[0] = 0;
+    GrowPlan plan;
+    return grow_check(jobs, n, mode, prior_wh, limit_wh, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
+}
+
+int fxjps_absorb_prior_grow(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
+                            fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS]) {
+    static_assert(offsetof(fx::GrowTable, changed) == 0, "the counters come back from the head of the staged input");
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior_grow")) return rr;
+    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
+    const DevCtx& d0 = h->devs[0];
+    for (size_t p = 0; p < d0.priors.size(); p++) {
+        prior_wh[2 * p] = d0.priors[p].W;
+        prior_wh[2 * p + 1] = d0.priors[p].H;
+    }
+    GrowPlan plan;
+    char why[400] = "";
+    if (grow_check(jobs, n, mode, prior_wh, limit_wh, out, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = 0;
+    if (n == 0) return FXJPS_OK;
+    // every context writes its own grown copies from the caller's raws (host copies, no collective); the priors that the
+    // world-frame calls read are swapped only when all of them have succeeded, so a failure leaves every context as it was
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grow_on(h, h->devs[r], jobs, n, mode, plan); });
+    if (rc) {
+        drain_all(h);
+        (void)hipGetLastError();
+        return rc;
+    }
+    for (auto& d : h->devs)
+        for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++)
+            if (plan.prior[p].named) {
+                DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+                std::swap(pr.occ, pr.next);  // (the old buffer is the next grow's spare)
+                pr.W = (int)plan.prior[p].ext[0];
+                pr.H = (int)plan.prior[p].ext[1];
+            }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
     return FXJPS_OK;
 }
 

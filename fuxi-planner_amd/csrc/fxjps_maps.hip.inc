@@ -2065,3 +2065,84 @@ __global__ __launch_bounds__(256) void k_prior_absorb(AbsorbTable* __restrict__ 
     const uint64_t m = __ballot(flip);
     if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&T->changed[B.prior], (unsigned long long)__popcll(m));
 }
+
+// ---------------------------------------------------------------- ... into prior maps that grow (DESIGN.md section 3.21)
+// fxjps_absorb_prior_grow: every named prior is written anew, into a NEW buffer of the grown extents, as the n sequential
+// canvases of st:212-220 kept job after job would leave it.  The host has folded the geometry: per prior the grown
+// extents, where the old prior's cell (0, 0) lies in them (the sum of every job's at_pre) and the union box of its
+// rectangles; per job where its cell (0, 0) lies in the FINAL frame (its at_raw plus the at_pre of every later job on the
+// prior).  ONE launch over the cells of the new priors, the blocks dealt to the priors by GrowTable::first.  A thread owns
+// one cell of a new prior, adjacent lanes adjacent y.  Outside the union box it does not walk the jobs (a block that
+// misses the box does not even copy them); inside it walks the block's LDS copy of the prior's job records from the last
+// to the first and stops at the first job that decides the cell under the mode's rule, exactly as k_prior_absorb does.
+// An undecided cell takes the old prior's byte if it lies in the old prior's placement, else 0.  Every cell of the new
+// buffer is stored exactly once, by its owner, with a plain byte store; the old prior and the staged raws are only read,
+// so no thread reads a byte another writes, no atomic touches a map byte and the order of the threads does not matter.
+// Flips against the old byte (0 where the old prior has no cell) are counted as k_prior_absorb counts them.
+struct GrowBoxDev {
+    const uint8_t* old;     // the prior [oW][oH] as it is
+    uint8_t* out;           // the grown prior [nW][nH]: a buffer of its own
+    int32_t oW, oH, sx, sy; // the old extents, and the new cell that old cell (0, 0) lies on
+    int32_t nW, nH;
+    int32_t x0, y0, w, h;   // the union of the prior's rectangles in the new frame: every cell of it lies inside [nW][nH]
+    int32_t job0, njobs;    // its jobs, GrowTable::job[job0 .. job0 + njobs), in job order
+    int32_t prior, pad_;    // ... and its counter
+};
+struct GrowTable {
+    unsigned long long changed[ABSORB_PRIORS_MAX];  // staged as 0; what comes back
+    uint32_t first[ABSORB_PRIORS_MAX + 1];          // first[b]: the first block of prior b; first[nbox]: the grid size
+    int32_t nbox, mode;
+    GrowBoxDev box[ABSORB_PRIORS_MAX];
+    AbsorbJobDev job[ABSORB_JOBS_MAX];              // (x0, y0: in the grown prior's frame; the rectangle lies inside it)
+};
+
+__global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
+    __shared__ AbsorbJobDev s_job[ABSORB_JOBS_MAX];
+    const int nbox = T->nbox, mode = T->mode;
+    int b = 0;  // (block-uniform)
+    while (b + 1 < nbox && T->first[b + 1] <= blockIdx.x) b++;
+    const GrowBoxDev B = T->box[b];
+    const long long cells = (long long)B.nW * B.nH;
+    const long long c0 = (long long)(blockIdx.x - T->first[b]) * 256;
+    // does any of the block's cells [c0, c1] lie in a column of the union box?  (block-uniform; columns only: a block that
+    // spans more than one column covers every y of some of them)
+    const long long c1 = c0 + 255 < cells - 1 ? c0 + 255 : cells - 1;
+    const int bx0 = (int)(c0 / B.nH), bx1 = (int)(c1 / B.nH);
+    const bool near_box = bx0 < B.x0 + B.w && bx1 >= B.x0;
+    if (near_box) {
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(T->job + B.job0);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(s_job);
+        const int nw = B.njobs * (int)(sizeof(AbsorbJobDev) / 4);
+        for (int i = (int)threadIdx.x; i < nw; i += 256) dst[i] = src[i];
+        __syncthreads();  // (near_box is block-uniform and no thread has returned above: all of them reach it or none)
+    }
+    const long long c = c0 + threadIdx.x;
+    bool flip = false;
+    if (c < cells) {
+        const int x = (int)(c / B.nH), y = (int)(c - (long long)x * B.nH);
+        int val = -1;  // undecided
+        if (near_box && (unsigned)(x - B.x0) < (unsigned)B.w && (unsigned)(y - B.y0) < (unsigned)B.h) {
+            for (int k = B.njobs - 1; k >= 0; k--) {
+                const AbsorbJobDev& J = s_job[k];
+                const int i = x - J.x0, j = y - J.y0;
+                if ((unsigned)i >= (unsigned)J.w || (unsigned)j >= (unsigned)J.h) continue;
+                const uint8_t v = J.layout ? J.at[(size_t)j * (size_t)J.stride + (size_t)i] : J.at[(size_t)i * (size_t)J.stride + (size_t)j];
+                const bool occupied = J.layout ? (int8_t)v > 0 : v != 0;  // prepared_byte's predicate
+                const bool unknown = J.layout && v == 0xffu;              // -1 of an OccupancyGrid
+                if (mode == ABSORB_OVERWRITE || (mode == ABSORB_OCCUPIED && occupied) || (mode == ABSORB_KNOWN && !unknown)) {
+                    val = occupied ? 1 : 0;
+                    break;
+                }
+            }
+        }
+        const int ox = x - B.sx, oy = y - B.sy;
+        uint8_t old = 0;
+        if ((unsigned)ox < (unsigned)B.oW && (unsigned)oy < (unsigned)B.oH) old = B.old[(size_t)ox * (size_t)B.oH + (size_t)oy];
+        const uint8_t byte = val >= 0 ? (uint8_t)val : old;
+        B.out[(size_t)x * (size_t)B.nH + (size_t)y] = byte;
+        flip = (old != 0) != (byte != 0);
+    }
+    RECONV();
+    const uint64_t m = __ballot(flip);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&T->changed[B.prior], (unsigned long long)__popcll(m));
+}

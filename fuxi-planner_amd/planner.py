@@ -499,6 +499,7 @@ class Planner(object):
         occ = np.ascontiguousarray(np.asarray(matrix) > 0, dtype=np.uint8)
         if occ.ndim != 2:
             raise ValueError("a prior map must be 2-D")
+        self._origins().pop(int(prior), None)  # (an uploaded prior lies at the caller's ori_pre again)
         self._chk(self._L.fxjps_set_prior_map(self._h, int(prior), _lib.ptr(occ, C.c_uint8), occ.shape[0], occ.shape[1]))
 
     def set_prior_image(self, prior, gray):
@@ -517,6 +518,7 @@ class Planner(object):
 
     def clear_prior_map(self, prior):
         """Release prior map `prior` (a world job that names it is refused)."""
+        self._origins().pop(int(prior), None)
         self._chk(self._L.fxjps_set_prior_map(self._h, int(prior), None, 0, 0))
 
     def prepare_slots_world(self, jobs):
@@ -642,27 +644,100 @@ class Planner(object):
         named = sorted({int(a.prior) for a in arr[:n]})
         return [(int(a.inside), int(a.outside)) for a in arr[:n]], {p: int(changed[p]) for p in named}
 
-    def _tick_absorb(self, absorb, jobs, outs, crop, recs):
+    def absorb_prior_grow(self, jobs, mode="overwrite", crops=None, limit=None):
+        """absorb_prior on priors that GROW to what the vehicles have seen (fxjps_absorb_prior_grow: one launch whatever
+        len(jobs) is): every named prior becomes the canvas the nodes build each tick -- the union of the prior and the
+        detected map (st:212-220) -- kept, job after job; no cell of a rectangle is dropped.  jobs, crops and mode as
+        absorb_prior takes them; a job's ori_pre is the prior's origin as it is NOW, the same in every job that names the
+        prior (prior_origin(prior) once it has grown); its map_t comes from the job, or from the crop record, or is map_o +
+        extent * map_reso.  limit: None (8190), one number or a pair: the largest side a prior may grow to, per axis -- a
+        job that would exceed it refuses the whole call.  -> ([at per job: the cell of the grown prior that the
+        rectangle's cell (0, 0) landed on], {prior: {"W", "H", "shift", "origin", "changed"}}): the new extents, where
+        old cell (0, 0) lies now, the new world origin and the cells whose occupancy differs from the old byte at that
+        place.  The planner remembers each grown prior's origin (prior_origin); the library stores none.  On a refusal or
+        a failure every prior is what it was, byte for byte.  worldprep.grow_host is the same fold on the host."""
+        from . import worldprep
+        jobs = list(jobs)
+        n = len(jobs)
+        if mode not in _lib.ABSORB_MODES:
+            raise ValueError("mode %r is not one of %r" % (mode, tuple(_lib.ABSORB_MODES)))
+        if crops is not None and len(crops) != n:
+            raise ValueError("%d crop records for %d jobs" % (len(crops), n))
+        lim = None
+        if limit is not None:
+            lim = np.array([limit, limit] if np.isscalar(limit) else [limit[0], limit[1]], dtype=np.int32)
+        arr = (_lib.GrowJob * max(n, 1))()
+        keep = []  # (the raws, alive until the call has returned)
+        for v, (a, job) in enumerate(zip(arr, jobs)):
+            raw, map_o, map_reso = job[1], job[2], job[3]
+            prior, ori_pre, map_t = (tuple(job[8:11]) + (None, (-15, -15), None)[len(job[8:11]):])[:3]
+            if prior is None:
+                raise ValueError("job %d names no prior map" % v)
+            w = _lib.WorldJob()  # (raw, layout and extents as the world-frame calls take them)
+            keep.append(Planner._job_raw(w, 0, raw, 0, 0))
+            a.raw, a.layout, a.W0, a.H0 = w.raw, w.layout, w.W0, w.H0
+            rec = None if crops is None else crops[v]
+            lo, win = ((0, 0), (a.W0, a.H0)) if rec is None else (rec["lo"], rec["win"])
+            if rec is not None:
+                map_o, map_t = rec["map_o"], rec["map_t"]
+            if map_t is None:
+                map_t = worldprep.map_top(map_o, win, map_reso)
+            a.prior, a.map_reso = int(prior), float(map_reso)
+            for k in range(2):
+                a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k], a.map_t[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k]), float(map_t[k])
+        out = (_lib.PriorGrown * _lib.MAX_PRIOR_MAPS)()
+        self._chk(self._L.fxjps_absorb_prior_grow(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), out))
+        del keep
+        grown = {}
+        for p, g in enumerate(out):
+            if g.named:
+                grown[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
+                            "changed": int(g.changed)}
+                self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
+        return [(int(a.at[0]), int(a.at[1])) for a in arr[:n]], grown
+
+    def _origins(self):
+        if getattr(self, "_prior_origin", None) is None:
+            self._prior_origin = {}
+        return self._prior_origin
+
+    def prior_origin(self, prior):
+        """The world origin of prior map `prior` as absorb_prior_grow last left it, or None: the prior has not grown since
+        it was uploaded (set_prior_map and clear_prior_map forget the origin; it is then the caller's ori_pre again)."""
+        return self._origins().get(int(prior))
+
+    def _tick_absorb(self, absorb, jobs, outs, crop, recs, grow=None):
         """fleet_tick_world's absorb=: after the tick's prepare / refresh call, every job that names a prior is absorbed --
-        a cropped job through its window, unless it has none (not planned, refused).  recs[v]["absorbed"] is set."""
+        a cropped job through its window, unless it has none (not planned, refused).  recs[v]["absorbed"] is set.  grow:
+        None, or (grow_limit,): through absorb_prior_grow, and recs[v]["ori_pre"] / ["grown"] are set as well."""
         if absorb is None:
             return
         take, crops = [], []
         for v, job in enumerate(jobs):
             recs[v]["absorbed"] = None
+            if grow is not None:
+                recs[v]["grown"] = None
+                recs[v]["ori_pre"] = None if len(job) <= 8 or job[8] is None else tuple(float(x) for x in (job[9] if len(job) > 9 else (-15, -15)))
             if len(job) <= 8 or job[8] is None:
                 continue
             if crop and outs[v][-2] in (_lib.JOB_NOT_PLANNED, _lib.E_ARG):
                 continue
             take.append(v)
             crops.append(outs[v][-1] if crop else None)
-        if take:
+        if take and grow is not None:
+            _, grown = self.absorb_prior_grow([jobs[v] for v in take], absorb, crops if crop else None, grow[0])
+            for v, c in zip(take, crops):
+                raw = jobs[v][1]
+                win = c["win"] if crop else (raw[1], raw[2]) if isinstance(raw, tuple) else np.asarray(raw).shape
+                recs[v]["absorbed"] = (int(win[0]) * int(win[1]), 0)  # (nothing is dropped: the prior grows)
+                recs[v]["grown"] = grown[int(jobs[v][8])]
+        elif take:
             counts, _ = self.absorb_prior([jobs[v] for v in take], absorb, crops if crop else None)
             for v, c in zip(take, counts):
                 recs[v]["absorbed"] = c
 
     def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
-                         reuse=False, crop=False, throttle=None, check_kept=True, absorb=None):
+                         reuse=False, crop=False, throttle=None, check_kept=True, absorb=None, grow=False, grow_limit=None):
         """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
         prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
         job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
@@ -673,10 +748,22 @@ class Planner(object):
         tick's prepare / refresh call every job that names a prior is folded into it through absorb_prior (a cropped job
         through its window; not one that is not planned or refused), so THIS tick's records are what absorb=None gives and
         the next tick of every vehicle sees the merged prior; every record then has a further key, absorbed: (inside,
-        outside), or None for a job that was not absorbed."""
-        jobs = list(jobs)
+        outside), or None for a job that was not absorbed.  grow=True (needs absorb): the absorb step goes through
+        absorb_prior_grow, so a prior grows to what the vehicles have seen instead of dropping the cells outside it
+        (grow_limit: its `limit`); every record gains ori_pre -- the prior origin the job was prepared and absorbed with, None
+        without a prior -- and grown, the prior's record from absorb_prior_grow, or None for a job that was not absorbed.
+        Once a prior has a remembered origin (prior_origin), every job that names it is prepared and absorbed with that
+        origin instead of the job's own ori_pre, on grow=False ticks as well: the job's is the origin of the upload."""
+        if grow and absorb is None:
+            raise ValueError("grow=True needs absorb=")
+        jobs = [tuple(j) for j in jobs]
+        for v, j in enumerate(jobs):
+            at = self.prior_origin(j[8]) if len(j) > 8 and j[8] is not None else None
+            if at is not None:
+                jobs[v] = j[:9] + (at,) + j[10:]
         return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
-                                image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept, absorb=absorb)
+                                image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept, absorb=absorb,
+                                grow=(grow_limit,) if grow else None)
 
     def check_paths_slots(self, grid_ids, offsets, cells, shift=None):
         """Which kept paths do their slots' grids, as they are now, still allow (fxjps_check_paths_slots: one launch for
@@ -800,10 +887,10 @@ class Planner(object):
                                 throttle=throttle, check_kept=check_kept)
 
     def _fleet_tick(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels, reuse=False,
-                    world=False, crop=False, throttle=None, check_kept=True, absorb=None):
+                    world=False, crop=False, throttle=None, check_kept=True, absorb=None, grow=None):
         if throttle is not None:
             return self._fleet_tick_throttled(refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
-                                              reuse, world, crop, throttle, check_kept, absorb)
+                                              reuse, world, crop, throttle, check_kept, absorb, grow)
         from . import waypoints
         jobs = list(jobs)
         n = len(jobs)
@@ -819,11 +906,11 @@ class Planner(object):
             outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
             for v in range(n):
                 recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
-            self._tick_absorb(absorb, jobs, outs, True, recs)
+            self._tick_absorb(absorb, jobs, outs, True, recs, grow)
             outs = [o[:-2] for o in outs]
         elif world:  # (the call's own origin, canvas_shape and canvas_o lie behind the existing tuple)
             outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
-            self._tick_absorb(absorb, jobs, outs, False, recs)
+            self._tick_absorb(absorb, jobs, outs, False, recs, grow)
         else:
             outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
         variant_at = 7 if world else 5
@@ -857,7 +944,7 @@ class Planner(object):
         return recs
 
     def _fleet_tick_throttled(self, refresh, jobs, pos, global_goals, home, map_reso, map_o, prev_wp, prev_dim, publish, image_channels,
-                              reuse, world, crop, throttle, check_kept, absorb=None):
+                              reuse, world, crop, throttle, check_kept, absorb=None, grow=None):
         """_fleet_tick under a replan.FleetThrottle (fleet_tick_throttled's docstring): the same calls in the same order, the
         plan and the tick outputs over the due vehicles only, one check_paths_slots call in front of them."""
         from . import waypoints
@@ -878,11 +965,11 @@ class Planner(object):
             outs = self.refresh_slots_cropped(jobs) if refresh else self.prepare_slots_cropped(jobs)
             for v in range(n):
                 recs[v]["not_planned"] = outs[v][-2] == _lib.JOB_NOT_PLANNED
-            self._tick_absorb(absorb, jobs, outs, True, recs)
+            self._tick_absorb(absorb, jobs, outs, True, recs, grow)
             outs = [o[:-2] for o in outs]
         elif world:
             outs = self.refresh_slots_world(jobs) if refresh else self.prepare_slots_world(jobs)
-            self._tick_absorb(absorb, jobs, outs, False, recs)
+            self._tick_absorb(absorb, jobs, outs, False, recs, grow)
         else:
             outs = self.refresh_slots(jobs) if refresh else self.prepare_slots(jobs)
         variant_at = 7 if world else 5

@@ -9,7 +9,7 @@ int() truncate, and a ValueError where the library refuses.  Pinned by tests/gol
 values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).  crop_host is the host form
 of Planner.prepare_slots_cropped in the same way, pinned by tests/golden/cropprep.json (make_golden_cropprep.py), and
 absorb_host that of Planner.absorb_prior: the same slice assignment kept in the prior map, pinned by the canvases of
-worldprep.json.
+worldprep.json; grow_host is that of Planner.absorb_prior_grow: the whole canvas kept, pinned by the same canvases.
 """
 import math
 
@@ -167,6 +167,78 @@ def absorb_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None,
             target[known] = occ[known]
         changed = int(np.count_nonzero((target != 0) != before))
     return new, inside, win[0] * win[1] - inside, changed
+
+
+def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, win=None, map_t=None):
+    """One job of Planner.absorb_prior_grow on the host: absorb_host on a prior that GROWS to hold the rectangle -- the
+    canvas of st:212-220, the union of the prior and the detected map, kept as the next prior.  Arguments as absorb_host
+    takes them, and map_t, the rectangle's top (None: map_o + win * map_reso; a cropped job: the crop record's).  Per axis
+        o1 = min(map_o, ori_pre);  at_raw = trunc((map_o - o1) / reso);  at_pre = trunc((ori_pre - o1) / reso)
+        size = max(trunc((max(ori_pre + reso * W, map_t) - o1) / reso), at_pre + W, at_raw + win)
+    in merge_host's float64 operations and order.  The new prior has size cells a side: the old bytes unchanged at at_pre
+    (a 255 stays 255), the rectangle applied at at_raw under the mode's rule, every other cell 0.  size is the
+    reference's canvas extent except where its slice assignment would raise or clip: there the prior still grows.
+    -> (new prior uint8, new ori_pre [x, y] (o1), shift (at_pre: where old cell (0, 0) lies), at (at_raw: where rectangle
+    cell (0, 0) lies), changed: the cells whose occupancy (non-zero) differs from the old byte at that place, 0 where the
+    old prior had none).  Several jobs: call it job by job on the result (an earlier job's `at` then moves by every later
+    job's shift).  ValueError where the library refuses."""
+    if mode not in ABSORB_MODES:
+        raise ValueError("mode %r is not one of %r" % (mode, ABSORB_MODES))
+    pre = np.asarray(prior)
+    if pre.ndim != 2 or pre.shape[0] < 1 or pre.shape[1] < 1:
+        raise ValueError("the prior map must be 2-D and not empty")
+    if isinstance(raw, tuple):
+        data, width, height = raw
+        a = np.asarray(data, dtype=np.int8).reshape(-1)
+        if a.size != width * height:
+            raise ValueError("data has %d cells, expected %d" % (a.size, width * height))
+        m = a.reshape(height, width).T
+        unknown = m == -1
+    else:
+        m = np.asarray(raw)
+        unknown = None
+    if m.ndim != 2 or not (1 <= m.shape[0] <= 8190 and 1 <= m.shape[1] <= 8190):
+        raise ValueError("raw must be 2-D and 1..8190 cells a side")
+    occupied = m > 0
+    lo = [0, 0] if lo is None else [int(lo[0]), int(lo[1])]
+    win = [m.shape[k] - lo[k] for k in range(2)] if win is None else [int(win[0]), int(win[1])]
+    for k in range(2):
+        if win[k] < 1 or lo[k] < 0 or lo[k] + win[k] > m.shape[k]:
+            raise ValueError("axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %d cells" % (k, lo[k], win[k], m.shape[k]))
+    reso = float(map_reso)
+    if not (math.isfinite(reso) and reso > 0.0):
+        raise ValueError("map_reso %r must be finite and > 0" % (map_reso,))
+    o = _pair(map_o, "map_o")
+    op = _pair(ori_pre, "ori_pre")
+    top = _pair(map_t, "map_t") if map_t is not None else map_top(o, win, reso)
+    if not (math.isfinite(top[0]) and math.isfinite(top[1])):
+        raise ValueError("map_t is not finite")
+    ext = [int(pre.shape[0]), int(pre.shape[1])]
+    o1, at_raw, at_pre, size = [0.0, 0.0], [0, 0], [0, 0], [0, 0]
+    for k in range(2):
+        t_pre = op[k] + reso * ext[k]                                            # st:187
+        o1[k] = min(o[k], op[k])                                                 # st:212
+        at_raw[k] = _trunc((o[k] - o1[k]) / reso, "the detected map's index")    # st:213
+        at_pre[k] = _trunc((op[k] - o1[k]) / reso, "the prior's index")          # st:214
+        ref = _trunc((max(t_pre, top[k]) - o1[k]) / reso, "the canvas extent")   # st:215-216
+        size[k] = max(ref, at_pre[k] + ext[k], at_raw[k] + win[k])
+        if size[k] > 8190:
+            raise ValueError("axis %d: the prior would grow to %d cells, above 8190" % (k, size[k]))
+    placed = np.zeros(size, dtype=np.uint8)
+    placed[at_pre[0]:at_pre[0] + ext[0], at_pre[1]:at_pre[1] + ext[1]] = pre
+    new = placed.copy()
+    cut = tuple(slice(lo[k], lo[k] + win[k]) for k in range(2))
+    occ = occupied[cut]
+    target = new[at_raw[0]:at_raw[0] + win[0], at_raw[1]:at_raw[1] + win[1]]
+    if mode == "overwrite" or (mode == "known" and unknown is None):
+        target[...] = occ
+    elif mode == "occupied":
+        target[occ] = 1
+    else:
+        known = ~unknown[cut]
+        target[known] = occ[known]
+    changed = int(np.count_nonzero((new != 0) != (placed != 0)))
+    return new, o1, at_pre, at_raw, changed
 
 
 def merge_host(raw, map_o, map_reso, pos_xy, goal_xy, prior=None, ori_pre=(-15, -15), map_t=None):

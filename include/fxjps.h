@@ -116,8 +116,11 @@ typedef struct fxjps fxjps_t;
  *   850  fxjps_absorb_prior (the detected rectangles of up to 256 jobs pasted into the prior maps they name, on the device,
  *        in one launch whatever n is: what one vehicle has seen, every vehicle's next world-frame tick sees),
  *        fxjps_absorb_check (its argument check and placement without a handle), fxjps_absorb_job_size.
+ *   860  fxjps_absorb_prior_grow (fxjps_absorb_prior on priors that grow to what the vehicles have seen: the canvas the
+ *        nodes build every tick, kept as the next prior, in one launch whatever n is), fxjps_grow_check (its geometry and
+ *        refusals without a handle), fxjps_grow_job_size, fxjps_prior_grown_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 850
+#define FXJPS_VERSION 860
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -517,7 +520,8 @@ int fxjps_crop_size(void); /* sizeof(fxjps_crop_t) as the library was built */
  *     o1 = min(map_o, ori_pre);  at_raw = trunc((map_o - o1) / map_reso);  at_pre = trunc((ori_pre - o1) / map_reso)
  *     d  = at_raw - at_pre
  * Rectangle cell (i, j) is raw's cell (lo[0] + i, lo[1] + j) and lands on prior cell (d[0] + i, d[1] + j) if that cell lies
- * inside the prior; otherwise it is dropped and counted in `outside`: the prior does not grow.  A rectangle wholly outside
+ * inside the prior; otherwise it is dropped and counted in `outside`: the prior does not grow (fxjps_absorb_prior_grow below
+ * is the call under which it does).  A rectangle wholly outside
  * its prior is no error (inside = 0).
  *   The value read is the world-frame calls': layout 0 occupied when the byte is non-zero; layout 1 occupied when the int8
  * is > 0, and UNKNOWN when it is -1 (layout 0 has no unknown).  Jobs are applied in job order -- the result is that of n
@@ -559,6 +563,74 @@ typedef struct fxjps_absorb_job {
 int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, int64_t out_changed[FXJPS_MAX_PRIOR_MAPS]);
 int fxjps_absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, char* msg, int32_t msg_len);
 int fxjps_absorb_job_size(void); /* sizeof(fxjps_absorb_job_t) as the library was built */
+/* ---- The same fold on priors that GROW (version 860): the canvas the nodes build every tick as the union of the prior and
+ * the detected map (st:212-220 / ccst:397-405) and throw away after the search is kept as the next prior, so that a wall one
+ * vehicle has seen outside the extents uploaded before the flight is on every other vehicle's canvas from the next tick on.
+ *   State per prior: its bytes P[W][H] on the device and a world origin op, which the CALLER holds and hands in with
+ * every job (the library stores no origin).  One job -- a rectangle of win cells at world origin o = map_o, with top t =
+ * map_t and resolution reso -- is applied per axis k, in float64 with the reference's operations in the reference's
+ * order, truncating toward zero:
+ *     o1     = min(o, op)                               (st:212)
+ *     at_raw = trunc((o  - o1) / reso)                  (st:213)
+ *     at_pre = trunc((op - o1) / reso)                  (st:214)
+ *     t_pre  = op + reso * W                            (st:187, with the prior's CURRENT extents)
+ *     ref    = trunc((max(t_pre, t) - o1) / reso)       (st:215-216)
+ *     size   = max(ref, at_pre + W, at_raw + win)
+ * The new prior has size[0] x size[1] cells: the old bytes unchanged at (at_pre[0], at_pre[1]) -- a 255 stays 255 --, the
+ * rectangle applied at (at_raw[0], at_raw[1]) under the mode's rule of fxjps_absorb_prior (the same occupied and unknown
+ * predicates), every other cell 0; its origin is o1 (a min: no arithmetic).  size differs from the reference's ref only
+ * where the reference's slice assignment would raise or clip (a stated deviation: such a job still grows the prior).  Jobs
+ * naming one prior fold in job order, each on the extents and origin the one before left; priors are independent.
+ *   fxjps_grow_job_t: fxjps_absorb_job_t's fields (ori_pre: the prior's origin BEFORE the call, the same in every job that
+ * names the prior; inside = win[0] * win[1] and outside = 0 on return: nothing is dropped), then map_t -- the rectangle's
+ * top: the node's map_t, a cropped job's fxjps_crop_t::map_t -- and at: the cell of the prior AS THE CALL LEAVES IT that
+ * rectangle cell (0, 0) landed on.  out[p], one record per prior: named (0 / 1: whether a job names it); W, H after the
+ * call (a prior no job names: as they are, 0 0 = not set); shift: where old cell (0, 0) lies now; origin: the new world
+ * origin (0 0 for a prior no job names); changed: the cells of the new prior whose non-zero test differs from the old
+ * byte at that place, the old byte counting as 0 where the old prior had no cell (context 0's figure).
+ *   Whole-call refusals (FXJPS_E_ARG with the job's number in fxjps_last_error, before anything is queued or written):
+ * everything fxjps_absorb_prior refuses; a non-finite map_t; jobs naming one prior whose ori_pre or map_reso are not
+ * bit-equal; a grown side above limit_wh[k] (limit_wh NULL: 8190 on both axes; a limit outside 1 .. 8190 is refused); a
+ * truncated quotient outside int32; a rank handle; NULL out.  fxjps_grow_check is the same geometry and the same refusals
+ * without a handle (prior_wh as fxjps_absorb_check takes it): it fills inside / outside / at of every job and every field
+ * of out except changed.
+ *   Per context: one staged copy in (a table and the rows of each raw that hold its rectangle), ONE launch whatever n is
+ * -- a thread per cell of the new priors, every cell stored exactly once --, one copy back (16 counters) and one host
+ * wait.  Every context writes the grown priors into new buffers; buffers and extents are swapped in only after every
+ * context has succeeded, and on any failure, an allocation included, every context keeps the old prior byte for byte with
+ * its old extents.  Queued on the handle's stream: earlier world-frame calls have read the old prior, later ones read the
+ * new one -- with the NEW origin as their ori_pre --, and fxjps_get_prior_map returns the new extents and bytes.  No slot,
+ * no slot generation, no stored result, not the resident grid and no prior that no job names is touched; n == 0 returns
+ * FXJPS_OK with nothing named.  Forgetting old observations and trimming a prior are not part of this. */
+typedef struct fxjps_grow_job {
+    const void* raw;      /* in: as fxjps_absorb_job_t, field by field ... */
+    int32_t layout;
+    int32_t W0, H0;
+    int32_t lo[2], win[2];
+    int32_t prior;
+    int32_t reserved_;
+    double map_o[2];
+    double map_reso;
+    double ori_pre[2];    /* in: the prior's world origin before the call */
+    int64_t inside;       /* out: win[0] * win[1] */
+    int64_t outside;      /* out: 0 */
+    double map_t[2];      /* in: ... then the rectangle's top */
+    int32_t at[2];        /* out: the cell of the grown prior that rectangle cell (0, 0) landed on */
+} fxjps_grow_job_t;
+typedef struct fxjps_prior_grown {
+    int32_t named;        /* 1: a job names this prior */
+    int32_t W, H;         /* extents after the call */
+    int32_t shift[2];     /* the cell of the grown prior that old cell (0, 0) lies on */
+    int32_t reserved_;
+    double origin[2];     /* the grown prior's world origin */
+    int64_t changed;      /* cells whose occupancy differs from the old byte at that place (none: 0) */
+} fxjps_prior_grown_t;
+int fxjps_absorb_prior_grow(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
+                            fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS]);
+int fxjps_grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
+                     fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len);
+int fxjps_grow_job_size(void);    /* sizeof(fxjps_grow_job_t) as the library was built */
+int fxjps_prior_grown_size(void); /* sizeof(fxjps_prior_grown_t) as the library was built */
 /* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
  * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
  * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
