@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 860  # FXJPS_VERSION of include/fxjps.h
+VERSION = 870  # FXJPS_VERSION of include/fxjps.h
 PATH_VALID, PATH_EMPTY, PATH_BLOCKED, PATH_OUTSIDE, PATH_MALFORMED = 1, 0, 2, 3, -1  # FXJPS_PATH_*: fxjps_check_path's verdicts
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
@@ -30,11 +30,14 @@ SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxj
            "fxjps_set_slot_reuse", "fxjps_debug_slot_tiles", "fxjps_debug_slot_read_sets",
            "fxjps_check_path", "fxjps_check_paths_slots",
            "fxjps_absorb_prior", "fxjps_absorb_check", "fxjps_absorb_job_size",
-           "fxjps_absorb_prior_grow", "fxjps_grow_check", "fxjps_grow_job_size", "fxjps_prior_grown_size")
+           "fxjps_absorb_prior_grow", "fxjps_grow_check", "fxjps_grow_job_size", "fxjps_prior_grown_size",
+           "fxjps_absorb_prior_slide", "fxjps_slide_check", "fxjps_prior_keep_size", "fxjps_prior_slid_size")
 MAX_GRID_SLOTS = 256  # FXJPS_MAX_GRID_SLOTS
 MAX_PRIOR_MAPS = 16  # FXJPS_MAX_PRIOR_MAPS
 ABSORB_OVERWRITE, ABSORB_OCCUPIED, ABSORB_KNOWN = 0, 1, 2  # FXJPS_ABSORB_*: fxjps_absorb_prior's modes
 ABSORB_MODES = {"overwrite": ABSORB_OVERWRITE, "occupied": ABSORB_OCCUPIED, "known": ABSORB_KNOWN}
+KEEP_NONE, KEEP_ALWAYS, KEEP_OVER_LIMIT = 0, 1, 2  # FXJPS_KEEP_*: how fxjps_absorb_prior_slide uses a prior's keep window
+KEEP_USES = {"none": KEEP_NONE, "always": KEEP_ALWAYS, "over_limit": KEEP_OVER_LIMIT}
 JOB_NOT_PLANNED = 1  # FXJPS_JOB_NOT_PLANNED: a job's status from the cropped calls, the node does not plan on this tick
 
 
@@ -94,6 +97,18 @@ class PriorGrown(C.Structure):
     """fxjps_prior_grown_t: what fxjps_absorb_prior_grow made of one prior map."""
     _fields_ = [("named", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("shift", C.c_int32 * 2), ("reserved_", C.c_int32),
                 ("origin", C.c_double * 2), ("changed", C.c_int64)]
+
+
+class PriorKeep(C.Structure):
+    """fxjps_prior_keep_t: one prior's keep window, world metres (fxjps_absorb_prior_slide)."""
+    _fields_ = [("use", C.c_int32), ("reserved_", C.c_int32), ("lo", C.c_double * 2), ("hi", C.c_double * 2)]
+
+
+class PriorSlid(C.Structure):
+    """fxjps_prior_slid_t: what fxjps_absorb_prior_slide made of one prior map."""
+    _fields_ = [("named", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("shift", C.c_int32 * 2), ("trimmed", C.c_int32),
+                ("origin", C.c_double * 2), ("changed", C.c_int64), ("grown_wh", C.c_int32 * 2), ("cut_lo", C.c_int32 * 2),
+                ("cut_hi", C.c_int32 * 2)]
 
 
 class SlotPublish(C.Structure):
@@ -174,6 +189,11 @@ def load():
     if L.fxjps_grow_job_size() != C.sizeof(GrowJob) or L.fxjps_prior_grown_size() != C.sizeof(PriorGrown):
         raise FxjpsError(E_ARG, "%s has a %d-byte grow job and a %d-byte grown-prior record; this binding's are %d and %d bytes: rebuild it"
                          % (LIB_PATH, L.fxjps_grow_job_size(), L.fxjps_prior_grown_size(), C.sizeof(GrowJob), C.sizeof(PriorGrown)))
+    L.fxjps_prior_keep_size.restype = C.c_int
+    L.fxjps_prior_slid_size.restype = C.c_int
+    if L.fxjps_prior_keep_size() != C.sizeof(PriorKeep) or L.fxjps_prior_slid_size() != C.sizeof(PriorSlid):
+        raise FxjpsError(E_ARG, "%s has a %d-byte keep window and a %d-byte slid-prior record; this binding's are %d and %d bytes: rebuild it"
+                         % (LIB_PATH, L.fxjps_prior_keep_size(), L.fxjps_prior_slid_size(), C.sizeof(PriorKeep), C.sizeof(PriorSlid)))
     L.fxjps_last_timing_sized.restype = C.c_int
     L.fxjps_last_timing_sized.argtypes = [vp, vp, C.c_int64]
     L.fxjps_rank_preflight.restype = C.c_int
@@ -330,6 +350,11 @@ def load():
     L.fxjps_absorb_prior_grow.argtypes = [vp, C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, C.POINTER(PriorGrown)]
     L.fxjps_grow_check.restype = C.c_int  # (no handle, no device: the call's geometry and refusals)
     L.fxjps_grow_check.argtypes = [C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, p_i32, C.POINTER(PriorGrown), C.c_char_p, C.c_int32]
+    L.fxjps_absorb_prior_slide.restype = C.c_int
+    L.fxjps_absorb_prior_slide.argtypes = [vp, C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, C.POINTER(PriorKeep), C.POINTER(PriorSlid)]
+    L.fxjps_slide_check.restype = C.c_int  # (no handle, no device: the call's geometry and refusals)
+    L.fxjps_slide_check.argtypes = [C.POINTER(GrowJob), C.c_int32, C.c_int32, p_i32, p_i32, C.POINTER(PriorKeep), C.POINTER(PriorSlid), C.c_char_p,
+                                    C.c_int32]
     bind_host(L)
     _lib = L
     return L

@@ -4862,6 +4862,8 @@ struct GrowPlan {
     struct Job {
         long long at[2];
         size_t raw_off, raw_bytes, in_off;
+        long long row0 = 0;  // fxjps_absorb_prior_slide: the first staged row, counted in rows of the rectangle; staged: any at all
+        bool staged = true;
     };
     struct Prior {
         bool named = false;
@@ -4870,6 +4872,11 @@ struct GrowPlan {
         long long shift[2] = {0, 0};     // the sum of every job's at_pre
         double op[2] = {0.0, 0.0};       // the origin, job after job
         long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};  // the union box, in the final frame
+        // fxjps_absorb_prior_slide: the cells [k0, k1) of the grown frame that the new prior holds (grow: 0 and ext), whether a
+        // keep window was applied, and the new origin; ext, shift, lo / hi and every job's at stay in the GROWN frame
+        long long k0[2] = {0, 0}, k1[2] = {0, 0};
+        bool trimmed = false;
+        double origin[2] = {0.0, 0.0};
     };
     std::vector<Job> job;
     Prior prior[FXJPS_MAX_PRIOR_MAPS];
@@ -4880,8 +4887,10 @@ struct GrowPlan {
 // priors' extents alone: float64, the reference's operations in the reference's order (st:187, :212-216), job after job
 // on the extents and origin the job before left.  Writes nothing unless every job passes; then plan, every job's inside /
 // outside / at and every field of out but `changed`.  (The per-job argument checks are absorb_check's, word for word.)
+// keep (fxjps_absorb_prior_slide; NULL otherwise): a prior whose keep[p].use is not FXJPS_KEEP_NONE is cut to a window afterwards,
+// so its sides are not held to the limit job after job, only to int32; limit_out, if given, receives the limits in force.
 int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, fxjps_prior_grown_t* out, GrowPlan& plan,
-               char* msg, size_t len) {
+               char* msg, size_t len, const fxjps_prior_keep_t* keep = nullptr, long long* limit_out = nullptr) {
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return absorb_refuse(msg, len, "job 0: n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
     if (n > 0 && !jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
     if (!prior_wh) return absorb_refuse(msg, len, "job 0: NULL prior extents");
@@ -4893,6 +4902,7 @@ int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* p
             limit[k] = limit_wh[k];
             if (limit[k] < 1 || limit[k] > 8190) return absorb_refuse(msg, len, "job 0: axis %d: the limit %lld is not in 1 .. 8190", k, limit[k]);
         }
+    if (limit_out) limit_out[0] = limit[0], limit_out[1] = limit[1];
     plan = GrowPlan{};
     plan.job.resize((size_t)n);
     for (int j = 0; j < n; j++) {
@@ -4941,7 +4951,9 @@ int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* p
                 !trunc_i32((std::max(t_pre, a.map_t[k]) - o1) / reso, ref))                        // st:215-216
                 return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
             const long long size = std::max(ref, std::max(at_pre[k] + P.ext[k], at_raw + (long long)a.win[k]));
-            if (size > limit[k])
+            if (keep && keep[a.prior].use != FXJPS_KEEP_NONE) {
+                if (size > INT32_MAX) return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
+            } else if (size > limit[k])
                 return absorb_refuse(msg, len, "job %d: axis %d: prior %d would grow to %lld cells, above the limit of %lld", j, k, (int)a.prior, size, limit[k]);
             q.at[k] = at_raw;
             P.ext[k] = size;
@@ -4951,6 +4963,7 @@ int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* p
         for (int i = 0; i < j; i++)  // (the earlier rectangles on this prior move with the old prior)
             if (jobs[i].prior == a.prior)
                 for (int k = 0; k < 2; k++) plan.job[(size_t)i].at[k] += at_pre[k];
+        if (keep) continue;  // (slide_check stages what lies inside the windows, once it knows them)
         const size_t row = (size_t)(a.layout ? a.W0 : a.H0), k = a.layout ? 1 : 0;
         q.raw_off = (size_t)a.lo[k] * row;
         q.raw_bytes = (size_t)a.win[k] * row;
@@ -4987,7 +5000,9 @@ int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* p
 // One context's part of fxjps_absorb_prior_grow: the grown priors into the spare buffers (PriorBuf::next) with ONE copy
 // in, ONE launch, one copy back and one wait, whatever n is.  Nothing the world-frame calls read is touched; the
 // counters are left in d.h_absorb_out.
-int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, const GrowPlan& plan) {
+// window (fxjps_absorb_prior_slide): every new prior holds the cells [k0, k1) of its grown frame, a job wholly outside its
+// window is left out of the table, and the launch is k_prior_grow<true>.
+int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, const GrowPlan& plan, bool window = false) {
     HIPCHK(h, hipSetDevice(d.dev));
     HIPCHK(h, d.h_absorb_in.ensure(plan.in_bytes));
     HIPCHK(h, d.d_absorb_in.ensure(plan.in_bytes));
@@ -5001,16 +5016,20 @@ int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, 
         const GrowPlan::Prior& P = plan.prior[p];
         if (!P.named) continue;
         DevCtx::PriorBuf& pr = d.priors[(size_t)p];
-        HIPCHK(h, pr.next.ensure((size_t)(P.ext[0] * P.ext[1])));
+        const long long nW = window ? P.k1[0] - P.k0[0] : P.ext[0], nH = window ? P.k1[1] - P.k0[1] : P.ext[1];
+        HIPCHK(h, pr.next.ensure((size_t)(nW * nH)));
         fx::GrowBoxDev B{};
         B.job0 = nj;
         for (int j = 0; j < n; j++) {
             const fxjps_grow_job_t& a = jobs[j];
             const GrowPlan::Job& q = plan.job[(size_t)j];
-            if (a.prior != p) continue;
+            if (a.prior != p || !q.staged) continue;
             fx::AbsorbJobDev& J = T.job[nj++];
-            J.at = d.d_absorb_in.p + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]);
             J.stride = a.layout ? a.W0 : a.H0;
+            // (cell (i, j) of the rectangle is read at row * stride + column from here; rows below row0 are not staged and
+            // not read, so the address of row 0 is only ever an operand)
+            J.at = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d.d_absorb_in.p) + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]) -
+                                                    (size_t)q.row0 * (size_t)J.stride);
             J.layout = a.layout;
             J.x0 = (int32_t)q.at[0];
             J.y0 = (int32_t)q.at[1];
@@ -5025,23 +5044,30 @@ int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, 
         B.oH = pr.H;
         B.sx = (int32_t)P.shift[0];
         B.sy = (int32_t)P.shift[1];
-        B.nW = (int32_t)P.ext[0];
-        B.nH = (int32_t)P.ext[1];
+        B.nW = (int32_t)nW;
+        B.nH = (int32_t)nH;
         B.x0 = (int32_t)P.lo[0];
         B.y0 = (int32_t)P.lo[1];
         B.w = (int32_t)(P.hi[0] - P.lo[0]);
         B.h = (int32_t)(P.hi[1] - P.lo[1]);
         B.prior = p;
+        if (window) {
+            T.k0[nb][0] = (int32_t)P.k0[0];
+            T.k0[nb][1] = (int32_t)P.k0[1];
+        }
         T.first[nb] = at;
         T.box[nb++] = B;
-        at += (uint32_t)((P.ext[0] * P.ext[1] + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+        at += (uint32_t)((nW * nH + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
     }
     T.first[nb] = at;
     T.nbox = nb;
     memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
     if (nb == 0) return FXJPS_OK;  // (n == 0: nothing to queue)
     HIPCHK(h, hipMemcpyAsync(d.d_absorb_in.p, d.h_absorb_in.p, plan.in_bytes, hipMemcpyHostToDevice, d.stream));
-    hipLaunchKernelGGL(fx::k_prior_grow, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
+    if (window)
+        hipLaunchKernelGGL(fx::k_prior_grow<true>, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
+    else
+        hipLaunchKernelGGL(fx::k_prior_grow<false>, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(d.h_absorb_out.p, d.d_absorb_in.p, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
@@ -5087,6 +5113,162 @@ int fxjps_absorb_prior_grow(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32
                 std::swap(pr.occ, pr.next);  // (the old buffer is the next grow's spare)
                 pr.W = (int)plan.prior[p].ext[0];
                 pr.H = (int)plan.prior[p].ext[1];
+            }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
+    return FXJPS_OK;
+}
+
+// ------------------------------------------------------------------ ... into prior maps that slide
+int fxjps_prior_keep_size(void) { return (int)sizeof(fxjps_prior_keep_t); }
+int fxjps_prior_slid_size(void) { return (int)sizeof(fxjps_prior_slid_t); }
+
+namespace {
+// fxjps_absorb_prior_slide's refusals except a rank handle, and its whole geometry: grow_check's fold on copies of the jobs
+// (the per-job limit skipped for a prior with a keep window), then per prior the window -- float64, one division, one
+// truncation and a clamp on the double per bound -- and per job what of its rectangle lies inside.  Writes nothing unless
+// everything passes; then plan (in the GROWN frame, with k0 / k1 / origin per prior and the staged rows per job), every
+// job's inside / outside / at and every field of out but `changed`.
+int slide_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, const fxjps_prior_keep_t* keep,
+                fxjps_prior_slid_t* out, GrowPlan& plan, char* msg, size_t len) {
+    static const fxjps_prior_keep_t none[FXJPS_MAX_PRIOR_MAPS] = {};
+    if (!out) return absorb_refuse(msg, len, "job 0: NULL out");
+    const fxjps_prior_keep_t* K = keep ? keep : none;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        if (K[p].use < FXJPS_KEEP_NONE || K[p].use > FXJPS_KEEP_OVER_LIMIT)
+            return absorb_refuse(msg, len, "prior %d: keep.use %d is not FXJPS_KEEP_NONE, _ALWAYS or _OVER_LIMIT", p, (int)K[p].use);
+        if (K[p].use == FXJPS_KEEP_NONE) continue;
+        for (int k = 0; k < 2; k++) {
+            if (std::isnan(K[p].lo[k]) || std::isnan(K[p].hi[k])) return absorb_refuse(msg, len, "prior %d: axis %d: NaN in the keep window", p, k);
+            if (K[p].lo[k] > K[p].hi[k]) return absorb_refuse(msg, len, "prior %d: axis %d: the keep window's lo %g is above its hi %g", p, k, K[p].lo[k], K[p].hi[k]);
+        }
+    }
+    std::vector<fxjps_grow_job_t> fold;  // (grow_check fills at / inside / outside: not the caller's before every window has passed)
+    if (jobs && n > 0 && n <= FXJPS_MAX_GRID_SLOTS) fold.assign(jobs, jobs + n);
+    fxjps_prior_grown_t grown[FXJPS_MAX_PRIOR_MAPS];
+    long long limit[2];
+    if (int rc = grow_check(fold.empty() ? jobs : fold.data(), n, mode, prior_wh, limit_wh, grown, plan, msg, len, K, limit)) return rc;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        GrowPlan::Prior& P = plan.prior[p];
+        if (!P.named) {
+            if (K[p].use != FXJPS_KEEP_NONE) return absorb_refuse(msg, len, "prior %d: a keep window for a prior that no job names", p);
+            continue;
+        }
+        for (int k = 0; k < 2; k++) {
+            P.k0[k] = 0;
+            P.k1[k] = P.ext[k];
+            P.origin[k] = P.op[k];
+        }
+        if (K[p].use == FXJPS_KEEP_NONE || (K[p].use == FXJPS_KEEP_OVER_LIMIT && P.ext[0] <= limit[0] && P.ext[1] <= limit[1])) continue;
+        P.trimmed = true;
+        const double reso = fold[(size_t)P.first].map_reso;
+        for (int k = 0; k < 2; k++) {
+            const double G = (double)P.ext[k];
+            const double a = std::trunc((K[p].lo[k] - P.op[k]) / reso), b = std::trunc((K[p].hi[k] - P.op[k]) / reso);
+            P.k0[k] = (long long)(a < 0.0 ? 0.0 : a > G ? G : a);  // (clamped as a double: a bound may be infinite)
+            P.k1[k] = (long long)(b < 0.0 ? 0.0 : b > G ? G : b);
+            if (P.k1[k] <= P.k0[k])
+                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window holds no cell of the grown prior (cells %lld .. %lld of %lld)", p, k, P.k0[k],
+                                     P.k1[k], P.ext[k]);
+            if (P.k1[k] - P.k0[k] > limit[k])
+                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window of %lld cells is above the limit of %lld", p, k, P.k1[k] - P.k0[k], limit[k]);
+            if (P.k0[k] != 0) P.origin[k] = P.op[k] + reso * (double)P.k0[k];
+        }
+    }
+    // what of every rectangle lies inside its prior's window: the rows to stage and the union box, both in the grown frame
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) plan.prior[p].lo[0] = plan.prior[p].lo[1] = INT32_MAX, plan.prior[p].hi[0] = plan.prior[p].hi[1] = 0;
+    std::vector<long long> inside((size_t)n, 0);
+    plan.in_bytes = GROW_IN_RAWS;
+    for (int j = 0; j < n; j++) {
+        const fxjps_grow_job_t& a = fold[(size_t)j];
+        GrowPlan::Prior& P = plan.prior[a.prior];
+        GrowPlan::Job& q = plan.job[(size_t)j];
+        long long c0[2], c1[2];
+        for (int k = 0; k < 2; k++) {
+            c0[k] = std::max(q.at[k], P.k0[k]);
+            c1[k] = std::min(q.at[k] + (long long)a.win[k], P.k1[k]);
+        }
+        q.staged = c1[0] > c0[0] && c1[1] > c0[1];
+        q.raw_off = q.raw_bytes = 0;
+        q.in_off = plan.in_bytes;
+        q.row0 = 0;
+        if (!q.staged) continue;
+        inside[(size_t)j] = (c1[0] - c0[0]) * (c1[1] - c0[1]);
+        for (int k = 0; k < 2; k++) {
+            P.lo[k] = std::min(P.lo[k], c0[k]);
+            P.hi[k] = std::max(P.hi[k], c1[k]);
+        }
+        const size_t row = (size_t)(a.layout ? a.W0 : a.H0), r = a.layout ? 1 : 0;
+        q.row0 = c0[r] - q.at[r];
+        q.raw_off = (size_t)(a.lo[r] + q.row0) * row;
+        q.raw_bytes = (size_t)(c1[r] - c0[r]) * row;
+        plan.in_bytes += (q.raw_bytes + 15) & ~(size_t)15;
+        if (plan.in_bytes > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
+    }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        GrowPlan::Prior& P = plan.prior[p];
+        if (P.lo[0] > P.hi[0]) P.lo[0] = P.lo[1] = P.hi[0] = P.hi[1] = 0;  // (no rectangle reaches the window: an empty box)
+    }
+    for (int j = 0; j < n; j++) {
+        const GrowPlan::Prior& P = plan.prior[jobs[j].prior];
+        for (int k = 0; k < 2; k++) jobs[j].at[k] = (int32_t)(plan.job[(size_t)j].at[k] - P.k0[k]);
+        jobs[j].inside = inside[(size_t)j];
+        jobs[j].outside = (long long)jobs[j].win[0] * jobs[j].win[1] - inside[(size_t)j];
+    }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        const GrowPlan::Prior& P = plan.prior[p];
+        fxjps_prior_slid_t& g = out[p];
+        g.named = P.named ? 1 : 0;
+        g.trimmed = P.trimmed ? 1 : 0;
+        for (int k = 0; k < 2; k++) {
+            const int32_t as_is = prior_wh[2 * p + k];
+            (k ? g.H : g.W) = P.named ? (int32_t)(P.k1[k] - P.k0[k]) : as_is;
+            g.grown_wh[k] = P.named ? (int32_t)P.ext[k] : as_is;
+            g.cut_lo[k] = (int32_t)P.k0[k];
+            g.cut_hi[k] = P.named ? (int32_t)(P.ext[k] - P.k1[k]) : 0;
+            g.shift[k] = (int32_t)(P.shift[k] - P.k0[k]);
+            g.origin[k] = P.origin[k];
+        }
+    }
+    return FXJPS_OK;
+}
+}  // namespace
+
+int fxjps_slide_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
+                      const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len) {
+    if (msg && msg_len > 0) msg[0] = 0;
+    GrowPlan plan;
+    return slide_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
+}
+
+int fxjps_absorb_prior_slide(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
+                             const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS]) {
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior_slide")) return rr;
+    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
+    const DevCtx& d0 = h->devs[0];
+    for (size_t p = 0; p < d0.priors.size(); p++) {
+        prior_wh[2 * p] = d0.priors[p].W;
+        prior_wh[2 * p + 1] = d0.priors[p].H;
+    }
+    GrowPlan plan;
+    char why[400] = "";
+    if (slide_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = 0;
+    if (n == 0) return FXJPS_OK;
+    // as fxjps_absorb_prior_grow: every context writes its own new copies; they are swapped in only when all have succeeded
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grow_on(h, h->devs[r], jobs, n, mode, plan, true); });
+    if (rc) {
+        drain_all(h);
+        (void)hipGetLastError();
+        return rc;
+    }
+    for (auto& d : h->devs)
+        for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++)
+            if (plan.prior[p].named) {
+                DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+                std::swap(pr.occ, pr.next);  // (the old buffer is the next call's spare)
+                pr.W = (int)(plan.prior[p].k1[0] - plan.prior[p].k0[0]);
+                pr.H = (int)(plan.prior[p].k1[1] - plan.prior[p].k0[1]);
             }
     for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
     return FXJPS_OK;

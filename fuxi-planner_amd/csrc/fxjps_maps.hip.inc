@@ -2094,20 +2094,29 @@ struct GrowTable {
     int32_t nbox, mode;
     GrowBoxDev box[ABSORB_PRIORS_MAX];
     AbsorbJobDev job[ABSORB_JOBS_MAX];              // (x0, y0: in the grown prior's frame; the rectangle lies inside it)
+    int32_t k0[ABSORB_PRIORS_MAX][2];               // WINDOW only (behind everything k_prior_grow<false> reads): see below
 };
 
-__global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
+// WINDOW (fxjps_absorb_prior_slide, DESIGN.md section 3.22): the new buffer [nW][nH] holds only the cells [k0, k0 + (nW, nH))
+// of the grown frame, the prior's keep window; the grown frame itself exists nowhere.  A thread owns one cell of the WINDOW,
+// adjacent lanes adjacent y; its coordinates in the grown frame are the window's plus k0, and everything else -- sx, sy, the
+// union box (which the host has clipped to the window) and the jobs' x0, y0 -- stays in the grown frame, so the job walk,
+// the predicates, the old-byte fallback and the ballot count are the same lines.  Of a rectangle only the rows inside the
+// window are staged: a thread reads a raw only at a cell of its own, which lies in the window.  k0 = 0 with the grown
+// extents is a prior that is not cut.  <false> is fxjps_absorb_prior_grow's kernel as it was, instruction for instruction.
+template <bool WINDOW> __global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
     __shared__ AbsorbJobDev s_job[ABSORB_JOBS_MAX];
     const int nbox = T->nbox, mode = T->mode;
     int b = 0;  // (block-uniform)
     while (b + 1 < nbox && T->first[b + 1] <= blockIdx.x) b++;
     const GrowBoxDev B = T->box[b];
+    const int kx = WINDOW ? T->k0[b][0] : 0, ky = WINDOW ? T->k0[b][1] : 0;
     const long long cells = (long long)B.nW * B.nH;
     const long long c0 = (long long)(blockIdx.x - T->first[b]) * 256;
     // does any of the block's cells [c0, c1] lie in a column of the union box?  (block-uniform; columns only: a block that
     // spans more than one column covers every y of some of them)
     const long long c1 = c0 + 255 < cells - 1 ? c0 + 255 : cells - 1;
-    const int bx0 = (int)(c0 / B.nH), bx1 = (int)(c1 / B.nH);
+    const int bx0 = (int)(c0 / B.nH) + kx, bx1 = (int)(c1 / B.nH) + kx;
     const bool near_box = bx0 < B.x0 + B.w && bx1 >= B.x0;
     if (near_box) {
         const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(T->job + B.job0);
@@ -2119,7 +2128,8 @@ __global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
     const long long c = c0 + threadIdx.x;
     bool flip = false;
     if (c < cells) {
-        const int x = (int)(c / B.nH), y = (int)(c - (long long)x * B.nH);
+        const int wx = (int)(c / B.nH), wy = (int)(c - (long long)wx * B.nH);  // the cell in the new buffer ...
+        const int x = wx + kx, y = wy + ky;                                    // ... and in the grown frame
         int val = -1;  // undecided
         if (near_box && (unsigned)(x - B.x0) < (unsigned)B.w && (unsigned)(y - B.y0) < (unsigned)B.h) {
             for (int k = B.njobs - 1; k >= 0; k--) {
@@ -2139,7 +2149,7 @@ __global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
         uint8_t old = 0;
         if ((unsigned)ox < (unsigned)B.oW && (unsigned)oy < (unsigned)B.oH) old = B.old[(size_t)ox * (size_t)B.oH + (size_t)oy];
         const uint8_t byte = val >= 0 ? (uint8_t)val : old;
-        B.out[(size_t)x * (size_t)B.nH + (size_t)y] = byte;
+        B.out[(size_t)wx * (size_t)B.nH + (size_t)wy] = byte;
         flip = (old != 0) != (byte != 0);
     }
     RECONV();

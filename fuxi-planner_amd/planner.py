@@ -656,6 +656,22 @@ class Planner(object):
         old cell (0, 0) lies now, the new world origin and the cells whose occupancy differs from the old byte at that
         place.  The planner remembers each grown prior's origin (prior_origin); the library stores none.  On a refusal or
         a failure every prior is what it was, byte for byte.  worldprep.grow_host is the same fold on the host."""
+        arr, n, lim, keep = self._grow_jobs(jobs, mode, crops, limit)
+        out = (_lib.PriorGrown * _lib.MAX_PRIOR_MAPS)()
+        self._chk(self._L.fxjps_absorb_prior_grow(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), out))
+        del keep
+        grown = {}
+        for p, g in enumerate(out):
+            if g.named:
+                grown[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
+                            "changed": int(g.changed)}
+                self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
+        return [(int(a.at[0]), int(a.at[1])) for a in arr[:n]], grown
+
+    @staticmethod
+    def _grow_jobs(jobs, mode, crops, limit):
+        """absorb_prior_grow's and absorb_prior_slide's arguments as the library takes them -> (fxjps_grow_job_t array, n,
+        limit_wh or None, the raws: alive until the call has returned)."""
         from . import worldprep
         jobs = list(jobs)
         n = len(jobs)
@@ -667,7 +683,7 @@ class Planner(object):
         if limit is not None:
             lim = np.array([limit, limit] if np.isscalar(limit) else [limit[0], limit[1]], dtype=np.int32)
         arr = (_lib.GrowJob * max(n, 1))()
-        keep = []  # (the raws, alive until the call has returned)
+        keep = []
         for v, (a, job) in enumerate(zip(arr, jobs)):
             raw, map_o, map_reso = job[1], job[2], job[3]
             prior, ori_pre, map_t = (tuple(job[8:11]) + (None, (-15, -15), None)[len(job[8:11]):])[:3]
@@ -685,16 +701,48 @@ class Planner(object):
             a.prior, a.map_reso = int(prior), float(map_reso)
             for k in range(2):
                 a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k], a.map_t[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k]), float(map_t[k])
-        out = (_lib.PriorGrown * _lib.MAX_PRIOR_MAPS)()
-        self._chk(self._L.fxjps_absorb_prior_grow(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), out))
-        del keep
-        grown = {}
+        return arr, n, lim, keep
+
+    def absorb_prior_slide(self, jobs, mode="overwrite", crops=None, limit=None, keep=None, use="over_limit"):
+        """absorb_prior_grow followed, per prior, by a cut to a keep window, in the same single launch
+        (fxjps_absorb_prior_slide): a prior that moves with the fleet instead of refusing the call once a side would pass
+        the limit.  jobs, mode, crops and limit as absorb_prior_grow takes them.  keep: {prior: (lo_xy, hi_xy)}, the window
+        in world metres (an infinite bound: no cut on that side); a prior without one behaves exactly as under
+        absorb_prior_grow.  use: "always" -- cut on every call; "over_limit" -- the whole window is applied if and only
+        if a grown side exceeds the limit; "none"; or {prior: use} (a prior of keep that it leaves out: "none").  A prior
+        with a window is not held to the limit job after job; a window above the limit, one that holds no cell of the
+        grown prior and one for a prior no job names refuse the whole call.  -> ([(at, inside, outside) per job], {prior:
+        record}): at -- the cell of the prior as the call leaves it that the rectangle's cell (0, 0) lies on (it may be
+        negative), inside / outside -- the rectangle's cells in the window and the rest, which are dropped; the record
+        holds absorb_prior_grow's keys (shift may be negative; changed counts cells of the window only) and trimmed
+        (whether the window was applied), grown_wh (the extents the fold reached) and cut_lo / cut_hi (the cells cut off
+        each side of them).  prior_origin is updated as absorb_prior_grow updates it; on a refusal or a failure every
+        prior is what it was.  worldprep.slide_host is the same on the host."""
+        arr, n, lim, raws = self._grow_jobs(jobs, mode, crops, limit)
+        win = None
+        if keep:
+            win = (_lib.PriorKeep * _lib.MAX_PRIOR_MAPS)()
+            for p, (lo, hi) in keep.items():
+                u = use.get(p, "none") if isinstance(use, dict) else use
+                if u not in _lib.KEEP_USES:
+                    raise ValueError("use %r is not one of %r" % (u, tuple(_lib.KEEP_USES)))
+                if not 0 <= int(p) < _lib.MAX_PRIOR_MAPS:
+                    raise ValueError("keep names prior %r: not in 0 .. %d" % (p, _lib.MAX_PRIOR_MAPS - 1))
+                w = win[int(p)]
+                w.use = _lib.KEEP_USES[u]
+                for k in range(2):
+                    w.lo[k], w.hi[k] = float(lo[k]), float(hi[k])
+        out = (_lib.PriorSlid * _lib.MAX_PRIOR_MAPS)()
+        self._chk(self._L.fxjps_absorb_prior_slide(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), win, out))
+        del raws
+        slid = {}
         for p, g in enumerate(out):
             if g.named:
-                grown[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
-                            "changed": int(g.changed)}
+                slid[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
+                           "changed": int(g.changed), "trimmed": bool(g.trimmed), "grown_wh": (int(g.grown_wh[0]), int(g.grown_wh[1])),
+                           "cut_lo": (int(g.cut_lo[0]), int(g.cut_lo[1])), "cut_hi": (int(g.cut_hi[0]), int(g.cut_hi[1]))}
                 self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
-        return [(int(a.at[0]), int(a.at[1])) for a in arr[:n]], grown
+        return [((int(a.at[0]), int(a.at[1])), int(a.inside), int(a.outside)) for a in arr[:n]], slid
 
     def _origins(self):
         if getattr(self, "_prior_origin", None) is None:
@@ -709,7 +757,8 @@ class Planner(object):
     def _tick_absorb(self, absorb, jobs, outs, crop, recs, grow=None):
         """fleet_tick_world's absorb=: after the tick's prepare / refresh call, every job that names a prior is absorbed --
         a cropped job through its window, unless it has none (not planned, refused).  recs[v]["absorbed"] is set.  grow:
-        None, or (grow_limit,): through absorb_prior_grow, and recs[v]["ori_pre"] / ["grown"] are set as well."""
+        None, or (grow_limit, slide): through absorb_prior_grow, and recs[v]["ori_pre"] / ["grown"] are set as well; slide not
+        None: through absorb_prior_slide with each prior's keep box (_keep_boxes), and recs[v]["slid"] is set too."""
         if absorb is None:
             return
         take, crops = [], []
@@ -717,6 +766,8 @@ class Planner(object):
             recs[v]["absorbed"] = None
             if grow is not None:
                 recs[v]["grown"] = None
+                if grow[1] is not None:
+                    recs[v]["slid"] = None
                 recs[v]["ori_pre"] = None if len(job) <= 8 or job[8] is None else tuple(float(x) for x in (job[9] if len(job) > 9 else (-15, -15)))
             if len(job) <= 8 or job[8] is None:
                 continue
@@ -724,7 +775,13 @@ class Planner(object):
                 continue
             take.append(v)
             crops.append(outs[v][-1] if crop else None)
-        if take and grow is not None:
+        if take and grow is not None and grow[1] is not None:
+            sub = [jobs[v] for v in take]
+            per_job, slid = self.absorb_prior_slide(sub, absorb, crops if crop else None, grow[0], self._keep_boxes(sub, crops, grow[1]), "over_limit")
+            for v, (_, inside, outside) in zip(take, per_job):
+                recs[v]["absorbed"] = (inside, outside)
+                recs[v]["grown"] = recs[v]["slid"] = slid[int(jobs[v][8])]
+        elif take and grow is not None:
             _, grown = self.absorb_prior_grow([jobs[v] for v in take], absorb, crops if crop else None, grow[0])
             for v, c in zip(take, crops):
                 raw = jobs[v][1]
@@ -736,8 +793,29 @@ class Planner(object):
             for v, c in zip(take, counts):
                 recs[v]["absorbed"] = c
 
+    @staticmethod
+    def _keep_boxes(jobs, crops, margin):
+        """fleet_tick_world's slide=: per prior the box over the jobs that name it -- each job's rectangle [map_o, map_t] (the
+        crop record's for a cropped job), its pos_xy and its goal_xy -- widened by margin metres on every side: the
+        neighbourhood of the vehicles and of the way to their goals.  -> {prior: (lo_xy, hi_xy)}."""
+        from . import worldprep
+        boxes = {}
+        for job, rec in zip(jobs, crops):
+            raw, map_o = job[1], job[2]
+            if rec is not None:
+                map_o, map_t = rec["map_o"], rec["map_t"]
+            elif len(job) > 10 and job[10] is not None:
+                map_t = job[10]
+            else:
+                map_t = worldprep.map_top(map_o, (raw[1], raw[2]) if isinstance(raw, tuple) else np.asarray(raw).shape, job[3])
+            lo, hi = boxes.setdefault(int(job[8]), ([float("inf")] * 2, [float("-inf")] * 2))
+            for k in range(2):
+                pts = (float(map_o[k]), float(map_t[k]), float(job[4][k]), float(job[5][k]))
+                lo[k], hi[k] = min(lo[k], min(pts) - margin), max(hi[k], max(pts) + margin)
+        return {p: (tuple(lo), tuple(hi)) for p, (lo, hi) in boxes.items()}
+
     def fleet_tick_world(self, jobs, pos, global_goals, home, prev_wp=None, prev_dim=None, publish=True, image_channels=None, refresh=False,
-                         reuse=False, crop=False, throttle=None, check_kept=True, absorb=None, grow=False, grow_limit=None):
+                         reuse=False, crop=False, throttle=None, check_kept=True, absorb=None, grow=False, grow_limit=None, slide=None):
         """fleet_tick from world-frame jobs (as prepare_slots_world takes them): the maps are prepared through
         prepare_slots_world (refresh=True: refresh_slots_world), and each vehicle's resolution and shifted origin are the
         job's and the call's instead of the caller's.  The same records; kept / reused where refresh / reuse ask for them
@@ -753,9 +831,22 @@ class Planner(object):
         (grow_limit: its `limit`); every record gains ori_pre -- the prior origin the job was prepared and absorbed with, None
         without a prior -- and grown, the prior's record from absorb_prior_grow, or None for a job that was not absorbed.
         Once a prior has a remembered origin (prior_origin), every job that names it is prepared and absorbed with that
-        origin instead of the job's own ori_pre, on grow=False ticks as well: the job's is the origin of the upload."""
+        origin instead of the job's own ori_pre, on grow=False ticks as well: the job's is the origin of the upload.
+        slide: None, or a margin in metres, at least 0 (needs grow=True): the absorb step goes through absorb_prior_slide
+        with use="over_limit", so a prior that would pass grow_limit is cut to its keep box instead of refusing the tick --
+        per prior the box over the absorbed jobs that name it, covering each job's rectangle [map_o, map_t] (the crop
+        record's for a cropped job), pos_xy and goal_xy, widened by the margin on every side: the pre-known map between
+        the fleet and its goals survives, the strip left behind is dropped.  Every record gains slid: the prior's record from
+        absorb_prior_slide (grown is that record too), or None for a job that was not absorbed; absorbed is (inside,
+        outside) from the call.  slide=None: every output is what it is without it."""
         if grow and absorb is None:
             raise ValueError("grow=True needs absorb=")
+        if slide is not None:
+            if not grow:
+                raise ValueError("slide= needs grow=True")
+            slide = float(slide)
+            if not slide >= 0.0:
+                raise ValueError("slide= is a margin in metres, at least 0: not %r" % (slide,))
         jobs = [tuple(j) for j in jobs]
         for v, j in enumerate(jobs):
             at = self.prior_origin(j[8]) if len(j) > 8 and j[8] is not None else None
@@ -763,7 +854,7 @@ class Planner(object):
                 jobs[v] = j[:9] + (at,) + j[10:]
         return self._fleet_tick(refresh, jobs, pos, global_goals, home, [float(j[3]) for j in jobs], None, prev_wp, prev_dim, publish,
                                 image_channels, reuse, world=True, crop=crop, throttle=throttle, check_kept=check_kept, absorb=absorb,
-                                grow=(grow_limit,) if grow else None)
+                                grow=(grow_limit, slide) if grow else None)
 
     def check_paths_slots(self, grid_ids, offsets, cells, shift=None):
         """Which kept paths do their slots' grids, as they are now, still allow (fxjps_check_paths_slots: one launch for

@@ -9,7 +9,8 @@ int() truncate, and a ValueError where the library refuses.  Pinned by tests/gol
 values come from executing the reference's own lines (tests/golden/make_golden_worldprep.py).  crop_host is the host form
 of Planner.prepare_slots_cropped in the same way, pinned by tests/golden/cropprep.json (make_golden_cropprep.py), and
 absorb_host that of Planner.absorb_prior: the same slice assignment kept in the prior map, pinned by the canvases of
-worldprep.json; grow_host is that of Planner.absorb_prior_grow: the whole canvas kept, pinned by the same canvases.
+worldprep.json; grow_host is that of Planner.absorb_prior_grow: the whole canvas kept, pinned by the same canvases;
+window_host and slide_host are those of Planner.absorb_prior_slide: the grow_host fold, then a slice of it.
 """
 import math
 
@@ -169,7 +170,7 @@ def absorb_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None,
     return new, inside, win[0] * win[1] - inside, changed
 
 
-def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, win=None, map_t=None):
+def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, win=None, map_t=None, limit=(8190, 8190)):
     """One job of Planner.absorb_prior_grow on the host: absorb_host on a prior that GROWS to hold the rectangle -- the
     canvas of st:212-220, the union of the prior and the detected map, kept as the next prior.  Arguments as absorb_host
     takes them, and map_t, the rectangle's top (None: map_o + win * map_reso; a cropped job: the crop record's).  Per axis
@@ -181,7 +182,8 @@ def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, w
     -> (new prior uint8, new ori_pre [x, y] (o1), shift (at_pre: where old cell (0, 0) lies), at (at_raw: where rectangle
     cell (0, 0) lies), changed: the cells whose occupancy (non-zero) differs from the old byte at that place, 0 where the
     old prior had none).  Several jobs: call it job by job on the result (an earlier job's `at` then moves by every later
-    job's shift).  ValueError where the library refuses."""
+    job's shift).  limit: the largest side per axis (slide_host passes the call's, or int32's for a prior that is cut
+    afterwards).  ValueError where the library refuses."""
     if mode not in ABSORB_MODES:
         raise ValueError("mode %r is not one of %r" % (mode, ABSORB_MODES))
     pre = np.asarray(prior)
@@ -222,8 +224,8 @@ def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, w
         at_pre[k] = _trunc((op[k] - o1[k]) / reso, "the prior's index")          # st:214
         ref = _trunc((max(t_pre, top[k]) - o1[k]) / reso, "the canvas extent")   # st:215-216
         size[k] = max(ref, at_pre[k] + ext[k], at_raw[k] + win[k])
-        if size[k] > 8190:
-            raise ValueError("axis %d: the prior would grow to %d cells, above 8190" % (k, size[k]))
+        if size[k] > limit[k]:
+            raise ValueError("axis %d: the prior would grow to %d cells, above %d" % (k, size[k], limit[k]))
     placed = np.zeros(size, dtype=np.uint8)
     placed[at_pre[0]:at_pre[0] + ext[0], at_pre[1]:at_pre[1] + ext[1]] = pre
     new = placed.copy()
@@ -239,6 +241,131 @@ def grow_host(prior, ori_pre, raw, map_o, map_reso, mode="overwrite", lo=None, w
         target[known] = occ[known]
     changed = int(np.count_nonzero((new != 0) != (placed != 0)))
     return new, o1, at_pre, at_raw, changed
+
+
+KEEP_USES = ("none", "always", "over_limit")  # FXJPS_KEEP_NONE, _ALWAYS, _OVER_LIMIT
+
+
+def window_cells(extent, origin, map_reso, keep_lo, keep_hi):
+    """The cells [k0, k1) per axis that a keep window (world metres; an infinite bound: no cut on that side) leaves of a
+    prior of `extent` cells at `origin`, and the origin of the cut: per axis, in float64,
+        k0 = clamp(trunc((keep_lo - origin) / reso), 0, extent);  k1 = clamp(trunc((keep_hi - origin) / reso), 0, extent)
+        new origin = origin if k0 == 0 else origin + reso * k0
+    with the clamp on the float before the conversion.  -> (k0, k1, new origin).  ValueError where the library refuses:
+    NaN in a bound, lo > hi, a window that holds no cell (k1 <= k0)."""
+    reso = float(map_reso)
+    if not (math.isfinite(reso) and reso > 0.0):
+        raise ValueError("map_reso %r must be finite and > 0" % (map_reso,))
+    og = _pair(origin, "origin")
+    k0, k1, new = [0, 0], [0, 0], [0.0, 0.0]
+    for k in range(2):
+        lo, hi, G = float(keep_lo[k]), float(keep_hi[k]), float(int(extent[k]))
+        if math.isnan(lo) or math.isnan(hi):
+            raise ValueError("axis %d: NaN in the keep window" % k)
+        if lo > hi:
+            raise ValueError("axis %d: the keep window's lo %r is above its hi %r" % (k, lo, hi))
+        a, b = (lo - og[k]) / reso, (hi - og[k]) / reso
+        a = a if math.isinf(a) else float(math.trunc(a))
+        b = b if math.isinf(b) else float(math.trunc(b))
+        k0[k] = int(min(max(a, 0.0), G))
+        k1[k] = int(min(max(b, 0.0), G))
+        if k1[k] <= k0[k]:
+            raise ValueError("axis %d: the keep window holds no cell of the prior (cells %d .. %d of %d)" % (k, k0[k], k1[k], int(G)))
+        new[k] = og[k] if k0[k] == 0 else og[k] + reso * float(k0[k])
+    return k0, k1, new
+
+
+def window_host(prior, origin, map_reso, keep_lo, keep_hi):
+    """The cut of Planner.absorb_prior_slide on the host: -> (prior[k0[0]:k1[0], k0[1]:k1[1]] (a copy), new origin, cut_lo =
+    k0, cut_hi = extent - k1) with window_cells' arithmetic.  ValueError where the library refuses."""
+    pre = np.asarray(prior)
+    if pre.ndim != 2 or pre.shape[0] < 1 or pre.shape[1] < 1:
+        raise ValueError("the prior map must be 2-D and not empty")
+    k0, k1, new = window_cells(pre.shape, origin, map_reso, keep_lo, keep_hi)
+    return pre[k0[0]:k1[0], k0[1]:k1[1]].copy(), new, k0, [pre.shape[k] - k1[k] for k in range(2)]
+
+
+def slide_host(before, jobs, mode="overwrite", crops=None, limit=None, keep=None, use="over_limit"):
+    """Planner.absorb_prior_slide on the host, and the yardstick of its GPU tests: the grow_host fold job by job, then
+    window_host under the use / limit rule.  before: {prior: bytes [x][y]}; jobs, crops, mode, limit, keep ({prior: (lo_xy,
+    hi_xy)}) and use (one of KEEP_USES, or {prior: use}) as absorb_prior_slide takes them, every job's ori_pre the prior's
+    origin BEFORE the call.  A prior with a keep window is not held to the limit job after job (only to int32); its window is
+    applied under "always", under "over_limit" if and only if a grown side exceeds the limit; a side above the limit after
+    the cut is refused.  -> (after {prior: bytes}, records {named prior: {"W", "H", "shift", "origin", "changed", "trimmed",
+    "grown_wh", "cut_lo", "cut_hi"}}, [(at, inside, outside) per job]).  The host form materialises the grown frame, which
+    the library never does.  ValueError where the library refuses."""
+    jobs = list(jobs)
+    lim = [8190, 8190] if limit is None else [int(limit), int(limit)] if np.isscalar(limit) else [int(limit[0]), int(limit[1])]
+    if not all(1 <= x <= 8190 for x in lim):
+        raise ValueError("the limit %r is not in 1 .. 8190" % (lim,))
+    keep = {} if keep is None else {int(p): w for p, w in keep.items()}
+    uses = {p: (use.get(p, "none") if isinstance(use, dict) else use) for p in keep}
+    for p, u in uses.items():
+        if u not in KEEP_USES:
+            raise ValueError("prior %d: use %r is not one of %r" % (p, u, KEEP_USES))
+        if u != "none":
+            for k in range(2):
+                lo, hi = float(keep[p][0][k]), float(keep[p][1][k])
+                if math.isnan(lo) or math.isnan(hi) or lo > hi:
+                    raise ValueError("prior %d: axis %d: a NaN in the keep window, or lo above hi" % (p, k))
+    cur = {int(k): np.array(v, dtype=np.uint8) for k, v in before.items()}
+    origin, shift, at, first = {}, {}, [], {}
+    for v, wj in enumerate(jobs):
+        raw, map_o, reso, prior, ori_pre = wj[1], wj[2], wj[3], int(wj[8]), wj[9]
+        map_t = wj[10] if len(wj) > 10 else None
+        rec = crops[v] if crops is not None else None
+        lo, win = (None, None) if rec is None else (rec["lo"], rec["win"])
+        if rec is not None:
+            map_o, map_t = rec["map_o"], rec["map_t"]
+        if prior not in cur:
+            raise ValueError("job %d: prior %d is not set" % (v, prior))
+        if prior in first and (tuple(float(x) for x in ori_pre), float(reso)) != first[prior]:
+            raise ValueError("job %d: ori_pre / map_reso differ from those of an earlier job on prior %d" % (v, prior))
+        first.setdefault(prior, (tuple(float(x) for x in ori_pre), float(reso)))
+        held = uses.get(prior, "none") == "none"
+        new, o1, sh, a, _ = grow_host(cur[prior], origin.get(prior, ori_pre), raw, map_o, reso, mode, lo=lo, win=win, map_t=map_t,
+                                      limit=lim if held else (I32_MAX, I32_MAX))
+        for i, earlier in enumerate(jobs[:v]):  # (the earlier rectangles move with the old prior)
+            if int(earlier[8]) == prior:
+                at[i][0] = (at[i][0][0] + sh[0], at[i][0][1] + sh[1])
+        s = shift.get(prior, (0, 0))
+        shift[prior] = (s[0] + sh[0], s[1] + sh[1])
+        cur[prior], origin[prior] = new, [float(o1[0]), float(o1[1])]
+        size = win if win is not None else (raw[1], raw[2]) if isinstance(raw, tuple) else np.asarray(raw).shape
+        at.append([(a[0], a[1]), (int(size[0]), int(size[1])), prior])
+    for p, u in uses.items():
+        if u != "none" and p not in origin:
+            raise ValueError("prior %d: a keep window for a prior that no job names" % p)
+    records, k0s = {}, {}
+    for p in origin:
+        grown = cur[p]
+        old = np.zeros(grown.shape, dtype=np.uint8)
+        w, h = before[p].shape
+        old[shift[p][0]:shift[p][0] + w, shift[p][1]:shift[p][1] + h] = before[p]
+        u = uses.get(p, "none")
+        G = [int(grown.shape[0]), int(grown.shape[1])]
+        k0, k1, o = [0, 0], G, origin[p]
+        trimmed = u == "always" or (u == "over_limit" and (G[0] > lim[0] or G[1] > lim[1]))
+        if trimmed:
+            k0, k1, o = window_cells(G, origin[p], first[p][1], keep[p][0], keep[p][1])
+            for k in range(2):
+                if k1[k] - k0[k] > lim[k]:
+                    raise ValueError("prior %d: axis %d: the keep window of %d cells is above the limit of %d" % (p, k, k1[k] - k0[k], lim[k]))
+        cut = (slice(k0[0], k1[0]), slice(k0[1], k1[1]))
+        cur[p] = grown[cut].copy()
+        k0s[p] = k0
+        records[p] = {"W": k1[0] - k0[0], "H": k1[1] - k0[1], "shift": (shift[p][0] - k0[0], shift[p][1] - k0[1]), "origin": [float(o[0]), float(o[1])],
+                      "changed": int(np.count_nonzero((grown[cut] != 0) != (old[cut] != 0))), "trimmed": bool(trimmed), "grown_wh": (G[0], G[1]),
+                      "cut_lo": (k0[0], k0[1]), "cut_hi": (G[0] - k1[0], G[1] - k1[1])}
+    per_job = []
+    for a, win, p in at:
+        k0, ext = k0s[p], (records[p]["W"], records[p]["H"])
+        where = (a[0] - k0[0], a[1] - k0[1])
+        inside = 1
+        for k in range(2):
+            inside *= max(0, min(where[k] + win[k], ext[k]) - max(where[k], 0))
+        per_job.append((where, inside, win[0] * win[1] - inside))
+    return cur, records, per_job
 
 
 def merge_host(raw, map_o, map_reso, pos_xy, goal_xy, prior=None, ori_pre=(-15, -15), map_t=None):

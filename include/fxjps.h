@@ -119,8 +119,11 @@ typedef struct fxjps fxjps_t;
  *   860  fxjps_absorb_prior_grow (fxjps_absorb_prior on priors that grow to what the vehicles have seen: the canvas the
  *        nodes build every tick, kept as the next prior, in one launch whatever n is), fxjps_grow_check (its geometry and
  *        refusals without a handle), fxjps_grow_job_size, fxjps_prior_grown_size.
+ *   870  fxjps_absorb_prior_slide (fxjps_absorb_prior_grow followed, per prior, by a cut to a keep window in world metres,
+ *        in the same single launch: a prior that moves with the fleet instead of refusing at the limit), fxjps_slide_check
+ *        (its geometry and refusals without a handle), fxjps_prior_keep_size, fxjps_prior_slid_size.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 860
+#define FXJPS_VERSION 870
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -601,7 +604,8 @@ int fxjps_absorb_job_size(void); /* sizeof(fxjps_absorb_job_t) as the library wa
  * its old extents.  Queued on the handle's stream: earlier world-frame calls have read the old prior, later ones read the
  * new one -- with the NEW origin as their ori_pre --, and fxjps_get_prior_map returns the new extents and bytes.  No slot,
  * no slot generation, no stored result, not the resident grid and no prior that no job names is touched; n == 0 returns
- * FXJPS_OK with nothing named.  Forgetting old observations and trimming a prior are not part of this. */
+ * FXJPS_OK with nothing named.  Forgetting old observations is not part of this; trimming a prior is
+ * fxjps_absorb_prior_slide's, below. */
 typedef struct fxjps_grow_job {
     const void* raw;      /* in: as fxjps_absorb_job_t, field by field ... */
     int32_t layout;
@@ -631,6 +635,63 @@ int fxjps_grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int3
                      fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len);
 int fxjps_grow_job_size(void);    /* sizeof(fxjps_grow_job_t) as the library was built */
 int fxjps_prior_grown_size(void); /* sizeof(fxjps_prior_grown_t) as the library was built */
+/* ---- ... on priors that SLIDE (version 870): fxjps_absorb_prior_grow followed, per prior, by a cut to a keep window given
+ * in world metres, in the same single launch.  A fleet that flies away from its take-off area keeps the neighbourhood of
+ * its vehicles and goals and drops the strip left behind, instead of being refused once a side would pass the limit.  The
+ * grown frame is never materialised: the new buffer has the window's extents and a thread owns one cell of the window.
+ *   The jobs are fxjps_grow_job_t as it is, and the fold over a prior's jobs is fxjps_absorb_prior_grow's, unchanged: it
+ * gives the grown extents G[k], the origin og[k], shift and every job's at.  With reso the prior's map_reso, a prior whose
+ * keep[p].use applies is then cut per axis k, in float64, in this order:
+ *     k0 = clamp(trunc((keep.lo - og) / reso), 0, G)      k1 = clamp(trunc((keep.hi - og) / reso), 0, G)
+ *     new extent = k1 - k0      new origin = (k0 == 0) ? og : og + reso * (double)k0
+ *     cut_lo = k0, cut_hi = G - k1, shift -= k0, every job's at -= k0
+ * The clamp is done on the double, before the conversion, so a bound may be -inf / +inf: no cut on that side.  The result
+ * is, by definition, cells [k0[0]:k1[0], k0[1]:k1[1]] of the prior fxjps_absorb_prior_grow would leave.  A job's inside is
+ * the number of its rectangle's cells that lie in the window, outside the rest: those are dropped, as fxjps_absorb_prior
+ * drops cells.  changed counts the cells of the window whose non-zero test differs from the old byte at that place (0
+ * where the old prior has none); cells cut away are counted nowhere.  shift and at may be negative after the cut.
+ *   keep[p].use: FXJPS_KEEP_NONE -- prior p behaves exactly as under fxjps_absorb_prior_grow, the limit checked job after
+ * job; FXJPS_KEEP_ALWAYS -- cut on every call; FXJPS_KEEP_OVER_LIMIT -- the whole window (both axes) is applied if and only
+ * if G[k] > limit_wh[k] on some axis.  Under the latter two the per-job limit check is skipped (a grown extent must still
+ * fit int32, like every quotient), and after the cut an extent above limit_wh[k] is refused.  keep == NULL: all NONE, and
+ * then every byte and every field the two calls share equal fxjps_absorb_prior_grow's.
+ *   out[p]: fxjps_prior_grown_t's fields as the call leaves the prior; trimmed -- 1 if the window was applied, whatever it
+ * cut; grown_wh -- the extents the fold reached; cut_lo / cut_hi -- the cells cut off each side of them (a prior no job
+ * names: its extents as they are, nothing cut).
+ *   Further whole-call refusals (FXJPS_E_ARG, "prior p: ..." in fxjps_last_error, nothing queued or written): use outside
+ * 0 .. 2; NaN in a bound; lo > hi; a window with k1 <= k0 on an axis (it holds no cell of the grown prior); a window above
+ * the limit; keep[p].use != 0 for a prior no job names.  fxjps_slide_check: the same without a handle, as fxjps_grow_check.
+ *   The device side is fxjps_absorb_prior_grow's, word for word: one staged copy in (only the rows of each raw that hold
+ * the part of its rectangle inside the window; a job wholly outside stages nothing), ONE launch whatever n is, 16 counters
+ * back, one wait, on the handle's stream; every context writes into new buffers, which are swapped in with the extents
+ * only after every context has succeeded; any failure leaves every prior byte for byte as it was; a rank handle is
+ * refused; no slot, slot generation, stored result, resident grid or unnamed prior is touched; n == 0 returns FXJPS_OK with
+ * nothing named (a pure trim without jobs is not part of this, nor is decay by age). */
+#define FXJPS_KEEP_NONE       0   /* this prior behaves exactly as under fxjps_absorb_prior_grow */
+#define FXJPS_KEEP_ALWAYS     1   /* cut to the window on every call */
+#define FXJPS_KEEP_OVER_LIMIT 2   /* cut only if the grown extents exceed limit_wh on some axis */
+typedef struct fxjps_prior_keep {
+    int32_t use;          /* FXJPS_KEEP_* */
+    int32_t reserved_;
+    double lo[2], hi[2];  /* the keep window, world metres; -inf / +inf: no cut on that side */
+} fxjps_prior_keep_t;
+typedef struct fxjps_prior_slid {
+    int32_t named;        /* 1: a job names this prior */
+    int32_t W, H;         /* extents after the call */
+    int32_t shift[2];     /* the cell of the prior as the call leaves it that old cell (0, 0) lies on; may be negative */
+    int32_t trimmed;      /* 1: the keep window was applied */
+    double origin[2];     /* the prior's world origin after the call */
+    int64_t changed;      /* cells of the window whose occupancy differs from the old byte at that place (none: 0) */
+    int32_t grown_wh[2];  /* the extents the fold reached */
+    int32_t cut_lo[2], cut_hi[2]; /* the cells cut off each side of them */
+} fxjps_prior_slid_t;
+int fxjps_absorb_prior_slide(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
+                             const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS]);
+int fxjps_slide_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
+                      const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS], char* msg,
+                      int32_t msg_len);
+int fxjps_prior_keep_size(void); /* sizeof(fxjps_prior_keep_t) as the library was built */
+int fxjps_prior_slid_size(void); /* sizeof(fxjps_prior_slid_t) as the library was built */
 /* fxjps_plan_batch_slots_csr for the tick after: the same arguments, refusals, outputs and per-query codes, and every
  * output byte for byte what that call would return for the same arguments on the slots as they are now; afterwards the
  * handle's resident paths are the full batch's, in query order (fxjps_last_cells, fxjps_waypoint_slots_batch and
