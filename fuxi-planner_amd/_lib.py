@@ -105,10 +105,10 @@ class PriorKeep(C.Structure):
 
 
 class PriorSlid(C.Structure):
-    """fxjps_prior_slid_t: what fxjps_absorb_prior_slide made of one prior map."""
-    _fields_ = [("named", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("shift", C.c_int32 * 2), ("trimmed", C.c_int32),
-                ("origin", C.c_double * 2), ("changed", C.c_int64), ("grown_wh", C.c_int32 * 2), ("cut_lo", C.c_int32 * 2),
-                ("cut_hi", C.c_int32 * 2)]
+    """fxjps_prior_slid_t: what fxjps_absorb_prior_slide made of one prior map: fxjps_prior_grown_t's fields, `trimmed`
+    where that one has its reserved word, then what was cut."""
+    _fields_ = [("trimmed", C.c_int32) if f[0] == "reserved_" else f for f in PriorGrown._fields_] + \
+        [("grown_wh", C.c_int32 * 2), ("cut_lo", C.c_int32 * 2), ("cut_hi", C.c_int32 * 2)]
 
 
 class SlotPublish(C.Structure):

@@ -4658,22 +4658,54 @@ int fxjps_check_paths_slots(fxjps_t* h, int64_t nq, const int64_t* offsets, cons
     return FXJPS_OK;
 }
 
-// ------------------------------------------------------------------ detected maps into the prior maps (DESIGN.md 3.20)
+// ------------------------------------------------------------------ detected maps into the prior maps (DESIGN.md 3.20 - 3.22)
+// fxjps_absorb_prior pastes into the priors as they are, fxjps_absorb_prior_grow into priors that grow to what the jobs
+// cover, fxjps_absorb_prior_slide cuts every grown prior to a keep window.  One per-job argument check, one staging rule
+// and one plan record serve all three; grow and slide share one fold, of which grow is the window that keeps everything.
 int fxjps_absorb_job_size(void) { return (int)sizeof(fxjps_absorb_job_t); }
+int fxjps_grow_job_size(void) { return (int)sizeof(fxjps_grow_job_t); }
+int fxjps_prior_grown_size(void) { return (int)sizeof(fxjps_prior_grown_t); }
+int fxjps_prior_keep_size(void) { return (int)sizeof(fxjps_prior_keep_t); }
+int fxjps_prior_slid_size(void) { return (int)sizeof(fxjps_prior_slid_t); }
 
+extern "C++" {  // (the helpers are templates over the job, table and out record types)
 namespace {
 static_assert(fx::ABSORB_JOBS_MAX == FXJPS_MAX_GRID_SLOTS && fx::ABSORB_PRIORS_MAX == FXJPS_MAX_PRIOR_MAPS, "the kernel's table holds every job and a box per prior");
 static_assert(fx::ABSORB_OVERWRITE == FXJPS_ABSORB_OVERWRITE && fx::ABSORB_OCCUPIED == FXJPS_ABSORB_OCCUPIED && fx::ABSORB_KNOWN == FXJPS_ABSORB_KNOWN,
               "the kernel's modes are the header's");
+static_assert(offsetof(fx::AbsorbTable, changed) == 0 && offsetof(fx::GrowTable, changed) == 0, "the counters come back from the head of the staged input");
 constexpr size_t ABSORB_IN_RAWS = (sizeof(fx::AbsorbTable) + 15) & ~(size_t)15;
+constexpr size_t GROW_IN_RAWS = (sizeof(fx::GrowTable) + 15) & ~(size_t)15;
+template <class Job> constexpr bool IS_GROW_JOB = std::is_same<Job, fxjps_grow_job_t>::value;  // (fxjps_absorb_job_t is its prefix, field by field)
 
-// What the host derives from one job before anything is queued: where the rectangle lies in its prior and which rows of
-// raw are staged -- the rows (layout 0: x, layout 1: y) that hold the rectangle, one contiguous piece of raw.
-struct AbsorbPlan {
-    long long d[2];         // the prior cell that rectangle cell (0, 0) lands on
-    long long c0[2], c1[2]; // the rectangle clipped to the prior, in prior cells: [c0, c1)
-    long long inside;
-    size_t raw_off, raw_bytes, in_off;  // the piece of raw, and where it lies in the staged input (a job that misses its prior stages nothing)
+// What the host derives from the jobs before anything is queued.  Per job: where the rectangle lies in its frame -- the
+// prior as it is (absorb), the grown prior (grow, slide) -- what of it lies inside the cells the call keeps, and which rows
+// of raw are staged: rows (layout 0: x, layout 1: y) that hold those cells, one contiguous piece of raw.  Per prior: the
+// union box of its jobs' kept cells and, from the fold, the grown extents, where the old prior's cell (0, 0) lies in them,
+// the origin, and the window [k0, k1) of the grown frame that the new prior holds.
+struct PriorPlan {
+    struct Job {
+        long long at[2];         // the frame's cell that rectangle cell (0, 0) lands on
+        long long c0[2], c1[2];  // the rectangle clipped to the kept cells of its frame: [c0, c1)
+        long long inside;        // how many those are; a job with none stages nothing and is left out of the kernel's table
+        size_t raw_off, raw_bytes, in_off;  // the piece of raw, and where it lies in the staged input
+        long long row0;          // the first staged row, counted in rows of the rectangle
+    };
+    struct Prior {
+        long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};  // the union box, in the jobs' frame
+        // the fold's:
+        bool named = false;
+        int first = -1;                  // the first job that names it: every later one has its ori_pre and map_reso
+        long long ext[2] = {0, 0};       // the grown extents, job after job
+        long long shift[2] = {0, 0};     // the sum of every job's at_pre
+        double op[2] = {0.0, 0.0};       // the grown frame's origin, job after job
+        long long k0[2] = {0, 0}, k1[2] = {0, 0};  // the window; 0 and ext unless a keep window was applied (trimmed)
+        bool trimmed = false;
+        double origin[2] = {0.0, 0.0};   // the window's origin
+    };
+    std::vector<Job> job;
+    Prior prior[FXJPS_MAX_PRIOR_MAPS];
+    size_t in_bytes = 0;
 };
 
 int absorb_refuse(char* msg, size_t len, const char* fmt, ...) {
@@ -4686,152 +4718,429 @@ int absorb_refuse(char* msg, size_t len, const char* fmt, ...) {
     return FXJPS_E_ARG;
 }
 
-// Everything fxjps_absorb_prior refuses except a rank handle, from the arguments and the priors' extents alone; the
-// placement is world_call's: float64, the reference's operations in the reference's order (st:212-214).  Writes nothing
-// unless every job passes; then plan (n records, may be nullptr), in_bytes and every job's inside / outside.
-int absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, AbsorbPlan* plan, size_t* in_bytes, char* msg, size_t len) {
+int head_check(bool no_jobs, int32_t n, const int32_t* prior_wh, int32_t mode, char* msg, size_t len) {
     if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return absorb_refuse(msg, len, "job 0: n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
+    if (n > 0 && no_jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
     if (!prior_wh) return absorb_refuse(msg, len, "job 0: NULL prior extents");
     if (mode < 0 || mode > 2) return absorb_refuse(msg, len, "job 0: mode %d is not FXJPS_ABSORB_OVERWRITE, _OCCUPIED or _KNOWN", (int)mode);
-    std::vector<AbsorbPlan> own;
-    if (!plan) {
-        own.resize((size_t)n);
-        plan = own.data();
-    }
-    size_t total = ABSORB_IN_RAWS;
-    for (int j = 0; j < n; j++) {
-        const fxjps_absorb_job_t& a = jobs[j];
-        if (!a.raw) return absorb_refuse(msg, len, "job %d: NULL raw", j);
-        if (a.layout != 0 && a.layout != 1) return absorb_refuse(msg, len, "job %d: layout %d is not 0 or 1", j, (int)a.layout);
-        if (a.W0 < 1 || a.H0 < 1 || a.W0 > 8190 || a.H0 > 8190)
-            return absorb_refuse(msg, len, "job %d: bad extents (W0 %d, H0 %d): raw must be 1..8190 cells a side", j, (int)a.W0, (int)a.H0);
-        const long long ext[2] = {a.W0, a.H0};
-        for (int k = 0; k < 2; k++)
-            if (a.win[k] < 1 || a.lo[k] < 0 || (long long)a.lo[k] + a.win[k] > ext[k])
-                return absorb_refuse(msg, len, "job %d: axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %lld cells", j, k, (int)a.lo[k],
-                                     (int)a.win[k], ext[k]);
-        if (a.prior < 0 || a.prior >= FXJPS_MAX_PRIOR_MAPS) return absorb_refuse(msg, len, "job %d: prior %d is not in 0 .. %d", j, (int)a.prior, FXJPS_MAX_PRIOR_MAPS - 1);
-        const long long l[2] = {prior_wh[2 * a.prior], prior_wh[2 * a.prior + 1]};
-        if (l[0] < 1 || l[1] < 1) return absorb_refuse(msg, len, "job %d: prior %d is not set", j, (int)a.prior);
-        const double reso = a.map_reso;
-        if (!std::isfinite(reso) || !(reso > 0.0)) return absorb_refuse(msg, len, "job %d: map_reso %g must be finite and > 0", j, reso);
-        AbsorbPlan& p = plan[j];
-        p = AbsorbPlan{};
-        p.inside = 1;
-        for (int k = 0; k < 2; k++) {
-            if (!std::isfinite(a.map_o[k]) || !std::isfinite(a.ori_pre[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_o / ori_pre", j);
-            const double o1 = std::min(a.map_o[k], a.ori_pre[k]);  // st:212
-            long long at_raw, at_pre;
-            if (!trunc_i32((a.map_o[k] - o1) / reso, at_raw) || !trunc_i32((a.ori_pre[k] - o1) / reso, at_pre))  // st:213-214
-                return absorb_refuse(msg, len, "job %d: a placement index is outside int32", j);
-            p.d[k] = at_raw - at_pre;
-            p.c0[k] = std::max(p.d[k], 0ll);
-            p.c1[k] = std::min(p.d[k] + (long long)a.win[k], l[k]);
-            p.inside *= std::max(p.c1[k] - p.c0[k], 0ll);
-        }
-        if (p.inside > 0) {
-            const size_t row = (size_t)(a.layout ? a.W0 : a.H0), k = a.layout ? 1 : 0;
-            p.raw_off = (size_t)a.lo[k] * row;
-            p.raw_bytes = (size_t)a.win[k] * row;
-            p.in_off = total;
-            total += (p.raw_bytes + 15) & ~(size_t)15;
-            if (total > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
-        }
-    }
-    for (int j = 0; j < n; j++) {
-        jobs[j].inside = plan[j].inside;
-        jobs[j].outside = (long long)jobs[j].win[0] * jobs[j].win[1] - plan[j].inside;
-    }
-    if (in_bytes) *in_bytes = total;
     return FXJPS_OK;
 }
 
-// One context's part of fxjps_absorb_prior: ONE copy in, ONE launch, one copy back and one wait, whatever n is.  The
-// counters are left in d.h_absorb_out.
-int absorb_on(fxjps* h, DevCtx& d, const fxjps_absorb_job_t* jobs, int n, int mode, const std::vector<AbsorbPlan>& plan, size_t in_bytes) {
+// The argument checks of one job, for all three calls.
+template <class Job> int job_check(const Job& a, int j, const int32_t* prior_wh, char* msg, size_t len) {
+    if (!a.raw) return absorb_refuse(msg, len, "job %d: NULL raw", j);
+    if (a.layout != 0 && a.layout != 1) return absorb_refuse(msg, len, "job %d: layout %d is not 0 or 1", j, (int)a.layout);
+    if (a.W0 < 1 || a.H0 < 1 || a.W0 > 8190 || a.H0 > 8190)
+        return absorb_refuse(msg, len, "job %d: bad extents (W0 %d, H0 %d): raw must be 1..8190 cells a side", j, (int)a.W0, (int)a.H0);
+    const long long ext[2] = {a.W0, a.H0};
+    for (int k = 0; k < 2; k++)
+        if (a.win[k] < 1 || a.lo[k] < 0 || (long long)a.lo[k] + a.win[k] > ext[k])
+            return absorb_refuse(msg, len, "job %d: axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %lld cells", j, k, (int)a.lo[k],
+                                 (int)a.win[k], ext[k]);
+    if (a.prior < 0 || a.prior >= FXJPS_MAX_PRIOR_MAPS) return absorb_refuse(msg, len, "job %d: prior %d is not in 0 .. %d", j, (int)a.prior, FXJPS_MAX_PRIOR_MAPS - 1);
+    if (prior_wh[2 * a.prior] < 1 || prior_wh[2 * a.prior + 1] < 1) return absorb_refuse(msg, len, "job %d: prior %d is not set", j, (int)a.prior);
+    if (!std::isfinite(a.map_reso) || !(a.map_reso > 0.0)) return absorb_refuse(msg, len, "job %d: map_reso %g must be finite and > 0", j, a.map_reso);
+    for (int k = 0; k < 2; k++) {
+        if (!std::isfinite(a.map_o[k]) || !std::isfinite(a.ori_pre[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_o / ori_pre", j);
+        if constexpr (IS_GROW_JOB<Job>)
+            if (!std::isfinite(a.map_t[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_t", j);
+    }
+    return FXJPS_OK;
+}
+
+// The rectangle of job a, with cell (0, 0) on q.at, clipped to the cells [w0, w1) of its frame; P's union box takes what
+// is left.  -> whether any cell is.
+template <class Job> bool clip(const Job& a, PriorPlan::Job& q, PriorPlan::Prior& P, const long long w0[2], const long long w1[2]) {
+    for (int k = 0; k < 2; k++) {
+        q.c0[k] = std::max(q.at[k], w0[k]);
+        q.c1[k] = std::min(q.at[k] + (long long)a.win[k], w1[k]);
+    }
+    q.inside = std::max(q.c1[0] - q.c0[0], 0ll) * std::max(q.c1[1] - q.c0[1], 0ll);
+    if (q.inside > 0)
+        for (int k = 0; k < 2; k++) {
+            P.lo[k] = std::min(P.lo[k], q.c0[k]);
+            P.hi[k] = std::max(P.hi[k], q.c1[k]);
+        }
+    return q.inside > 0;
+}
+
+// `rows` rows of job j's rectangle from row0 on go into the staged input, behind the `total` bytes that are there.
+template <class Job> int stage(const Job& a, int j, PriorPlan::Job& q, long long row0, long long rows, size_t& total, char* msg, size_t len) {
+    const size_t row = (size_t)(a.layout ? a.W0 : a.H0);
+    q.row0 = row0;
+    q.raw_off = (size_t)(a.lo[a.layout ? 1 : 0] + row0) * row;
+    q.raw_bytes = (size_t)rows * row;
+    q.in_off = total;
+    total += (q.raw_bytes + 15) & ~(size_t)15;
+    if (total > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
+    return FXJPS_OK;
+}
+
+// What a passed check tells the caller of every job: its cells kept and dropped and, for grow and slide, the cell of the
+// prior AS THE CALL LEAVES IT that rectangle cell (0, 0) lies on.
+template <class Job> void write_jobs(Job* jobs, int n, const PriorPlan& plan) {
+    for (int j = 0; j < n; j++) {
+        const PriorPlan::Job& q = plan.job[(size_t)j];
+        jobs[j].inside = q.inside;
+        jobs[j].outside = (long long)jobs[j].win[0] * jobs[j].win[1] - q.inside;
+        if constexpr (IS_GROW_JOB<Job>)
+            for (int k = 0; k < 2; k++) jobs[j].at[k] = (int32_t)(q.at[k] - plan.prior[jobs[j].prior].k0[k]);
+    }
+}
+
+// Everything fxjps_absorb_prior refuses except a rank handle, from the arguments and the priors' extents alone.  Every job
+// is placed against the prior as it is with ITS ori_pre and clipped to it; the placement is world_call's: float64, the
+// reference's operations in the reference's order (st:212-214).  (Not the fold below, which moves the origin job after
+// job: that is not bit-equal in float64.)  Writes nothing unless every job passes; then plan and every job's inside /
+// outside.
+int absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, PriorPlan& plan, char* msg, size_t len) {
+    if (int rc = head_check(!jobs, n, prior_wh, mode, msg, len)) return rc;
+    plan = PriorPlan{};
+    plan.job.resize((size_t)n);
+    plan.in_bytes = ABSORB_IN_RAWS;
+    const long long none[2] = {0, 0};
+    for (int j = 0; j < n; j++) {
+        const fxjps_absorb_job_t& a = jobs[j];
+        if (int rc = job_check(a, j, prior_wh, msg, len)) return rc;
+        PriorPlan::Job& q = plan.job[(size_t)j];
+        for (int k = 0; k < 2; k++) {
+            const double o1 = std::min(a.map_o[k], a.ori_pre[k]);  // st:212
+            long long at_raw, at_pre;
+            if (!trunc_i32((a.map_o[k] - o1) / a.map_reso, at_raw) || !trunc_i32((a.ori_pre[k] - o1) / a.map_reso, at_pre))  // st:213-214
+                return absorb_refuse(msg, len, "job %d: a placement index is outside int32", j);
+            q.at[k] = at_raw - at_pre;
+        }
+        const long long l[2] = {prior_wh[2 * a.prior], prior_wh[2 * a.prior + 1]};
+        if (clip(a, q, plan.prior[a.prior], none, l))  // (the rectangle's rows whole: the kernel clips)
+            if (int rc = stage(a, j, q, 0, a.win[a.layout ? 1 : 0], plan.in_bytes, msg, len)) return rc;
+    }
+    write_jobs(jobs, n, plan);
+    return FXJPS_OK;
+}
+
+// The geometry of fxjps_absorb_prior_grow and fxjps_absorb_prior_slide and everything they refuse but a rank handle and a
+// NULL out, from the arguments and the priors' extents alone; reads the jobs and writes only plan.  The fold is float64,
+// the reference's operations in the reference's order (st:187, :212-216), job after job on the extents and origin the job
+// before left.  Then per prior the window: the whole grown frame, or -- keep[p].use says when -- the keep window, by one
+// division, one truncation and a clamp on the double per bound.  A prior that a keep window may cut is not held to the
+// limit job after job, only to int32; its window is.  Then per job what of its rectangle lies inside the window: the rows
+// to stage and the union box.  keep == NULL: no prior has a window, which is fxjps_absorb_prior_grow.
+int prior_fold(const fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, const fxjps_prior_keep_t* keep,
+               PriorPlan& plan, char* msg, size_t len) {
+    const auto use = [keep](int p) -> int { return keep ? keep[p].use : FXJPS_KEEP_NONE; };
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        if (use(p) < FXJPS_KEEP_NONE || use(p) > FXJPS_KEEP_OVER_LIMIT)
+            return absorb_refuse(msg, len, "prior %d: keep.use %d is not FXJPS_KEEP_NONE, _ALWAYS or _OVER_LIMIT", p, use(p));
+        if (use(p) == FXJPS_KEEP_NONE) continue;
+        for (int k = 0; k < 2; k++) {
+            if (std::isnan(keep[p].lo[k]) || std::isnan(keep[p].hi[k])) return absorb_refuse(msg, len, "prior %d: axis %d: NaN in the keep window", p, k);
+            if (keep[p].lo[k] > keep[p].hi[k])
+                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window's lo %g is above its hi %g", p, k, keep[p].lo[k], keep[p].hi[k]);
+        }
+    }
+    if (int rc = head_check(!jobs, n, prior_wh, mode, msg, len)) return rc;
+    long long limit[2] = {8190, 8190};
+    if (limit_wh)
+        for (int k = 0; k < 2; k++) {
+            limit[k] = limit_wh[k];
+            if (limit[k] < 1 || limit[k] > 8190) return absorb_refuse(msg, len, "job 0: axis %d: the limit %lld is not in 1 .. 8190", k, limit[k]);
+        }
+    plan = PriorPlan{};
+    plan.job.resize((size_t)n);
+    plan.in_bytes = GROW_IN_RAWS;
+    for (int j = 0; j < n; j++) {
+        const fxjps_grow_job_t& a = jobs[j];
+        if (int rc = job_check(a, j, prior_wh, msg, len)) return rc;
+        PriorPlan::Prior& P = plan.prior[a.prior];
+        if (!P.named) {
+            P.named = true;
+            P.first = j;
+            for (int k = 0; k < 2; k++) {
+                P.ext[k] = prior_wh[2 * a.prior + k];
+                P.op[k] = a.ori_pre[k];
+            }
+        } else {
+            const fxjps_grow_job_t& f = jobs[P.first];
+            if (memcmp(f.ori_pre, a.ori_pre, sizeof(a.ori_pre)) != 0 || memcmp(&f.map_reso, &a.map_reso, sizeof(double)) != 0)
+                return absorb_refuse(msg, len, "job %d: ori_pre / map_reso are not bit-equal to those of job %d, which names prior %d as well", j, P.first,
+                                     (int)a.prior);
+        }
+        const double reso = a.map_reso;
+        PriorPlan::Job& q = plan.job[(size_t)j];
+        long long at_pre[2];
+        for (int k = 0; k < 2; k++) {
+            const double o = a.map_o[k], op = P.op[k];
+            const double o1 = std::min(o, op);                       // st:212
+            const double t_pre = op + reso * (double)P.ext[k];       // st:187, with the current extents
+            long long at_raw, ref;
+            if (!trunc_i32((o - o1) / reso, at_raw) || !trunc_i32((op - o1) / reso, at_pre[k]) ||  // st:213-214
+                !trunc_i32((std::max(t_pre, a.map_t[k]) - o1) / reso, ref))                        // st:215-216
+                return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
+            const long long size = std::max(ref, std::max(at_pre[k] + P.ext[k], at_raw + (long long)a.win[k]));
+            if (use(a.prior) != FXJPS_KEEP_NONE) {
+                if (size > INT32_MAX) return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
+            } else if (size > limit[k])
+                return absorb_refuse(msg, len, "job %d: axis %d: prior %d would grow to %lld cells, above the limit of %lld", j, k, (int)a.prior, size, limit[k]);
+            q.at[k] = at_raw;
+            P.ext[k] = size;
+            P.op[k] = o1;
+            P.shift[k] += at_pre[k];
+        }
+        for (int i = 0; i < j; i++)  // (the earlier rectangles on this prior move with the old prior)
+            if (jobs[i].prior == a.prior)
+                for (int k = 0; k < 2; k++) plan.job[(size_t)i].at[k] += at_pre[k];
+    }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        PriorPlan::Prior& P = plan.prior[p];
+        if (!P.named) {
+            if (use(p) != FXJPS_KEEP_NONE) return absorb_refuse(msg, len, "prior %d: a keep window for a prior that no job names", p);
+            continue;
+        }
+        for (int k = 0; k < 2; k++) {
+            P.k1[k] = P.ext[k];
+            P.origin[k] = P.op[k];
+        }
+        if (use(p) == FXJPS_KEEP_NONE || (use(p) == FXJPS_KEEP_OVER_LIMIT && P.ext[0] <= limit[0] && P.ext[1] <= limit[1])) continue;
+        P.trimmed = true;
+        const double reso = jobs[P.first].map_reso;
+        for (int k = 0; k < 2; k++) {
+            const double G = (double)P.ext[k];
+            const double a = std::trunc((keep[p].lo[k] - P.op[k]) / reso), b = std::trunc((keep[p].hi[k] - P.op[k]) / reso);
+            P.k0[k] = (long long)(a < 0.0 ? 0.0 : a > G ? G : a);  // (clamped as a double: a bound may be infinite)
+            P.k1[k] = (long long)(b < 0.0 ? 0.0 : b > G ? G : b);
+            if (P.k1[k] <= P.k0[k])
+                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window holds no cell of the grown prior (cells %lld .. %lld of %lld)", p, k, P.k0[k],
+                                     P.k1[k], P.ext[k]);
+            if (P.k1[k] - P.k0[k] > limit[k])
+                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window of %lld cells is above the limit of %lld", p, k, P.k1[k] - P.k0[k], limit[k]);
+            if (P.k0[k] != 0) P.origin[k] = P.op[k] + reso * (double)P.k0[k];
+        }
+    }
+    for (int j = 0; j < n; j++) {  // (of a rectangle only the rows inside the window are staged; all of them where nothing is cut)
+        const fxjps_grow_job_t& a = jobs[j];
+        PriorPlan::Prior& P = plan.prior[a.prior];
+        PriorPlan::Job& q = plan.job[(size_t)j];
+        const int r = a.layout ? 1 : 0;
+        if (clip(a, q, P, P.k0, P.k1))
+            if (int rc = stage(a, j, q, q.c0[r] - q.at[r], q.c1[r] - q.c0[r], plan.in_bytes, msg, len)) return rc;
+    }
+    for (PriorPlan::Prior& P : plan.prior)
+        if (P.lo[0] > P.hi[0]) P.lo[0] = P.lo[1] = P.hi[0] = P.hi[1] = 0;  // (no rectangle reaches the window: an empty box)
+    return FXJPS_OK;
+}
+
+// fxjps_grow_check (Out = fxjps_prior_grown_t, keep NULL) and fxjps_slide_check (fxjps_prior_slid_t): the fold, and once it
+// has passed -- nothing is written before -- every job's inside / outside / at and every field of out but `changed`.  The
+// slid record begins as the grown record does.
+template <class Out> int fold_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
+                                    const fxjps_prior_keep_t* keep, Out* out, PriorPlan& plan, char* msg, size_t len) {
+    constexpr bool SLID = std::is_same<Out, fxjps_prior_slid_t>::value;
+    // (a NULL out: fxjps_slide_check refuses it before anything else, fxjps_grow_check behind the extents and before the mode)
+    if (!out && (SLID || !head_check(!jobs, n, prior_wh, 0, nullptr, 0))) return absorb_refuse(msg, len, "job 0: NULL out");
+    if (int rc = prior_fold(jobs, n, mode, prior_wh, limit_wh, keep, plan, msg, len)) return rc;
+    write_jobs(jobs, n, plan);
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        const PriorPlan::Prior& P = plan.prior[p];
+        Out& g = out[p];
+        g.named = P.named ? 1 : 0;
+        for (int k = 0; k < 2; k++) {
+            const int32_t as_is = prior_wh[2 * p + k];
+            (k ? g.H : g.W) = P.named ? (int32_t)(P.k1[k] - P.k0[k]) : as_is;
+            g.shift[k] = (int32_t)(P.shift[k] - P.k0[k]);
+            g.origin[k] = P.origin[k];
+            if constexpr (SLID) {
+                g.grown_wh[k] = P.named ? (int32_t)P.ext[k] : as_is;
+                g.cut_lo[k] = (int32_t)P.k0[k];
+                g.cut_hi[k] = (int32_t)(P.ext[k] - P.k1[k]);
+            }
+        }
+        if constexpr (SLID)
+            g.trimmed = P.trimmed ? 1 : 0;
+        else
+            g.reserved_ = 0;
+    }
+    return FXJPS_OK;
+}
+
+// ---- one context's part of a call: ONE copy in, ONE launch, one copy back and one wait, whatever n is.  The staged input
+// begins with the kernel's table; the counters at its head are left in d.h_absorb_out.
+template <class Table> int table_begin(fxjps* h, DevCtx& d, size_t in_bytes, int mode, Table*& T) {
     HIPCHK(h, hipSetDevice(d.dev));
     HIPCHK(h, d.h_absorb_in.ensure(in_bytes));
     HIPCHK(h, d.d_absorb_in.ensure(in_bytes));
     HIPCHK(h, d.h_absorb_out.ensure(FXJPS_MAX_PRIOR_MAPS));
-    fx::AbsorbTable& T = *reinterpret_cast<fx::AbsorbTable*>(d.h_absorb_in.p);
-    memset(&T, 0, sizeof(T));
-    T.mode = mode;
-    int nb = 0, nj = 0;
-    uint32_t at = 0;
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
-        fx::AbsorbBoxDev B{};
-        long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};
-        B.job0 = nj;
-        for (int j = 0; j < n; j++) {
-            const fxjps_absorb_job_t& a = jobs[j];
-            const AbsorbPlan& q = plan[(size_t)j];
-            if (a.prior != p || q.inside <= 0) continue;
-            fx::AbsorbJobDev& J = T.job[nj++];
-            J.at = d.d_absorb_in.p + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]);
-            J.stride = a.layout ? a.W0 : a.H0;
-            J.layout = a.layout;
-            J.x0 = (int32_t)q.d[0];
-            J.y0 = (int32_t)q.d[1];
-            J.w = a.win[0];
-            J.h = a.win[1];
-            memcpy(d.h_absorb_in.p + q.in_off, static_cast<const uint8_t*>(a.raw) + q.raw_off, q.raw_bytes);
-            for (int k = 0; k < 2; k++) {
-                lo[k] = std::min(lo[k], q.c0[k]);
-                hi[k] = std::max(hi[k], q.c1[k]);
-            }
-        }
-        B.njobs = nj - B.job0;
-        if (B.njobs == 0) continue;
-        const DevCtx::PriorBuf& pr = d.priors[(size_t)p];
-        B.occ = pr.occ.p;
-        B.pH = pr.H;
-        B.x0 = (int32_t)lo[0];
-        B.y0 = (int32_t)lo[1];
-        B.w = (int32_t)(hi[0] - lo[0]);
-        B.h = (int32_t)(hi[1] - lo[1]);
-        B.prior = p;
-        T.first[nb] = at;
-        T.box[nb++] = B;
-        at += (uint32_t)(((long long)B.w * B.h + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+    T = reinterpret_cast<Table*>(d.h_absorb_in.p);
+    memset(T, 0, sizeof(Table));
+    T->mode = mode;
+    return FXJPS_OK;
+}
+
+// The jobs of prior p that stage anything, in job order, as job[nj ...], and their rows into the staged input.  -> nj
+template <class Job> int table_jobs(DevCtx& d, fx::AbsorbJobDev* job, int nj, const Job* jobs, int n, int p, const PriorPlan& plan) {
+    for (int j = 0; j < n; j++) {
+        const Job& a = jobs[j];
+        const PriorPlan::Job& q = plan.job[(size_t)j];
+        if (a.prior != p || q.inside <= 0) continue;
+        fx::AbsorbJobDev& J = job[nj++];
+        J.stride = a.layout ? a.W0 : a.H0;
+        // (cell (i, j) of the rectangle is read at row * stride + column from here; rows below row0 are not staged and not
+        // read, so the address of row 0 is only ever an operand)
+        J.at = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d.d_absorb_in.p) + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]) -
+                                                (size_t)q.row0 * (size_t)J.stride);
+        J.layout = a.layout;
+        J.x0 = (int32_t)q.at[0];
+        J.y0 = (int32_t)q.at[1];
+        J.w = a.win[0];
+        J.h = a.win[1];
+        memcpy(d.h_absorb_in.p + q.in_off, static_cast<const uint8_t*>(a.raw) + q.raw_off, q.raw_bytes);
     }
-    T.first[nb] = at;
-    T.nbox = nb;
-    if (nb == 0) {  // (no rectangle meets its prior: nothing to queue)
-        memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
-        return FXJPS_OK;
-    }
+    return nj;
+}
+
+template <class Table> int table_run(fxjps* h, DevCtx& d, size_t in_bytes, uint32_t blocks, void (*kernel)(Table*)) {
+    memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
+    if (blocks == 0) return FXJPS_OK;  // (no box: nothing to queue)
     HIPCHK(h, hipMemcpyAsync(d.d_absorb_in.p, d.h_absorb_in.p, in_bytes, hipMemcpyHostToDevice, d.stream));
-    hipLaunchKernelGGL(fx::k_prior_absorb, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::AbsorbTable*>(d.d_absorb_in.p));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, d.stream, reinterpret_cast<Table*>(d.d_absorb_in.p));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(d.h_absorb_out.p, d.d_absorb_in.p, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(h, hipStreamSynchronize(d.stream));
     return FXJPS_OK;
 }
+
+// fxjps_absorb_prior on one context: a box per prior that a rectangle meets, over the union of its clipped rectangles.
+int absorb_on(fxjps* h, DevCtx& d, const fxjps_absorb_job_t* jobs, int n, int mode, const PriorPlan& plan) {
+    fx::AbsorbTable* T;
+    if (int rc = table_begin(h, d, plan.in_bytes, mode, T)) return rc;
+    int nb = 0, nj = 0;
+    uint32_t at = 0;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
+        const PriorPlan::Prior& P = plan.prior[p];
+        fx::AbsorbBoxDev B{};
+        B.job0 = nj;
+        nj = table_jobs(d, T->job, nj, jobs, n, p, plan);
+        B.njobs = nj - B.job0;
+        if (B.njobs == 0) continue;
+        const DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+        B.occ = pr.occ.p;
+        B.pH = pr.H;
+        B.x0 = (int32_t)P.lo[0];
+        B.y0 = (int32_t)P.lo[1];
+        B.w = (int32_t)(P.hi[0] - P.lo[0]);
+        B.h = (int32_t)(P.hi[1] - P.lo[1]);
+        B.prior = p;
+        T->first[nb] = at;
+        T->box[nb++] = B;
+        at += (uint32_t)(((long long)B.w * B.h + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+    }
+    T->first[nb] = at;
+    T->nbox = nb;
+    return table_run(h, d, plan.in_bytes, at, fx::k_prior_absorb);
+}
+
+// fxjps_absorb_prior_grow and (window) fxjps_absorb_prior_slide on one context: a box per named prior, over the cells
+// [k0, k1) of its grown frame, written into the spare buffer (PriorBuf::next).  Nothing the world-frame calls read is
+// touched.  The job records and the union box stay in the grown frame; the launch is k_prior_grow<window>.
+int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, const PriorPlan& plan, bool window) {
+    fx::GrowTable* T;
+    if (int rc = table_begin(h, d, plan.in_bytes, mode, T)) return rc;
+    int nb = 0, nj = 0;
+    uint32_t at = 0;
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
+        const PriorPlan::Prior& P = plan.prior[p];
+        if (!P.named) continue;
+        DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+        const long long nW = P.k1[0] - P.k0[0], nH = P.k1[1] - P.k0[1];
+        HIPCHK(h, pr.next.ensure((size_t)(nW * nH)));
+        fx::GrowBoxDev B{};
+        B.job0 = nj;
+        nj = table_jobs(d, T->job, nj, jobs, n, p, plan);
+        B.njobs = nj - B.job0;
+        B.old = pr.occ.p;
+        B.out = pr.next.p;
+        B.oW = pr.W;
+        B.oH = pr.H;
+        B.sx = (int32_t)P.shift[0];
+        B.sy = (int32_t)P.shift[1];
+        B.nW = (int32_t)nW;
+        B.nH = (int32_t)nH;
+        B.x0 = (int32_t)P.lo[0];
+        B.y0 = (int32_t)P.lo[1];
+        B.w = (int32_t)(P.hi[0] - P.lo[0]);
+        B.h = (int32_t)(P.hi[1] - P.lo[1]);
+        B.prior = p;
+        T->k0[nb][0] = (int32_t)P.k0[0];  // (0 unless a window was applied; k_prior_grow<false> does not read it)
+        T->k0[nb][1] = (int32_t)P.k0[1];
+        T->first[nb] = at;
+        T->box[nb++] = B;
+        at += (uint32_t)((nW * nH + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
+    }
+    T->first[nb] = at;
+    T->nbox = nb;
+    return window ? table_run(h, d, plan.in_bytes, at, fx::k_prior_grow<true>) : table_run(h, d, plan.in_bytes, at, fx::k_prior_grow<false>);
+}
+
+// The priors' extents as the checks take them: context 0's (every context holds the same).
+void prior_extents(const fxjps* h, int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS]) {
+    const DevCtx& d0 = h->devs[0];
+    for (size_t p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
+        prior_wh[2 * p] = p < d0.priors.size() ? d0.priors[p].W : 0;
+        prior_wh[2 * p + 1] = p < d0.priors.size() ? d0.priors[p].H : 0;
+    }
+}
+
+// fxjps_absorb_prior_grow and fxjps_absorb_prior_slide (Out = fxjps_prior_slid_t: the window kernel).  Every context writes
+// its own new copies from the caller's raws (host copies, no collective); the priors that the world-frame calls read are
+// swapped only when all of them have succeeded, so a failure leaves every context as it was.
+template <class Out> int grow_call(fxjps* h, const char* what, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
+                                   const fxjps_prior_keep_t* keep, Out* out) {
+    constexpr bool WINDOW = std::is_same<Out, fxjps_prior_slid_t>::value;
+    if (!h) return FXJPS_E_ARG;
+    if (int rr = refuse_on_rank_handle(h, what)) return rr;
+    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS];
+    prior_extents(h, prior_wh);
+    PriorPlan plan;
+    char why[400] = "";
+    if (fold_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = 0;
+    if (n == 0) return FXJPS_OK;
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grow_on(h, h->devs[r], jobs, n, mode, plan, WINDOW); });
+    if (rc) {
+        drain_all(h);
+        (void)hipGetLastError();
+        return rc;
+    }
+    for (auto& d : h->devs)
+        for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++)
+            if (plan.prior[p].named) {
+                DevCtx::PriorBuf& pr = d.priors[(size_t)p];
+                std::swap(pr.occ, pr.next);  // (the old buffer is the next call's spare)
+                pr.W = (int)(plan.prior[p].k1[0] - plan.prior[p].k0[0]);
+                pr.H = (int)(plan.prior[p].k1[1] - plan.prior[p].k0[1]);
+            }
+    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
+    return FXJPS_OK;
+}
 }  // namespace
+}  // extern "C++"
 
 int fxjps_absorb_check(fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, char* msg, int32_t msg_len) {
     if (msg && msg_len > 0) msg[0] = 0;
-    return absorb_check(jobs, n, mode, prior_wh, nullptr, nullptr, msg, msg_len > 0 ? (size_t)msg_len : 0);
+    PriorPlan plan;
+    return absorb_check(jobs, n, mode, prior_wh, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
 }
 
 int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t mode, int64_t out_changed[FXJPS_MAX_PRIOR_MAPS]) {
-    static_assert(offsetof(fx::AbsorbTable, changed) == 0, "the counters come back from the head of the staged input");
     if (!h) return FXJPS_E_ARG;
     if (!out_changed) return fail(h, FXJPS_E_ARG, "job 0: NULL out_changed");
     if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior")) return rr;
-    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
-    const DevCtx& d0 = h->devs[0];
-    for (size_t p = 0; p < d0.priors.size(); p++) {
-        prior_wh[2 * p] = d0.priors[p].W;
-        prior_wh[2 * p + 1] = d0.priors[p].H;
-    }
-    std::vector<AbsorbPlan> plan((size_t)std::max(n, 0));
-    size_t in_bytes = 0;
+    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS];
+    prior_extents(h, prior_wh);
+    PriorPlan plan;
     char why[400] = "";
-    if (absorb_check(jobs, n, mode, prior_wh, plan.data(), &in_bytes, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
-    // every context pastes into its own copy of the priors from the caller's raws (host copies, no collective)
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return absorb_on(h, h->devs[r], jobs, n, mode, plan, in_bytes); });
+    if (absorb_check(jobs, n, mode, prior_wh, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
+    // every context pastes into its own copy of the priors, in place, from the caller's raws (host copies, no collective)
+    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return absorb_on(h, h->devs[r], jobs, n, mode, plan); });
     if (rc) {
         drain_all(h);
         for (int j = 0; j < n; j++)  // (a prior whose paste failed on one context is released on all of them, as fxjps_set_prior_map does)
@@ -4848,430 +5157,28 @@ int fxjps_absorb_prior(fxjps_t* h, fxjps_absorb_job_t* jobs, int32_t n, int32_t 
     return FXJPS_OK;
 }
 
-// ------------------------------------------------------------------ ... into prior maps that grow
-int fxjps_grow_job_size(void) { return (int)sizeof(fxjps_grow_job_t); }
-int fxjps_prior_grown_size(void) { return (int)sizeof(fxjps_prior_grown_t); }
-
-namespace {
-constexpr size_t GROW_IN_RAWS = (sizeof(fx::GrowTable) + 15) & ~(size_t)15;
-
-// What the host folds from the jobs before anything is queued.  Per job: where the rectangle lies in the prior as the
-// call leaves it, and which rows of raw are staged (as AbsorbPlan).  Per prior: the grown extents, where the old prior's
-// cell (0, 0) lies in them, the new origin and the union box of its rectangles.
-struct GrowPlan {
-    struct Job {
-        long long at[2];
-        size_t raw_off, raw_bytes, in_off;
-        long long row0 = 0;  // fxjps_absorb_prior_slide: the first staged row, counted in rows of the rectangle; staged: any at all
-        bool staged = true;
-    };
-    struct Prior {
-        bool named = false;
-        int first = -1;                  // the first job that names it: every later one has its ori_pre and map_reso
-        long long ext[2] = {0, 0};       // the extents, job after job
-        long long shift[2] = {0, 0};     // the sum of every job's at_pre
-        double op[2] = {0.0, 0.0};       // the origin, job after job
-        long long lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {0, 0};  // the union box, in the final frame
-        // fxjps_absorb_prior_slide: the cells [k0, k1) of the grown frame that the new prior holds (grow: 0 and ext), whether a
-        // keep window was applied, and the new origin; ext, shift, lo / hi and every job's at stay in the GROWN frame
-        long long k0[2] = {0, 0}, k1[2] = {0, 0};
-        bool trimmed = false;
-        double origin[2] = {0.0, 0.0};
-    };
-    std::vector<Job> job;
-    Prior prior[FXJPS_MAX_PRIOR_MAPS];
-    size_t in_bytes = GROW_IN_RAWS;
-};
-
-// Everything fxjps_absorb_prior_grow refuses except a rank handle, and the whole geometry, from the arguments and the
-// priors' extents alone: float64, the reference's operations in the reference's order (st:187, :212-216), job after job
-// on the extents and origin the job before left.  Writes nothing unless every job passes; then plan, every job's inside /
-// outside / at and every field of out but `changed`.  (The per-job argument checks are absorb_check's, word for word.)
-// keep (fxjps_absorb_prior_slide; NULL otherwise): a prior whose keep[p].use is not FXJPS_KEEP_NONE is cut to a window afterwards,
-// so its sides are not held to the limit job after job, only to int32; limit_out, if given, receives the limits in force.
-int grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, fxjps_prior_grown_t* out, GrowPlan& plan,
-               char* msg, size_t len, const fxjps_prior_keep_t* keep = nullptr, long long* limit_out = nullptr) {
-    if (n < 0 || n > FXJPS_MAX_GRID_SLOTS) return absorb_refuse(msg, len, "job 0: n = %d jobs: must be 0 .. %d", (int)n, FXJPS_MAX_GRID_SLOTS);
-    if (n > 0 && !jobs) return absorb_refuse(msg, len, "job 0: NULL jobs");
-    if (!prior_wh) return absorb_refuse(msg, len, "job 0: NULL prior extents");
-    if (!out) return absorb_refuse(msg, len, "job 0: NULL out");
-    if (mode < 0 || mode > 2) return absorb_refuse(msg, len, "job 0: mode %d is not FXJPS_ABSORB_OVERWRITE, _OCCUPIED or _KNOWN", (int)mode);
-    long long limit[2] = {8190, 8190};
-    if (limit_wh)
-        for (int k = 0; k < 2; k++) {
-            limit[k] = limit_wh[k];
-            if (limit[k] < 1 || limit[k] > 8190) return absorb_refuse(msg, len, "job 0: axis %d: the limit %lld is not in 1 .. 8190", k, limit[k]);
-        }
-    if (limit_out) limit_out[0] = limit[0], limit_out[1] = limit[1];
-    plan = GrowPlan{};
-    plan.job.resize((size_t)n);
-    for (int j = 0; j < n; j++) {
-        const fxjps_grow_job_t& a = jobs[j];
-        if (!a.raw) return absorb_refuse(msg, len, "job %d: NULL raw", j);
-        if (a.layout != 0 && a.layout != 1) return absorb_refuse(msg, len, "job %d: layout %d is not 0 or 1", j, (int)a.layout);
-        if (a.W0 < 1 || a.H0 < 1 || a.W0 > 8190 || a.H0 > 8190)
-            return absorb_refuse(msg, len, "job %d: bad extents (W0 %d, H0 %d): raw must be 1..8190 cells a side", j, (int)a.W0, (int)a.H0);
-        const long long ext[2] = {a.W0, a.H0};
-        for (int k = 0; k < 2; k++)
-            if (a.win[k] < 1 || a.lo[k] < 0 || (long long)a.lo[k] + a.win[k] > ext[k])
-                return absorb_refuse(msg, len, "job %d: axis %d: the rectangle (%d + %d) is empty or does not lie inside raw's %lld cells", j, k, (int)a.lo[k],
-                                     (int)a.win[k], ext[k]);
-        if (a.prior < 0 || a.prior >= FXJPS_MAX_PRIOR_MAPS) return absorb_refuse(msg, len, "job %d: prior %d is not in 0 .. %d", j, (int)a.prior, FXJPS_MAX_PRIOR_MAPS - 1);
-        GrowPlan::Prior& P = plan.prior[a.prior];
-        if (!P.named) {
-            P.ext[0] = prior_wh[2 * a.prior];
-            P.ext[1] = prior_wh[2 * a.prior + 1];
-        }
-        if (P.ext[0] < 1 || P.ext[1] < 1) return absorb_refuse(msg, len, "job %d: prior %d is not set", j, (int)a.prior);
-        const double reso = a.map_reso;
-        if (!std::isfinite(reso) || !(reso > 0.0)) return absorb_refuse(msg, len, "job %d: map_reso %g must be finite and > 0", j, reso);
-        for (int k = 0; k < 2; k++) {
-            if (!std::isfinite(a.map_o[k]) || !std::isfinite(a.ori_pre[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_o / ori_pre", j);
-            if (!std::isfinite(a.map_t[k])) return absorb_refuse(msg, len, "job %d: a non-finite map_t", j);
-        }
-        if (!P.named) {
-            P.named = true;
-            P.first = j;
-            P.op[0] = a.ori_pre[0];
-            P.op[1] = a.ori_pre[1];
-        } else {
-            const fxjps_grow_job_t& f = jobs[P.first];
-            if (memcmp(f.ori_pre, a.ori_pre, sizeof(a.ori_pre)) != 0 || memcmp(&f.map_reso, &a.map_reso, sizeof(double)) != 0)
-                return absorb_refuse(msg, len, "job %d: ori_pre / map_reso are not bit-equal to those of job %d, which names prior %d as well", j, P.first,
-                                     (int)a.prior);
-        }
-        GrowPlan::Job& q = plan.job[(size_t)j];
-        long long at_pre[2];
-        for (int k = 0; k < 2; k++) {
-            const double o = a.map_o[k], op = P.op[k];
-            const double o1 = std::min(o, op);                       // st:212
-            const double t_pre = op + reso * (double)P.ext[k];       // st:187, with the current extents
-            long long at_raw, ref;
-            if (!trunc_i32((o - o1) / reso, at_raw) || !trunc_i32((op - o1) / reso, at_pre[k]) ||  // st:213-214
-                !trunc_i32((std::max(t_pre, a.map_t[k]) - o1) / reso, ref))                        // st:215-216
-                return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
-            const long long size = std::max(ref, std::max(at_pre[k] + P.ext[k], at_raw + (long long)a.win[k]));
-            if (keep && keep[a.prior].use != FXJPS_KEEP_NONE) {
-                if (size > INT32_MAX) return absorb_refuse(msg, len, "job %d: a placement index or the canvas extent is outside int32", j);
-            } else if (size > limit[k])
-                return absorb_refuse(msg, len, "job %d: axis %d: prior %d would grow to %lld cells, above the limit of %lld", j, k, (int)a.prior, size, limit[k]);
-            q.at[k] = at_raw;
-            P.ext[k] = size;
-            P.op[k] = o1;
-            P.shift[k] += at_pre[k];
-        }
-        for (int i = 0; i < j; i++)  // (the earlier rectangles on this prior move with the old prior)
-            if (jobs[i].prior == a.prior)
-                for (int k = 0; k < 2; k++) plan.job[(size_t)i].at[k] += at_pre[k];
-        if (keep) continue;  // (slide_check stages what lies inside the windows, once it knows them)
-        const size_t row = (size_t)(a.layout ? a.W0 : a.H0), k = a.layout ? 1 : 0;
-        q.raw_off = (size_t)a.lo[k] * row;
-        q.raw_bytes = (size_t)a.win[k] * row;
-        q.in_off = plan.in_bytes;
-        plan.in_bytes += (q.raw_bytes + 15) & ~(size_t)15;
-        if (plan.in_bytes > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
-    }
-    for (int j = 0; j < n; j++) {
-        GrowPlan::Prior& P = plan.prior[jobs[j].prior];
-        const GrowPlan::Job& q = plan.job[(size_t)j];
-        for (int k = 0; k < 2; k++) {
-            P.lo[k] = std::min(P.lo[k], q.at[k]);
-            P.hi[k] = std::max(P.hi[k], q.at[k] + (long long)jobs[j].win[k]);
-            jobs[j].at[k] = (int32_t)q.at[k];
-        }
-        jobs[j].inside = (long long)jobs[j].win[0] * jobs[j].win[1];
-        jobs[j].outside = 0;
-    }
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
-        const GrowPlan::Prior& P = plan.prior[p];
-        fxjps_prior_grown_t& g = out[p];
-        g.named = P.named ? 1 : 0;
-        g.W = P.named ? (int32_t)P.ext[0] : prior_wh[2 * p];
-        g.H = P.named ? (int32_t)P.ext[1] : prior_wh[2 * p + 1];
-        g.reserved_ = 0;
-        for (int k = 0; k < 2; k++) {
-            g.shift[k] = (int32_t)P.shift[k];
-            g.origin[k] = P.op[k];
-        }
-    }
-    return FXJPS_OK;
-}
-
-// One context's part of fxjps_absorb_prior_grow: the grown priors into the spare buffers (PriorBuf::next) with ONE copy
-// in, ONE launch, one copy back and one wait, whatever n is.  Nothing the world-frame calls read is touched; the
-// counters are left in d.h_absorb_out.
-// window (fxjps_absorb_prior_slide): every new prior holds the cells [k0, k1) of its grown frame, a job wholly outside its
-// window is left out of the table, and the launch is k_prior_grow<true>.
-int grow_on(fxjps* h, DevCtx& d, const fxjps_grow_job_t* jobs, int n, int mode, const GrowPlan& plan, bool window = false) {
-    HIPCHK(h, hipSetDevice(d.dev));
-    HIPCHK(h, d.h_absorb_in.ensure(plan.in_bytes));
-    HIPCHK(h, d.d_absorb_in.ensure(plan.in_bytes));
-    HIPCHK(h, d.h_absorb_out.ensure(FXJPS_MAX_PRIOR_MAPS));
-    fx::GrowTable& T = *reinterpret_cast<fx::GrowTable*>(d.h_absorb_in.p);
-    memset(&T, 0, sizeof(T));
-    T.mode = mode;
-    int nb = 0, nj = 0;
-    uint32_t at = 0;
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {  // (jobs grouped by prior, in job order within a prior)
-        const GrowPlan::Prior& P = plan.prior[p];
-        if (!P.named) continue;
-        DevCtx::PriorBuf& pr = d.priors[(size_t)p];
-        const long long nW = window ? P.k1[0] - P.k0[0] : P.ext[0], nH = window ? P.k1[1] - P.k0[1] : P.ext[1];
-        HIPCHK(h, pr.next.ensure((size_t)(nW * nH)));
-        fx::GrowBoxDev B{};
-        B.job0 = nj;
-        for (int j = 0; j < n; j++) {
-            const fxjps_grow_job_t& a = jobs[j];
-            const GrowPlan::Job& q = plan.job[(size_t)j];
-            if (a.prior != p || !q.staged) continue;
-            fx::AbsorbJobDev& J = T.job[nj++];
-            J.stride = a.layout ? a.W0 : a.H0;
-            // (cell (i, j) of the rectangle is read at row * stride + column from here; rows below row0 are not staged and
-            // not read, so the address of row 0 is only ever an operand)
-            J.at = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d.d_absorb_in.p) + q.in_off + (size_t)(a.layout ? a.lo[0] : a.lo[1]) -
-                                                    (size_t)q.row0 * (size_t)J.stride);
-            J.layout = a.layout;
-            J.x0 = (int32_t)q.at[0];
-            J.y0 = (int32_t)q.at[1];
-            J.w = a.win[0];
-            J.h = a.win[1];
-            memcpy(d.h_absorb_in.p + q.in_off, static_cast<const uint8_t*>(a.raw) + q.raw_off, q.raw_bytes);
-        }
-        B.njobs = nj - B.job0;
-        B.old = pr.occ.p;
-        B.out = pr.next.p;
-        B.oW = pr.W;
-        B.oH = pr.H;
-        B.sx = (int32_t)P.shift[0];
-        B.sy = (int32_t)P.shift[1];
-        B.nW = (int32_t)nW;
-        B.nH = (int32_t)nH;
-        B.x0 = (int32_t)P.lo[0];
-        B.y0 = (int32_t)P.lo[1];
-        B.w = (int32_t)(P.hi[0] - P.lo[0]);
-        B.h = (int32_t)(P.hi[1] - P.lo[1]);
-        B.prior = p;
-        if (window) {
-            T.k0[nb][0] = (int32_t)P.k0[0];
-            T.k0[nb][1] = (int32_t)P.k0[1];
-        }
-        T.first[nb] = at;
-        T.box[nb++] = B;
-        at += (uint32_t)((nW * nH + 255) / 256);  // (at most 16 x 8190 x 8190 / 256 blocks)
-    }
-    T.first[nb] = at;
-    T.nbox = nb;
-    memset(d.h_absorb_out.p, 0, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long));
-    if (nb == 0) return FXJPS_OK;  // (n == 0: nothing to queue)
-    HIPCHK(h, hipMemcpyAsync(d.d_absorb_in.p, d.h_absorb_in.p, plan.in_bytes, hipMemcpyHostToDevice, d.stream));
-    if (window)
-        hipLaunchKernelGGL(fx::k_prior_grow<true>, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
-    else
-        hipLaunchKernelGGL(fx::k_prior_grow<false>, dim3(at), dim3(256), 0, d.stream, reinterpret_cast<fx::GrowTable*>(d.d_absorb_in.p));
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(d.h_absorb_out.p, d.d_absorb_in.p, FXJPS_MAX_PRIOR_MAPS * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(h, hipStreamSynchronize(d.stream));
-    return FXJPS_OK;
-}
-}  // namespace
-
 int fxjps_grow_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
                      fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len) {
     if (msg && msg_len > 0) msg[0] = 0;
-    GrowPlan plan;
-    return grow_check(jobs, n, mode, prior_wh, limit_wh, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
+    PriorPlan plan;
+    return fold_check(jobs, n, mode, prior_wh, limit_wh, nullptr, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
 }
 
 int fxjps_absorb_prior_grow(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
                             fxjps_prior_grown_t out[FXJPS_MAX_PRIOR_MAPS]) {
-    static_assert(offsetof(fx::GrowTable, changed) == 0, "the counters come back from the head of the staged input");
-    if (!h) return FXJPS_E_ARG;
-    if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior_grow")) return rr;
-    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
-    const DevCtx& d0 = h->devs[0];
-    for (size_t p = 0; p < d0.priors.size(); p++) {
-        prior_wh[2 * p] = d0.priors[p].W;
-        prior_wh[2 * p + 1] = d0.priors[p].H;
-    }
-    GrowPlan plan;
-    char why[400] = "";
-    if (grow_check(jobs, n, mode, prior_wh, limit_wh, out, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = 0;
-    if (n == 0) return FXJPS_OK;
-    // every context writes its own grown copies from the caller's raws (host copies, no collective); the priors that the
-    // world-frame calls read are swapped only when all of them have succeeded, so a failure leaves every context as it was
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grow_on(h, h->devs[r], jobs, n, mode, plan); });
-    if (rc) {
-        drain_all(h);
-        (void)hipGetLastError();
-        return rc;
-    }
-    for (auto& d : h->devs)
-        for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++)
-            if (plan.prior[p].named) {
-                DevCtx::PriorBuf& pr = d.priors[(size_t)p];
-                std::swap(pr.occ, pr.next);  // (the old buffer is the next grow's spare)
-                pr.W = (int)plan.prior[p].ext[0];
-                pr.H = (int)plan.prior[p].ext[1];
-            }
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
-    return FXJPS_OK;
+    return grow_call(h, "fxjps_absorb_prior_grow", jobs, n, mode, limit_wh, nullptr, out);
 }
-
-// ------------------------------------------------------------------ ... into prior maps that slide
-int fxjps_prior_keep_size(void) { return (int)sizeof(fxjps_prior_keep_t); }
-int fxjps_prior_slid_size(void) { return (int)sizeof(fxjps_prior_slid_t); }
-
-namespace {
-// fxjps_absorb_prior_slide's refusals except a rank handle, and its whole geometry: grow_check's fold on copies of the jobs
-// (the per-job limit skipped for a prior with a keep window), then per prior the window -- float64, one division, one
-// truncation and a clamp on the double per bound -- and per job what of its rectangle lies inside.  Writes nothing unless
-// everything passes; then plan (in the GROWN frame, with k0 / k1 / origin per prior and the staged rows per job), every
-// job's inside / outside / at and every field of out but `changed`.
-int slide_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh, const fxjps_prior_keep_t* keep,
-                fxjps_prior_slid_t* out, GrowPlan& plan, char* msg, size_t len) {
-    static const fxjps_prior_keep_t none[FXJPS_MAX_PRIOR_MAPS] = {};
-    if (!out) return absorb_refuse(msg, len, "job 0: NULL out");
-    const fxjps_prior_keep_t* K = keep ? keep : none;
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
-        if (K[p].use < FXJPS_KEEP_NONE || K[p].use > FXJPS_KEEP_OVER_LIMIT)
-            return absorb_refuse(msg, len, "prior %d: keep.use %d is not FXJPS_KEEP_NONE, _ALWAYS or _OVER_LIMIT", p, (int)K[p].use);
-        if (K[p].use == FXJPS_KEEP_NONE) continue;
-        for (int k = 0; k < 2; k++) {
-            if (std::isnan(K[p].lo[k]) || std::isnan(K[p].hi[k])) return absorb_refuse(msg, len, "prior %d: axis %d: NaN in the keep window", p, k);
-            if (K[p].lo[k] > K[p].hi[k]) return absorb_refuse(msg, len, "prior %d: axis %d: the keep window's lo %g is above its hi %g", p, k, K[p].lo[k], K[p].hi[k]);
-        }
-    }
-    std::vector<fxjps_grow_job_t> fold;  // (grow_check fills at / inside / outside: not the caller's before every window has passed)
-    if (jobs && n > 0 && n <= FXJPS_MAX_GRID_SLOTS) fold.assign(jobs, jobs + n);
-    fxjps_prior_grown_t grown[FXJPS_MAX_PRIOR_MAPS];
-    long long limit[2];
-    if (int rc = grow_check(fold.empty() ? jobs : fold.data(), n, mode, prior_wh, limit_wh, grown, plan, msg, len, K, limit)) return rc;
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
-        GrowPlan::Prior& P = plan.prior[p];
-        if (!P.named) {
-            if (K[p].use != FXJPS_KEEP_NONE) return absorb_refuse(msg, len, "prior %d: a keep window for a prior that no job names", p);
-            continue;
-        }
-        for (int k = 0; k < 2; k++) {
-            P.k0[k] = 0;
-            P.k1[k] = P.ext[k];
-            P.origin[k] = P.op[k];
-        }
-        if (K[p].use == FXJPS_KEEP_NONE || (K[p].use == FXJPS_KEEP_OVER_LIMIT && P.ext[0] <= limit[0] && P.ext[1] <= limit[1])) continue;
-        P.trimmed = true;
-        const double reso = fold[(size_t)P.first].map_reso;
-        for (int k = 0; k < 2; k++) {
-            const double G = (double)P.ext[k];
-            const double a = std::trunc((K[p].lo[k] - P.op[k]) / reso), b = std::trunc((K[p].hi[k] - P.op[k]) / reso);
-            P.k0[k] = (long long)(a < 0.0 ? 0.0 : a > G ? G : a);  // (clamped as a double: a bound may be infinite)
-            P.k1[k] = (long long)(b < 0.0 ? 0.0 : b > G ? G : b);
-            if (P.k1[k] <= P.k0[k])
-                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window holds no cell of the grown prior (cells %lld .. %lld of %lld)", p, k, P.k0[k],
-                                     P.k1[k], P.ext[k]);
-            if (P.k1[k] - P.k0[k] > limit[k])
-                return absorb_refuse(msg, len, "prior %d: axis %d: the keep window of %lld cells is above the limit of %lld", p, k, P.k1[k] - P.k0[k], limit[k]);
-            if (P.k0[k] != 0) P.origin[k] = P.op[k] + reso * (double)P.k0[k];
-        }
-    }
-    // what of every rectangle lies inside its prior's window: the rows to stage and the union box, both in the grown frame
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) plan.prior[p].lo[0] = plan.prior[p].lo[1] = INT32_MAX, plan.prior[p].hi[0] = plan.prior[p].hi[1] = 0;
-    std::vector<long long> inside((size_t)n, 0);
-    plan.in_bytes = GROW_IN_RAWS;
-    for (int j = 0; j < n; j++) {
-        const fxjps_grow_job_t& a = fold[(size_t)j];
-        GrowPlan::Prior& P = plan.prior[a.prior];
-        GrowPlan::Job& q = plan.job[(size_t)j];
-        long long c0[2], c1[2];
-        for (int k = 0; k < 2; k++) {
-            c0[k] = std::max(q.at[k], P.k0[k]);
-            c1[k] = std::min(q.at[k] + (long long)a.win[k], P.k1[k]);
-        }
-        q.staged = c1[0] > c0[0] && c1[1] > c0[1];
-        q.raw_off = q.raw_bytes = 0;
-        q.in_off = plan.in_bytes;
-        q.row0 = 0;
-        if (!q.staged) continue;
-        inside[(size_t)j] = (c1[0] - c0[0]) * (c1[1] - c0[1]);
-        for (int k = 0; k < 2; k++) {
-            P.lo[k] = std::min(P.lo[k], c0[k]);
-            P.hi[k] = std::max(P.hi[k], c1[k]);
-        }
-        const size_t row = (size_t)(a.layout ? a.W0 : a.H0), r = a.layout ? 1 : 0;
-        q.row0 = c0[r] - q.at[r];
-        q.raw_off = (size_t)(a.lo[r] + q.row0) * row;
-        q.raw_bytes = (size_t)(c1[r] - c0[r]) * row;
-        plan.in_bytes += (q.raw_bytes + 15) & ~(size_t)15;
-        if (plan.in_bytes > ((size_t)1 << 30)) return absorb_refuse(msg, len, "job %d: more than 2^30 bytes to stage", j);
-    }
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
-        GrowPlan::Prior& P = plan.prior[p];
-        if (P.lo[0] > P.hi[0]) P.lo[0] = P.lo[1] = P.hi[0] = P.hi[1] = 0;  // (no rectangle reaches the window: an empty box)
-    }
-    for (int j = 0; j < n; j++) {
-        const GrowPlan::Prior& P = plan.prior[jobs[j].prior];
-        for (int k = 0; k < 2; k++) jobs[j].at[k] = (int32_t)(plan.job[(size_t)j].at[k] - P.k0[k]);
-        jobs[j].inside = inside[(size_t)j];
-        jobs[j].outside = (long long)jobs[j].win[0] * jobs[j].win[1] - inside[(size_t)j];
-    }
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) {
-        const GrowPlan::Prior& P = plan.prior[p];
-        fxjps_prior_slid_t& g = out[p];
-        g.named = P.named ? 1 : 0;
-        g.trimmed = P.trimmed ? 1 : 0;
-        for (int k = 0; k < 2; k++) {
-            const int32_t as_is = prior_wh[2 * p + k];
-            (k ? g.H : g.W) = P.named ? (int32_t)(P.k1[k] - P.k0[k]) : as_is;
-            g.grown_wh[k] = P.named ? (int32_t)P.ext[k] : as_is;
-            g.cut_lo[k] = (int32_t)P.k0[k];
-            g.cut_hi[k] = P.named ? (int32_t)(P.ext[k] - P.k1[k]) : 0;
-            g.shift[k] = (int32_t)(P.shift[k] - P.k0[k]);
-            g.origin[k] = P.origin[k];
-        }
-    }
-    return FXJPS_OK;
-}
-}  // namespace
 
 int fxjps_slide_check(fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* prior_wh, const int32_t* limit_wh,
                       const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS], char* msg, int32_t msg_len) {
     if (msg && msg_len > 0) msg[0] = 0;
-    GrowPlan plan;
-    return slide_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
+    PriorPlan plan;
+    return fold_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, msg, msg_len > 0 ? (size_t)msg_len : 0);
 }
 
 int fxjps_absorb_prior_slide(fxjps_t* h, fxjps_grow_job_t* jobs, int32_t n, int32_t mode, const int32_t* limit_wh,
                              const fxjps_prior_keep_t keep[FXJPS_MAX_PRIOR_MAPS], fxjps_prior_slid_t out[FXJPS_MAX_PRIOR_MAPS]) {
-    if (!h) return FXJPS_E_ARG;
-    if (int rr = refuse_on_rank_handle(h, "fxjps_absorb_prior_slide")) return rr;
-    int32_t prior_wh[2 * FXJPS_MAX_PRIOR_MAPS] = {};
-    const DevCtx& d0 = h->devs[0];
-    for (size_t p = 0; p < d0.priors.size(); p++) {
-        prior_wh[2 * p] = d0.priors[p].W;
-        prior_wh[2 * p + 1] = d0.priors[p].H;
-    }
-    GrowPlan plan;
-    char why[400] = "";
-    if (slide_check(jobs, n, mode, prior_wh, limit_wh, keep, out, plan, why, sizeof(why))) return fail(h, FXJPS_E_ARG, "%s", why);
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = 0;
-    if (n == 0) return FXJPS_OK;
-    // as fxjps_absorb_prior_grow: every context writes its own new copies; they are swapped in only when all have succeeded
-    int rc = run_side_by_side(h->devs.size(), [&](size_t r) -> int { return grow_on(h, h->devs[r], jobs, n, mode, plan, true); });
-    if (rc) {
-        drain_all(h);
-        (void)hipGetLastError();
-        return rc;
-    }
-    for (auto& d : h->devs)
-        for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++)
-            if (plan.prior[p].named) {
-                DevCtx::PriorBuf& pr = d.priors[(size_t)p];
-                std::swap(pr.occ, pr.next);  // (the old buffer is the next call's spare)
-                pr.W = (int)(plan.prior[p].k1[0] - plan.prior[p].k0[0]);
-                pr.H = (int)(plan.prior[p].k1[1] - plan.prior[p].k0[1]);
-            }
-    for (int p = 0; p < FXJPS_MAX_PRIOR_MAPS; p++) out[p].changed = (int64_t)h->devs[0].h_absorb_out.p[p];
-    return FXJPS_OK;
+    return grow_call(h, "fxjps_absorb_prior_slide", jobs, n, mode, limit_wh, keep, out);
 }
 
 int fxjps_last_timing(fxjps_t* h, fxjps_timing_t* out) {

@@ -2024,6 +2024,15 @@ struct AbsorbTable {
 };
 static_assert(sizeof(AbsorbJobDev) % 4 == 0, "the job records are copied to LDS word by word");
 
+// The flips of a wavefront into its prior's counter, for k_prior_absorb and k_prior_grow: one ballot, and one atomic add if
+// it saw any.  Every lane of the block calls it.  (The box lookup, the copy of the job records to LDS and the job walk stay
+// written out in both kernels: as inlined helpers each of them changed the instructions the compiler emits.)
+__device__ __forceinline__ void prior_count_flips(unsigned long long* counter, bool flip) {
+    RECONV();
+    const uint64_t m = __ballot(flip);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
 __global__ __launch_bounds__(256) void k_prior_absorb(AbsorbTable* __restrict__ T) {
     __shared__ AbsorbJobDev s_job[ABSORB_JOBS_MAX];
     const int nbox = T->nbox, mode = T->mode;
@@ -2061,9 +2070,7 @@ __global__ __launch_bounds__(256) void k_prior_absorb(AbsorbTable* __restrict__ 
             flip = (old != 0) != (val != 0);
         }
     }
-    RECONV();
-    const uint64_t m = __ballot(flip);
-    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&T->changed[B.prior], (unsigned long long)__popcll(m));
+    prior_count_flips(&T->changed[B.prior], flip);
 }
 
 // ---------------------------------------------------------------- ... into prior maps that grow (DESIGN.md section 3.21)
@@ -2103,7 +2110,7 @@ struct GrowTable {
 // union box (which the host has clipped to the window) and the jobs' x0, y0 -- stays in the grown frame, so the job walk,
 // the predicates, the old-byte fallback and the ballot count are the same lines.  Of a rectangle only the rows inside the
 // window are staged: a thread reads a raw only at a cell of its own, which lies in the window.  k0 = 0 with the grown
-// extents is a prior that is not cut.  <false> is fxjps_absorb_prior_grow's kernel as it was, instruction for instruction.
+// extents is a prior that is not cut.  <false> is fxjps_absorb_prior_grow's kernel: it reads no k0 and adds none.
 template <bool WINDOW> __global__ __launch_bounds__(256) void k_prior_grow(GrowTable* __restrict__ T) {
     __shared__ AbsorbJobDev s_job[ABSORB_JOBS_MAX];
     const int nbox = T->nbox, mode = T->mode;
@@ -2152,7 +2159,5 @@ template <bool WINDOW> __global__ __launch_bounds__(256) void k_prior_grow(GrowT
         B.out[(size_t)wx * (size_t)B.nH + (size_t)wy] = byte;
         flip = (old != 0) != (byte != 0);
     }
-    RECONV();
-    const uint64_t m = __ballot(flip);
-    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&T->changed[B.prior], (unsigned long long)__popcll(m));
+    prior_count_flips(&T->changed[B.prior], flip);
 }

@@ -615,29 +615,7 @@ class Planner(object):
         clears the prior's), "occupied" (only ever adds obstacles) or "known" (cells that are -1 in a message leave the
         prior as it is).  -> ([(inside, outside) per job], {prior: cells whose occupancy flipped}).  No slot, no stored
         result and not the resident grid is touched.  worldprep.absorb_host is the same paste on the host."""
-        jobs = list(jobs)
-        n = len(jobs)
-        if mode not in _lib.ABSORB_MODES:
-            raise ValueError("mode %r is not one of %r" % (mode, tuple(_lib.ABSORB_MODES)))
-        if crops is not None and len(crops) != n:
-            raise ValueError("%d crop records for %d jobs" % (len(crops), n))
-        arr = (_lib.AbsorbJob * max(n, 1))()
-        keep = []  # (the raws, alive until the call has returned)
-        for v, (a, job) in enumerate(zip(arr, jobs)):
-            raw, map_o, map_reso = job[1], job[2], job[3]
-            prior, ori_pre = (tuple(job[8:10]) + (None, (-15, -15))[len(job[8:10]):])[:2]
-            if prior is None:
-                raise ValueError("job %d names no prior map" % v)
-            w = _lib.WorldJob()  # (raw, layout and extents as the world-frame calls take them)
-            keep.append(Planner._job_raw(w, 0, raw, 0, 0))
-            a.raw, a.layout, a.W0, a.H0 = w.raw, w.layout, w.W0, w.H0
-            rec = None if crops is None else crops[v]
-            lo, win = ((0, 0), (a.W0, a.H0)) if rec is None else (rec["lo"], rec["win"])
-            if rec is not None:
-                map_o = rec["map_o"]
-            a.prior, a.map_reso = int(prior), float(map_reso)
-            for k in range(2):
-                a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k])
+        arr, n, _, keep = self._prior_jobs(jobs, mode, crops, None, _lib.AbsorbJob)
         changed = np.zeros(_lib.MAX_PRIOR_MAPS, dtype=np.int64)
         self._chk(self._L.fxjps_absorb_prior(self._h, arr, n, _lib.ABSORB_MODES[mode], _lib.ptr(changed, C.c_int64)))
         del keep
@@ -656,22 +634,17 @@ class Planner(object):
         old cell (0, 0) lies now, the new world origin and the cells whose occupancy differs from the old byte at that
         place.  The planner remembers each grown prior's origin (prior_origin); the library stores none.  On a refusal or
         a failure every prior is what it was, byte for byte.  worldprep.grow_host is the same fold on the host."""
-        arr, n, lim, keep = self._grow_jobs(jobs, mode, crops, limit)
+        arr, n, lim, keep = self._prior_jobs(jobs, mode, crops, limit, _lib.GrowJob)
         out = (_lib.PriorGrown * _lib.MAX_PRIOR_MAPS)()
         self._chk(self._L.fxjps_absorb_prior_grow(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), out))
         del keep
-        grown = {}
-        for p, g in enumerate(out):
-            if g.named:
-                grown[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
-                            "changed": int(g.changed)}
-                self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
+        grown = {p: self._prior_record(p, g) for p, g in enumerate(out) if g.named}
         return [(int(a.at[0]), int(a.at[1])) for a in arr[:n]], grown
 
     @staticmethod
-    def _grow_jobs(jobs, mode, crops, limit):
-        """absorb_prior_grow's and absorb_prior_slide's arguments as the library takes them -> (fxjps_grow_job_t array, n,
-        limit_wh or None, the raws: alive until the call has returned)."""
+    def _prior_jobs(jobs, mode, crops, limit, job_type):
+        """absorb_prior's (job_type _lib.AbsorbJob), absorb_prior_grow's and absorb_prior_slide's (_lib.GrowJob: with map_t)
+        arguments as the library takes them -> (job array, n, limit_wh or None, the raws: alive until the call has returned)."""
         from . import worldprep
         jobs = list(jobs)
         n = len(jobs)
@@ -682,7 +655,7 @@ class Planner(object):
         lim = None
         if limit is not None:
             lim = np.array([limit, limit] if np.isscalar(limit) else [limit[0], limit[1]], dtype=np.int32)
-        arr = (_lib.GrowJob * max(n, 1))()
+        arr = (job_type * max(n, 1))()
         keep = []
         for v, (a, job) in enumerate(zip(arr, jobs)):
             raw, map_o, map_reso = job[1], job[2], job[3]
@@ -695,13 +668,24 @@ class Planner(object):
             rec = None if crops is None else crops[v]
             lo, win = ((0, 0), (a.W0, a.H0)) if rec is None else (rec["lo"], rec["win"])
             if rec is not None:
-                map_o, map_t = rec["map_o"], rec["map_t"]
-            if map_t is None:
-                map_t = worldprep.map_top(map_o, win, map_reso)
+                map_o = rec["map_o"]
             a.prior, a.map_reso = int(prior), float(map_reso)
             for k in range(2):
-                a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k], a.map_t[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k]), float(map_t[k])
+                a.lo[k], a.win[k], a.map_o[k], a.ori_pre[k] = int(lo[k]), int(win[k]), float(map_o[k]), float(ori_pre[k])
+            if job_type is _lib.GrowJob:
+                if rec is not None:
+                    map_t = rec["map_t"]
+                if map_t is None:
+                    map_t = worldprep.map_top(map_o, win, map_reso)
+                a.map_t[0], a.map_t[1] = float(map_t[0]), float(map_t[1])
         return arr, n, lim, keep
+
+    def _prior_record(self, p, g):
+        """What absorb_prior_grow and absorb_prior_slide return of prior p, from the keys their out records share; the
+        planner remembers the new origin."""
+        self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
+        return {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
+                "changed": int(g.changed)}
 
     def absorb_prior_slide(self, jobs, mode="overwrite", crops=None, limit=None, keep=None, use="over_limit"):
         """absorb_prior_grow followed, per prior, by a cut to a keep window, in the same single launch
@@ -718,7 +702,7 @@ class Planner(object):
         (whether the window was applied), grown_wh (the extents the fold reached) and cut_lo / cut_hi (the cells cut off
         each side of them).  prior_origin is updated as absorb_prior_grow updates it; on a refusal or a failure every
         prior is what it was.  worldprep.slide_host is the same on the host."""
-        arr, n, lim, raws = self._grow_jobs(jobs, mode, crops, limit)
+        arr, n, lim, raws = self._prior_jobs(jobs, mode, crops, limit, _lib.GrowJob)
         win = None
         if keep:
             win = (_lib.PriorKeep * _lib.MAX_PRIOR_MAPS)()
@@ -735,13 +719,9 @@ class Planner(object):
         out = (_lib.PriorSlid * _lib.MAX_PRIOR_MAPS)()
         self._chk(self._L.fxjps_absorb_prior_slide(self._h, arr, n, _lib.ABSORB_MODES[mode], None if lim is None else _lib.ptr(lim, C.c_int32), win, out))
         del raws
-        slid = {}
-        for p, g in enumerate(out):
-            if g.named:
-                slid[p] = {"W": int(g.W), "H": int(g.H), "shift": (int(g.shift[0]), int(g.shift[1])), "origin": [float(g.origin[0]), float(g.origin[1])],
-                           "changed": int(g.changed), "trimmed": bool(g.trimmed), "grown_wh": (int(g.grown_wh[0]), int(g.grown_wh[1])),
-                           "cut_lo": (int(g.cut_lo[0]), int(g.cut_lo[1])), "cut_hi": (int(g.cut_hi[0]), int(g.cut_hi[1]))}
-                self._origins()[p] = (float(g.origin[0]), float(g.origin[1]))
+        slid = {p: dict(self._prior_record(p, g), trimmed=bool(g.trimmed), grown_wh=(int(g.grown_wh[0]), int(g.grown_wh[1])),
+                        cut_lo=(int(g.cut_lo[0]), int(g.cut_lo[1])), cut_hi=(int(g.cut_hi[0]), int(g.cut_hi[1])))
+                for p, g in enumerate(out) if g.named}
         return [((int(a.at[0]), int(a.at[1])), int(a.inside), int(a.outside)) for a in arr[:n]], slid
 
     def _origins(self):

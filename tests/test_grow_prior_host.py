@@ -332,6 +332,37 @@ def test_every_refusal_fires_in_the_check_and_writes_nothing():
     assert check(jobs[:16], wh)[0] == 0
 
 
+def test_argument_faults_are_refused_alike_by_the_absorb_check_and_the_grow_check():
+    """One per-job argument check serves both calls: what both refuse, both refuse with the same words, writing nothing.
+    (Left out: an int32 overflow on axis 0 with a non-finite value on axis 1, where either fault may be the one named.)"""
+    from fuxi_planner_amd import _lib
+    check = checker()
+    L = _lib.load()
+    msg = C.create_string_buffer(400)
+    raw = np.zeros((6, 8), dtype=np.uint8)
+    wh = extents(p2=(10, 12))
+    nan, inf = float("nan"), float("inf")
+    n_prefix = C.sizeof(_lib.AbsorbJob)
+    bad = [("n", dict(n=257)), ("mode", dict(mode=3)), ("extents", dict(no_extents=True)), ("raw", dict(raw=None)), ("layout", dict(layout=2)),
+           ("extents", dict(W0=0)), ("extents", dict(W0=8191)), ("rectangle", dict(win=(0, 8))), ("rectangle", dict(lo=(1, 0))),
+           ("rectangle", dict(lo=(0, 3), win=(2, 6))), ("prior", dict(prior=16)), ("not set", dict(prior=5)), ("map_reso", dict(map_reso=0.0)),
+           ("map_reso", dict(map_reso=nan)), ("non-finite", dict(map_o=(nan, 0.0))), ("non-finite", dict(map_o=(0.0, inf))),
+           ("non-finite", dict(ori_pre=(-inf, 0.0))), ("non-finite", dict(ori_pre=(0.0, nan)))]
+    for word, kw in bad:
+        call = {k: kw.pop(k) for k in ("n", "mode", "no_extents") if k in kw}
+        jobs = [make_job(raw), make_job(raw, **kw)]
+        rc, text, arr, out, before = check(jobs, wh, **call)
+        assert rc == _lib.E_ARG and word in text and text.startswith("job 1:" if kw else "job 0:"), (word, kw, call, rc, text)
+        assert outputs(arr, out) == before, word
+        absorb = (_lib.AbsorbJob * 2)()    # the same two jobs: the absorb job is the grow job's prefix
+        for a, g in zip(absorb, jobs):
+            C.memmove(C.addressof(a), C.addressof(g), n_prefix)
+            a.inside, a.outside = -3, -5
+        rc = L.fxjps_absorb_check(absorb, call.get("n", 2), call.get("mode", 0), None if call.get("no_extents") else _lib.ptr(wh, C.c_int32), msg, len(msg))
+        assert rc == _lib.E_ARG and msg.value.decode() == text, (word, rc, msg.value.decode(), text)
+        assert [(a.inside, a.outside) for a in absorb] == [(-3, -5)] * 2, word
+
+
 def test_the_limit_holds_exactly_at_the_edge():
     from fuxi_planner_amd import _lib
     check = checker()
