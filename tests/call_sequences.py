@@ -13,6 +13,21 @@ A failure message carries the ops up to the failing step as Python literals: run
 
 Op records are dicts of ints, floats, strings and lists.  A grid is a recipe {"W", "H", "seed", "p", "set"}: random bytes of
 density p from numpy's RandomState(seed), then the listed [x, y, value] cells; `grid_of` expands it.
+
+The profiles `world` and `world_two_contexts` have a generator of their own (_WorldGen, with its own draws: the op lists
+of the four earlier profiles are what they were, pinned by digest in the host test).  Their state is the shared prior
+maps: Model.prior is {index: bytes, the origin they lie at now, the origin they were uploaded with, whether a grow or slide
+has moved them since}, written by set_prior_map / set_prior_image / clear_prior_map and by absorb_prior / absorb_prior_grow /
+absorb_prior_slide (the named priors only; no slot, generation, stored result or resident path), read by every world-frame
+and cropped job -- which carries the prior's index and the origin the model holds when it is drawn, now and then the
+upload's origin after a grow.  Expected outputs are worldprep's host references (absorb_host, slide_host -- the grow_host
+fold --, crop_host, merge_host) and, for check_paths_slots on the last slots batch's paths, waypoints.check_path on the
+slots as they are now.  After every op that writes a prior or is refused on one, and on every 8th step, every set prior
+is read back; prior_origin is compared after every op that names a prior.  A world job is {"slot", "raw", "msg" (handed in
+as an OccupancyGrid message with -1 cells), "start", "goal", "ifa", "variant", "prior" (an index or None), "at" (the raw's
+origin in cells from ORI_PRE), "ori" (the prior's origin it carries)}; a fold's job is {"prior", "raw", "msg", "at", "ori"[,
+"crop": the vehicle's cell -- the job is absorbed through worldprep.crop_host's record]}; a keep window is [lo_xy, hi_xy]
+with None for an infinite bound.
 """
 import contextlib
 import io
@@ -27,6 +42,8 @@ ORI_PRE = (-3.0, 2.0)    # the world origin of prior map 0
 E_ARG, E_NOGRID = -1, -4
 Q_BAD_START = -2
 PROFILES = ("single", "tiles", "two_contexts", "shim")
+WORLD_PROFILES = ("world", "world_two_contexts")  # the shared prior maps, the cropped prepares, the path checks: their own draws
+ALL_PROFILES = PROFILES + WORLD_PROFILES
 SEEDS = (0, 1, 2, 3)     # the sequences the CPU and the GPU suites run per profile
 STEPS = 120              # ... and their length before the closing round
 MPLS = (6, 400)          # max_path_len of the stored and the slot batches: 6 cuts some paths (PATH_TOO_LONG)
@@ -61,8 +78,18 @@ def world_job(j):
     map_o = (ORI_PRE[0] + j["at"][0] * R, ORI_PRE[1] + j["at"][1] * R)
     pos = (map_o[0] + (j["start"][0] + 0.5) * R, map_o[1] + (j["start"][1] + 0.5) * R)
     goal = (map_o[0] + (j["goal"][0] + 0.5) * R, map_o[1] + (j["goal"][1] + 0.5) * R)
+    if j.get("msg"):
+        raw = (msg_of(j["raw"]), j["raw"]["W"], j["raw"]["H"])
     t = (j["slot"], raw, map_o, R, pos, goal, j["ifa"], j["variant"])
+    if "ori" in j:  # (the world profiles: a prior index or None, and the origin the job carries)
+        return t + (j["prior"], tuple(j["ori"]) if j["ori"] is not None else (-15.0, -15.0))
     return t + (0, ORI_PRE) if j["prior"] else t
+
+
+def prior_job(j):
+    """An absorb / grow / slide job record -> the tuple Planner.absorb_prior takes (a world job whose slot, position, goal,
+    ifa and variant are not read)."""
+    return world_job(dict(j, slot=0, start=[0, 0], goal=[0, 0], ifa=0, variant=0))
 
 
 def slot_job(j):
@@ -103,10 +130,107 @@ def world_prepared(job, prior):
     from fuxi_planner_amd import worldprep
     slot, raw, map_o, reso, pos, goal, ifa, variant = job[:8]
     canvas, shape, co, s, g = worldprep.merge_host(raw, map_o, reso, pos, goal, prior=prior if len(job) > 8 else None,
-                                                   ori_pre=job[9] if len(job) > 9 else (-15, -15))
+                                                   ori_pre=job[9] if len(job) > 9 else (-15, -15), map_t=job[10] if len(job) > 10 else None)
     grid, out = prepared(canvas, s, g, ifa, variant)
     origin = list(-np.asarray(out[2]) * reso + np.asarray(co, dtype=np.float64))
     return grid, out, (origin, tuple(shape), [float(co[0]), float(co[1])])
+
+
+def named_prior(priors, job):
+    """The bytes of the prior a world job (Planner's tuple) names out of priors {index: bytes}; None for a job without one;
+    a ValueError -- the call is refused -- for one that is not set."""
+    p = job[8] if len(job) > 8 else None
+    if p is None:
+        return None
+    if p not in priors:
+        raise ValueError("prior %d is not set" % p)
+    return priors[p]
+
+
+def refusing(fn, *args):
+    """fn(*args); the ValueError with which a host reference refuses becomes the model's Refused (FXJPS_E_ARG)."""
+    try:
+        return fn(*args)
+    except ValueError:
+        raise Refused("FxjpsError", E_ARG)
+
+
+NO_OUT = ((0, 0), (0, 0), (0, 0), (0, 0), 0, False)  # what a cropped job that takes no part in the call reports: ok False ...
+NO_WORLD = ([0.0, 0.0], (0, 0), [0.0, 0.0])           # ... and no origin, canvas extents or canvas origin
+
+
+def crop_prepared(job, priors):
+    """A cropped job (Planner's tuple) by worldprep.crop_host and world_prepared -> (grid, prepare's tuple, the three world
+    outputs, (status, crop record)).  grid None: the job is not planned or refused on its own (fxjps.h: the cases 1 and 2),
+    its outputs are 0 and its slot is left empty."""
+    from fuxi_planner_amd import worldprep
+    raw = job[1] if isinstance(job[1], tuple) else (np.asarray(job[1]) > 0).astype(np.uint8)  # (the binding hands a matrix in as 0 / 1)
+    rec, outcome, window = worldprep.crop_host(raw, job[2], job[3], job[4], job[6])
+    prior = named_prior(priors, job)  # (a prior that is not set refuses the whole call, whatever the crop says)
+    if outcome != 0:
+        return None, NO_OUT, NO_WORLD, (outcome, rec)
+    wj = (job[0], window, rec["map_o"]) + tuple(job[3:8]) + (job[8] if len(job) > 8 else None, job[9] if len(job) > 9 else (-15, -15), rec["map_t"])
+    grid, out, w = world_prepared(wj, prior)
+    return grid, out, w, (0, rec)
+
+
+def keep_of(op):
+    """The keep windows of a slide record ({prior: [lo_xy, hi_xy]}, None for an infinite bound) as Planner takes them."""
+    inf = float("inf")
+    return {int(p): ([-inf if v is None else v for v in w[0]], [inf if v is None else v for v in w[1]]) for p, w in op["keep"].items()}
+
+
+def crops_of(jobs):
+    """The crop records of a fold's job records, as Planner's crops= takes them: None for a job absorbed whole; for a job
+    with a "crop" cell worldprep.crop_host's record of the message with the vehicle in the middle of that cell -- the
+    rectangle absorbed is then the record's window.  None if no job has one."""
+    from fuxi_planner_amd import worldprep
+    out = []
+    for j in jobs:
+        if j.get("crop") is None:
+            out.append(None)
+            continue
+        wj = world_job(dict(j, slot=0, start=j["crop"], goal=[0, 0], ifa=0, variant=0))
+        raw = wj[1] if isinstance(wj[1], tuple) else (np.asarray(wj[1]) > 0).astype(np.uint8)
+        rec, outcome, window = worldprep.crop_host(raw, wj[2], wj[3], wj[4], 0)
+        if outcome != 0:
+            raise ValueError("a message without a window cannot be absorbed through its crop record")
+        out.append(rec)
+    return out if any(r is not None for r in out) else None
+
+
+def fold_of(before, op):
+    """prior_fold of a fold's op record."""
+    return prior_fold(before, [prior_job(j) for j in op["jobs"]], op, crops_of(op["jobs"]))
+
+
+def prior_fold(before, jobs, op, crops=None):
+    """An absorb_prior / absorb_prior_grow / absorb_prior_slide record on the priors `before` ({index: bytes}), by
+    worldprep.absorb_host job by job and worldprep.slide_host (without windows: the grow_host fold).  jobs and crops as
+    Planner's call takes them.  -> (the named priors' bytes afterwards, the new origins of those that grew or slid, what
+    Planner's call returns).  ValueError where the library refuses."""
+    from fuxi_planner_amd import worldprep
+    for v, wj in enumerate(jobs):
+        if wj[8] not in before:
+            raise ValueError("job %d: prior %d is not set" % (v, wj[8]))
+    named = sorted({wj[8] for wj in jobs})
+    if op["op"] == "absorb_prior":
+        cur, counts = dict(before), []
+        for v, wj in enumerate(jobs):
+            rec = crops[v] if crops is not None else None
+            lo, win = (None, None) if rec is None else (rec["lo"], rec["win"])
+            cur[wj[8]], inside, outside, _ = worldprep.absorb_host(cur[wj[8]], wj[9], wj[1], wj[2] if rec is None else rec["map_o"], wj[3], op["mode"],
+                                                                   lo=lo, win=win)
+            counts.append((inside, outside))
+        return {p: cur[p] for p in named}, {}, (counts, {p: int(np.count_nonzero((cur[p] != 0) != (before[p] != 0))) for p in named})
+    slide = op["op"] == "absorb_prior_slide"
+    cur, records, per_job = worldprep.slide_host(before, jobs, op["mode"], crops, op["limit"], keep_of(op) if slide else None,
+                                                 op["use"] if slide else "none")
+    if slide:
+        ret = ([(tuple(a), i, o) for a, i, o in per_job], records)
+    else:
+        ret = ([tuple(a) for a, i, o in per_job], {p: {f: r[f] for f in ("W", "H", "shift", "origin", "changed")} for p, r in records.items()})
+    return {p: cur[p] for p in named}, {p: records[p]["origin"] for p in named}, ret
 
 
 def default_mpl(W, H):
@@ -150,7 +274,8 @@ class Model(object):
         self.queries = None    # (starts, goals, hchoice, max_path_len) of set_queries
         self.slots = {}        # slot -> bytes
         self.gen = {}          # slot -> generation (fxjps.h: the set and prepare calls bump every slot they name, the refresh calls those not kept)
-        self.prior = None
+        self.prior = {}        # index -> {"bytes": uint8 [W][H], "origin": where it lies now, "upload": where it was uploaded,
+        #                        "moved": a grow or slide has run since the upload (Planner.prior_origin is the origin then)}
         self.mode = 0
         self.prev = None       # the previous replan_slots while its stored results stand: ids, s, g, hchoice, mpl, gen, status
         self.last = None       # the last batch: kind "resident" / "slots", nq, ids, shapes, and (from run) off, cells
@@ -187,6 +312,17 @@ class Model(object):
     def slot_set(self, slot, grid):
         self.slots[slot] = np.ascontiguousarray(grid, dtype=np.uint8)
         self._bump(slot)
+
+    def slot_empty(self, slot):
+        """A cropped job that is not planned or refused: the slot is left empty and its generation moves."""
+        self.slots.pop(slot, None)
+        self._bump(slot)
+
+    def prior_set(self, p, occ, origin):
+        self.prior[p] = {"bytes": np.ascontiguousarray(occ, dtype=np.uint8), "origin": tuple(origin), "upload": tuple(origin), "moved": False}
+
+    def prior_bytes(self):
+        return {p: d["bytes"] for p, d in self.prior.items()}
 
     def slot_refresh(self, slot, grid):
         """-> kept, by the header's rule: the slot holds a grid of the same extents and bytes."""
@@ -310,22 +446,53 @@ def expect(m, op, oracle=None):
             m.slot_set(slot, (grid_of(g) == 1).astype(np.uint8))
     elif k == "refresh_grid_slots":
         e["kept"] = [m.slot_refresh(slot, (grid_of(g) == 1).astype(np.uint8)) for slot, g in op["jobs"]]
-    elif k in ("prepare_slots", "refresh_slots", "prepare_slots_world", "refresh_slots_world"):
-        outs = []
+    elif k in ("prepare_slots", "refresh_slots", "prepare_slots_world", "refresh_slots_world", "prepare_slots_cropped", "refresh_slots_cropped"):
+        done = []  # (every job is computed before a slot is written: a whole-call refusal leaves the model as it was)
         for j in op["jobs"]:
-            if k.endswith("_world"):
-                grid, out, w = world_prepared(world_job(j), m.prior)
+            tail = ()
+            if k.endswith("_cropped"):
+                grid, out, w, tail = refusing(crop_prepared, world_job(j), m.prior_bytes())
+            elif k.endswith("_world"):
+                wj = world_job(j)
+                grid, out, w = refusing(lambda: world_prepared(wj, named_prior(m.prior_bytes(), wj)))
             else:
                 grid, out = prepared(grid_of(j["raw"]), j["start"], j["goal"], j["ifa"], j["variant"])
                 w = ()
-            if k.startswith("refresh"):
-                outs.append(out + (True, m.slot_refresh(j["slot"], grid)) + w)
+            done.append((grid, out, w, tail))
+        outs = []
+        for j, (grid, out, w, tail) in zip(op["jobs"], done):
+            if grid is None:  # (a cropped job that is not planned, or refused on its own: fxjps.h, the cases 1 and 2)
+                m.slot_empty(j["slot"])
+                outs.append(out + ((False,) if k.startswith("refresh") else ()) + w + tail)
+            elif k.startswith("refresh"):
+                outs.append(out + (True, m.slot_refresh(j["slot"], grid)) + w + tail)
             else:
                 m.slot_set(j["slot"], grid)
-                outs.append(out + (True,) + w)
+                outs.append(out + (True,) + w + tail)
         e["outs"] = outs
-    elif k == "set_prior_map":
-        m.prior = grid_of(op["g"])
+    elif k in ("set_prior_map", "set_prior_image"):
+        from fuxi_planner_amd import worldprep
+        occ = grid_of(op["g"]) > 0 if k == "set_prior_map" else worldprep.prior_from_image(gray_of(op["gray"]))
+        m.prior_set(op["prior"], occ, op.get("origin", ORI_PRE))  # (the moved origin is forgotten with the old entry)
+    elif k == "clear_prior_map":
+        m.prior.pop(op["prior"], None)
+    elif k in ("get_prior_map", "prior_origin"):
+        if k == "get_prior_map" and op["prior"] not in m.prior:
+            raise Refused("FxjpsError", E_ARG)
+    elif k in ("absorb_prior", "absorb_prior_grow", "absorb_prior_slide"):
+        # (only the named priors are written: no slot, no generation, no stored result, not the resident grid, not m.last)
+        after, origin, e["ret"] = refusing(fold_of, m.prior_bytes(), op)
+        for p, b in after.items():
+            m.prior[p] = dict(m.prior[p], bytes=b)
+            if p in origin:
+                m.prior[p].update(origin=tuple(origin[p]), moved=True)
+    elif k == "check_paths_slots":
+        L = m.last
+        if L is None or L["kind"] != "slots" or any(i not in m.slots for i in L["ids"]):
+            raise Refused("FxjpsError", E_ARG)
+        if L["off"] is not None:  # (the slots as they are NOW: they may have been rewritten since the batch)
+            from fuxi_planner_amd import waypoints
+            e["checks"] = [waypoints.check_path(L["cells"][L["off"][q]:L["off"][q + 1]], m.slots[L["ids"][q]], op["shift"]) for q in range(L["nq"])]
     elif k in ("plan_batch_slots", "replan_slots", "jps1_method_many"):
         if k == "jps1_method_many":
             expect(m, {"op": "refresh_grid_slots", "jobs": [[v, c[0]] for v, c in enumerate(op["calls"])]})
@@ -363,6 +530,8 @@ def expect(m, op, oracle=None):
         pass  # (another handle: refused there, nothing here)
     else:
         raise ValueError("unknown op %r" % (k,))
+    if "csr" in e:  # (the paths the batch leaves resident: what the waypoint calls and check_paths_slots run on)
+        m.last["off"], m.last["cells"] = e["csr"][0], e["csr"][1]
     return e
 
 
@@ -384,9 +553,9 @@ EMPTY_SLOTS = (253, 254, 255)  # ... and name these, which nothing writes, where
 
 class _Gen(object):
     def __init__(self, seed, profile):
-        self.rs = np.random.RandomState(1000003 * (PROFILES.index(profile) + 1) + seed)
+        self.rs = np.random.RandomState(1000003 * (ALL_PROFILES.index(profile) + 1) + seed)
         self.profile, self.seed = profile, seed
-        self.m = Model(2 if profile == "two_contexts" else 1)
+        self.m = Model(2 if profile in ("two_contexts", "world_two_contexts") else 1)
         self.ops = []
         self.count = {}
         self.raw = None      # the recipe and arguments of the last prepare / refresh of the resident grid
@@ -612,14 +781,14 @@ class _Gen(object):
 
     def check_job(self, j, world):
         if world:
-            grid, out, w = world_prepared(world_job(j), self.m.prior)
+            grid, out, w = world_prepared(world_job(j), self.m.prior[0]["bytes"] if j["prior"] else None)
         else:
             grid, out = prepared(grid_of(j["raw"]), j["start"], j["goal"], j["ifa"], j["variant"])
         assert all(0 <= out[a][b] < grid.shape[b] for a in (0, 1) for b in (0, 1)) and max(grid.shape) <= 160
 
     def op_slot_jobs(self, kind):
         world = kind.endswith("_world")
-        if world and self.m.prior is None:
+        if world and 0 not in self.m.prior:
             self.emit({"op": "set_prior_map", "prior": 0, "g": self.spec(W=self.ri(5, 40), H=self.ri(5, 40), p=0.1)})
         slots = sorted(self.rs.choice(NSLOTS, self.ri(1, 3), replace=False).tolist())
         jobs = [self.slot_job(s, world) for s in slots]
@@ -971,8 +1140,465 @@ class _Gen(object):
         return self.emit({"op": "jps1_method_many", "calls": calls, "hchoice": self.ri(1, 2)})
 
 
+# ------------------------------------------------------------------ the generator of the world profiles
+WORLD_KINDS = ("set_prior_map", "set_prior_image", "clear_prior_map", "get_prior_map", "prior_origin", "absorb_prior", "absorb_prior_grow",
+               "absorb_prior_slide", "prepare_slots_cropped", "refresh_slots_cropped", "check_paths_slots")
+WORLD_OLD_KINDS = ("prepare_slots_world", "refresh_slots_world", "plan_batch_slots", "replan_slots", "set_slot_reuse", "get_grid_slot", "publish_slots",
+                   "select_slots_batch", "tick_outputs_slots")
+WORLD_REFUSALS = ("prior_not_set", "grow_past_limit", "slide_empty_window", "window_unnamed_prior", "unequal_ori_pre", "world_cleared_prior")
+PRIORS = (0, 1, 15)   # the prior maps the world profiles upload
+UNSET_PRIOR = 7       # ... and one they never do
+MODES = ("overwrite", "occupied", "known")
+USES = ("always", "over_limit", "none")
+
+
+class _WorldGen(_Gen):
+    """The sequences of the world profiles: the shared prior maps and every call that reads them.  Everything lies on the
+    lattice ORI_PRE + R * integers, so every quotient of the references' arithmetic is exact."""
+
+    def __init__(self, seed, profile):
+        _Gen.__init__(self, seed, profile)
+        self.cleared = set()  # priors released and not uploaded again
+        self.cropped = {}     # slot -> whether its last job was a cropped one
+
+    # -- geometry
+    def xy(self, c):
+        return [ORI_PRE[0] + c[0] * R, ORI_PRE[1] + c[1] * R]
+
+    def cell_xy(self, o):
+        return [int(round((o[0] - ORI_PRE[0]) / R)), int(round((o[1] - ORI_PRE[1]) / R))]
+
+    def raw_spec(self, p=None):
+        sp = self.spec(W=self.ri(3, 24), H=self.ri(3, 24), p=float(self.rs.choice([0.0, 0.05, 0.2, 0.5])) if p is None else p)
+        return self.changed(sp, self.ri(0, 3), (0, 1, 7, 255))  # (bytes other than 0 / 1: every one an obstacle)
+
+    def place(self, p, w, h, where=None):
+        """Where (cells from ORI_PRE) a w x h raw lies relative to prior p, per axis: inside, across the low or the high
+        edge, or wholly outside on either side."""
+        d = self.m.prior[p]
+        c, ext, at = self.cell_xy(d["origin"]), d["bytes"].shape, []
+        for k, n in enumerate((w, h)):
+            kind = where[k] if where else str(self.rs.choice(["in", "in", "lo", "hi", "out_lo", "out_hi"]))
+            if kind == "in":
+                at.append(c[k] + self.ri(0, max(ext[k] - n, 0)))
+            elif kind == "lo":
+                at.append(c[k] - self.ri(1, max(n - 1, 1)))
+            elif kind == "hi":
+                at.append(c[k] + ext[k] - self.ri(1, max(n - 1, 1)))
+            elif kind == "out_lo":
+                at.append(c[k] - n - self.ri(0, 4))
+            else:
+                at.append(c[k] + ext[k] + self.ri(0, 4))
+        return at
+
+    # -- priors
+    def op_set_prior(self, p=None, image=None, big=False):
+        p = PRIORS[self.ri(0, 2)] if p is None else p
+        image = bool(self.rs.random_sample() < 0.3) if image is None else image
+        origin = self.xy([self.ri(-8, 8), self.ri(-8, 8)])
+        lo = 25 if big else 5
+        self.cleared.discard(p)
+        if image:
+            return self.emit({"op": "set_prior_image", "prior": p, "gray": {"rows": self.ri(lo, 40), "cols": self.ri(lo, 40), "seed": self.ri(0, 2 ** 30)},
+                              "origin": origin})
+        return self.emit({"op": "set_prior_map", "prior": p, "g": self.spec(W=self.ri(lo, 40), H=self.ri(lo, 40), p=float(self.rs.choice([0.05, 0.1, 0.3]))),
+                          "origin": origin})
+
+    def a_prior(self):
+        """A prior that is set (one is uploaded when none is)."""
+        if not self.m.prior:
+            self.op_set_prior(image=False)
+        live = sorted(self.m.prior)
+        return live[self.ri(0, len(live) - 1)]
+
+    def pjob(self, p, where=None, dens=None, crop=0.0):
+        """A fold's job on prior p.  crop: the share of jobs absorbed through a crop record (the window of the message's
+        occupied cells and a vehicle's cell) where the message has such a window."""
+        sp = self.raw_spec(dens)
+        j = {"prior": p, "raw": sp, "msg": bool(self.ri(0, 1)), "at": self.place(p, sp["W"], sp["H"], where), "ori": list(self.m.prior[p]["origin"])}
+        if self.rs.random_sample() < crop:
+            j["crop"] = [self.ri(0, sp["W"] - 1), self.ri(0, sp["H"] - 1)]
+            try:
+                crops_of([j])
+            except ValueError:
+                del j["crop"]
+        return j
+
+    def fits(self, op):
+        try:
+            fold_of(self.m.prior_bytes(), op)
+        except ValueError:
+            return False
+        return True
+
+    def around(self, jobs, margin=None, open_side=True):
+        """Keep windows around the jobs of each prior they name: [lo_xy, hi_xy] in world metres, None for an infinite bound."""
+        keep = {}
+        for p in sorted({j["prior"] for j in jobs}):
+            mine = [j for j in jobs if j["prior"] == p]
+            mg = self.ri(0, 6) if margin is None else margin
+            lo = self.xy([min(j["at"][k] for j in mine) - mg for k in range(2)])
+            hi = self.xy([max(j["at"][k] + (j["raw"]["W"], j["raw"]["H"])[k] for j in mine) + mg for k in range(2)])
+            if open_side and self.rs.random_sample() < 0.4:
+                (lo if self.ri(0, 1) else hi)[self.ri(0, 1)] = None
+            keep[p] = [lo, hi]
+        return keep
+
+    def op_absorb(self, kind, jobs=None, **kw):
+        """One absorb / grow / slide call that the library accepts (drawn again until the host reference accepts it)."""
+        for _ in range(40):
+            js = [self.pjob(self.a_prior(), crop=0.35) for _ in range(self.ri(1, 3))] if jobs is None else jobs
+            op = {"op": kind, "jobs": js, "mode": kw.get("mode") or MODES[self.ri(0, 2)]}
+            if kind != "absorb_prior":
+                op["limit"] = kw.get("limit") or self.ri(48, 96)
+            if kind == "absorb_prior_slide":
+                op["keep"] = kw["keep"] if "keep" in kw else {p: w for p, w in self.around(js).items() if self.rs.random_sample() < 0.8}
+                op["use"] = kw.get("use") or USES[int(self.rs.choice([0, 0, 1, 1, 2]))]
+            if self.fits(op):
+                return self.emit(op)
+            if jobs is not None:
+                raise AssertionError("the forced %s is refused: %r" % (kind, op))
+            if kind != "absorb_prior" and len(self.m.prior) and self.rs.random_sample() < 0.3:
+                self.op_set_prior(self.a_prior(), image=False)  # (a prior that has outgrown every limit is uploaded anew)
+        raise AssertionError("no acceptable %s drawn" % kind)
+
+    # -- world-frame and cropped jobs
+    def job_ok(self, j, cropped=False, priors=None):
+        priors = self.m.prior_bytes() if priors is None else priors
+        try:
+            wj = world_job(j)
+            if cropped:
+                grid, out, w, tail = crop_prepared(wj, priors)
+                if grid is None:
+                    return True
+            else:
+                grid, out, w = world_prepared(wj, named_prior(priors, wj))
+        except (IndexError, ValueError):
+            return False
+        return all(0 <= out[a][b] < grid.shape[b] for a in (0, 1) for b in (0, 1)) and max(grid.shape) <= 160
+
+    def wjob(self, slot, p="draw", where=None, ori=None, cropped=False, dens=None):
+        """A world or cropped job whose preparation succeeds on the priors as they are.  ori: the origin it carries (None:
+        the one the model holds now)."""
+        for _ in range(80):
+            pp = (self.a_prior() if self.rs.random_sample() < 0.8 else None) if p == "draw" else p
+            sp = self.raw_spec(float(self.rs.choice([0.0, 0.05, 0.2])) if dens is None else dens)
+            W, H = sp["W"], sp["H"]
+            j = {"slot": slot, "raw": sp, "msg": bool(self.ri(0, 1)), "start": [self.ri(0, W - 1), self.ri(0, H - 1)],
+                 "goal": [self.ri(0, W - 1), self.ri(0, H - 1)], "ifa": self.ri(0, 2), "variant": self.ri(0, 1), "prior": pp,
+                 "at": self.place(pp, W, H, where) if pp is not None else [self.ri(-20, 20), self.ri(-20, 20)],
+                 "ori": None if pp is None else list(self.m.prior[pp]["origin"]) if ori is None else list(ori)}
+            if cropped:
+                r = self.rs.random_sample()
+                if r < 0.12:
+                    j["start"][self.ri(0, 1)] = -2  # (the vehicle left of or below the message: the job is refused on its own)
+                elif r < 0.22:
+                    j["raw"] = dict(sp, p=0.0, set=[])  # (no occupied cell: not planned)
+            if self.job_ok(j, cropped):
+                return j
+        raise AssertionError("no preparable world job drawn")
+
+    def op_world_jobs(self, kind, slots=None, jobs=None):
+        cropped = kind.endswith("_cropped")
+        if jobs is None:
+            slots = sorted(self.rs.choice(NSLOTS, self.ri(1, 3), replace=False).tolist()) if slots is None else slots
+            jobs = []
+            for s in slots:
+                old, j = self.slot_raw.get(s), None
+                r = self.rs.random_sample()
+                if kind.startswith("refresh") and old is not None and self.cropped.get(s) == cropped and r < 0.7 and (old["prior"] is None or old["prior"] in self.m.prior):
+                    # (the slot's last job again, as it was or with a few cells changed, at the prior's present origin)
+                    j = dict(old, ori=None if old["prior"] is None else list(self.m.prior[old["prior"]]["origin"]))
+                    if r < 0.25:
+                        j["raw"] = self.changed(old["raw"], self.ri(1, 3))
+                    j = j if self.job_ok(j, cropped) else None
+                jobs.append(j or self.wjob(s, cropped=cropped))
+        for j in jobs:
+            self.slot_raw[j["slot"]] = j
+            self.cropped[j["slot"]] = cropped
+        return self.emit({"op": kind, "jobs": jobs})
+
+    def slots_live(self, n=2):
+        while len(self.m.slots) < n:
+            self.op_world_jobs("prepare_slots_world", slots=[s for s in range(NSLOTS) if s not in self.m.slots][:2])
+
+    def replan_naming(self, slot):
+        """A new replan_slots whose first query runs on `slot`."""
+        live = sorted(self.m.slots)
+        ids = [slot] + [live[self.ri(0, len(live) - 1)] for _ in range(self.ri(1, 5))]
+        s, g = self.queries([self.m.slots[i] for i in ids], len(ids))
+        self.last_replan = {"ids": ids, "s": s, "g": g, "hchoice": self.ri(1, 2), "mpl": 400}
+        return self.emit(dict(self.last_replan, op="replan_slots"))
+
+    def op_check_paths(self, shift="draw"):
+        L = self.m.last
+        if L is None or L["kind"] != "slots" or L["nq"] < 1:
+            self.slots_live()
+            self.op_plan_batch_slots()
+        if shift == "draw":
+            shift = None if self.rs.random_sample() < 0.5 else [self.ri(-2, 2), self.ri(-2, 2)]
+        return self.emit({"op": "check_paths_slots", "shift": shift})
+
+    # -- refusals
+    def op_refusal(self, which):
+        self.count["refused: " + which] = self.count.get("refused: " + which, 0) + 1
+        p = self.a_prior()
+        kind = str(self.rs.choice(["absorb_prior", "absorb_prior_grow", "absorb_prior_slide"]))
+        extra = {"limit": 96, "keep": {}, "use": "none"}
+        if which == "prior_not_set":
+            unset = [q for q in PRIORS if q not in self.m.prior] + [UNSET_PRIOR]
+            jobs = [self.pjob(p), dict(self.pjob(p), prior=unset[0])]
+            return self.emit(dict(extra, op=kind, jobs=jobs[self.ri(0, 1):], mode=MODES[self.ri(0, 2)]))
+        if which == "grow_past_limit":  # (no window: a side above the limit refuses the call)
+            j = self.pjob(p)
+            k = self.ri(0, 1)
+            j["at"][k] = self.cell_xy(self.m.prior[p]["origin"])[k] + self.m.prior[p]["bytes"].shape[k] + self.ri(60, 90)
+            kind = str(self.rs.choice(["absorb_prior_grow", "absorb_prior_slide"]))
+            return self.emit(dict(extra, op=kind, jobs=[self.pjob(p, ("in", "in")), j], mode=MODES[self.ri(0, 2)], limit=self.ri(48, 96)))
+        if which == "slide_empty_window":
+            j = self.pjob(p, ("in", "in"))
+            far = self.xy([j["at"][0] - 400, j["at"][1]])
+            return self.emit({"op": "absorb_prior_slide", "jobs": [j], "mode": MODES[self.ri(0, 2)], "limit": 96,
+                              "keep": {p: [[far[0], None], [far[0] + 2 * R, None]]}, "use": "always"})
+        if which == "window_unnamed_prior":
+            j = self.pjob(p, ("in", "in"))
+            other = [q for q in PRIORS if q != p][self.ri(0, 1)]
+            return self.emit({"op": "absorb_prior_slide", "jobs": [j], "mode": MODES[self.ri(0, 2)], "limit": 96,
+                              "keep": {**self.around([j], open_side=False), other: [[None, None], [None, None]]}, "use": "always"})
+        if which == "unequal_ori_pre":
+            a, b = self.pjob(p, ("in", "in")), self.pjob(p, ("in", "in"))
+            b["ori"] = [b["ori"][0] + R, b["ori"][1]]
+            kind = str(self.rs.choice(["absorb_prior_grow", "absorb_prior_slide"]))
+            return self.emit(dict(extra, op=kind, jobs=[a, b], mode=MODES[self.ri(0, 2)]))
+        # a world job that names a prior after its clear_prior_map
+        if not self.cleared:
+            self.emit({"op": "clear_prior_map", "prior": p})
+            self.cleared.add(p)
+        q = sorted(self.cleared)[0]
+        self.slots_live()
+        sp = self.raw_spec(0.05)
+        j = {"slot": self.ri(0, NSLOTS - 1), "raw": sp, "msg": False, "start": [0, 0], "goal": [sp["W"] - 1, sp["H"] - 1], "ifa": 1, "variant": 0, "prior": q,
+             "at": [self.ri(-8, 8), self.ri(-8, 8)], "ori": self.xy([0, 0])}
+        return self.emit({"op": str(self.rs.choice(["prepare_slots_world", "refresh_slots_world", "prepare_slots_cropped"])), "jobs": [j]})
+
+    # -- the orders every sequence holds
+    def forced(self):
+        for p in PRIORS:
+            self.op_set_prior(p, image=(p == 15))
+        self.op_world_jobs("prepare_slots_world", slots=[0, 1])
+        self.op_world_jobs("prepare_slots_world", slots=[2, 3])
+        self.op_replan_slots(fresh=True)
+
+    def changing_absorb(self, p, judge):
+        """An absorb_prior record on prior p (cells inside it, mostly occupied) for which judge(the priors afterwards) holds."""
+        for _ in range(60):
+            op = {"op": "absorb_prior", "jobs": [self.pjob(p, ("in", "in"), dens=float(self.rs.choice([0.5, 0.9])))], "mode": MODES[self.ri(0, 1)]}
+            after, _, ret = fold_of(self.m.prior_bytes(), op)
+            if ret[1][p] > 0 and judge({**self.m.prior_bytes(), **after}):
+                return op
+        raise AssertionError("no absorb drawn that changes what it has to")
+
+    def seq_prior_changes_under_a_slot(self, tiles=False):
+        """A slot prepared from a prior, its queries stored, the prior rewritten under it by an absorb: the replan hands
+        every path back (no slot was touched); the refresh with the SAME job is not kept; the replan then searches."""
+        if tiles != bool(self.m.mode):
+            self.emit({"op": "set_slot_reuse", "mode": "tiles" if tiles else "generation"})
+        p = PRIORS[self.ri(0, 2)]
+        self.op_set_prior(p, image=False, big=True)  # (larger than every raw: some of its cells lie on the canvas beside the raw)
+        slot = self.ri(0, NSLOTS - 1)
+        j = self.wjob(slot, p, ("in", "in"))
+        self.op_world_jobs("prepare_slots_world", jobs=[j])
+        self.replan_naming(slot)
+
+        def differs(priors):
+            if not self.job_ok(j, priors=priors):
+                return False
+            grid = world_prepared(world_job(j), priors[p])[0]
+            return grid.shape != self.m.slots[slot].shape or not np.array_equal(grid, self.m.slots[slot])
+        self.emit(self.changing_absorb(p, differs))
+        self.op_replan_slots(fresh=False, move=0.0)
+        self.op_world_jobs("refresh_slots_world", jobs=[dict(j)])
+        self.op_replan_slots(fresh=False, move=0.0)
+
+    def seq_absorb_elsewhere(self):
+        """An absorb that changes another prior only: the replan hands every path back, the refresh with the same job is kept."""
+        p0 = self.a_prior()
+        p1 = [q for q in PRIORS if q != p0][self.ri(0, 1)]
+        if p1 not in self.m.prior:
+            self.op_set_prior(p1, image=False)
+        slot = self.ri(0, NSLOTS - 1)
+        j = self.wjob(slot, p0)
+        self.op_world_jobs(str(self.rs.choice(["prepare_slots_world", "refresh_slots_world"])), jobs=[j])
+        self.replan_naming(slot)
+        self.emit(self.changing_absorb(p1, lambda priors: True))
+        self.op_replan_slots(fresh=False, move=0.0)
+        self.op_world_jobs("refresh_slots_world", jobs=[dict(j)])
+        self.op_replan_slots(fresh=False, move=0.0)
+
+    def seq_grow_moves_origin(self):
+        """A grow that moves a prior's origin between two equal replans; jobs with the new and with the upload's origin;
+        then the prior uploaded again: the moved origin is forgotten."""
+        p = PRIORS[self.ri(0, 2)]
+        self.op_set_prior(p, image=False)
+        self.slots_live()
+        self.op_replan_slots(fresh=True)
+        k = self.ri(0, 1)
+        where = [None, None]
+        where[k], where[1 - k] = str(self.rs.choice(["lo", "out_lo"])), str(self.rs.choice(["in", "hi", "lo"]))
+        self.op_absorb("absorb_prior_grow", [self.pjob(p, where), self.pjob(p)], limit=96)
+        self.op_replan_slots(fresh=False, move=0.0)
+        self.emit({"op": "prior_origin", "prior": p})
+        slot = self.ri(0, NSLOTS - 1)
+        try:  # (legal for prepare_slots_world: merge_host's result at that origin, where the two rectangles fit its canvas)
+            self.op_world_jobs("prepare_slots_world", jobs=[self.wjob(slot, p, ori=self.m.prior[p]["upload"])])
+        except AssertionError:
+            pass
+        self.op_world_jobs("prepare_slots_world", jobs=[self.wjob((slot + 1) % NSLOTS, p)])
+        self.op_set_prior(p, image=bool(self.ri(0, 1)))
+        self.emit({"op": "prior_origin", "prior": p})
+        self.emit({"op": "get_prior_map", "prior": p})
+
+    def seq_refused_grow_between_two(self):
+        p = PRIORS[self.ri(0, 2)]
+        self.op_set_prior(p, image=False)
+        self.op_absorb("absorb_prior_grow", [self.pjob(p, ("hi", "in"))], limit=96)
+        self.op_refusal("grow_past_limit")
+        self.op_absorb("absorb_prior_grow", [self.pjob(p, ("in", "lo"))], limit=96)
+
+    def seq_slides(self):
+        """A slide that always cuts cells off the low side; an over_limit slide within the limit (not trimmed); one past
+        it (trimmed to the window around its job); a slot prepared from the prior that slid."""
+        p = PRIORS[self.ri(0, 2)]
+        self.op_set_prior(p, image=False, big=True)
+        c = self.cell_xy(self.m.prior[p]["origin"])
+        k = self.ri(0, 1)
+        lo = [None, None]
+        lo[k] = self.xy([c[0] + self.ri(1, 4), c[1] + self.ri(1, 4)])[k]
+        self.op_absorb("absorb_prior_slide", [self.pjob(p, ("in", "in"))], limit=96, keep={p: [lo, [None, None]]}, use="always")
+        js = [self.pjob(p, ("in", "in")), self.pjob(p, ("in", "in"))]
+        self.op_absorb("absorb_prior_slide", js, limit=96, keep=self.around(js), use="over_limit")
+        far = self.pjob(p)
+        c, ext = self.cell_xy(self.m.prior[p]["origin"]), self.m.prior[p]["bytes"].shape
+        far["at"] = [c[0] + ext[0] + self.ri(30, 50), c[1] + self.ri(-3, 3)]
+        self.op_absorb("absorb_prior_slide", [far], limit=48, keep=self.around([far], margin=self.ri(1, 8), open_side=False), use="over_limit")
+        self.emit({"op": "prior_origin", "prior": p})
+        self.op_world_jobs("prepare_slots_world", jobs=[self.wjob(self.ri(0, NSLOTS - 1), p)])
+
+    def seq_slide_grow_absorb(self):
+        """Slide, then grow, then absorb on ONE prior, each at the origin the call before left, the other priors untouched
+        in between; then a slot prepared from it."""
+        p = self.a_prior()
+        if max(self.m.prior[p]["bytes"].shape) > 40:
+            self.op_set_prior(p, image=False)
+        js = [self.pjob(p, crop=0.5), self.pjob(p)]
+        self.op_absorb("absorb_prior_slide", js, limit=96, keep=self.around(js, open_side=False), use="always")
+        self.op_absorb("absorb_prior_grow", [self.pjob(p, (str(self.rs.choice(["lo", "hi"])), "in"))], limit=96)
+        self.op_absorb("absorb_prior", [self.pjob(p, crop=0.5), self.pjob(p, ("in", "in"), dens=0.5)])
+        kind = str(self.rs.choice(["prepare_slots_world", "prepare_slots_cropped"]))
+        self.op_world_jobs(kind, jobs=[self.wjob(self.ri(0, NSLOTS - 1), p, cropped=kind.endswith("_cropped"))])
+
+    def seq_cleared_prior(self):
+        p = self.a_prior()
+        self.emit({"op": "clear_prior_map", "prior": p})
+        self.cleared.add(p)
+        self.op_refusal("world_cleared_prior")
+        self.emit({"op": "prior_origin", "prior": p})
+        self.op_set_prior(p)
+
+    def seq_check_paths(self):
+        """The paths of a slots batch judged on the slots as they are now: as the batch left them, with one of them
+        rewritten (denser), moved by a small and by a large shift; the resident paths are still the batch's afterwards."""
+        self.slots_live(3)
+        self.op_plan_batch_slots() if self.ri(0, 1) else self.op_replan_slots(fresh=True)
+        self.op_check_paths(None)
+        ids = self.m.last["ids"]
+        self.op_world_jobs("prepare_slots_world", jobs=[self.wjob(ids[self.ri(0, len(ids) - 1)], dens=float(self.rs.choice([0.35, 0.5])))])
+        self.op_check_paths(None)
+        self.op_check_paths([self.ri(-1, 1), self.ri(1, 2)])
+        self.op_check_paths([self.ri(150, 300), 0])
+        self.op_wp("select_slots_batch")
+
+    def step(self):
+        r = self.rs.random_sample()
+        self.slots_live()
+        if r < 0.05:
+            return self.op_refusal(WORLD_REFUSALS[self.ri(0, len(WORLD_REFUSALS) - 1)])
+        if r < 0.11:
+            return self.op_set_prior()
+        if r < 0.13:
+            if len(self.m.prior) < 2:
+                return self.op_set_prior()
+            p = self.a_prior()
+            self.cleared.add(p)
+            return self.emit({"op": "clear_prior_map", "prior": p})
+        if r < 0.21:
+            return self.op_absorb("absorb_prior")
+        if r < 0.28:
+            return self.op_absorb("absorb_prior_grow")
+        if r < 0.35:
+            return self.op_absorb("absorb_prior_slide")
+        if r < 0.39:
+            return self.emit({"op": str(self.rs.choice(["get_prior_map", "prior_origin"])), "prior": self.a_prior()})
+        if r < 0.48:
+            return self.op_world_jobs(str(self.rs.choice(["prepare_slots_cropped", "refresh_slots_cropped"])))
+        if r < 0.50:
+            return self.op_check_paths()
+        if r < 0.60:
+            return self.op_world_jobs(str(self.rs.choice(["prepare_slots_world", "refresh_slots_world"])))
+        if r < 0.64:
+            return self.op_plan_batch_slots()
+        if r < 0.76:
+            return self.op_replan_slots()
+        if r < 0.79:
+            return self.emit({"op": "set_slot_reuse", "mode": str(self.rs.choice(["generation", "tiles"]))})
+        if r < 0.85:
+            return self.op_readback(str(self.rs.choice(["publish_slots", "get_grid_slot"])))
+        if r < 0.93:
+            return self.op_wp(str(self.rs.choice(["select_slots_batch", "tick_outputs_slots"])))
+        return self.op_replan_slots(fresh=False if getattr(self, "last_replan", None) is not None else None)
+
+
+def _generate_world(seed, n_steps, profile):
+    g = _WorldGen(seed, profile)
+    g.forced()
+    seqs = [lambda: g.seq_prior_changes_under_a_slot(False), lambda: g.seq_prior_changes_under_a_slot(True), g.seq_absorb_elsewhere, g.seq_slide_grow_absorb,
+            g.seq_grow_moves_origin, g.seq_refused_grow_between_two, g.seq_slides, g.seq_cleared_prior, g.seq_check_paths, g.seq_check_paths]
+    order = g.rs.permutation(len(seqs)).tolist()
+    marks = sorted(g.rs.choice(np.arange(6, max(n_steps - 10, 20)), len(seqs), replace=False).tolist())
+    which = 0
+    while len(g.ops) < n_steps or which < len(seqs):
+        if which < len(seqs) and (len(g.ops) >= marks[which] or len(g.ops) >= n_steps):
+            seqs[order[which]]()
+            which += 1
+            continue
+        g.step()
+    # the closing round: every refusal once, every kind three times, whatever was drawn
+    closing = {"set_prior_map": lambda: g.op_set_prior(image=False), "set_prior_image": lambda: g.op_set_prior(image=True),
+               "clear_prior_map": lambda: (g.cleared.add(g.a_prior()), g.emit({"op": "clear_prior_map", "prior": sorted(g.cleared & set(g.m.prior))[0]})),
+               "get_prior_map": lambda: g.emit({"op": "get_prior_map", "prior": g.a_prior()}), "prior_origin": lambda: g.emit({"op": "prior_origin", "prior": g.a_prior()}),
+               "absorb_prior": lambda: g.op_absorb("absorb_prior"), "absorb_prior_grow": lambda: g.op_absorb("absorb_prior_grow"),
+               "absorb_prior_slide": lambda: g.op_absorb("absorb_prior_slide"), "prepare_slots_cropped": lambda: g.op_world_jobs("prepare_slots_cropped"),
+               "refresh_slots_cropped": lambda: g.op_world_jobs("refresh_slots_cropped"), "check_paths_slots": g.op_check_paths,
+               "prepare_slots_world": lambda: g.op_world_jobs("prepare_slots_world"), "refresh_slots_world": lambda: g.op_world_jobs("refresh_slots_world"),
+               "plan_batch_slots": lambda: (g.slots_live(), g.op_plan_batch_slots()), "replan_slots": lambda: (g.slots_live(), g.op_replan_slots()),
+               "set_slot_reuse": lambda: g.emit({"op": "set_slot_reuse", "mode": ["generation", "tiles"][g.ri(0, 1)]}),
+               "publish_slots": lambda: (g.slots_live(), g.op_readback("publish_slots")), "get_grid_slot": lambda: (g.slots_live(), g.op_readback("get_grid_slot")),
+               "select_slots_batch": lambda: (g.slots_live(), g.op_wp("select_slots_batch")), "tick_outputs_slots": lambda: (g.slots_live(), g.op_wp("tick_outputs_slots"))}
+    for which in WORLD_REFUSALS:
+        if g.count.get("refused: " + which, 0) < 1:
+            g.op_refusal(which)
+    for kind in kinds_of(profile):
+        for _ in range(50):
+            if g.count.get(kind, 0) >= 3:
+                break
+            closing[kind]()
+    return g.ops
+
+
 def generate(seed, n_steps, profile):
     """-> the op records of sequence `seed` of `profile`: a function of its arguments alone."""
+    if profile in WORLD_PROFILES:
+        return _generate_world(seed, n_steps, profile)
     g = _Gen(seed, profile)
     g.forced()
     if profile == "tiles":
@@ -1016,6 +1642,8 @@ def generate(seed, n_steps, profile):
 
 def kinds_of(profile):
     """The op kinds a sequence of `profile` holds at least three times each."""
+    if profile in WORLD_PROFILES:
+        return list(WORLD_KINDS + WORLD_OLD_KINDS)
     out = [k for k in KINDS if k != "set_slot_reuse" or profile == "tiles"]
     return out + (["jps1_method", "jps1_method_many"] if profile == "shim" else [])
 
@@ -1135,10 +1763,20 @@ def execute(p, op, wp, fresh):
         jobs = [slot_job(j) for j in op["jobs"]]
         jobs = [(j[0], (msg_of(r["raw"]), r["raw"]["W"], r["raw"]["H"])) + j[2:] if r["raw"]["seed"] % 2 else j for j, r in zip(jobs, op["jobs"])]
         return getattr(p, k)(jobs)
-    if k in ("prepare_slots_world", "refresh_slots_world"):
+    if k in ("prepare_slots_world", "refresh_slots_world", "prepare_slots_cropped", "refresh_slots_cropped"):
         return getattr(p, k)([world_job(j) for j in op["jobs"]])
     if k == "set_prior_map":
         return p.set_prior_map(op["prior"], grid_of(op["g"]))
+    if k == "set_prior_image":
+        return p.set_prior_image(op["prior"], gray_of(op["gray"]))
+    if k in ("clear_prior_map", "get_prior_map", "prior_origin"):
+        return getattr(p, k)(op["prior"])
+    if k == "absorb_prior":
+        return p.absorb_prior([prior_job(j) for j in op["jobs"]], op["mode"], crops_of(op["jobs"]))
+    if k == "absorb_prior_grow":
+        return p.absorb_prior_grow([prior_job(j) for j in op["jobs"]], op["mode"], crops_of(op["jobs"]), op["limit"])
+    if k == "absorb_prior_slide":
+        return p.absorb_prior_slide([prior_job(j) for j in op["jobs"]], op["mode"], crops_of(op["jobs"]), op["limit"], keep_of(op), op["use"])
     if k in ("plan_batch_slots", "replan_slots"):
         out = getattr(p, k)(op["ids"], op["s"], op["g"], op["hchoice"], op["mpl"])
         return (out, p.timing()["reused"]) if k == "replan_slots" else out
@@ -1208,6 +1846,8 @@ def _step(p, wp, m, op, i, oracle, fresh, contexts):
         if k in ("select_st_batch", "select_ccst_batch", "select_slots_batch", "tick_outputs_slots"):
             slots_form = k in ("select_slots_batch", "tick_outputs_slots")
             got = None if refused is None else call_wp(wp, op, op["nq"], (np.zeros(op["nq"] + 1, np.int64), None) if slots_form else None)
+        elif k == "check_paths_slots":  # (the explicit paths of the last slots batch: the generator draws the op only after one)
+            got = p.check_paths_slots(before_last["ids"], before_last["off"], before_last["cells"], op["shift"])
         else:
             got = execute(p, op, wp, fresh)
         raised = None
@@ -1221,6 +1861,7 @@ def _step(p, wp, m, op, i, oracle, fresh, contexts):
         assert type(raised).__name__ == refused.kind and (refused.code is None or getattr(raised, "code", None) == refused.code), \
             "refused with %r, expected %s %r" % (raised, refused.kind, refused.code)
         assert m.last is before_last
+        _check_priors(p, m, op, i, True)
         return
     if k in ("plan", "jps1_method") and e["csr"][3][0] < 0:
         want = IndexError if e["csr"][3][0] == Q_BAD_START else RuntimeError
@@ -1284,11 +1925,40 @@ def _step(p, wp, m, op, i, oracle, fresh, contexts):
     elif k == "refresh_grid_slots":
         assert list(got) == e["kept"], "kept %r, expected %r" % (list(got), e["kept"])
         wrote_slots = tuple(s for s, g in op["jobs"])
-    elif k in ("prepare_slots", "refresh_slots", "prepare_slots_world", "refresh_slots_world"):
+    elif k in ("prepare_slots", "refresh_slots", "prepare_slots_world", "refresh_slots_world", "prepare_slots_cropped", "refresh_slots_cropped"):
         assert len(got) == len(e["outs"])
         for j, (a, b) in enumerate(zip(got, e["outs"])):
             assert same(tuple(a), tuple(b)), "job %d: outputs %r, the host's %r" % (j, a, b)
         wrote_slots = tuple(j["slot"] for j in op["jobs"])
+        for s in wrote_slots:
+            if s not in m.slots:  # (a cropped job that was not planned or refused on its own leaves its slot empty)
+                try:
+                    p.get_grid_slot(s)
+                except Exception as ex:  # noqa: BLE001
+                    assert type(ex).__name__ == "FxjpsError" and ex.code == E_ARG, "slot %d must be empty: get_grid_slot raised %r" % (s, ex)
+                else:
+                    raise AssertionError("slot %d must be empty after a job that took no part in the call" % s)
+    elif k == "prior_origin":
+        want = m.prior[op["prior"]]["origin"] if op["prior"] in m.prior and m.prior[op["prior"]]["moved"] else None
+        assert same(got, want), "prior_origin(%d) is %r, expected %r" % (op["prior"], got, want)
+    elif k == "get_prior_map":
+        want = m.prior[op["prior"]]["bytes"]
+        assert got.shape == want.shape and same(got, want), "prior %d: %r bytes differ from the model's %r" % (op["prior"], got.shape, want.shape)
+    elif k in ("absorb_prior", "absorb_prior_grow", "absorb_prior_slide"):
+        assert len(got) == 2 and same(list(got[0]), list(e["ret"][0])), "per job %r, the host's %r" % (got[0], e["ret"][0])
+        assert sorted(got[1]) == sorted(e["ret"][1]), "priors named %r, expected %r" % (sorted(got[1]), sorted(e["ret"][1]))
+        for q in sorted(got[1]):
+            if isinstance(got[1][q], dict):
+                for f in sorted(e["ret"][1][q]):
+                    assert same(got[1][q][f], e["ret"][1][q][f]), "prior %d: %s %r, the host's %r" % (q, f, got[1][q][f], e["ret"][1][q][f])
+            else:
+                assert got[1][q] == e["ret"][1][q], "prior %d: changed %r, the host's %r" % (q, got[1][q], e["ret"][1][q])
+    elif k == "check_paths_slots":
+        verdict, seg, cell = got
+        for q, (v, sg, c) in enumerate(e["checks"]):
+            assert (int(verdict[q]), int(seg[q]), (int(cell[q][0]), int(cell[q][1]))) == (v, sg, c), \
+                "path %d on slot %d: %r, check_path on the slot's bytes %r" % (q, m.last["ids"][q], (int(verdict[q]), int(seg[q]), cell[q].tolist()), (v, sg, c))
+        assert m.last is before_last
     elif k == "plan_batch_slots":
         _csr_equal(got, e["csr"], k)
     elif k in ("replan_slots", "jps1_method_many"):
@@ -1340,6 +2010,8 @@ def _step(p, wp, m, op, i, oracle, fresh, contexts):
     if "csr" in e:
         m.last["off"], m.last["cells"] = e["csr"][0], e["csr"][1]
 
+    _check_priors(p, m, op, i, False)
+
     # the derived maps: after every write, and every 8th step whatever the op was
     if wrote_grid or (i % 8 == 7 and m.grid is not None):
         check_maps(p.debug_maps(), m.grid, "resident maps", exact=m.whole, ever_free=m.ever_free)
@@ -1351,6 +2023,34 @@ def _step(p, wp, m, op, i, oracle, fresh, contexts):
                 occ, maps = p.debug_slot_context(c, s)
                 assert same(occ, m.slots[s]), "slot %d on context %d: bytes differ" % (s, c)
                 check_maps(maps, m.slots[s], "maps of slot %d on context %d" % (s, c))
+
+
+PRIOR_WRITERS = ("set_prior_map", "set_prior_image", "clear_prior_map", "absorb_prior", "absorb_prior_grow", "absorb_prior_slide")
+
+
+def _check_priors(p, m, op, i, refused):
+    """prior_origin of every prior the op names; get_prior_map of EVERY set prior (the unnamed ones too) after an op that
+    writes a prior or is refused on one, and on every 8th step; a named prior that is not set must be refused."""
+    k = op["op"]
+    named = {op["prior"]} if "prior" in op else set()
+    named |= {j["prior"] for j in op.get("jobs", ()) if isinstance(j, dict) and "ori" in j and j["prior"] is not None}
+    for q in sorted(named):
+        want = m.prior[q]["origin"] if q in m.prior and m.prior[q]["moved"] else None
+        got = p.prior_origin(q)
+        assert same(got, want), "prior_origin(%d) is %r, expected %r" % (q, got, want)
+    if not (k in PRIOR_WRITERS or (refused and named) or (i % 8 == 7 and m.prior)):
+        return
+    for q, d in sorted(m.prior.items()):
+        got = p.get_prior_map(q)
+        assert got.shape == d["bytes"].shape, "prior %d has %r cells, the model's %r" % (q, got.shape, d["bytes"].shape)
+        assert same(got, d["bytes"]), "prior %d: bytes differ from the model's at %r" % (q, np.argwhere(got != d["bytes"])[:5].tolist())
+    for q in sorted(named - set(m.prior)):
+        try:
+            p.get_prior_map(q)
+        except Exception as ex:  # noqa: BLE001
+            assert type(ex).__name__ == "FxjpsError" and ex.code == E_ARG, "get_prior_map(%d) raised %r" % (q, ex)
+        else:
+            raise AssertionError("prior %d must not be set" % q)
 
 
 def _refresh_flags(out5, changed, mode, cells, e):

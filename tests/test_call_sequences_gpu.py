@@ -13,13 +13,21 @@ and checked for coverage.
 Profiles: `single` -- Planner([0]), the generation rule; `tiles` -- the same with set_slot_reuse among the ops;
 `two_contexts` -- Planner([0, 0]): replan_slots is a plain batch, every flag 0, context 1's copies are read as well;
 `shim` -- the ops run on default_planner() with jps1.method and jps1.method_many among them, the printed costs compared
-as test_gpu_parity.py compares them.
+as test_gpu_parity.py compares them; `world` -- Planner([0]) and `world_two_contexts` -- Planner([0, 0]): the shared
+prior maps (set_prior_map / set_prior_image / clear_prior_map, absorb_prior, absorb_prior_grow, absorb_prior_slide with keep
+windows and limits of 48 .. 96 cells, get_prior_map, prior_origin), the cropped prepares and check_paths_slots among the
+world-frame prepares, replans, read-backs and waypoint calls they interact with.  There every set prior is read back
+after each call that writes or is refused on one, the outputs and records of the folds are worldprep's host references'
+field by field, and context 1's copy of a prior shows through the slots prepared from it, whose bytes and derived maps
+are read on context 1 after every slot write.  No sequence of these two profiles has failed on the library so far.
 
 A failure names seed, step and the ops up to it as Python literals; `replay(ops)` below runs such a list.
 
 Per-test times on an MI355X (pytest's call durations; a sequence is 120 drawn steps plus the forced and the closing
 ops): single 0.42 - 0.70 s, tiles 0.41 - 0.53 s, two_contexts 0.73 - 0.92 s, shim 0.45 - 0.56 s, the scripted replay
-0.03 s; the file's 17 tests 9.6 s.
+0.03 s; the file's 17 tests 9.6 s.  With the world profiles: world 0.29 - 0.35 s, world_two_contexts 0.45 - 0.56 s (the
+earlier ones in the same run: single 0.41 - 0.68 s, tiles 0.39 - 0.50 s, two_contexts 0.74 - 0.96 s, shim 0.42 - 0.54 s); the
+file's 25 tests 12.8 s.
 
 The order test_st_rule_on_resident_paths_after_a_smaller_grid replays: fxjps_waypoint_st_batch on resident paths has to size
 its table of angles from the grid the batch ran on, not from the one resident now -- else, on a handle whose table is
@@ -48,6 +56,18 @@ def replay(ops, oracle, devices=(0,)):
 def test_sequence_on_one_handle(oracle, profile, seed):
     import fuxi_planner_amd as fx
     dev = [0, 0] if profile == "two_contexts" else [0]
+    with fx.Planner(dev) as p:
+        cs.run(p, cs.generate(seed, STEPS, profile), oracle, fresh=lambda: fx.Planner(dev), contexts=len(dev), seed=(profile, seed))
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("profile", ["world", "world_two_contexts"])
+def test_world_sequence_on_one_handle(oracle, profile, seed):
+    """The shared prior maps as the most mutable state of a handle: absorbed into, grown, slid, uploaded again and
+    released between the world-frame and cropped prepares that read them, the replans that must not notice and the
+    path checks on slots rewritten since their batch."""
+    import fuxi_planner_amd as fx
+    dev = [0, 0] if profile == "world_two_contexts" else [0]
     with fx.Planner(dev) as p:
         cs.run(p, cs.generate(seed, STEPS, profile), oracle, fresh=lambda: fx.Planner(dev), contexts=len(dev), seed=(profile, seed))
 
