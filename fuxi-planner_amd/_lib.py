@@ -13,7 +13,7 @@ Q_NOPATH, Q_PATH_TOO_LONG, Q_BAD_START, Q_CAPACITY = 0, -1, -2, -3
 BACKEND_HIP = 1
 
 # every symbol include/fxjps.h declares (tests check the .so exports all of them)
-VERSION = 870  # FXJPS_VERSION of include/fxjps.h
+VERSION = 880  # FXJPS_VERSION of include/fxjps.h
 PATH_VALID, PATH_EMPTY, PATH_BLOCKED, PATH_OUTSIDE, PATH_MALFORMED = 1, 0, 2, 3, -1  # FXJPS_PATH_*: fxjps_check_path's verdicts
 SYMBOLS = ("fxjps_version", "fxjps_timing_size", "fxjps_last_timing_sized", "fxjps_rank_preflight", "fxjps_reserve_grid",
            "fxjps_device_count", "fxjps_create", "fxjps_rank_unique_id", "fxjps_create_rank", "fxjps_set_grid_rank", "fxjps_destroy", "fxjps_last_error",
@@ -46,7 +46,8 @@ class Timing(C.Structure):
                 ("retried", C.c_int64), ("pops", C.c_int64), ("pushes", C.c_int64), ("far_refills", C.c_int64),
                 ("slow_pops", C.c_int64), ("table_wipes", C.c_int64), ("reused", C.c_int64), ("table_direct", C.c_int64),
                 ("waves", C.c_int64), ("waves_short", C.c_int64), ("head_launch_ms", C.c_double), ("batch_launch_ms", C.c_double),
-                ("solo_timeouts", C.c_int64)]
+                ("solo_timeouts", C.c_int64), ("host_tail_queries", C.c_int64), ("host_tail_ms", C.c_double),
+                ("host_tail_late", C.c_int64)]
 
 
 class SlotJob(C.Structure):

@@ -11,17 +11,20 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/fxjps.h"
+#include "fxjps_host_search.h"
 #include "fxjps_kernels.hip.inc"
 #include "fxjps_owned.h"
 #include "fxjps_results.h"
@@ -148,6 +151,123 @@ struct MappedWordRes {  // one zeroed uint32_t in a 64-byte pinned allocation
 using Stream = fx::Owned<StreamRes>;
 using Event = fx::Owned<EventRes>;
 using MappedWord = fx::Owned<MappedWordRes>;
+
+// The host tail: the first `kh` queries of a batch's longest-first order are searched by host
+// threads (fxjps_host_search.cpp) beside the device search, on host copies of the resident grid's maps.  One per context,
+// behind a pointer (a context moves; threads, a mutex and atomics do not).  The threads of a batch are created before
+// anything is launched -- a thread that cannot be created leaves the whole batch to the device -- wait for `go`, pull
+// queries from `next` and are joined by whoever ends the batch: finish_search, an error path (drain_all) or the destructor.
+// A query a thread did not finish keeps the watchdog's code in `len` and goes to the large pool like any other such code:
+// a loaded or failing host costs speed, never a result.
+constexpr uint32_t HOST_TAIL_MAX = 64, HOST_TAIL_THREADS_MAX = 12;
+struct HostTail {
+    // across batches
+    uint32_t kh_cap = HOST_TAIL_MAX;  // halved by every batch whose host part outlasted the device's, doubled again (up to
+                                      // HOST_TAIL_MAX) by 16 batches in a row whose host part was on time
+    int late_run = 0;                 // late batches in a row (3: off for this handle, as solo_timeouts_run)
+    int ontime_run = 0;               // batches on time in a row since the share last changed
+    uint64_t maps_gen = ~0ull;        // DevCtx::map_gen the host copies were taken at
+    fxh::Maps maps;
+    HBuf<uint16_t> jd;
+    HBuf<fx::BmWord> bm;
+    HBuf<int32_t> comp;
+    Stream stream;  // the map copies' own
+    Event ev_grid, ev_maps;
+    std::vector<uint32_t> lut;
+    std::vector<std::unique_ptr<fxh::Searcher>> searchers;
+    HBuf<uint32_t> path, ids;  // [kh][max_len] packed cells, [kh] query ids
+    HBuf<int32_t> len;
+    HBuf<double> cost;
+    // the batch in progress
+    std::vector<std::thread> threads;
+    std::mutex mu;
+    std::condition_variable cv;
+    int go = 0;  // 0: wait, 1: search, -1: leave
+    std::atomic<uint32_t> next{0}, ended{0};
+    std::atomic<bool> cancel{false};
+    std::atomic<unsigned long long> pops{0}, pushes{0};
+    double t_first = 0, t_last = 0;  // first thread's start, last thread's end (under mu)
+    uint32_t kh = 0;
+    const int32_t *starts = nullptr, *goals = nullptr;
+    const uint32_t* order = nullptr;
+    int hchoice = 0, max_len = 0;
+    uint64_t max_pops = 0;
+    // ... and what it left for the timing record
+    uint32_t done_kh = 0;
+    double done_ms = 0;
+    bool done_late = false;
+
+    void work(size_t t) {
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return go != 0; });
+            if (go < 0) return;
+        }
+        const double t0 = now_s();
+        try {
+            for (uint32_t i = next.fetch_add(1); i < kh && !cancel.load(std::memory_order_relaxed); i = next.fetch_add(1)) {
+                const uint32_t q = order[i];
+                const fxh::Result R = searchers[t]->plan(maps, lut.data(), hchoice, starts[2 * q], starts[2 * q + 1], goals[2 * q], goals[2 * q + 1],
+                                                         max_len, path.p + (size_t)i * (size_t)max_len, max_pops);
+                cost.p[i] = R.cost;
+                len.p[i] = R.len;
+                pops += R.pops;
+                pushes += R.pushes;
+            }
+        } catch (...) {  // (std::bad_alloc in a table or a heap: the query keeps the watchdog's code)
+        }
+        const double t1 = now_s();
+        std::lock_guard<std::mutex> lk(mu);
+        t_first = ended.load() == 0 ? t0 : std::min(t_first, t0);
+        t_last = ended.load() == 0 ? t1 : std::max(t_last, t1);
+        ended++;
+    }
+    // T threads for the next batch, waiting; false (and none left) when one of them cannot be created
+    bool spawn(size_t T) {
+        go = 0;
+        next = 0;
+        ended = 0;
+        cancel = false;
+        pops = 0;
+        pushes = 0;
+        try {
+            if (lut.empty()) {
+                lut.resize(11 * 256);
+                fxh::dirlut_fill(lut.data());
+            }
+            while (searchers.size() < T) searchers.emplace_back(new fxh::Searcher());
+            threads.reserve(T);
+            for (size_t t = 0; t < T; t++) threads.emplace_back([this, t] { work(t); });
+        } catch (...) {  // std::system_error: no more threads; std::bad_alloc
+            release(-1);
+            return false;
+        }
+        return true;
+    }
+    void release(int how) {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            go = how;
+        }
+        cv.notify_all();
+        if (how < 0) join();
+    }
+    void join() {
+        for (auto& t : threads)
+            if (t.joinable()) t.join();
+        threads.clear();
+    }
+    // an error path, or the end of the handle: whatever runs stops after its current query
+    void abandon() {
+        if (threads.empty()) return;
+        cancel = true;
+        release(go == 0 ? -1 : go);
+        join();
+        kh = 0;
+        maps_gen = ~0ull;  // (a copy may not have landed: the next batch takes the maps again)
+    }
+    ~HostTail() { abandon(); }
+};
 
 struct ScratchCfg {
     uint32_t nwaves = 0;
@@ -324,6 +444,11 @@ struct DevCtx : GridBufs {
     HBuf<uint8_t> h_absorb_in;
     DBuf<uint8_t> d_absorb_in;
     HBuf<unsigned long long> h_absorb_out;
+    // the host tail: the generation of the resident grid's maps (moved by every call that writes the grid or its maps:
+    // alloc_grid, derive_maps, update_cells_async -- every set_grid*, update_cells*, prepare_*, refresh_* and replan_frame*
+    // goes through one of them), and the tail's state once a batch has used it (last: destroyed first, while the streams exist)
+    uint64_t map_gen = 0;
+    std::unique_ptr<HostTail> tail;
 
     DevCtx() = default;
     DevCtx(DevCtx&&) = default;  // (std::vector<DevCtx>::resize; nothing moves a context that is in use)
@@ -331,8 +456,10 @@ struct DevCtx : GridBufs {
     // Whatever is queued may still use the buffers: both streams are drained, then every member gives back what it holds,
     // with the context's device current.
     ~DevCtx() {
+        if (tail) tail->abandon();
         if (dev < 0) return;
         (void)hipSetDevice(dev);
+        if (tail && tail->stream) (void)hipStreamSynchronize(tail->stream);  // (a map copy reads the grid's buffers)
         if (stream_solo) (void)hipStreamSynchronize(stream_solo);
         if (stream) (void)hipStreamSynchronize(stream);
     }
@@ -441,46 +568,11 @@ int fail(fxjps* h, int code, const char* fmt, ...) {
                         #call, hipGetErrorString(e__), __FILE__, __LINE__);                      \
     } while (0)
 
-// nodeNeighbours (jps1.py:49-93) on a neighbour mask: which direction each of the 8 rays of a node
-// follows in the search kernel.  pd = (dX+1)*4 + (dY+1) of direction(c, came_from[c]) (jps1.py:40-47),
-// 5 = no parent (the start node, `type(parent) != tuple`, :51).
-uint32_t dirlut_entry(uint32_t pd, uint32_t nbm) {
-    auto occ = [&](int dx, int dy) -> bool { return (nbm >> fx::nbit(dx, dy)) & 1u; };
-    auto blocked = [&](int dx, int dy) -> bool {  // blocked(c, dx, dy), jps1.py:14-31, border == occupied
-        if (dx != 0 && dy != 0) return (occ(dx, 0) && occ(0, dy)) || occ(dx, dy);
-        return occ(dx, dy);
-    };
-    uint32_t codes[8];
-    int n = 0;
-    auto add = [&](int dx, int dy) { codes[n++] = (uint32_t)((dx + 1) * 4 + (dy + 1)); };
-    const int pdx = (int)(pd >> 2) - 1, pdy = (int)(pd & 3u) - 1;
-    if (pd == fx::PD_NONE) {  // :51-56
-        static const int all8[8][2] = {{-1, 0}, {0, -1}, {1, 0}, {0, 1}, {-1, -1}, {-1, 1}, {1, -1}, {1, 1}};
-        for (auto& d : all8)
-            if (!blocked(d[0], d[1])) add(d[0], d[1]);
-    } else if (pdx < -1 || pdx > 1 || pdy < -1 || pdy > 1) {
-        // not a direction code
-    } else if (pdx != 0 && pdy != 0) {  // :59-73
-        if (!blocked(0, pdy)) add(0, pdy);
-        if (!blocked(pdx, 0)) add(pdx, 0);
-        if ((!blocked(0, pdy) || !blocked(pdx, 0)) && !blocked(pdx, pdy)) add(pdx, pdy);
-        if (blocked(-pdx, 0) && !blocked(0, pdy)) add(-pdx, pdy);
-        if (blocked(0, -pdy) && !blocked(pdx, 0)) add(pdx, -pdy);
-    } else if (pdx == 0) {  // :76-83; the guard at :77 tests the node itself, which is free
-        if (!blocked(0, pdy)) add(0, pdy);
-        if (blocked(1, 0)) add(1, pdy);
-        if (blocked(-1, 0)) add(-1, pdy);
-    } else {  // :85-92
-        if (!blocked(pdx, 0)) {
-            add(pdx, 0);
-            if (blocked(0, 1)) add(pdx, 1);
-            if (blocked(0, -1)) add(pdx, -1);
-        }
-    }
-    uint32_t v = 0;
-    for (int g = 0; g < 8; g++) v |= (g < n ? codes[g] : fx::DIR_NONE) << (4 * g);
-    return v;
-}
+// nodeNeighbours (jps1.py:49-93) as a table: one definition for the device's table and the host search (fxjps_host_search.cpp)
+using fxh::dirlut_entry;
+static_assert(fxh::PD_NONE == fx::PD_NONE && fxh::DIR_NONE == fx::DIR_NONE && fxh::QI_WATCHDOG == fx::QI_WATCHDOG &&
+                  sizeof(fxh::BmWord) == sizeof(fx::BmWord),
+              "the host search reads the device's maps and codes");
 
 GridDev grid_of(const GridBufs& d) {
     GridDev G;
@@ -510,6 +602,7 @@ int derive_maps(fxjps* h, DevCtx& d, bool whole = true, GridBufs* slot = nullptr
     HIPCHK(h, hipSetDevice(d.dev));
     GridBufs& g = slot ? *slot : d;
     if (slot) whole = true;
+    if (!slot) d.map_gen++;
     if (!whole && !d.dirty && !d.ccl_full) return FXJPS_OK;
     const bool box = !whole && d.dirty && (d.bx1 - d.bx0 + 1) * 2 <= g.PW && (d.by1 - d.by0 + 1) * 2 <= g.PH;
     const GridDev G = grid_of(g);
@@ -665,6 +758,7 @@ int alloc_grid_bufs(fxjps* h, GridBufs& d, int W, int H) {
 
 int alloc_grid(fxjps* h, DevCtx& d, int W, int H) {
     HIPCHK(h, hipSetDevice(d.dev));
+    d.map_gen++;
     // The search scratch is sized by the grid's shape.  A new grid of the SAME shape keeps the pools as they are -- what
     // earlier searches left in the visited tables carries their generation tags and reads as empty, exactly as between two
     // batches on one grid -- so a caller that uploads a changed map every tick (jps1.method) does not pay for sizing and
@@ -951,6 +1045,134 @@ void fill_search_args(const DevCtx& d, const BatchReq& req, int pool, SearchArgs
     }
 }
 
+// ---- the host tail of a batch that has a head launch (launch_search): how many queries of the head of the longest-first
+// order the host takes, its threads created and waiting.  0: the device keeps everything -- a shape the host search does
+// not take, the knob, a handle whose host was late three batches in a row, or anything that could not be had (memory, a
+// thread): decided here, before anything is launched.
+// FXJPS_HOST_TAIL=<queries> (0: off) and FXJPS_HOST_THREADS=<threads> are read per call.  A share named that way is taken
+// as it stands (a measurement and test aid, as FXJPS_SOLO: a sweep must run the setting it names); the load control --
+// half the share after a late batch, off after three in a row -- governs the default share.
+// (profiles/host_tail.txt section 2: on config 2 the settings from 8 to 24 queries lie within 1 % of each other; 16 on 8
+// threads has the best median among those whose host part was never late -- 24 on 8 threads was, in 10 of 48 steps)
+constexpr uint32_t HOST_TAIL_DEFAULT = 16, HOST_TAIL_THREADS_DEFAULT = 8;
+uint32_t host_tail_begin(fxjps* h, DevCtx& d, const BatchReq& req, const ScratchCfg& c) {
+    uint32_t kh = HOST_TAIL_DEFAULT, T = HOST_TAIL_THREADS_DEFAULT;
+    if (d.tail) d.tail->done_kh = 0;
+    const char* named = getenv("FXJPS_HOST_TAIL");
+    if (named) kh = (uint32_t)std::min(std::max(0, atoi(named)), (int)HOST_TAIL_MAX);
+    if (const char* e = getenv("FXJPS_HOST_THREADS")) T = (uint32_t)std::min(std::max(1, atoi(e)), (int)HOST_TAIL_THREADS_MAX);
+    if (kh == 0u || h->devs.size() != 1 || c.direct_ly == 0u || req.slots || req.track() || d.st.on || getenv("FXJPS_QSTAT") ||
+        req.max_len > (1 << 16) || req.cells > (1ull << 20))
+        return 0u;
+    if (!d.tail) {
+        try {
+            d.tail.reset(new HostTail());
+        } catch (...) {
+            return 0u;
+        }
+    }
+    HostTail& t = *d.tail;
+    t.abandon();  // (nothing runs here between two batches; an error path joined already)
+    if (!named) {
+        kh = std::min(kh, t.kh_cap);
+        if (t.late_run >= 3 || kh == 0u) return 0u;
+    }
+    T = std::min(T, kh);
+    const bool copy = t.maps_gen != d.map_gen;
+    bool ok = t.path.ensure((size_t)kh * (size_t)req.max_len) == hipSuccess && t.ids.ensure(kh) == hipSuccess && t.len.ensure(kh) == hipSuccess &&
+              t.cost.ensure(kh) == hipSuccess;
+    if (ok && copy) {
+        t.maps_gen = ~0ull;
+        ok = t.jd.ensure((size_t)d.PW * d.NS * 8) == hipSuccess && t.bm.ensure((size_t)4 * d.LINES * d.WORDS) == hipSuccess &&
+             t.comp.ensure((size_t)d.W * d.H) == hipSuccess && (t.stream || t.stream.create(hipStreamNonBlocking) == hipSuccess) &&
+             (t.ev_grid || t.ev_grid.create(hipEventDisableTiming) == hipSuccess) && (t.ev_maps || t.ev_maps.create(hipEventDisableTiming) == hipSuccess) &&
+             hipEventRecord(t.ev_grid, d.stream) == hipSuccess;  // (the maps are complete here: the copies wait for this, not for the search)
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        return 0u;
+    }
+    for (uint32_t i = 0; i < kh; i++) {
+        t.ids.p[i] = d.h_order[i];
+        t.len.p[i] = fx::QI_WATCHDOG;  // (until a thread has the query's result)
+        t.cost.p[i] = 0.0;
+    }
+    t.starts = req.starts + 2 * d.q0;
+    t.goals = req.goals + 2 * d.q0;
+    t.order = d.h_order.data();
+    t.hchoice = req.hchoice;
+    t.max_len = req.max_len;
+    t.max_pops = 64ull * (unsigned long long)req.cells + 4096ull;  // (the kernel's bound, fill_search_args)
+    t.kh = kh;  // (what the threads pull up to; they wait for host_tail_go)
+    if (!t.spawn(T)) {
+        t.kh = 0;  // no thread could be had: the device keeps the whole order, and finish_search has nothing to put
+        return 0u;
+    }
+    return kh;
+}
+
+// The device launches are queued: on the first batch of a map generation the maps travel to the host on a stream of their
+// own beside the search, and the threads start when they have landed.
+int host_tail_go(fxjps* h, DevCtx& d) {
+    HostTail& t = *d.tail;
+    if (t.maps_gen != d.map_gen) {
+        HIPCHK(h, hipStreamWaitEvent(t.stream, t.ev_grid, 0));
+        HIPCHK(h, hipMemcpyAsync(t.jd.p, d.jd.p, (size_t)d.PW * d.NS * 8 * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(h, hipMemcpyAsync(t.bm.p, d.bm.p, (size_t)4 * d.LINES * d.WORDS * sizeof(fx::BmWord), hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(h, hipMemcpyAsync(t.comp.p, d.comp.p, (size_t)d.W * d.H * sizeof(int32_t), hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(h, hipEventRecord(t.ev_maps, t.stream));
+        HIPCHK(h, hipEventSynchronize(t.ev_maps));
+        t.maps.jd = t.jd.p;
+        t.maps.bm = reinterpret_cast<const fxh::BmWord*>(t.bm.p);
+        t.maps.comp = t.comp.p;
+        t.maps.W = d.W;
+        t.maps.H = d.H;
+        t.maps.NS = d.NS;
+        t.maps.LINES = d.LINES;
+        t.maps.WORDS = d.WORDS;
+        t.maps_gen = d.map_gen;
+    }
+    t.release(1);
+    return FXJPS_OK;
+}
+
+// The host has seen the device search finish: whether the host part is the later one (the load control: the share halves,
+// three such batches in a row switch the tail off for the handle), then its results into the batch's device buffers.
+int host_tail_end(fxjps* h, DevCtx& d, const BatchReq& req) {
+    HostTail& t = *d.tail;
+    const uint32_t kh = t.kh;
+    const bool late = t.ended.load() < (uint32_t)t.threads.size();
+    t.join();
+    t.kh = 0;
+    // the load control: a late batch halves the share of the next one (never to nothing: three late batches IN A ROW are
+    // what switches the tail off), and a host that is on time again for 16 batches in a row gets the share back step by step
+    if (late) {
+        t.kh_cap = std::max(1u, std::min(t.kh_cap, kh) / 2u);
+        t.late_run++;
+        t.ontime_run = 0;
+    } else {
+        t.late_run = 0;
+        if (++t.ontime_run >= 16) {
+            t.kh_cap = std::min(HOST_TAIL_MAX, t.kh_cap * 2u);
+            t.ontime_run = 0;
+        }
+    }
+    t.done_kh = kh;
+    t.done_ms = (t.t_last - t.t_first) * 1e3;
+    t.done_late = late;
+    void *dp_ids = nullptr, *dp_path = nullptr, *dp_len = nullptr, *dp_cost = nullptr;
+    HIPCHK(h, hipHostGetDevicePointer(&dp_ids, t.ids.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_path, t.path.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_len, t.len.p, 0));
+    HIPCHK(h, hipHostGetDevicePointer(&dp_cost, t.cost.p, 0));
+    hipLaunchKernelGGL(fx::k_host_tail_put, dim3(kh), dim3(256), 0, d.stream, (const uint32_t*)dp_ids, (const uint32_t*)dp_path, (const int32_t*)dp_len,
+                       (const double*)dp_cost, req.max_len, (long long)d.nq, d.d_path.p, d.d_len.p, d.d_cost.p, d.d_counters.p,
+                       (unsigned long long)t.pops.load(), (unsigned long long)t.pushes.load());
+    HIPCHK(h, hipGetLastError());
+    DBG("host tail: %u queries, %.3f ms%s", kh, t.done_ms, late ? " (late)" : "");
+    return FXJPS_OK;
+}
+
 int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint32_t* d_order, uint32_t nrun) {
     const ScratchCfg& c = d.cfg[pool];
     const bool track = req.track();
@@ -981,6 +1203,16 @@ int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint
         nsolo = 0;
     nsolo = std::min<uint32_t>(nsolo, 512u) & ~(live_solo - 1u);
     if (nsolo != 0u) waves = std::min<uint32_t>(waves, (uint32_t)wpb_down(c.nwaves - nsolo));
+    // The host tail: where there is a head launch, the very first queries of the order go to host threads instead (a host
+    // core runs such a chain of dependent pops about twice as fast as a lone wavefront: profiles/host_tail.txt), and both
+    // launches take theirs from behind them.
+    const uint32_t kh = nsolo != 0u ? host_tail_begin(h, d, req, c) : 0u;
+    if (kh != 0u) {
+        d_order += kh;
+        nrun -= kh;
+        A.order = d_order;
+        A.nrun = nrun;
+    }
 
     if (pool != 0 || nsolo != 0u || (uint64_t)nrun > (uint64_t)d.n_cu * live_main || d.share * h->mem_div > 1) live_main = 0u;
     if (pool == 0) d.run.waves_used = waves;
@@ -1059,6 +1291,7 @@ int launch_search(fxjps* h, DevCtx& d, const BatchReq& req, int pool, const uint
         HIPCHK(h, hipGetLastError());
     }
     d.run.launches += nsolo != 0u ? 2 : 1;  // (the two launches overlap: the events span both)
+    if (kh != 0u) return host_tail_go(h, d);
     return FXJPS_OK;
 }
 
@@ -1188,6 +1421,8 @@ int finish_search(fxjps* h, DevCtx& d, const BatchReq& req) {
     DBG("waiting for the search kernel");
     HIPCHK(h, hipStreamSynchronize(d.stream));
     DBG("search kernel done");
+    if (d.tail && d.tail->kh != 0u)
+        if (int rc = host_tail_end(h, d, req)) return rc;
     if (!d.st.on) {  // (a streamed batch: the kernel left the lengths in h_len)
         HIPCHK(h, hipMemcpyAsync(d.h_len.p, d.d_len.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
         HIPCHK(h, hipStreamSynchronize(d.stream));
@@ -1570,7 +1805,15 @@ void collect_timing(fxjps* h) {
     T.head_launch_ms = 0;
     T.batch_launch_ms = 0;
     T.solo_timeouts = 0;
+    T.host_tail_queries = 0;
+    T.host_tail_ms = 0;
+    T.host_tail_late = 0;
     for (auto& d : h->devs) {
+        if (d.tail && d.tail->done_kh != 0u && d.nq > 0 && d.run.had_solo) {
+            T.host_tail_queries += d.tail->done_kh;
+            T.host_tail_ms = std::max(T.host_tail_ms, d.tail->done_ms);
+            if (d.tail->done_late) T.host_tail_late = 1;
+        }
         T.head_launch_ms = std::max(T.head_launch_ms, d.run.head_ms);
         T.batch_launch_ms = std::max(T.batch_launch_ms, d.run.batch_ms);
         T.solo_timeouts += d.solo_timeouts;
@@ -1704,7 +1947,9 @@ int finish_set_grid(fxjps* h, int W, int H, bool wait = true) {
 void drain_all(fxjps* h) {
     const std::string keep = h->err;
     for (auto& d : h->devs) {
+        if (d.tail) d.tail->abandon();  // (host threads of a batch that failed half-way)
         if (hipSetDevice(d.dev) == hipSuccess) {
+            if (d.tail && d.tail->stream) (void)hipStreamSynchronize(d.tail->stream);
             if (d.stream_solo) (void)hipStreamSynchronize(d.stream_solo);  // (a head launch may still be running)
             (void)hipStreamSynchronize(d.stream);
         }
@@ -2477,6 +2722,7 @@ int update_cells_async(fxjps_t* h, const int32_t* xy, const uint8_t* val, int64_
     if (!h->have_grid) return fail(h, FXJPS_E_NOGRID, "cell update before fxjps_set_grid");
     if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && (!xy || !val))) return fail(h, FXJPS_E_ARG, "bad update arrays");
     if (n == 0 && !(derive && h->maps_stale)) return FXJPS_OK;
+    for (auto& d : h->devs) d.map_gen++;  // (the cells and the component labels change here, the other maps in derive_maps)
     // the box of the cells of the list that lie on the grid
     int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
     bool have_box = false;

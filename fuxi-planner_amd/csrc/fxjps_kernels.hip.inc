@@ -3419,6 +3419,28 @@ __global__ __launch_bounds__(64) void k_counters_out(const unsigned long long* _
     host[threadIdx.x] = counters[threadIdx.x];
 }
 
+// The results of the queries the host searched beside the device (fxjps.hip, HostTail) into their slots of the batch's
+// device buffers, where packing, the retry path and the resident forms look for them: block i puts query ids[i].  The
+// sources are pinned host memory.  Queued when the search is over, so the sums of the host's pops and pushes are plain adds.
+__global__ __launch_bounds__(256) void k_host_tail_put(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ path, const int32_t* __restrict__ len,
+                                                       const double* __restrict__ cost, int max_len, long long nq, uint32_t* __restrict__ out_path,
+                                                       int32_t* __restrict__ out_len, double* __restrict__ out_cost,
+                                                       unsigned long long* __restrict__ counters, unsigned long long pops, unsigned long long pushes) {
+    const uint32_t i = blockIdx.x, q = ids[i];
+    if (i == 0u && threadIdx.x == 0u) {
+        counters[0] += pops;
+        counters[1] += pushes;
+    }
+    if ((long long)q >= nq) return;
+    const int32_t n = len[i];
+    const int cells = n < 0 ? 0 : (n > max_len ? max_len : n);
+    for (int k = (int)threadIdx.x; k < cells; k += 256) out_path[(size_t)q * (size_t)max_len + (size_t)k] = path[(size_t)i * (size_t)max_len + (size_t)k];
+    if (threadIdx.x == 0u) {
+        out_len[q] = n;
+        out_cost[q] = cost[i];
+    }
+}
+
 // ---------------------------------------------------------------- CSR packing
 // Exclusive scan of max(len, 0) over nq entries, one block.
 __global__ __launch_bounds__(1024) void k_scan_len(const int32_t* __restrict__ len, long long nq,

@@ -122,8 +122,19 @@ typedef struct fxjps fxjps_t;
  *   870  fxjps_absorb_prior_slide (fxjps_absorb_prior_grow followed, per prior, by a cut to a keep window in world metres,
  *        in the same single launch: a prior that moves with the fleet instead of refusing at the limit), fxjps_slide_check
  *        (its geometry and refusals without a handle), fxjps_prior_keep_size, fxjps_prior_slid_size.
+ *   880  the host tail: a batch of 4 096 .. 32 768 queries on a handle that has its device to itself may leave the first
+ *        queries of its longest-first order to host threads, which search them on host copies of the grid's maps beside
+ *        the device search (results are the same bytes).  Where: one context, the device not shared with another handle
+ *        (fxjps_set_memory_share), the resident grid of at most 2^20 cells, not a slots batch, not fxjps_replan_frame*, not
+ *        a streamed batch (FXJPS_STREAM_RESULTS=1), max_path_len <= 65 536, not under FXJPS_QSTAT.  The default share is 16
+ *        queries on 8 threads.  Load control: a batch whose host part ends after the device search halves the share of the
+ *        next batch (at least 1), 16 batches in a row that were on time double it again, three late batches in a row
+ *        switch the tail off for the handle's lifetime (host_tail_queries == 0 from then on).  FXJPS_HOST_TAIL=<queries>
+ *        (0 = off, at most 64; a share named this way is taken as it stands, the load control does not touch it) and
+ *        FXJPS_HOST_THREADS=<threads> (at most 12) are read per call.
+ *        fxjps_timing_t grew by host_tail_queries, host_tail_ms, host_tail_late.
  * fxjps_timing_t only ever grows at its end. */
-#define FXJPS_VERSION 870
+#define FXJPS_VERSION 880
 int fxjps_version(void);
 
 /* Number of HIP devices visible, or a negative code. */
@@ -803,6 +814,11 @@ typedef struct fxjps_timing {
     int64_t solo_timeouts;   /* waits for the head launch's blocks to report from their CUs that ran into their 5 ms bound,
                                 since the handle was created (3 in a row on a device: it runs its batches as one launch from
                                 then on; a lone one is the cold first launch of a kernel) */
+    int64_t host_tail_queries; /* queries of the last batch that host threads searched beside the device (0: none; their pops
+                                  and pushes are in the sums above) */
+    double host_tail_ms;       /* ... from the first thread's start to the last thread's end */
+    int64_t host_tail_late;    /* 1: they ended after the device search (the next batch gives the host half as many; three
+                                  such batches in a row and the handle leaves everything to the device) */
 } fxjps_timing_t;
 /* fxjps_last_timing writes sizeof(fxjps_timing_t) bytes AS THE LIBRARY WAS BUILT: a host compiled against an older header
  * checks fxjps_version() == FXJPS_VERSION (or fxjps_timing_size() == sizeof(fxjps_timing_t)) first, or calls
